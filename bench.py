@@ -564,6 +564,30 @@ def cpu_baseline(pr, gpu_hist, gpu_paths):
 
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: what the timed path's last step returned (name -> [B,...] device tensor) as dirname/<name>.npy in float32.  When the
+    whole would exceed DUMP_LIMIT_BYTES, the same fixed, seeded sample of rows of every output is written.  -> what the line records of it."""
+    os.makedirs(dirname, exist_ok=True)
+    B = next(iter(outputs.values())).shape[0]
+    row_bytes = sum(4 * t[0].numel() for t in outputs.values())
+    rows = None
+    if B * row_bytes > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // row_bytes
+        rows = np.sort(np.random.Generator(np.random.PCG64(20261015)).choice(B, size=n, replace=False))
+    files = {}
+    for name, t in outputs.items():
+        a = t.detach().float().cpu().numpy()
+        if rows is not None:
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        files[name] = list(a.shape)
+    return {"dir": dirname, "files": files, "dtype": "float32",
+            "rows": "all" if rows is None else f"{len(rows)} of {B}, numpy PCG64(20261015) choice without replacement, ascending"}
+
+
 class ApiRunner:
     """step() = what a user of the reference does per batch: ``planner(map_designs, start_maps, goal_maps)`` on the reference's [B,1,H,W]
     tensors, default (same-call) solvability verdict, outputs allocated by the call.  ``placement``:
@@ -680,7 +704,12 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="dev: gloo lets N ranks share ONE GPU (with --share-gpu) to exercise every world > 1 branch of this script on a 1-GPU box")
     ap.add_argument("--share-gpu", action="store_true", help="dev: every rank uses cuda:0 (only with --dist-backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline pass's last step returned (histories, paths) as DIR/<name>.npy in "
+                         "float32 (rank 0's rows; a fixed, seeded sample of them above 64 MB).  The inputs depend on the arguments only")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode == "train":
+        ap.error("--dump-outputs: only the forward mode (the headline) writes its outputs")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as plain `python bench.py --gpus N`: re-launch one rank per GPU the way the driver does
@@ -786,6 +815,7 @@ def main():
         prewarm(warm, dev)  # (bare launches on batches of their OWN: the headline's batches stay unsearched)
     first_fresh = run._i
     dt, dev_ms = timed_loop(run, args.steps, args.warmup, world, dev, collate)
+    last_out = run.out  # what the headline pass's last timed step returned (--dump-outputs)
     all_first_visits = n_fresh > 0 and run._i <= len(run.sets)
     iters = run.iters.cpu().numpy()
     assert int(run.status.abs().sum().item()) == 0, "unsolvable map in the synthetic batch"
@@ -900,6 +930,9 @@ def main():
             "mean_iters_per_map": float(iters.mean()), "max_iters_per_map": int(iters.max()),
             "device_ms_per_step": dev_ms / args.steps,
         }
+        if args.dump_outputs:  # (after every timed pass of this process)
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, {"histories": last_out.histories, "paths": last_out.paths})
+        del last_out
         if n_gpus == 1 and not args.no_cpu_baseline:
             _log("cpu baseline")
             out["cpu_baseline"] = cpu_baseline(pr, hist, paths)

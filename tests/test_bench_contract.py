@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -114,3 +115,49 @@ def test_sharded_step_collates_per_bucket_over_rccl_in_a_one_rank_group():
     assert "FAILED" not in note and "ONE all-gather per 2 steps" in note and "emitted by the search launch itself" in note, note
     assert j["config"]["distributed"]["backend"] == "nccl" and j["config"]["distributed"]["world_size"] == 1
     assert j["value"] > 0 and j["config"]["host_lane"].startswith("native")
+
+
+def test_dump_outputs_writes_float32_and_samples_fixed_rows_above_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: every output as <name>.npy in float32; above the size limit the SAME seeded rows of every output, the same on
+    every call"""
+    sys.path.insert(0, ROOT)
+    import bench
+    hist = torch.arange(10 * 2 * 3, dtype=torch.float32).reshape(10, 1, 2, 3)
+    paths = (hist.long() % 2)
+    info = bench.dump_outputs(str(tmp_path / "all"), {"histories": hist, "paths": paths})
+    assert info["rows"] == "all" and info["files"] == {"histories": [10, 1, 2, 3], "paths": [10, 1, 2, 3]}
+    a = np.load(tmp_path / "all" / "histories.npy")
+    b = np.load(tmp_path / "all" / "paths.npy")
+    assert a.dtype == np.float32 and b.dtype == np.float32
+    assert np.array_equal(a, hist.numpy()) and np.array_equal(b, paths.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 4 * 2 * 6)  # room for 4 rows of both outputs
+    for d in ("s1", "s2"):
+        info = bench.dump_outputs(str(tmp_path / d), {"histories": hist, "paths": paths})
+        assert info["files"]["histories"] == [4, 1, 2, 3]
+    s1 = np.load(tmp_path / "s1" / "histories.npy")
+    assert np.array_equal(s1, np.load(tmp_path / "s2" / "histories.npy"))
+    rows = s1[:, 0, 0, 0].astype(np.int64) // 6  # (row r of hist starts with 6 r)
+    assert (np.diff(rows) > 0).all() and np.array_equal(np.load(tmp_path / "s1" / "paths.npy"), paths.numpy()[rows].astype(np.float32))
+    assert s1.nbytes + np.load(tmp_path / "s1" / "paths.npy").nbytes <= bench.DUMP_LIMIT_BYTES
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_same_on_every_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's histories and paths, float32, within 64 MB; the same arguments give the same inputs, so two
+    runs write the same arrays; `--steps` is the number of timed steps the line reports"""
+    got = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                            "--no-secondary", "--no-natural", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["dump_outputs"]["rows"] == "all"
+        h, p = np.load(d / "histories.npy"), np.load(d / "paths.npy")
+        assert h.dtype == np.float32 and p.dtype == np.float32 and h.shape == p.shape == (4096, 1, 32, 32)
+        assert h.nbytes + p.nbytes <= 64 << 20
+        assert p.sum() > 0 and (p <= h).all()  # (a path cell is an expanded cell: the goal is reached in eval mode)
+        got.append((h, p))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
