@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define NASTAR_VERSION 600 /* 0.6.0: nastar_forward_batchloop_finish (the reference's batch loop to the letter, any size, no host round trip), NASTAR_FLAG_MARK_COUPLED; the A/B flags left the ABI; 0.5.0: nastar_forward_ex (status summary, checked placement), nastar_placement_from_levels; 0.4.1: nastar_forward_ordered (placement); 0.4.0: round-4 search instruction stream, unit-cost LDS layout */
+#define NASTAR_VERSION 700 /* 0.7.0: the masked entry points nastar_forward_ex_masked / nastar_forward_batchloop_finish_masked / nastar_backward_replay_ordered_masked (DifferentiableAstar.neighbor_filter, NASTAR_NEIGHBORS_*); 0.6.0: nastar_forward_batchloop_finish (the reference's batch loop to the letter, any size, no host round trip), NASTAR_FLAG_MARK_COUPLED; the A/B flags left the ABI; 0.5.0: nastar_forward_ex (status summary, checked placement), nastar_placement_from_levels; 0.4.1: nastar_forward_ordered (placement); 0.4.0: round-4 search instruction stream, unit-cost LDS layout */
 
 /* status codes (function return values) */
 #define NASTAR_OK 0
@@ -94,6 +94,18 @@ extern "C" {
  * returns for the map searched alone, nastar_forward_batchloop_finish completes it to the batch run.  (The unit-cost layout never sets it:
  * cost = 1 everywhere.) */
 #define NASTAR_SUMMARY_COUPLED 14
+
+/* The search neighbourhood: DifferentiableAstar.neighbor_filter (differentiable_astar.py:140-143), the 3x3 filter that both expand() calls of
+ * every step convolve with (:228, :234), as a 9-bit mask -- bit r*3+c is set <=> filter cell (r, c) is 1.  expand() is conv2d, a
+ * cross-correlation: filter cell (a, b) opens the neighbour at offset (1-a, 1-b) of the selected cell (a point reflection: cell (0,1), top
+ * middle, opens the cell one row BELOW).  Supported filters have weights in {0, 1} and a zero centre: a mask with bit 4 or any bit >= 9 set is
+ * NASTAR_ERR_UNSUPPORTED.  The entry points without a mask argument search NASTAR_NEIGHBORS_MOORE8 (the reference's default filter) on their
+ * fastest kernels; the _masked ones run the compiled step loops with the mask for EVERY mask, Moore-8 included (what the mask costs is
+ * measurable: nothing else differs).  The heuristic stays the reference's (Chebyshev + 0.001 Euclidean, :26-52) for every filter; a map that
+ * the neighbourhood cannot solve ends with NASTAR_ERR_UNSOLVABLE like any other.  The all-zero mask is legal: every map is unsolvable unless
+ * its start is its goal. */
+#define NASTAR_NEIGHBORS_MOORE8 0x1EF       /* [[1,1,1],[1,0,1],[1,1,1]] */
+#define NASTAR_NEIGHBORS_VON_NEUMANN 0x0AA  /* [[0,1,0],[1,0,1],[0,1,0]] */
 
 int nastar_version(void);
 
@@ -168,6 +180,14 @@ int nastar_forward_ex(const float* cost, const float* start, const float* goal, 
  */
 int nastar_completion_supported(int H, int W);
 
+/* nastar_forward_ex with the neighbourhood of a neighbor_filter (NASTAR_NEIGHBORS_* above); every other argument as there.  The compiled step
+ * loops (never the hand-scheduled 16 / 32 / 64 streams or the unit-cost layout: NASTAR_FLAG_UNIT_COST is ignored) and the large-map kernel. */
+int nastar_forward_ex_masked(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
+                             double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
+                             int32_t* iters_out, int32_t* status_out, uint8_t* packed_out, void* workspace, size_t workspace_bytes,
+                             int flags, const int32_t* order, int32_t* order_out, int32_t* status_summary, int32_t* completion_counter,
+                             unsigned neighbor_mask, void* stream);
+
 /*
  * The reference's BATCH LOOP to the letter (differentiable_astar.py:203-252, :219-225, :251-252), for the class of inputs in which it matters.
  * The reference steps EVERY map until all maps of the batch select their goal in the same step; a finished map keeps its goal on the open
@@ -190,6 +210,11 @@ size_t nastar_batchloop_workspace_bytes(int B, int H, int W, int max_iters);
 int nastar_forward_batchloop_finish(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
                                     double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
                                     int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream);
+/* nastar_forward_batchloop_finish after a nastar_forward_ex_masked launch: the SAME neighbor_mask (NASTAR_NEIGHBORS_*) */
+int nastar_forward_batchloop_finish_masked(const float* cost, const float* start, const float* goal, const float* passable, int B, int H,
+                                           int W, double g_ratio, int max_iters, float* histories_out, int64_t* paths_out,
+                                           int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out, void* workspace,
+                                           size_t workspace_bytes, unsigned neighbor_mask, void* stream);
 /* Spin (pause loop, at most timeout_us) until *word_host != 0; returns 1 when it is, 0 on timeout.  HOST pointer (pinned memory). */
 int nastar_host_wait_nonzero(const volatile int32_t* word_host, int timeout_us);
 
@@ -235,6 +260,14 @@ int nastar_backward_replay_ordered(const float* grad_histories, const float* his
                                    const float* passable, const int32_t* sel_log, int B, int H, int W, double g_ratio,
                                    int max_iters, const int32_t* iters, const int32_t* t_batch_dev, float* grad_cost_out,
                                    void* workspace, size_t workspace_bytes, int flags, const int32_t* order, void* stream);
+/* nastar_backward_replay_ordered for the log of a nastar_forward_ex_masked search: the replay rebuilds the open sets with the SAME
+ * neighbor_mask (the compiled replay loop; the hand-scheduled 16 / 32 one hard-wires Moore-8) */
+int nastar_backward_replay_ordered_masked(const float* grad_histories, const float* histories, const float* opt_trajs,
+                                          const float* grad_loss_dev, const float* cost, const float* start, const float* goal,
+                                          const float* passable, const int32_t* sel_log, int B, int H, int W, double g_ratio,
+                                          int max_iters, const int32_t* iters, const int32_t* t_batch_dev, float* grad_cost_out,
+                                          void* workspace, size_t workspace_bytes, int flags, const int32_t* order,
+                                          unsigned neighbor_mask, void* stream);
 
 /*
  * Backward of `histories` w.r.t. `cost` (paths carry no gradient):

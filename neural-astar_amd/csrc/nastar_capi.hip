@@ -110,169 +110,22 @@ __global__ __launch_bounds__(1024) void nastar_order_check_kernel(const int* __r
 // LOGH > 0 && LOGW > 0: the map is exactly (1<<LOGH) x (1<<LOGW) (compile-time sizes, immediate ds offsets).
 // CPL_T: chunk minima per lane (1 or 4) when known at compile time, 0 = runtime.
 // kAsm: the selection/expansion loop is a hand-scheduled instruction stream (nastar_search_asm4 / _asm3 / _asm.hip.h; 16x16, 32x32, 64x64)
+// kMasked: the neighbourhood is DifferentiableAstar.neighbor_filter (nmask, see neighbour_enabled) instead of the Moore-8 stencil; compiled
+// step loops only (kAsm = false).  Both kernels share one body, nastar_forward_compact_body.inc.
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, bool kAsm = false>
 __global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCArgs a, const float rcp_sqrtW)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int b = placed_map(a.order, a.order_bad, a.B);
-    if ((unsigned)b >= (unsigned)a.B) return;  // not a permutation (and not checked: NASTAR_FLAG_CHECK_ORDER): never read or write outside the batch
-    const bool lockstep = !kAsm && (a.flags & NASTAR_FLAG_LOCKSTEP);  // (forward_impl picks a compiled instantiation for it)
-    if (lockstep && a.marks != nullptr && a.marks[b] == 0) return;    // not in the batch-coupled class: the early-exit launch's outputs stand
-    const int lane = threadIdx.x;
-    CompactDims d = a.d;
-    if constexpr (LOGH > 0 && LOGW > 0) {
-        d.H = 1 << LOGH;
-        d.W = 1 << LOGW;
-        d.HW = 1 << (LOGH + LOGW);
-        d.nchunks = d.HW >> CCL;
-        d.HWp = d.HW;
-        d.CPL = (d.nchunks + 63) / 64;
-        d.NCp = d.CPL * 64;
-        d.magicW = (uint32_t)((1ull << 32) >> LOGW) + 1u;
-    }
-    const CompactLds l = carve_compact_lds(smem, d);
-    const size_t off = (size_t)b * (size_t)d.HW;
+    constexpr bool kMasked = false;
+    constexpr uint32_t nmask = NASTAR_NEIGHBORS_MOORE8;
+#include "nastar_forward_compact_body.inc"
+}
 
-    int start_idx, goal_idx;
-    constexpr int kLoadIter = (kVec4 && LOGH > 0 && LOGW > 0 && LOGH + LOGW >= 8) ? (1 << (LOGH + LOGW - 8)) : 0;
-    bool any_signed = true;
-    // round-3 instruction stream (raw-bit keys): every cost >= +0 and 0 <= g_ratio <= 1 so that every priority is >= +0
-    compact_load_map<kVec4, kLoadIter>(d, l, a.cost + off, a.start + off, a.goal + off, a.passable + off, lane, start_idx, goal_idx,
-                                       kAsm ? &any_signed : nullptr);
-#ifdef NASTAR_DEV
-    const bool raw = kAsm && !any_signed && !(a.flags & NASTAR_FLAG_ASM_V2) && d.gr >= 0.f && d.omg >= 0.f;
-#else
-    const bool raw = kAsm && !any_signed && d.gr >= 0.f && d.omg >= 0.f;
-#endif
-    const int gi = goal_idx < 0 ? 0 : goal_idx;
-    const int goal_r = (int)div_magic((uint32_t)gi, d.magicW);
-    const int goal_c = gi - goal_r * d.W;
-
-    const CompactLane lc = make_compact_lane(d, lane);
-    int status = NASTAR_OK;
-    int iters = 0;
-    bool solved = false, coupled = false;
-    bool goal_hit = false;
-    const bool probe = lockstep && a.bitmap != nullptr;
-    const int budget = (lockstep && a.t_end != nullptr) ? __builtin_amdgcn_readfirstlane(*a.t_end + 1) : a.max_iters;
-    uint32_t bits = 0u;  // probe: goal selections of the current 32 steps
-    uint32_t* const bm = probe ? a.bitmap + (size_t)b * (size_t)a.bitmap_words : nullptr;
-    if (start_idx < 0 || goal_idx < 0) {
-        status = NASTAR_ERR_UNSOLVABLE;  // not a one-hot start/goal map
-    } else {
-        // round-4 stream (nastar_search_asm4.hip.h) wherever raw-bit keys apply (costs >= +0, 0 <= g_ratio <= 1: every priority is >= +0); a map with a
-        // negative / NaN cost takes the round-2 stream with its order-preserving key transform (nastar_search_asm.hip.h).  The development build
-        // (make dev) can also select the round-3 stream and switch the 64x64 dive off: csrc/nastar_dev_flags.h, stream-equality tests.
-        // half: g_ratio == 0.5 -- the two products of f = g_ratio g + (1 - g_ratio) h are exact and drop out of the key
-#ifdef NASTAR_DEV
-        const bool asm4 = raw && !(a.flags & NASTAR_FLAG_ASM_V3);
-        const bool no_dive = (a.flags & NASTAR_FLAG_NO_DIVE) != 0;
-#else
-        const bool asm4 = raw;
-#endif
-        const bool half = asm4 && d.gr == 0.5f && d.omg == 0.5f;
-        compact_open_start<kFastDiv>(d, l, lane, start_idx, goal_r, goal_c, rcp_sqrtW, raw, half);
-        int s = 0;
-        if constexpr (kAsm) {
-            static_assert(LOGW > 0 && LOGW == LOGH && (CPL_T == 1 || CPL_T == 4) && kFastDiv, "asm loop: 16x16, 32x32, 64x64");
-            int* const log_row = kLog ? a.sel_log + (size_t)b * (size_t)a.max_iters : nullptr;
-            // searching wavefronts issue ahead of the ones still loading their map or already storing their result (the launch waits for the
-            // longest SEARCH): maze32 159.4 -> 157.7 us, rand32 75.6 -> 75.0 us per 4096 maps, same box, two runs each; 3-4 batches in flight unchanged at 57 M maps/s (profiles/r03/prio_*.json, prio_streams.txt)
-            __builtin_amdgcn_s_setprio(3);
-            constexpr bool kD = CPL_T == 4;  // only the 64x64 instantiation dives (nastar_search_asm4.hip.h)
-#ifdef NASTAR_DEV
-            if (asm4 && kD && no_dive) {
-                if (half) s = search_loop_asm4<LOGW, kLog, false, true, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
-                else s = search_loop_asm4<LOGW, kLog, false, false, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
-            } else if (raw && !asm4 && kD && no_dive) {
-                s = compact_search_loop_asm3<LOGW, kLog, false>(d, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
-            } else if (raw && !asm4) {
-                s = compact_search_loop_asm3<LOGW, kLog>(d, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
-            } else
-#endif
-            if (asm4) {
-                s = half ? search_loop_asm4<LOGW, kLog, kD, true, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row)
-                         : search_loop_asm4<LOGW, kLog, kD, false, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
-            } else {
-                s = compact_search_loop_asm<LOGW, kLog>(d, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
-            }
-            __builtin_amdgcn_s_setprio(0);
-        } else
-        while (iters < budget) {  // :203 for t in range(Tmax)
-            uint2 mine;
-            s = compact_select<CPL_T>(d, l, lane, mine);
-            if (s < 0 || (s == goal_idx && !lockstep)) break;  // single exit test: open list empty (:68 would divide by zero) or goal
-            if constexpr (kLog) {
-                if (lane == 0) a.sel_log[(size_t)b * (size_t)a.max_iters + iters] = s;
-            }
-            if (probe) {
-                if (s == goal_idx) bits |= 1u << (iters & 31);
-                if ((iters & 31) == 31) {
-                    if (lane == 0) bm[iters >> 5] = bits;
-                    bits = 0u;
-                }
-            }
-            ++iters;
-            // lock-step mode: the reference's loop to the letter -- a selected goal is expanded like any cell, stays open, and the map is stepped
-            // on (it may wander: NASTAR_SUMMARY_COUPLED) until the caller's step count is reached
-            goal_hit |= s == goal_idx;
-            compact_expand<LOGW, kFastDiv, CPL_T>(d, l, lc, lane, s, goal_r, goal_c, rcp_sqrtW, mine, s == goal_idx);
-        }
-        if (probe) {  // the words this map's search did not reach say "no goal selection"; nothing else is written
-            if (lane == 0) {
-                if (iters & 31) bm[iters >> 5] = bits;
-                for (int w = (iters + 31) >> 5; w < a.bitmap_words; ++w) bm[w] = 0u;
-            }
-            return;
-        }
-        if (lockstep && goal_hit && lane == 0) l.gc[goal_idx].x = NASTAR_NEG_INF;  // histories holds the goal (:222-223); nothing reads its g any more
-        if (kAsm ? (s != -2) : (iters < budget)) {
-            if (s < 0) {
-                status = NASTAR_ERR_UNSOLVABLE;
-            } else {  // :219-220,:251 reached the goal: every later step of the reference is a fixed point
-                if constexpr (kLog) {
-                    if (lane == 0) a.sel_log[(size_t)b * (size_t)a.max_iters + iters] = s;
-                }
-                ++iters;
-                solved = true;
-                if (a.summary != nullptr || a.marks_out != nullptr) {
-                    // Is this map now at a FIXED POINT of the reference's batch loop?  The reference keeps stepping a finished map until every
-                    // map of the batch selects its goal in the same step (:224 the goal stays open, :251); this kernel stops here.  The two
-                    // agree iff the goal's own expansion opens nothing that beats the goal: true for every g_ratio in [0.5, 1) with costs >= 0
-                    // (f(n) - f(goal) = (2 g_ratio - 1) c_goal + (1 - g_ratio)(h0(n) + c_n) > 0), not for g_ratio < 0.5 with an expensive goal
-                    // cell, g_ratio = 1 with a zero-cost one, or negative costs.  Detected here, reported as summary[NASTAR_SUMMARY_COUPLED].
-                    const int nr = goal_r + lc.dr, nc = goal_c + lc.dc;
-                    const bool inb = lc.is_nb & ((unsigned)nr < (unsigned)d.H) & ((unsigned)nc < (unsigned)d.W);
-                    const int n = inb ? s + lc.off : s;
-                    const float2 gg = l.gc[s], gn = l.gc[n];
-                    const float g2 = gg.x + gg.y;
-                    const uint32_t kn = compact_key<kFastDiv>(d, g2, d.omg * (heuristic0_fast(nr, nc, goal_r, goal_c) + gn.y), rcp_sqrtW);
-                    const uint32_t kg = compact_key<kFastDiv>(d, gg.x, d.omg * (heuristic0_fast(goal_r, goal_c, goal_r, goal_c) + gg.y), rcp_sqrtW);
-                    const bool beats = inb & (gn.x > g2) & ((kn < kg) | ((kn == kg) & (n < s)));
-                    coupled = __ballot(beats) != 0ull;
-                    if (coupled && a.summary != nullptr && lane == 0) a.summary[NASTAR_SUMMARY_COUPLED] = 1;
-                    wave_order();
-                }
-                if (lane == 0) l.gc[s].x = NASTAR_NEG_INF;  // :222-223 the goal joins the closed list
-            }
-        }
-    }
-    wave_sync();
-    // histories depend on the closed list only: their stores are issued first and drain under the serial backtrack
-    compact_store_hist<kVec4>(d, l, lane, a.hist + off);
-    if (probe) return;  // (a map without a one-hot start / goal: the early-exit launch reported it, it is never marked)
-    if (lane == 0) {
-        a.iters[b] = iters;
-        a.status[b] = status;
-        if (a.marks_out != nullptr) a.marks_out[b] = coupled ? 1 : 0;
-        if (status != NASTAR_OK && a.summary) a.summary[status] = 1;  // plain idempotent store: the word may be host-mapped (no atomics over PCIe)
-        if (a.order_out) note_completion(a.order_out, a.B, b);
-        // (the COUPLED note above is a summary cell like any other: it must be visible before this search counts itself -- ADVICE r5)
-        if (a.done_counter) note_done(a.done_counter, a.summary, a.B, status != NASTAR_OK || coupled);
-    }
-    if (goal_idx >= 0) compact_backtrack<(LOGW == LOGH ? LOGW : 0)>(d, l, lane, start_idx, goal_idx, solved ? d.HW : iters - 1);
-    compact_store_outputs<kVec4, false>(d, l, lane, a.hist + off, a.paths + off,
-                                        a.packed ? a.packed + (size_t)b * (size_t)(d.HW >> 2) : nullptr);
+// the compiled step loop with the neighbourhood of a neighbor_filter (nastar_forward_ex_masked): nmask is a kernel argument (an SGPR)
+template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
+__global__ __launch_bounds__(64) void nastar_forward_compact_masked_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask)
+{
+    constexpr bool kAsm = false, kMasked = true;
+#include "nastar_forward_compact_body.inc"
 }
 
 // ---- forward, UNIT-COST layout (nastar_search_unit.hip.h; NASTAR_FLAG_UNIT_COST): cost map == obstacle map, every value 0.0 or 1.0 ----
@@ -576,6 +429,9 @@ constexpr int NASTAR_FLAG_NO_ASM = 0, NASTAR_FLAG_ASM_V2 = 0, NASTAR_FLAG_ASM_V3
 
 // map widths for which the FMA-based division by fl32(sqrt(W)) was verified bit-exact against IEEE division for
 // every fp32 f in [2^-100, FLT_MAX] (tools/fastdiv_check.c); widths whose sqrt is a power of two divide exactly.
+// a neighbor_filter mask of the masked entry points: weights in {0, 1} over the 3x3 cells, the centre cell (bit 4) clear
+static bool neighbor_mask_valid(unsigned m) { return (m & ~0x1FFu) == 0u && (m & 0x10u) == 0u; }
+
 static bool fastdiv_verified(int W)
 {
     static const int ok[] = {2, 8, 32, 128, 512, 10, 12, 20, 24, 28, 40, 45, 48, 50, 60, 96, 100,  // exhaustively checked
@@ -651,7 +507,7 @@ static int forward_impl(const float* cost, const float* start, const float* goal
                         int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out, void* workspace,
                         size_t workspace_bytes, int flags, void* stream, uint8_t* packed_out, bool* packed_done,
                         const int32_t* order = nullptr, int32_t* order_out = nullptr, int32_t* summary = nullptr, int32_t* done_counter = nullptr,
-                        const LockArgs* lock = nullptr)
+                        const LockArgs* lock = nullptr, bool masked = false, uint32_t nmask = NASTAR_NEIGHBORS_MOORE8)
 {
     *packed_done = false;
     if (!cost || !start || !goal || !passable || !histories_out || !paths_out || !iters_out || !status_out)
@@ -696,7 +552,12 @@ static int forward_impl(const float* cost, const float* start, const float* goal
         const size_t hl = hybrid_lds_bytes(hd.HW);
         if (hl > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
         int rc2;
-        if (lockstep) rc2 = fd ? launch(nastar_forward_hybrid_kernel<true, true>, B, hl, s, ha) : launch(nastar_forward_hybrid_kernel<false, true>, B, hl, s, ha);
+        if (masked) {  // (nastar_forward_ex_masked: the neighbourhood of a neighbor_filter)
+            if (lockstep) rc2 = fd ? launch(nastar_forward_hybrid_masked_kernel<true, true>, B, hl, s, ha, nmask)
+                                   : launch(nastar_forward_hybrid_masked_kernel<false, true>, B, hl, s, ha, nmask);
+            else rc2 = fd ? launch(nastar_forward_hybrid_masked_kernel<true, false>, B, hl, s, ha, nmask)
+                          : launch(nastar_forward_hybrid_masked_kernel<false, false>, B, hl, s, ha, nmask);
+        } else if (lockstep) rc2 = fd ? launch(nastar_forward_hybrid_kernel<true, true>, B, hl, s, ha) : launch(nastar_forward_hybrid_kernel<false, true>, B, hl, s, ha);
         else rc2 = fd ? launch(nastar_forward_hybrid_kernel<true, false>, B, hl, s, ha) : launch(nastar_forward_hybrid_kernel<false, false>, B, hl, s, ha);
         if (rc2) return rc2;
         if (!ha.bitmap) hipLaunchKernelGGL(nastar_hybrid_store_kernel, grid2, dim3(256), 0, s, ha);  // (a probe launch has no outputs)
@@ -738,6 +599,26 @@ static int forward_impl(const float* cost, const float* start, const float* goal
         const bool lg = sel_log_out != nullptr;
         void (*kern)(const FwdCArgs, const float) = nullptr;
         c.B = B;
+        if (masked) {
+            // a neighbor_filter: the compiled step loops with the mask (never the hand-scheduled streams or the unit-cost layout, whose
+            // instruction streams hard-wire the Moore-8 stencil), same size ladder as below
+            void (*mk)(const FwdCArgs, const float, const uint32_t) = nullptr;
+#define NASTAR_MPICK(V4, LW, LH, CPL, FD) \
+    mk = lg ? &nastar_forward_compact_masked_kernel<V4, LW, LH, CPL, FD, true> : &nastar_forward_compact_masked_kernel<V4, LW, LH, CPL, FD, false>
+            if (vec4 && fast && H == 32 && W == 32) { NASTAR_MPICK(true, 5, 5, 1, true); }
+            else if (vec4 && fast && H == 64 && W == 64) { NASTAR_MPICK(true, 6, 6, 4, true); }
+            else if (vec4 && fast && H == 16 && W == 16) { NASTAR_MPICK(true, 4, 4, 1, true); }
+            else if (vec4 && fast && c.d.CPL == 1) { NASTAR_MPICK(true, 0, 0, 1, true); }
+            else if (vec4 && fast) { NASTAR_MPICK(true, 0, 0, 0, true); }
+            else if (vec4) { NASTAR_MPICK(true, 0, 0, 0, false); }
+            else if (fast) { NASTAR_MPICK(false, 0, 0, 0, true); }
+            else { NASTAR_MPICK(false, 0, 0, 0, false); }
+#undef NASTAR_MPICK
+            const bool rank_after = order_out && (long long)B > resident_capacity(lds);
+            if (rank_after) c.order_out = nullptr;
+            const int mrc = launch(mk, B, lds, s, c, rcp, nmask);
+            return (mrc == NASTAR_OK && rank_after) ? rank_order_after(iters_out, B, order_out, s) : mrc;
+        }
 #define NASTAR_CPICK(V4, LW, LH, CPL, FD) \
     kern = lg ? &nastar_forward_compact_kernel<V4, LW, LH, CPL, FD, true> : &nastar_forward_compact_kernel<V4, LW, LH, CPL, FD, false>
         const bool use_asm = !(flags & (NASTAR_FLAG_NO_ASM | NASTAR_FLAG_LOCKSTEP));  // (lock-step mode lives in the compiled step loops)
@@ -801,23 +682,45 @@ int nastar_forward_ordered(const float* cost, const float* start, const float* g
                              status_out, packed_out, workspace, workspace_bytes, flags, order, order_out, nullptr, nullptr, stream);
 }
 
-int nastar_forward_ex(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
-                      int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
-                      uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
-                      int32_t* status_summary, int32_t* completion_counter, void* stream)
+static int forward_ex_impl(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
+                           int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
+                           uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
+                           int32_t* status_summary, int32_t* completion_counter, void* stream, bool masked, uint32_t nmask)
 {
     if ((order || order_out) && B > 0 && H > 0 && W > 0 && needs_global_state(H, W)) return NASTAR_ERR_UNSUPPORTED;  // LDS-resident searches only
     bool done = false;
     int rc = forward_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out,
                           iters_out, status_out, workspace, workspace_bytes, flags, stream, packed_out, &done, order, order_out, status_summary,
-                          completion_counter);
+                          completion_counter, nullptr, masked, nmask);
     if (rc != NASTAR_OK || done || !packed_out) return rc;
     return nastar_pack_outputs(histories_out, paths_out, B, H, W, packed_out, stream);
 }
 
-int nastar_forward_batchloop_finish(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
-                                    double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
-                                    int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream)
+int nastar_forward_ex(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
+                      int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
+                      uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
+                      int32_t* status_summary, int32_t* completion_counter, void* stream)
+{
+    return forward_ex_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                           packed_out, workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, stream, false,
+                           NASTAR_NEIGHBORS_MOORE8);
+}
+
+int nastar_forward_ex_masked(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
+                             int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
+                             uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
+                             int32_t* status_summary, int32_t* completion_counter, unsigned neighbor_mask, void* stream)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    return forward_ex_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                           packed_out, workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, stream, true,
+                           neighbor_mask);
+}
+
+static int batchloop_finish_impl(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
+                                 double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
+                                 int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream, bool masked,
+                                 uint32_t nmask)
 {
     if (!cost || !start || !goal || !passable || !histories_out || !paths_out || !iters_out || !status_out || !workspace) return NASTAR_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || max_iters <= 0) return NASTAR_ERR_BAD_SHAPE;
@@ -835,7 +738,7 @@ int nastar_forward_batchloop_finish(const float* cost, const float* start, const
     // 1. PROBE: the marked maps in lock-step mode over the whole budget; which steps select the goal?  (no outputs)
     la.bitmap = bitmap;
     int rc = forward_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, nullptr, iters_out, status_out, workspace,
-                          workspace_bytes, NASTAR_FLAG_LOCKSTEP, stream, nullptr, &done, nullptr, nullptr, nullptr, nullptr, &la);
+                          workspace_bytes, NASTAR_FLAG_LOCKSTEP, stream, nullptr, &done, nullptr, nullptr, nullptr, nullptr, &la, masked, nmask);
     if (rc) return rc;
     // 2. the first step at which EVERY map of the batch selects its goal
     const int words = la.bitmap_words;
@@ -848,7 +751,25 @@ int nastar_forward_batchloop_finish(const float* cost, const float* start, const
     la.bitmap = nullptr;
     la.t_end = tcell;
     return forward_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out, workspace,
-                        workspace_bytes, NASTAR_FLAG_LOCKSTEP, stream, nullptr, &done, nullptr, nullptr, nullptr, nullptr, &la);
+                        workspace_bytes, NASTAR_FLAG_LOCKSTEP, stream, nullptr, &done, nullptr, nullptr, nullptr, nullptr, &la, masked, nmask);
+}
+
+int nastar_forward_batchloop_finish(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
+                                    double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
+                                    int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return batchloop_finish_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out,
+                                 status_out, workspace, workspace_bytes, stream, false, NASTAR_NEIGHBORS_MOORE8);
+}
+
+int nastar_forward_batchloop_finish_masked(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
+                                           double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
+                                           int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes,
+                                           unsigned neighbor_mask, void* stream)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    return batchloop_finish_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out,
+                                 status_out, workspace, workspace_bytes, stream, true, neighbor_mask);
 }
 
 int nastar_completion_supported(int H, int W)
@@ -942,7 +863,7 @@ size_t nastar_backward_workspace_bytes(int B, int H, int W, int max_iters)
 static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* start, const float* goal, const float* passable,
                                 const int32_t* sel_log, int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters,
                                 const int32_t* t_batch_dev, float* grad_cost_out, void* workspace, size_t workspace_bytes, void* stream,
-                                int flags = 0)
+                                int flags = 0, bool masked = false, uint32_t nmask = NASTAR_NEIGHBORS_MOORE8)
 {
     if (!cost || !start || !goal || !passable || !sel_log || !iters || !grad_cost_out || !workspace) return NASTAR_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || max_iters <= 0) return NASTAR_ERR_BAD_SHAPE;
@@ -978,7 +899,7 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
     if ((flags & ~(kKnownFlags)) != 0) return NASTAR_ERR_UNSUPPORTED;
     const bool wide = bwdr_wide(a.d.HW, max_iters);  // (history stamps are 16-bit otherwise)
     // (the hand-scheduled loop closes every selected cell: a lock-step log, whose goal selections leave the goal open, takes the general loop)
-    if ((flags & (NASTAR_FLAG_NO_ASM | NASTAR_FLAG_LOCKSTEP)) == 0 && fast && H == W && (W == 32 || W == 16) && aligned16(cost) && aligned16(start) &&
+    if (!masked && (flags & (NASTAR_FLAG_NO_ASM | NASTAR_FLAG_LOCKSTEP)) == 0 && fast && H == W && (W == 32 || W == 16) && aligned16(cost) && aligned16(start) &&
         aligned16(goal) && aligned16(passable) && aligned16(grad_cost_out) && bwdr_asm_lds_bytes(a.d.HW, max_steps) <= kMaxLdsBytes) {
         // hand-scheduled replay loop (nastar_backward_replay_asm.hip.h): the reference's training sizes
         const size_t lds = bwdr_asm_lds_bytes(a.d.HW, max_steps);
@@ -989,6 +910,12 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
         // history in LDS as long as at least 2 maps (or what the state alone allows) stay resident per CU
         const size_t st = bwdr_state_bytes(a.d.HWp), with_hist = st + (size_t)hlen * 16;
         const bool hist_lds = with_hist <= kMaxLdsBytes && (kMaxLdsBytes / with_hist >= 2 || kMaxLdsBytes / st < 2);
+        if (masked) {  // (nastar_backward_replay_ordered_masked: the open sets of a neighbor_filter's search)
+            if (hist_lds) return fast ? launch(nastar_backward_replay_masked_kernel<false, true, true>, B, with_hist, s, a, rcp, nmask)
+                                      : launch(nastar_backward_replay_masked_kernel<false, true, false>, B, with_hist, s, a, rcp, nmask);
+            return fast ? launch(nastar_backward_replay_masked_kernel<false, false, true>, B, st, s, a, rcp, nmask)
+                        : launch(nastar_backward_replay_masked_kernel<false, false, false>, B, st, s, a, rcp, nmask);
+        }
         if (hist_lds) return fast ? launch(nastar_backward_replay_kernel<false, true, true>, B, with_hist, s, a, rcp)
                                   : launch(nastar_backward_replay_kernel<false, true, false>, B, with_hist, s, a, rcp);
         return fast ? launch(nastar_backward_replay_kernel<false, false, true>, B, st, s, a, rcp)
@@ -1007,7 +934,12 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
     if (wide) hipLaunchKernelGGL(nastar_bwdr_fill_kernel<true>, grid2, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(nastar_bwdr_fill_kernel<false>, grid2, dim3(256), 0, s, a);
     int rc2;
-    if (wide) rc2 = fast ? launch(nastar_backward_replay_kernel<true, false, true, true>, B, 64, s, a, rcp)
+    if (masked) {
+        if (wide) rc2 = fast ? launch(nastar_backward_replay_masked_kernel<true, false, true, true>, B, 64, s, a, rcp, nmask)
+                             : launch(nastar_backward_replay_masked_kernel<true, false, false, true>, B, 64, s, a, rcp, nmask);
+        else rc2 = fast ? launch(nastar_backward_replay_masked_kernel<true, false, true>, B, 64, s, a, rcp, nmask)
+                        : launch(nastar_backward_replay_masked_kernel<true, false, false>, B, 64, s, a, rcp, nmask);
+    } else if (wide) rc2 = fast ? launch(nastar_backward_replay_kernel<true, false, true, true>, B, 64, s, a, rcp)
                          : launch(nastar_backward_replay_kernel<true, false, false, true>, B, 64, s, a, rcp);
     else rc2 = fast ? launch(nastar_backward_replay_kernel<true, false, true>, B, 64, s, a, rcp)
                     : launch(nastar_backward_replay_kernel<true, false, false>, B, 64, s, a, rcp);
@@ -1054,10 +986,11 @@ int nastar_backward_l1_replay(const float* histories, const float* opt_trajs, co
                                 grad_cost_out, workspace, workspace_bytes, stream);
 }
 
-int nastar_backward_replay_ordered(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
-                                   const float* cost, const float* start, const float* goal, const float* passable, const int32_t* sel_log,
-                                   int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters, const int32_t* t_batch_dev,
-                                   float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, void* stream)
+static int backward_replay_ordered_impl(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
+                                        const float* cost, const float* start, const float* goal, const float* passable, const int32_t* sel_log,
+                                        int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters, const int32_t* t_batch_dev,
+                                        float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, void* stream,
+                                        bool masked, uint32_t nmask)
 {
     if (!grad_histories && (!histories || !opt_trajs)) return NASTAR_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0) return NASTAR_ERR_BAD_SHAPE;
@@ -1076,7 +1009,29 @@ int nastar_backward_replay_ordered(const float* grad_histories, const float* his
         if (rc) return rc;
     }
     return backward_replay_impl(a, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_iters, iters, t_batch_dev,
-                                grad_cost_out, workspace, workspace_bytes, stream, flags);
+                                grad_cost_out, workspace, workspace_bytes, stream, flags, masked, nmask);
+}
+
+int nastar_backward_replay_ordered(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
+                                   const float* cost, const float* start, const float* goal, const float* passable, const int32_t* sel_log,
+                                   int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters, const int32_t* t_batch_dev,
+                                   float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, void* stream)
+{
+    return backward_replay_ordered_impl(grad_histories, histories, opt_trajs, grad_loss_dev, cost, start, goal, passable, sel_log, B, H, W, g_ratio,
+                                        max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order, stream, false,
+                                        NASTAR_NEIGHBORS_MOORE8);
+}
+
+int nastar_backward_replay_ordered_masked(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
+                                          const float* cost, const float* start, const float* goal, const float* passable, const int32_t* sel_log,
+                                          int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters, const int32_t* t_batch_dev,
+                                          float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order,
+                                          unsigned neighbor_mask, void* stream)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    return backward_replay_ordered_impl(grad_histories, histories, opt_trajs, grad_loss_dev, cost, start, goal, passable, sel_log, B, H, W, g_ratio,
+                                        max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order, stream, true,
+                                        neighbor_mask);
 }
 
 int nastar_pack_outputs(const float* histories, const int64_t* paths, int B, int H, int W, uint8_t* packed_out, void* stream)

@@ -199,4 +199,13 @@ __device__ __forceinline__ void neighbour_delta(int j, int& dr, int& dc)
     dc = (k - 3 * q) - 1;
 }
 
+// DifferentiableAstar.neighbor_filter (:140-143, used by both expand() calls :228, :234) as a 9-bit mask: bit r*3+c <=> filter cell (r, c)
+// is 1 (include/nastar.h: NASTAR_NEIGHBORS_*).  expand() is conv2d, a CROSS-correlation: filter cell (a, b) opens the neighbour at offset
+// (1-a, 1-b), so lane j (offset cell k = j + (j >= 4) of neighbour_delta) is gated by filter cell 8 - k.  Wave-uniform mask, per-lane result.
+__device__ __forceinline__ bool neighbour_enabled(int lane, uint32_t nmask)
+{
+    const int k = lane + (lane >= 4);
+    return (lane < 8) & (((nmask >> ((uint32_t)(8 - k) & 31u)) & 1u) != 0u);
+}
+
 }  // namespace nastar

@@ -1,0 +1,164 @@
+// nastar_forward_compact_body.inc -- the body of nastar_forward_compact_kernel and nastar_forward_compact_masked_kernel (nastar_capi.hip),
+// included INSIDE each kernel: the kernel without a mask keeps, token for token, the body it had before the masked one existed, so its
+// instruction stream is unchanged (a shared __device__ function changes how the optimiser sees the body and with it the register allocation).
+// In scope: the kernel's template parameters, `a`, `rcp_sqrtW`, and `constexpr bool kMasked` / `nmask` (the neighbor_filter mask, an SGPR).
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int b = placed_map(a.order, a.order_bad, a.B);
+    if ((unsigned)b >= (unsigned)a.B) return;  // not a permutation (and not checked: NASTAR_FLAG_CHECK_ORDER): never read or write outside the batch
+    const bool lockstep = !kAsm && (a.flags & NASTAR_FLAG_LOCKSTEP);  // (forward_impl picks a compiled instantiation for it)
+    if (lockstep && a.marks != nullptr && a.marks[b] == 0) return;    // not in the batch-coupled class: the early-exit launch's outputs stand
+    const int lane = threadIdx.x;
+    CompactDims d = a.d;
+    if constexpr (LOGH > 0 && LOGW > 0) {
+        d.H = 1 << LOGH;
+        d.W = 1 << LOGW;
+        d.HW = 1 << (LOGH + LOGW);
+        d.nchunks = d.HW >> CCL;
+        d.HWp = d.HW;
+        d.CPL = (d.nchunks + 63) / 64;
+        d.NCp = d.CPL * 64;
+        d.magicW = (uint32_t)((1ull << 32) >> LOGW) + 1u;
+    }
+    const CompactLds l = carve_compact_lds(smem, d);
+    const size_t off = (size_t)b * (size_t)d.HW;
+
+    int start_idx, goal_idx;
+    constexpr int kLoadIter = (kVec4 && LOGH > 0 && LOGW > 0 && LOGH + LOGW >= 8) ? (1 << (LOGH + LOGW - 8)) : 0;
+    bool any_signed = true;
+    // round-3 instruction stream (raw-bit keys): every cost >= +0 and 0 <= g_ratio <= 1 so that every priority is >= +0
+    compact_load_map<kVec4, kLoadIter>(d, l, a.cost + off, a.start + off, a.goal + off, a.passable + off, lane, start_idx, goal_idx,
+                                       kAsm ? &any_signed : nullptr);
+#ifdef NASTAR_DEV
+    const bool raw = kAsm && !any_signed && !(a.flags & NASTAR_FLAG_ASM_V2) && d.gr >= 0.f && d.omg >= 0.f;
+#else
+    const bool raw = kAsm && !any_signed && d.gr >= 0.f && d.omg >= 0.f;
+#endif
+    const int gi = goal_idx < 0 ? 0 : goal_idx;
+    const int goal_r = (int)div_magic((uint32_t)gi, d.magicW);
+    const int goal_c = gi - goal_r * d.W;
+
+    const CompactLane lc = make_compact_lane<kMasked>(d, lane, nmask);  // (kMasked: lanes 0-7 gated by the mask -- the goal-expansion test of the COUPLED note reads them too)
+    int status = NASTAR_OK;
+    int iters = 0;
+    bool solved = false, coupled = false;
+    bool goal_hit = false;
+    const bool probe = lockstep && a.bitmap != nullptr;
+    const int budget = (lockstep && a.t_end != nullptr) ? __builtin_amdgcn_readfirstlane(*a.t_end + 1) : a.max_iters;
+    uint32_t bits = 0u;  // probe: goal selections of the current 32 steps
+    uint32_t* const bm = probe ? a.bitmap + (size_t)b * (size_t)a.bitmap_words : nullptr;
+    if (start_idx < 0 || goal_idx < 0) {
+        status = NASTAR_ERR_UNSOLVABLE;  // not a one-hot start/goal map
+    } else {
+        // round-4 stream (nastar_search_asm4.hip.h) wherever raw-bit keys apply (costs >= +0, 0 <= g_ratio <= 1: every priority is >= +0); a map with a
+        // negative / NaN cost takes the round-2 stream with its order-preserving key transform (nastar_search_asm.hip.h).  The development build
+        // (make dev) can also select the round-3 stream and switch the 64x64 dive off: csrc/nastar_dev_flags.h, stream-equality tests.
+        // half: g_ratio == 0.5 -- the two products of f = g_ratio g + (1 - g_ratio) h are exact and drop out of the key
+#ifdef NASTAR_DEV
+        const bool asm4 = raw && !(a.flags & NASTAR_FLAG_ASM_V3);
+        const bool no_dive = (a.flags & NASTAR_FLAG_NO_DIVE) != 0;
+#else
+        const bool asm4 = raw;
+#endif
+        const bool half = asm4 && d.gr == 0.5f && d.omg == 0.5f;
+        compact_open_start<kFastDiv>(d, l, lane, start_idx, goal_r, goal_c, rcp_sqrtW, raw, half);
+        int s = 0;
+        if constexpr (kAsm) {
+            static_assert(LOGW > 0 && LOGW == LOGH && (CPL_T == 1 || CPL_T == 4) && kFastDiv, "asm loop: 16x16, 32x32, 64x64");
+            int* const log_row = kLog ? a.sel_log + (size_t)b * (size_t)a.max_iters : nullptr;
+            // searching wavefronts issue ahead of the ones still loading their map or already storing their result (the launch waits for the
+            // longest SEARCH): maze32 159.4 -> 157.7 us, rand32 75.6 -> 75.0 us per 4096 maps, same box, two runs each; 3-4 batches in flight unchanged at 57 M maps/s (profiles/r03/prio_*.json, prio_streams.txt)
+            __builtin_amdgcn_s_setprio(3);
+            constexpr bool kD = CPL_T == 4;  // only the 64x64 instantiation dives (nastar_search_asm4.hip.h)
+#ifdef NASTAR_DEV
+            if (asm4 && kD && no_dive) {
+                if (half) s = search_loop_asm4<LOGW, kLog, false, true, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
+                else s = search_loop_asm4<LOGW, kLog, false, false, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
+            } else if (raw && !asm4 && kD && no_dive) {
+                s = compact_search_loop_asm3<LOGW, kLog, false>(d, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
+            } else if (raw && !asm4) {
+                s = compact_search_loop_asm3<LOGW, kLog>(d, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
+            } else
+#endif
+            if (asm4) {
+                s = half ? search_loop_asm4<LOGW, kLog, kD, true, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row)
+                         : search_loop_asm4<LOGW, kLog, kD, false, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
+            } else {
+                s = compact_search_loop_asm<LOGW, kLog>(d, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
+            }
+            __builtin_amdgcn_s_setprio(0);
+        } else
+        while (iters < budget) {  // :203 for t in range(Tmax)
+            uint2 mine;
+            s = compact_select<CPL_T>(d, l, lane, mine);
+            if (s < 0 || (s == goal_idx && !lockstep)) break;  // single exit test: open list empty (:68 would divide by zero) or goal
+            if constexpr (kLog) {
+                if (lane == 0) a.sel_log[(size_t)b * (size_t)a.max_iters + iters] = s;
+            }
+            if (probe) {
+                if (s == goal_idx) bits |= 1u << (iters & 31);
+                if ((iters & 31) == 31) {
+                    if (lane == 0) bm[iters >> 5] = bits;
+                    bits = 0u;
+                }
+            }
+            ++iters;
+            // lock-step mode: the reference's loop to the letter -- a selected goal is expanded like any cell, stays open, and the map is stepped
+            // on (it may wander: NASTAR_SUMMARY_COUPLED) until the caller's step count is reached
+            goal_hit |= s == goal_idx;
+            compact_expand<LOGW, kFastDiv, CPL_T>(d, l, lc, lane, s, goal_r, goal_c, rcp_sqrtW, mine, s == goal_idx);
+        }
+        if (probe) {  // the words this map's search did not reach say "no goal selection"; nothing else is written
+            if (lane == 0) {
+                if (iters & 31) bm[iters >> 5] = bits;
+                for (int w = (iters + 31) >> 5; w < a.bitmap_words; ++w) bm[w] = 0u;
+            }
+            return;
+        }
+        if (lockstep && goal_hit && lane == 0) l.gc[goal_idx].x = NASTAR_NEG_INF;  // histories holds the goal (:222-223); nothing reads its g any more
+        if (kAsm ? (s != -2) : (iters < budget)) {
+            if (s < 0) {
+                status = NASTAR_ERR_UNSOLVABLE;
+            } else {  // :219-220,:251 reached the goal: every later step of the reference is a fixed point
+                if constexpr (kLog) {
+                    if (lane == 0) a.sel_log[(size_t)b * (size_t)a.max_iters + iters] = s;
+                }
+                ++iters;
+                solved = true;
+                if (a.summary != nullptr || a.marks_out != nullptr) {
+                    // Is this map now at a FIXED POINT of the reference's batch loop?  The reference keeps stepping a finished map until every
+                    // map of the batch selects its goal in the same step (:224 the goal stays open, :251); this kernel stops here.  The two
+                    // agree iff the goal's own expansion opens nothing that beats the goal: true for every g_ratio in [0.5, 1) with costs >= 0
+                    // (f(n) - f(goal) = (2 g_ratio - 1) c_goal + (1 - g_ratio)(h0(n) + c_n) > 0), not for g_ratio < 0.5 with an expensive goal
+                    // cell, g_ratio = 1 with a zero-cost one, or negative costs.  Detected here, reported as summary[NASTAR_SUMMARY_COUPLED].
+                    const int nr = goal_r + lc.dr, nc = goal_c + lc.dc;
+                    const bool inb = lc.is_nb & ((unsigned)nr < (unsigned)d.H) & ((unsigned)nc < (unsigned)d.W);
+                    const int n = inb ? s + lc.off : s;
+                    const float2 gg = l.gc[s], gn = l.gc[n];
+                    const float g2 = gg.x + gg.y;
+                    const uint32_t kn = compact_key<kFastDiv>(d, g2, d.omg * (heuristic0_fast(nr, nc, goal_r, goal_c) + gn.y), rcp_sqrtW);
+                    const uint32_t kg = compact_key<kFastDiv>(d, gg.x, d.omg * (heuristic0_fast(goal_r, goal_c, goal_r, goal_c) + gg.y), rcp_sqrtW);
+                    const bool beats = inb & (gn.x > g2) & ((kn < kg) | ((kn == kg) & (n < s)));
+                    coupled = __ballot(beats) != 0ull;
+                    if (coupled && a.summary != nullptr && lane == 0) a.summary[NASTAR_SUMMARY_COUPLED] = 1;
+                    wave_order();
+                }
+                if (lane == 0) l.gc[s].x = NASTAR_NEG_INF;  // :222-223 the goal joins the closed list
+            }
+        }
+    }
+    wave_sync();
+    // histories depend on the closed list only: their stores are issued first and drain under the serial backtrack
+    compact_store_hist<kVec4>(d, l, lane, a.hist + off);
+    if (probe) return;  // (a map without a one-hot start / goal: the early-exit launch reported it, it is never marked)
+    if (lane == 0) {
+        a.iters[b] = iters;
+        a.status[b] = status;
+        if (a.marks_out != nullptr) a.marks_out[b] = coupled ? 1 : 0;
+        if (status != NASTAR_OK && a.summary) a.summary[status] = 1;  // plain idempotent store: the word may be host-mapped (no atomics over PCIe)
+        if (a.order_out) note_completion(a.order_out, a.B, b);
+        // (the COUPLED note above is a summary cell like any other: it must be visible before this search counts itself -- ADVICE r5)
+        if (a.done_counter) note_done(a.done_counter, a.summary, a.B, status != NASTAR_OK || coupled);
+    }
+    if (goal_idx >= 0) compact_backtrack<(LOGW == LOGH ? LOGW : 0)>(d, l, lane, start_idx, goal_idx, solved ? d.HW : iters - 1);
+    compact_store_outputs<kVec4, false>(d, l, lane, a.hist + off, a.paths + off,
+                                        a.packed ? a.packed + (size_t)b * (size_t)(d.HW >> 2) : nullptr);

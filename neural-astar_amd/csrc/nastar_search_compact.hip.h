@@ -239,16 +239,18 @@ __device__ __forceinline__ int compact_select(const CompactDims& d, const Compac
 
 struct CompactLane {
     int dr, dc, off;
-    bool is_nb;   // lanes 0..7: Moore neighbour j of s*
+    bool is_nb;   // lanes 0..7: Moore neighbour j of s* (and, masked, opened by the neighbor_filter)
     bool is_chk;  // lanes 16..31: cell (lane - 16) of the chunk that holds s*
     uint32_t pcode;
 };
 
-__device__ __forceinline__ CompactLane make_compact_lane(const CompactDims& d, int lane)
+// kMasked: lanes 0..7 relax only the neighbours the neighbor_filter mask `nmask` opens (neighbour_enabled)
+template <bool kMasked = false>
+__device__ __forceinline__ CompactLane make_compact_lane(const CompactDims& d, int lane, uint32_t nmask = 0u)
 {
     CompactLane lc;
     neighbour_delta(lane & 7, lc.dr, lc.dc);
-    lc.is_nb = lane < 8;
+    lc.is_nb = kMasked ? neighbour_enabled(lane, nmask) : lane < 8;
     lc.is_chk = (lane & 48) == 16;
     lc.off = lc.dr * d.W + lc.dc;
     lc.pcode = P_PASS | (uint32_t)(lane & 7);

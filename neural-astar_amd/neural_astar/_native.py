@@ -42,8 +42,10 @@ EXPORTED_SYMBOLS = (
     "nastar_forward_packed",
     "nastar_forward_ordered",
     "nastar_forward_ex",
+    "nastar_forward_ex_masked",
     "nastar_batchloop_workspace_bytes",
     "nastar_forward_batchloop_finish",
+    "nastar_forward_batchloop_finish_masked",
     "nastar_completion_supported",
     "nastar_host_wait_nonzero",
     "nastar_placement_from_levels",
@@ -51,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "nastar_backward_workspace_bytes",
     "nastar_backward_replay",
     "nastar_backward_replay_ordered",
+    "nastar_backward_replay_ordered_masked",
     "nastar_backward_l1_replay",
     "nastar_l1_loss",
     "nastar_policy_rollout",
@@ -219,6 +222,14 @@ def load() -> ctypes.CDLL:
     lib.nastar_backward_replay.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, ci, vp]
     lib.nastar_backward_replay_ordered.restype = ci
     lib.nastar_backward_replay_ordered.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, ci, vp, vp]
+    # the masked entry points (DifferentiableAstar.neighbor_filter): one `unsigned neighbor_mask` in front of the stream
+    cu = ctypes.c_uint
+    lib.nastar_forward_ex_masked.restype = ci
+    lib.nastar_forward_ex_masked.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, cz, ci, vp, vp, vp, vp, cu, vp]
+    lib.nastar_forward_batchloop_finish_masked.restype = ci
+    lib.nastar_forward_batchloop_finish_masked.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, cz, cu, vp]
+    lib.nastar_backward_replay_ordered_masked.restype = ci
+    lib.nastar_backward_replay_ordered_masked.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, ci, vp, cu, vp]
     lib.nastar_backward_l1_replay.restype = ci
     lib.nastar_backward_l1_replay.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, vp]
     lib.nastar_l1_loss.restype = ci

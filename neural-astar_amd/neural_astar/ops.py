@@ -43,6 +43,9 @@ SUMMARY_WORDS = 16  # NASTAR_SUMMARY_WORDS
 SUMMARY_BAD_ORDER = 15  # NASTAR_SUMMARY_BAD_ORDER
 SUMMARY_COUPLED = 14  # NASTAR_SUMMARY_COUPLED: a NOTE (a finished map is not at a fixed point of the reference's batch loop), cells 1..13 are errors
 SUMMARY_ERRORS = slice(1, 14)
+# DifferentiableAstar.neighbor_filter as a 9-bit mask (include/nastar.h NASTAR_NEIGHBORS_*): bit r*3+c <=> filter cell (r, c) is 1
+NEIGHBORS_MOORE8 = 0x1EF
+NEIGHBORS_VON_NEUMANN = 0x0AA
 # development knob: flag bits OR-ed into every forward launch.  NASTAR_FLAG_UNIT_COST = 64 works with the product library; the A/B switches
 # of csrc/nastar_dev_flags.h (NO_ASM = 8, ASM_V2 = 16, NO_DIVE = 32, ASM_V3 = 128) need the development build: NASTAR_LIB=.../libnastar_hip_dev.so
 FORWARD_FLAGS = int(os.environ.get("NASTAR_FORWARD_FLAGS", "0"))
@@ -187,7 +190,7 @@ def in_lds(H: int, W: int) -> bool:
 
 
 def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, order, order_out, check_order, summary_ptr, dev,
-                   one_meta=False, stream_ptr=None, out_4d=False, counter_ptr=0, keep=None, exact=False):
+                   one_meta=False, stream_ptr=None, out_4d=False, counter_ptr=0, keep=None, exact=False, neighbor_mask=None):
     """allocate the five outputs and issue ONE nastar_forward_ex launch on torch's current stream (shared by the custom ops and the
     no-autograd fast path).  cost / start / goal / passable: contiguous fp32 tensors of B*H*W elements (any leading shape).
     ``keep``: a list that receives the launch's temporaries (its workspace) when the launch goes to ANOTHER stream than the one the
@@ -195,7 +198,9 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
     ``exact``: the reference's BATCH LOOP to the letter (include/nastar.h: nastar_forward_batchloop_finish) -- the launch marks the maps that
     are not at a fixed point of that loop when they reach their goal, and three more launches on the same stream re-run exactly those in
     lock-step mode up to the step at which every map of the batch selects its goal.  No host round trip; nothing happens when no map is
-    marked (always so for g_ratio in [0.5, 1) with costs >= 0)."""
+    marked (always so for g_ratio in [0.5, 1) with costs >= 0).
+    ``neighbor_mask``: None = the reference's default neighbourhood (Moore-8) on the fastest kernels; an int = the search neighbourhood of a
+    ``neighbor_filter`` (NEIGHBORS_*), searched by the masked entry points (nastar_forward_ex_masked: the compiled step loops, for every mask)."""
     shape = (B, 1, H, W) if out_4d else (B, H, W)
     hist = torch.empty(shape, dtype=torch.float32, device=dev)
     paths = torch.empty(shape, dtype=torch.int64, device=dev)
@@ -239,15 +244,21 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
     if exact:
         fin = args[:9] + (hist.data_ptr(), paths.data_ptr(), sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(),
                           workspace.data_ptr(), ws_bytes, sp)
+    fwd, finish = lib.nastar_forward_ex, lib.nastar_forward_batchloop_finish
+    if neighbor_mask is not None:  # the masked entry points: one `neighbor_mask` in front of the stream
+        fwd, finish = lib.nastar_forward_ex_masked, lib.nastar_forward_batchloop_finish_masked
+        args = args[:-1] + (int(neighbor_mask), sp)
+        if fin is not None:
+            fin = fin[:-1] + (int(neighbor_mask), sp)
     if dev.index is None or torch.cuda.current_device() == dev.index:
-        rc = lib.nastar_forward_ex(*args)
+        rc = fwd(*args)
         if not rc and fin is not None:
-            rc = lib.nastar_forward_batchloop_finish(*fin)
+            rc = finish(*fin)
     else:
         with torch.cuda.device(dev):
-            rc = lib.nastar_forward_ex(*args)
+            rc = fwd(*args)
             if not rc and fin is not None:
-                rc = lib.nastar_forward_batchloop_finish(*fin)
+                rc = finish(*fin)
     if rc:
         _native.check(rc, "nastar_forward_ex")
     return hist, paths, iters, status, sel_log
@@ -255,20 +266,27 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
 
 @torch.library.custom_op("nastar::astar_forward", mutates_args=())
 def astar_forward(cost: torch.Tensor, start: torch.Tensor, goal: torch.Tensor, passable: torch.Tensor,
-                  g_ratio: float, max_iters: int, want_log: bool, flags: int = 0, summary_ptr: int = 0, exact: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                  g_ratio: float, max_iters: int, want_log: bool, flags: int = 0, summary_ptr: int = 0, exact: bool = False,
+                  neighbor_mask: int = NEIGHBORS_MOORE8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """Returns (histories [B,H,W] f32, paths [B,H,W] i64, iters [B] i32, status [B] i32, sel_log [B,T] i32 or [0]).
     ``flags``: NASTAR_FLAG_* of include/nastar.h (e.g. ``FLAG_UNIT_COST`` when cost and passable are ONE binary tensor);
-    ``summary_ptr``: address of a ``StatusBoard`` row (0 = none) that receives the launch's status summary; ``exact``: see ``_launch_search``."""
+    ``summary_ptr``: address of a ``StatusBoard`` row (0 = none) that receives the launch's status summary; ``exact``: see ``_launch_search``;
+    ``neighbor_mask``: the search neighbourhood (NEIGHBORS_*, DifferentiableAstar.neighbor_filter); the backward replays with the same one."""
     _require_device(cost, start, goal, passable)
     lib = _native.load()
     cost, start, goal, passable = (x.contiguous() for x in (cost, start, goal, passable))
     B, H, W = cost.shape
     return _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, None, None, False, summary_ptr, cost.device,
-                          exact=exact)
+                          exact=exact, neighbor_mask=_mask_arg(neighbor_mask))
+
+
+def _mask_arg(neighbor_mask: int) -> Optional[int]:
+    """the custom ops' `neighbor_mask` -> ``_launch_search``'s: Moore-8 keeps the entry points (and kernels) without a mask"""
+    return None if int(neighbor_mask) == NEIGHBORS_MOORE8 else int(neighbor_mask)
 
 
 @astar_forward.register_fake
-def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags=0, summary_ptr=0, exact=False):
+def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags=0, summary_ptr=0, exact=False, neighbor_mask=NEIGHBORS_MOORE8):
     B, H, W = cost.shape
     return (cost.new_empty((B, H, W)), cost.new_empty((B, H, W), dtype=torch.int64),
             cost.new_empty((B,), dtype=torch.int32), cost.new_empty((B,), dtype=torch.int32),
@@ -278,7 +296,8 @@ def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags=0, summar
 @torch.library.custom_op("nastar::astar_forward_ordered", mutates_args=("order_out",))
 def astar_forward_ordered(cost: torch.Tensor, start: torch.Tensor, goal: torch.Tensor, passable: torch.Tensor, g_ratio: float,
                           max_iters: int, want_log: bool, flags: int, order: Optional[torch.Tensor],
-                          order_out: Optional[torch.Tensor], check_order: bool = True, summary_ptr: int = 0, exact: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                          order_out: Optional[torch.Tensor], check_order: bool = True, summary_ptr: int = 0, exact: bool = False,
+                          neighbor_mask: int = NEIGHBORS_MOORE8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """``astar_forward`` with a placement (include/nastar.h: nastar_forward_ex): workgroup i searches map ``order[i]`` (int32 [B], a
     permutation of 0..B-1, or None = identity).  Same five outputs as ``astar_forward``.  ``order_out`` (int32 [B + 1] from
     ``new_placement_buffer``, or None) receives in [:B] the maps in reverse order of search completion in this launch -- the ``order``
@@ -291,11 +310,12 @@ def astar_forward_ordered(cost: torch.Tensor, start: torch.Tensor, goal: torch.T
     cost, start, goal, passable = (x.contiguous() for x in (cost, start, goal, passable))
     B, H, W = cost.shape
     return _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, order, order_out, check_order,
-                          summary_ptr, cost.device, exact=exact)
+                          summary_ptr, cost.device, exact=exact, neighbor_mask=_mask_arg(neighbor_mask))
 
 
 @astar_forward_ordered.register_fake
-def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags, order, order_out, check_order=True, summary_ptr=0, exact=False):
+def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags, order, order_out, check_order=True, summary_ptr=0, exact=False,
+      neighbor_mask=NEIGHBORS_MOORE8):
     B, H, W = cost.shape
     return (cost.new_empty((B, H, W)), cost.new_empty((B, H, W), dtype=torch.int64),
             cost.new_empty((B,), dtype=torch.int32), cost.new_empty((B,), dtype=torch.int32),
@@ -305,7 +325,8 @@ def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags, order, o
 def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, g_ratio: float,
                   max_iters: int, want_log: bool = False, flags: int = 0, order: Optional[torch.Tensor] = None,
                   order_out: Optional[torch.Tensor] = None, check_order: bool = True, summary_ptr: int = 0, stream_ptr: Optional[int] = None,
-                  out_4d: bool = False, counter_ptr: int = 0, keep: Optional[list] = None, exact: bool = False, lib=None):
+                  out_4d: bool = False, counter_ptr: int = 0, keep: Optional[list] = None, exact: bool = False, lib=None,
+                  neighbor_mask: Optional[int] = None):
     """The search launch WITHOUT the torch.library dispatch: what ``DifferentiableAstar.forward`` calls when no gradient can flow
     (``torch.no_grad()`` / inputs that do not require one) and nothing is being traced -- the custom-op machinery costs more host time
     than the launch itself at 4096 maps.  Takes the reference's [B,1,H,W] tensors (or [B,H,W]) as they are; same five outputs
@@ -315,7 +336,7 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
     allocated on the CURRENT stream: the caller orders the two streams before anyone reads or frees them, passes contiguous inputs --
     a copy made here would be made on the current stream, after the caller ordered the streams -- and holds ``keep``, the list that
     receives the launch's workspace, until that stream is done).  ``exact``: the reference's batch loop to the letter (``_launch_search``).
-    ``lib``: another build of the C ABI (``_native.load_dev()``: stream-equality tests)."""
+    ``lib``: another build of the C ABI (``_native.load_dev()``: stream-equality tests).  ``neighbor_mask``: see ``_launch_search``."""
     if stream_ptr is not None and not (cost_maps.is_contiguous() and start_maps.is_contiguous() and goal_maps.is_contiguous()
                                        and obstacles_maps.is_contiguous()):
         raise ValueError("search_nograd(stream_ptr=...): the maps must be contiguous (make the copies before ordering the streams)")
@@ -341,7 +362,8 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
     if not goal_maps.is_contiguous():
         goal_maps = goal_maps.contiguous()
     return _launch_search(lib if lib is not None else _native.load(), cost_maps, start_maps, goal_maps, obstacles_maps, B, H, W, g_ratio, max_iters,
-                          want_log, flags, order, order_out, check_order, summary_ptr, cost_maps.device, True, stream_ptr, out_4d, counter_ptr, keep, exact)
+                          want_log, flags, order, order_out, check_order, summary_ptr, cost_maps.device, True, stream_ptr, out_4d, counter_ptr, keep, exact,
+                          neighbor_mask)
 
 
 def order_from_levels(levels: torch.Tensor) -> torch.Tensor:
@@ -438,11 +460,13 @@ def placement_from_iters(iters: torch.Tensor) -> torch.Tensor:
 @torch.library.custom_op("nastar::astar_backward_replay", mutates_args=())
 def astar_backward_replay(grad_hist: torch.Tensor, cost: torch.Tensor, start: torch.Tensor, goal: torch.Tensor,
                           passable: torch.Tensor, sel_log: torch.Tensor, g_ratio: float, max_iters: int, iters: torch.Tensor,
-                          t_batch: Optional[torch.Tensor], order: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+                          t_batch: Optional[torch.Tensor], order: Optional[torch.Tensor] = None, flags: int = 0,
+                          neighbor_mask: int = NEIGHBORS_MOORE8) -> torch.Tensor:
     """dL/dcost by replaying the forward's selection log (csrc/nastar_backward_replay.hip.h): any map size the forward takes
     (1,179,648 cells; 32-bit history stamps above 65519), O(9) accounting work per step.  ``order`` (int32 permutation of 0..B-1): workgroup i replays map order[i] --
     the forward's own completion order (``astar_forward_ordered``'s ``order_out``) puts the longest replays first.  ``flags``:
-    ``FLAG_LOCKSTEP`` for the log of an ``exact`` forward (goal selections before the last entry: the general replay loop)."""
+    ``FLAG_LOCKSTEP`` for the log of an ``exact`` forward (goal selections before the last entry: the general replay loop).
+    ``neighbor_mask``: the neighbourhood the forward searched (NEIGHBORS_*; anything but Moore-8: nastar_backward_replay_ordered_masked)."""
     _require_device(grad_hist, cost, start, goal, passable)
     lib = _native.load()
     grad_hist, cost, start, goal, passable, sel_log = (x.contiguous() for x in (grad_hist, cost, start, goal, passable, sel_log))
@@ -454,7 +478,14 @@ def astar_backward_replay(grad_hist: torch.Tensor, cost: torch.Tensor, start: to
         raise RuntimeError(f"nastar_backward_replay: unsupported map size {H}x{W}")
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        if order is None:
+        if int(neighbor_mask) != NEIGHBORS_MOORE8:
+            rc = lib.nastar_backward_replay_ordered_masked(grad_hist.data_ptr(), None, None, None, cost.data_ptr(), start.data_ptr(), goal.data_ptr(),
+                                                           passable.data_ptr(), sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters),
+                                                           iters.data_ptr(), t_batch.data_ptr() if t_batch is not None else None, grad_cost.data_ptr(),
+                                                           ws.data_ptr(), ws_bytes, int(flags),
+                                                           _order_ptr(order, B, dev, True) if order is not None else None, int(neighbor_mask),
+                                                           _stream_ptr(dev))
+        elif order is None:
             rc = lib.nastar_backward_replay(grad_hist.data_ptr(), cost.data_ptr(), start.data_ptr(), goal.data_ptr(),
                                             passable.data_ptr(), sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters),
                                             iters.data_ptr(), t_batch.data_ptr() if t_batch is not None else None,
@@ -469,7 +500,7 @@ def astar_backward_replay(grad_hist: torch.Tensor, cost: torch.Tensor, start: to
 
 
 @astar_backward_replay.register_fake
-def _(grad_hist, cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_batch, order=None, flags=0):
+def _(grad_hist, cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_batch, order=None, flags=0, neighbor_mask=NEIGHBORS_MOORE8):
     return torch.empty_like(cost)
 
 
@@ -480,13 +511,15 @@ def _setup_context(ctx, inputs, output):
     ctx.g_ratio = g_ratio
     ctx.max_iters = max_iters
     ctx.lockstep = bool(inputs[9]) if len(inputs) > 9 else False  # `exact`: the log may hold goal selections before its last entry
+    ctx.neighbor_mask = int(inputs[10]) if len(inputs) > 10 else NEIGHBORS_MOORE8  # the replay rebuilds the open sets of THIS neighbourhood
+    ctx.n_inputs = len(inputs)
     ctx.set_materialize_grads(False)  # no zero-filled gradient tensors for paths / iters / status / sel_log (4 fill launches per step)
 
 
 def _backward(ctx, g_hist, g_paths, g_iters, g_status, g_log):
     cost, start, goal, passable, iters, sel_log = ctx.saved_tensors
     if g_hist is None:
-        return (None,) * 10
+        return (None,) * ctx.n_inputs
     # t_batch: the reference's batch-wide loop index (differentiable_astar.py:251-255).  BatchCoupling lets the
     # sharded planner substitute the maximum over ALL ranks so gradients match a single-device run.
     t_batch = BatchCoupling.t_batch(iters)
@@ -494,8 +527,9 @@ def _backward(ctx, g_hist, g_paths, g_iters, g_status, g_log):
         raise RuntimeError("backward needs the forward's selection log: call astar_forward(..., want_log=True) "
                            "(DifferentiableAstar.forward does whenever cost_maps.requires_grad)")
     grad_cost = torch.ops.nastar.astar_backward_replay(g_hist.contiguous(), cost, start, goal, passable, sel_log,
-                                                       ctx.g_ratio, ctx.max_iters, iters, t_batch, None, FLAG_LOCKSTEP if ctx.lockstep else 0)
-    return (grad_cost,) + (None,) * 9
+                                                       ctx.g_ratio, ctx.max_iters, iters, t_batch, None, FLAG_LOCKSTEP if ctx.lockstep else 0,
+                                                       ctx.neighbor_mask)
+    return (grad_cost,) + (None,) * (ctx.n_inputs - 1)
 
 
 astar_forward.register_autograd(_backward, setup_context=_setup_context)

@@ -445,6 +445,9 @@ class InFlightPlanner:
         dev = cost.device
         self._setup(dev)
         astar = self.planner.astar
+        if astar.neighbor_mask() is not None:
+            raise NotImplementedError("InFlightPlanner searches with the default (Moore-8) neighbourhood only: planner.astar.neighbor_filter is "
+                                      f"{astar.neighbor_filter.detach().reshape(-1).tolist()} -- call the planner itself, which honours it")
         k = self._k % self.n_streams
         st = self._streams[k]
         same = passable is cost

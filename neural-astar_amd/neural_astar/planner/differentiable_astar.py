@@ -212,8 +212,11 @@ class DifferentiableAstar(nn.Module):
         super().__init__()
         nf = torch.ones(1, 1, 3, 3)
         nf[0, 0, 1, 1] = 0
-        # never read by the kernel (the Moore-8 stencil is hard-wired) but part of every reference checkpoint
+        # the search neighbourhood (reference :140-143, both expand() calls of every step convolve with it): forward() hands it to the kernels as
+        # a 9-bit mask (neighbor_mask()); the default filter keeps the Moore-8 kernels
         self.neighbor_filter = nn.Parameter(nf, requires_grad=False)
+        self._nf_key = self._filter_key()
+        self._nf_mask: Optional[int] = None  # None = Moore-8
         # the reference keeps its heuristic as an INSTANCE attribute (:143), i.e. as something a user may replace; the kernels hard-wire that
         # function (Chebyshev + 0.001 Euclidean): forward() refuses, loudly, to run with anything else in this attribute
         self.get_heuristic = get_heuristic
@@ -234,6 +237,44 @@ class DifferentiableAstar(nn.Module):
         # placement memory of the batch the NEXT forward() searches (see Placement); consumed by that call
         self.placement: Optional[Placement] = None
 
+    # ---- the neighbourhood: neighbor_filter -> the kernels' 9-bit mask ----------------------------------------------------------------------
+    def _filter_key(self):
+        f = self.neighbor_filter
+        return (id(f), f.data_ptr(), f.device, f._version) if f is not None else None
+
+    def neighbor_mask(self) -> Optional[int]:
+        """The search neighbourhood of ``neighbor_filter`` as the kernels take it (include/nastar.h NASTAR_NEIGHBORS_*): bit r*3+c <=> filter cell
+        (r, c) is 1; None for the default Moore-8 filter (the unmasked kernels).  expand() is conv2d, a cross-correlation: filter cell (a, b) opens
+        the neighbour at offset (1-a, 1-b) of the selected cell.  Supported: a [1,1,3,3] filter with weights in {0, 1} and a zero centre (any other
+        weight blends g-values and parent indices in the reference -- not a search); anything else raises NotImplementedError.
+
+        Reading a filter that lives on the device is a host synchronisation, so the mask is cached, keyed on the tensor's identity, data_ptr,
+        device and version counter, and re-read only when one of them changes: load_state_dict, copy_ / fill_ under no_grad, a new Parameter and
+        .to() / .cuda() (which keep the values: no read at all) are all seen.  NOT seen: in-place edits through ``.data`` (torch does not
+        version them) -- assign through ``with torch.no_grad(): neighbor_filter.copy_(...)`` instead.  Inside a hipGraph capture or a
+        torch.compile trace the cached mask is used as it is, and a filter that changed since it was cached (or was never read) raises.
+        What was captured or traced keeps the mask it was captured / traced with: a graph replayed, or a compiled function called again,
+        after the filter changed still searches the old neighbourhood (capture or compile again after changing the filter)."""
+        key = self._filter_key()
+        if key == self._nf_key:
+            return self._nf_mask
+        f = self.neighbor_filter
+        if torch.compiler.is_compiling() or (f is not None and f.is_cuda and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("DifferentiableAstar.neighbor_filter changed since its mask was last read (or was never read), and reading "
+                               "it now -- a host synchronisation -- is impossible inside a hipGraph capture / torch.compile trace: call "
+                               "forward() once outside the capture / trace after changing the filter")
+        mask = _filter_mask(f)  # raises for an unsupported filter (nothing cached: every call raises)
+        self._nf_key, self._nf_mask = key, (None if mask == ops.NEIGHBORS_MOORE8 else mask)
+        return self._nf_mask
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to() / .cuda() / .half() move or cast the filter without changing its 0 / 1 values: carry a valid cached mask over (no device read)
+        valid = self._nf_key is not None and self._nf_key == self._filter_key()
+        out = super()._apply(fn, *args, **kwargs)
+        if valid:
+            self._nf_key = self._filter_key()
+        return out
+
     # run-time bookkeeping (device events, pinned flags, the latest status tensors) is not module state: copy.deepcopy(planner)
     # (EMA / best-model snapshots), pickling and torch.save(planner) must work after any forward()
     def __getstate__(self):
@@ -249,6 +290,8 @@ class DifferentiableAstar(nn.Module):
         self.__dict__.setdefault("_pending", [])
         self.__dict__.setdefault("_calls", 0)
         self.__dict__.setdefault("placement", None)
+        self.__dict__.setdefault("_nf_mask", None)
+        self._nf_key = None  # (a new process / a copied tensor: read the filter again on first use)
 
     def raise_if_unsolvable(self, wait: bool = True) -> None:
         """Deliver the deferred verdicts: raise ``UnsolvableMapError`` if an earlier ``forward()`` call met an unsolvable map.
@@ -330,15 +373,17 @@ class DifferentiableAstar(nn.Module):
             self._pending.pop(0).raise_if_unsolvable()
         return False
 
-    def exact_search(self, cost_maps, start_maps, goal_maps, passable, max_iters, want_log=False, out_4d=True):
+    def exact_search(self, cost_maps, start_maps, goal_maps, passable, max_iters, want_log=False, out_4d=True, neighbor_mask=-1):
         """The reference's batch loop to the letter for a batch in which a finished map is NOT at a fixed point (NASTAR_SUMMARY_COUPLED;
         DESIGN.md section 2.3): every map of the class is stepped, goal selections included, until the first step at which ALL maps of the
         batch select their goal (reference :219-225, :251) or the budget ends -- the search launch with marks + nastar_forward_batchloop_finish
-        (include/nastar.h), any map size, no host round trip.  -> (histories, paths, iters, status, sel_log)"""
+        (include/nastar.h), any map size, no host round trip.  -> (histories, paths, iters, status, sel_log).  ``neighbor_mask``: -1 = this
+        module's (``neighbor_mask()``)"""
+        nmask = self.neighbor_mask() if neighbor_mask == -1 else neighbor_mask
         return ops.search_nograd(cost_maps, start_maps, goal_maps, passable, self.g_ratio, max_iters, want_log, 0, None, None, False, 0, None, out_4d,
-                                 0, None, True)
+                                 0, None, True, neighbor_mask=nmask)
 
-    def _repair_in_place(self, inputs, outputs, max_iters, want_log):
+    def _repair_in_place(self, inputs, outputs, max_iters, want_log, neighbor_mask=None):
         """for a DEFERRED verdict: the launch it belongs to reported the note after its outputs had been handed out -- run the exact search now
         and overwrite those tensors (histories, paths, iters, status, sel_log) before the caller, who asked for the verdict first, reads them"""
         import weakref
@@ -356,7 +401,7 @@ class DifferentiableAstar(nn.Module):
                 raise RuntimeError("a batch searched with check_solvable='deferred' holds a map that is not at a fixed point of the reference's batch loop "
                                    "(negative costs), and its inputs were released before the verdict was collected: the outputs still alive are those of "
                                    "each map searched alone.  Keep the inputs until raise_if_unsolvable(), or use check_solvable=True (DESIGN.md section 2.3)")
-            new = self.exact_search(*src, max_iters, want_log, out_4d=False)
+            new = self.exact_search(*src, max_iters, want_log, out_4d=False, neighbor_mask=neighbor_mask)
             for old, fresh in zip(live, new):
                 if old is not None and fresh is not None and old.numel() == fresh.numel():
                     old.data.copy_(fresh.reshape(old.shape))
@@ -447,7 +492,7 @@ class DifferentiableAstar(nn.Module):
         if verdict & (1 << ops.SUMMARY_COUPLED) and B > 1:
             # a finished map of this batch is not at a fixed point of the reference's batch loop (negative costs): the batch again, exactly
             hist, paths, iters, status, _ = self.exact_search(cost_maps, start_maps, goal_maps, cost_maps if same else obstacles_maps,
-                                                              ops.max_iters_for(W, self.Tmax, self.training))
+                                                              ops.max_iters_for(W, self.Tmax, self.training), neighbor_mask=None)
             self.last_status, self.last_iters = status, iters
             self.last_packed = None  # (the slot holds the masks of the first launch)
         return AstarOutput(hist, paths, [])
@@ -462,7 +507,8 @@ class DifferentiableAstar(nn.Module):
             raise NotImplementedError("DifferentiableAstar.get_heuristic was replaced: the MI355X search kernels hard-wire the reference's heuristic "
                                       "(Chebyshev + 0.001 x Euclidean, differentiable_astar.py:26-52) and would silently ignore another one")
         self.last_packed = None
-        if (self.check_solvable is True and not store_intermediate_results and not self._pending and type(cost_maps) is torch.Tensor
+        nmask = self.neighbor_mask()  # None: the default (Moore-8) filter -- its kernels, its native host lane, its unit-cost layout
+        if (nmask is None and self.check_solvable is True and not store_intermediate_results and not self._pending and type(cost_maps) is torch.Tensor
                 and not (cost_maps.requires_grad and torch.is_grad_enabled())):
             out = self._forward_fast(cost_maps, start_maps, goal_maps, obstacles_maps)
             if out is not None:
@@ -484,7 +530,7 @@ class DifferentiableAstar(nn.Module):
         # the unit-cost layout pays with SEVERAL launches in flight (more maps resident per CU); one launch at a time is a serial chain whose
         # length does not depend on the layout (probe_boundary: 117 us unit vs 114 us general per placed 4096-map launch), so forward()
         # takes it only on request -- parallel.InFlightPlanner is where "auto" means "unit-cost first"
-        unit = same and not want_log and self.unit_cost is True
+        unit = same and not want_log and self.unit_cost is True and nmask is None
         in_lds = ops.in_lds(H, W)
         # a recurring batch starts its longest searches first (Placement), a fresh one by its loader's hint; maps whose state lives in HBM take no placement
         if self.placement is None and not hasattr(start_maps, "placement_order"):
@@ -492,6 +538,8 @@ class DifferentiableAstar(nn.Module):
             check_order = False
         else:
             order, order_out, check_order, pl = self.resolve_placement(B, start_maps, in_lds)
+            if nmask is not None and needs_grad:
+                order = order_out = None  # (a neighbor_filter under autograd: the plain differentiable op, no placement)
         dev = cost_maps.device
         compiling = torch.compiler.is_compiling()
         # (no status protocol while a hipGraph is captured or torch.compile traces: its host side would run once, at capture / trace time)
@@ -512,16 +560,18 @@ class DifferentiableAstar(nn.Module):
             if not traced:
                 # no gradient can flow and nothing is tracing: straight to the C ABI (no torch.library dispatch)
                 return ops.search_nograd(cost_maps, start_maps, goal_maps, passable_maps, self.g_ratio, max_iters, want_log, flags, order, order_out,
-                                         check_order, sptr_now, None, True, cptr_now, None, exact_now)
+                                         check_order, sptr_now, None, True, cptr_now, None, exact_now, neighbor_mask=nmask)
             cost, start, goal, passable = cost_maps[:, 0], start_maps[:, 0], goal_maps[:, 0], obstacles_maps[:, 0]
-            if needs_grad and in_lds and (order is not None or order_out is not None or B >= ops.PLACEMENT_MIN_BATCH):
+            mask_arg = ops.NEIGHBORS_MOORE8 if nmask is None else nmask
+            if needs_grad and in_lds and nmask is None and (order is not None or order_out is not None or B >= ops.PLACEMENT_MIN_BATCH):
                 # large batches under autograd: the replay backward starts longest-first, by the order THIS forward's searches finish in
                 o = ops.astar_forward_placed(cost, start, goal, passable, self.g_ratio, max_iters, 0, order, order_out, check_order, sptr_now, exact_now)
             elif order is None and order_out is None:
-                o = torch.ops.nastar.astar_forward(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, sptr_now, exact_now)
+                o = torch.ops.nastar.astar_forward(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, sptr_now, exact_now,
+                                                   mask_arg)
             else:
                 o = torch.ops.nastar.astar_forward_ordered(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, order, order_out,
-                                                           check_order, sptr_now, exact_now)
+                                                           check_order, sptr_now, exact_now, mask_arg)
             return o[0].unsqueeze(1), o[1].unsqueeze(1), o[2], o[3], o[4]
 
         try:
@@ -537,7 +587,8 @@ class DifferentiableAstar(nn.Module):
             if needs_grad:
                 repair = _refuse_late_repair
             else:  # (no graph holds these tensors: a late verdict that reports the note completes them in place)
-                repair = self._repair_in_place((cost_maps, start_maps, goal_maps, passable_maps), (hist, paths, iters, status, sel_log), max_iters, want_log)
+                repair = self._repair_in_place((cost_maps, start_maps, goal_maps, passable_maps), (hist, paths, iters, status, sel_log), max_iters, want_log,
+                                               nmask)
         coupled = self.note_status(status, iters, None, row, flagged=bool(cptr) and not traced, repair=repair)
         if coupled and not exact:
             # the same-call verdict says a finished map of this batch is not at a fixed point (negative costs): the batch again, exactly
@@ -549,6 +600,19 @@ class DifferentiableAstar(nn.Module):
         if store_intermediate_results:
             intermediate_results = _intermediate_results(hist[:, 0], paths[:, 0], goal_maps[:, 0], iters, sel_log)
         return AstarOutput(hist, paths, intermediate_results)
+
+
+def _filter_mask(f) -> int:
+    """neighbor_filter -> the 9-bit mask (bit r*3+c <=> cell (r, c) is 1); NotImplementedError, naming the values, for any other filter"""
+    if f is None or tuple(f.shape) != (1, 1, 3, 3):
+        raise NotImplementedError(f"DifferentiableAstar.neighbor_filter of shape {None if f is None else tuple(f.shape)}: the MI355X search kernels "
+                                  "take a [1, 1, 3, 3] filter (the reference's, differentiable_astar.py:140-143)")
+    vals = [float(v) for v in f.detach().reshape(-1).cpu().tolist()]
+    if any(v not in (0.0, 1.0) for v in vals) or vals[4] != 0.0:
+        raise NotImplementedError(f"DifferentiableAstar.neighbor_filter = {vals}: the MI355X search kernels take weights in {{0, 1}} with a zero "
+                                  "centre -- any other weight scales g2 and blends the open set and the parent indices in the reference "
+                                  "(differentiable_astar.py:228-249), which is not a search; it is refused rather than run as Moore-8")
+    return sum(1 << i for i, v in enumerate(vals) if v == 1.0)
 
 
 _BAD_ORDER_WARNED = False

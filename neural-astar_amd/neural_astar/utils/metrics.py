@@ -38,11 +38,12 @@ def plan_with_vanilla(planner: NeuralAstar, map_designs: torch.Tensor, start_map
     """Learned planner + VanillaAstar on the same problems in ONE search launch (eval-mode budgets, no gradients).
 
     Requires ``planner.g_ratio == g_ratio_vanilla`` (the reference's ``PlannerModule`` builds ``VanillaAstar()`` with the
-    default 0.5, training.py:46) because one launch has one ``g_ratio``; otherwise it falls back to two launches."""
+    default 0.5, training.py:46) because one launch has one ``g_ratio``; otherwise it falls back to two launches.  So does a planner whose
+    ``neighbor_filter`` is not the default: one launch has one neighbourhood, and the reference's ``VanillaAstar()`` searches Moore-8."""
     with torch.no_grad():
         cost = planner.encode(map_designs, start_maps, goal_maps)
         passable = map_designs if not planner.learn_obstacles else torch.ones_like(start_maps)
-        if float(planner.g_ratio) != float(g_ratio_vanilla) or planner.training:
+        if float(planner.g_ratio) != float(g_ratio_vanilla) or planner.training or planner.astar.neighbor_mask() is not None:
             va = VanillaAstar(g_ratio=g_ratio_vanilla).to(map_designs.device).eval()
             return planner.perform_astar(cost, start_maps, goal_maps, passable), va(map_designs, start_maps, goal_maps)
         B = map_designs.shape[0]

@@ -186,7 +186,9 @@ def fused_l1_step(planner: VanillaAstar, map_designs: torch.Tensor, start_maps: 
     # The fused node computes mean|histories - opt_trajs| for ONE trajectory per map.  The reference's L1Loss broadcasts
     # histories [B,1,H,W] against opt_trajs [B,S,H,W] when num_starts S > 1 (training.py:58), and use_differentiable_astar=False
     # selects another planner altogether: both go through the planner's own forward + nn.L1Loss, exactly like the reference.
-    if opt_trajs.shape[1] != 1 or opt_trajs.shape[-2:] != start_maps.shape[-2:] or not getattr(planner, "use_differentiable_astar", True):
+    # A neighbor_filter other than the default takes the same route (the fused node replays the Moore-8 neighbourhood).
+    if (opt_trajs.shape[1] != 1 or opt_trajs.shape[-2:] != start_maps.shape[-2:] or not getattr(planner, "use_differentiable_astar", True)
+            or planner.astar.neighbor_mask() is not None):
         outputs = planner(map_designs, start_maps, goal_maps)
         return nn.L1Loss()(outputs.histories, opt_trajs), outputs
     if hasattr(planner, "encode"):
