@@ -427,11 +427,18 @@ constexpr int kKnownFlags = NASTAR_FLAG_UNIT_COST | NASTAR_FLAG_CHECK_ORDER | NA
 constexpr int NASTAR_FLAG_NO_ASM = 0, NASTAR_FLAG_ASM_V2 = 0, NASTAR_FLAG_ASM_V3 = 0, NASTAR_FLAG_NO_DIVE = 0;  // (host-side tests below fold away)
 #endif
 
-// map widths for which the FMA-based division by fl32(sqrt(W)) was verified bit-exact against IEEE division for
-// every fp32 f in [2^-100, FLT_MAX] (tools/fastdiv_check.c); widths whose sqrt is a power of two divide exactly.
 // a neighbor_filter mask of the masked entry points: weights in {0, 1} over the 3x3 cells, the centre cell (bit 4) clear
 static bool neighbor_mask_valid(unsigned m) { return (m & ~0x1FFu) == 0u && (m & 0x10u) == 0u; }
 
+// the neighbourhood of a launch: the Moore-8 stencil of the plain kernels, or (the _masked entry points) a neighbor_filter's mask, searched by
+// the masked twin of each kernel for EVERY mask, Moore-8 included
+struct Neighbourhood {
+    bool masked = false;
+    uint32_t mask = NASTAR_NEIGHBORS_MOORE8;
+};
+
+// map widths for which the FMA-based division by fl32(sqrt(W)) was verified bit-exact against IEEE division for
+// every fp32 f in [2^-100, FLT_MAX] (tools/fastdiv_check.c); widths whose sqrt is a power of two divide exactly.
 static bool fastdiv_verified(int W)
 {
     static const int ok[] = {2, 8, 32, 128, 512, 10, 12, 20, 24, 28, 40, 45, 48, 50, 60, 96, 100,  // exhaustively checked
@@ -439,6 +446,33 @@ static bool fastdiv_verified(int W)
     for (int w : ok)
         if (w == W) return true;
     return false;
+}
+
+template <bool kMasked, bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
+static auto compiled_compact_kernel()
+{
+    if constexpr (kMasked) return &nastar_forward_compact_masked_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
+    else return &nastar_forward_compact_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
+}
+
+// the compact-state kernel for a map: a hand-scheduled stream where one exists (Moore-8 only: the streams hard-wire the stencil), else the
+// compiled step loop -- compile-time sizes for 16x16, 32x32 and 64x64, one chunk minimum per lane, or runtime sizes
+template <bool kMasked, bool kLog>
+static auto compact_kernel(const CompactDims& d, bool vec4, bool fast, bool use_asm)
+{
+    if constexpr (!kMasked) {
+        if (use_asm && vec4 && fast && d.H == 32 && d.W == 32) return &nastar_forward_compact_kernel<true, 5, 5, 1, true, kLog, true>;
+        if (use_asm && vec4 && fast && d.H == 16 && d.W == 16) return &nastar_forward_compact_kernel<true, 4, 4, 1, true, kLog, true>;
+        if (use_asm && vec4 && fast && d.H == 64 && d.W == 64) return &nastar_forward_compact_kernel<true, 6, 6, 4, true, kLog, true>;
+    }
+    if (vec4 && fast && d.H == 32 && d.W == 32) return compiled_compact_kernel<kMasked, true, 5, 5, 1, true, kLog>();
+    if (vec4 && fast && d.H == 64 && d.W == 64) return compiled_compact_kernel<kMasked, true, 6, 6, 4, true, kLog>();
+    if (vec4 && fast && d.H == 16 && d.W == 16) return compiled_compact_kernel<kMasked, true, 4, 4, 1, true, kLog>();
+    if (vec4 && fast && d.CPL == 1) return compiled_compact_kernel<kMasked, true, 0, 0, 1, true, kLog>();
+    if (vec4 && fast) return compiled_compact_kernel<kMasked, true, 0, 0, 0, true, kLog>();
+    if (vec4) return compiled_compact_kernel<kMasked, true, 0, 0, 0, false, kLog>();
+    if (fast) return compiled_compact_kernel<kMasked, false, 0, 0, 0, true, kLog>();
+    return compiled_compact_kernel<kMasked, false, 0, 0, 0, false, kLog>();
 }
 
 }  // namespace nastar
@@ -484,17 +518,7 @@ static int check_order(const int32_t* order, int B, void* workspace, size_t work
     return NASTAR_OK;
 }
 
-// order_out for a multi-round launch: maps sorted by their step counts, longest first (nastar_placement.hip.h: counting sort, one
-// workgroup, same stream); the trailing counter cell is not used and stays 0
-static int rank_order_after(const int32_t* iters, int B, int32_t* order_out, hipStream_t s)
-{
-    hipLaunchKernelGGL(nastar_rank_levels_kernel, dim3(1), dim3(PLC_RANK_THREADS), 0, s, iters, B, order_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
-}
-
-// the lock-step launches of nastar_forward_batchloop_finish hand these through forward_impl
+// the lock-step launches of nastar_forward_batchloop_finish
 struct LockArgs {
     const int* marks = nullptr;
     const int* t_end = nullptr;
@@ -502,165 +526,153 @@ struct LockArgs {
     int bitmap_words = 0;
 };
 
-static int forward_impl(const float* cost, const float* start, const float* goal, const float* passable, int B, int H,
-                        int W, double g_ratio, int max_iters, float* histories_out, int64_t* paths_out,
-                        int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out, void* workspace,
-                        size_t workspace_bytes, int flags, void* stream, uint8_t* packed_out, bool* packed_done,
-                        const int32_t* order = nullptr, int32_t* order_out = nullptr, int32_t* summary = nullptr, int32_t* done_counter = nullptr,
-                        const LockArgs* lock = nullptr, bool masked = false, uint32_t nmask = NASTAR_NEIGHBORS_MOORE8)
+// one forward launch as an entry point describes it; the optional parts stay null (Moore-8) unless the entry point takes them
+struct FwdLaunch {
+    const float *cost, *start, *goal, *passable;
+    int B, H, W;
+    double g_ratio;
+    int max_iters;
+    float* histories_out;
+    int64_t* paths_out;
+    int32_t *sel_log_out, *iters_out, *status_out;
+    void* workspace;
+    size_t workspace_bytes;
+    int flags;
+    void* stream;
+    uint8_t* packed_out = nullptr;
+    const int32_t* order = nullptr;
+    int32_t *order_out = nullptr, *summary = nullptr, *done_counter = nullptr;
+    LockArgs lock = {};
+    Neighbourhood nb = {};
+};
+
+// large map: cells in the caller's HBM workspace, open list in LDS (nastar_search_hybrid.hip.h)
+static int forward_hybrid(const FwdLaunch& f, int* marks_out)
 {
-    *packed_done = false;
-    if (!cost || !start || !goal || !passable || !histories_out || !paths_out || !iters_out || !status_out)
-        return NASTAR_ERR_NULL;
-    if (flags & ~kKnownFlags) return NASTAR_ERR_UNSUPPORTED;  // (A/B switches of the development build: make dev, csrc/nastar_dev_flags.h)
-    if (B <= 0 || H <= 0 || W <= 0 || max_iters <= 0) return NASTAR_ERR_BAD_SHAPE;
-    if ((long long)H * W > kMaxGlobalCells) return NASTAR_ERR_UNSUPPORTED;
-    const bool lockstep = (flags & NASTAR_FLAG_LOCKSTEP) != 0;
-    const WsLayout wl = ws_layout(B, H, W, flags);
-    if (wl.total > 0 && !lock) {  // (the lock-step launches of the finish call were checked there)
-        if (!workspace) return NASTAR_ERR_NULL;
-        if (workspace_bytes < wl.total) return NASTAR_ERR_WORKSPACE;
+    if (!f.workspace) return NASTAR_ERR_NULL;
+    const size_t slab = hybrid_slab_bytes(f.H * f.W);
+    if (f.workspace_bytes < (size_t)f.B * slab) return NASTAR_ERR_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(f.stream);
+    FwdHybridArgs ha;
+    ha.cost = f.cost; ha.start = f.start; ha.goal = f.goal; ha.passable = f.passable;
+    ha.hist = f.histories_out; ha.paths = reinterpret_cast<long long*>(f.paths_out);
+    ha.sel_log = f.sel_log_out; ha.iters = f.iters_out; ha.status = f.status_out; ha.summary = f.summary;
+    ha.workspace = static_cast<unsigned char*>(f.workspace); ha.slab_bytes = slab; ha.max_iters = f.max_iters;
+    ha.marks_out = marks_out;
+    ha.marks = f.lock.marks; ha.t_end = f.lock.t_end; ha.bitmap = f.lock.bitmap; ha.bitmap_words = f.lock.bitmap_words;
+    HybridDims& hd = ha.d;
+    hd.H = f.H; hd.W = f.W; hd.HW = f.H * f.W;
+    hd.nchunks = (hd.HW + 63) / 64; hd.nsuper = (hd.nchunks + 63) / 64; hd.spl = (hd.nsuper + 63) / 64;
+    hd.gr = (float)f.g_ratio; hd.omg = (float)(1.0 - f.g_ratio); hd.sqrtW = (float)sqrt((double)f.W);
+    hd.rcp_sqrtW = 1.0f / hd.sqrtW;
+    hd.inv_W = 1.0f / (float)f.W;
+    // headers (start / goal cell per map) to -1: the fill launch raises them with atomicMax
+    hipLaunchKernelGGL(nastar_hybrid_header_kernel, dim3((unsigned)((f.B + 255) / 256)), dim3(256), 0, s, ha.workspace, slab,
+                       hybrid_header_offset(hd.HW), f.B);
+    const unsigned per_map = (unsigned)((hd.nchunks * 64 + 255) / 256);
+    const dim3 grid2(per_map < 64u ? per_map : 64u, (unsigned)f.B);
+    hipLaunchKernelGGL(nastar_hybrid_fill_kernel, grid2, dim3(256), 0, s, ha);
+    const size_t hl = hybrid_lds_bytes(hd.HW);
+    if (hl > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
+    const int rc = with_bools([&](auto fd, auto lk, auto masked) {
+        if constexpr (masked) return launch(nastar_forward_hybrid_masked_kernel<fd, lk>, f.B, hl, s, ha, f.nb.mask);
+        else return launch(nastar_forward_hybrid_kernel<fd, lk>, f.B, hl, s, ha);
+    }, fastdiv_verified(f.W), (f.flags & NASTAR_FLAG_LOCKSTEP) != 0, f.nb.masked);
+    if (rc) return rc;
+    if (!ha.bitmap) hipLaunchKernelGGL(nastar_hybrid_store_kernel, grid2, dim3(256), 0, s, ha);  // (a probe launch has no outputs)
+    hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return hip_fail(he, "kernel launch");
+    return NASTAR_OK;
+}
+
+// unit-cost layout (nastar_search_unit.hip.h)
+static int forward_unit(const FwdCArgs& c, int* marks_out, size_t lds, float rcp, hipStream_t s)
+{
+    if (marks_out) {  // unit costs are never in the batch-coupled class (f(n) - f(goal) >= 1.001 - 0.001 g_ratio > 0 with every cost 1)
+        hipError_t me = hipMemsetAsync(marks_out, 0, (size_t)c.B * 4, s);
+        if (me != hipSuccess) return hip_fail(me, "hipMemsetAsync");
     }
-    int* marks_out = (!lockstep && (flags & NASTAR_FLAG_MARK_COUPLED)) ? reinterpret_cast<int*>(static_cast<unsigned char*>(workspace) + wl.marks_off) : nullptr;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (needs_global_state(H, W)) {
-        // large map: cells in the caller's HBM workspace, open list in LDS (nastar_search_hybrid.hip.h)
-        if (!workspace) return NASTAR_ERR_NULL;
-        const size_t slab = hybrid_slab_bytes(H * W);
-        if (workspace_bytes < (size_t)B * slab) return NASTAR_ERR_WORKSPACE;
-        FwdHybridArgs ha;
-        ha.cost = cost; ha.start = start; ha.goal = goal; ha.passable = passable;
-        ha.hist = histories_out; ha.paths = reinterpret_cast<long long*>(paths_out);
-        ha.sel_log = sel_log_out; ha.iters = iters_out; ha.status = status_out; ha.summary = summary;
-        ha.workspace = static_cast<unsigned char*>(workspace); ha.slab_bytes = slab; ha.max_iters = max_iters;
-        ha.marks_out = marks_out;
-        ha.marks = lock ? lock->marks : nullptr; ha.t_end = lock ? lock->t_end : nullptr;
-        ha.bitmap = lock ? lock->bitmap : nullptr; ha.bitmap_words = lock ? lock->bitmap_words : 0;
-        HybridDims& hd = ha.d;
-        hd.H = H; hd.W = W; hd.HW = H * W;
-        hd.nchunks = (hd.HW + 63) / 64; hd.nsuper = (hd.nchunks + 63) / 64; hd.spl = (hd.nsuper + 63) / 64;
-        hd.gr = (float)g_ratio; hd.omg = (float)(1.0 - g_ratio); hd.sqrtW = (float)sqrt((double)W);
-        hd.rcp_sqrtW = 1.0f / hd.sqrtW;
-        hd.inv_W = 1.0f / (float)W;
-        // headers (start / goal cell per map) to -1: the fill launch raises them with atomicMax
-        hipLaunchKernelGGL(nastar_hybrid_header_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, ha.workspace, slab,
-                           hybrid_header_offset(hd.HW), B);
-        const unsigned per_map = (unsigned)((hd.nchunks * 64 + 255) / 256);
-        const dim3 grid2(per_map < 64u ? per_map : 64u, (unsigned)B);
-        hipLaunchKernelGGL(nastar_hybrid_fill_kernel, grid2, dim3(256), 0, s, ha);
-        const bool fd = fastdiv_verified(W);
-        const size_t hl = hybrid_lds_bytes(hd.HW);
-        if (hl > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
-        int rc2;
-        if (masked) {  // (nastar_forward_ex_masked: the neighbourhood of a neighbor_filter)
-            if (lockstep) rc2 = fd ? launch(nastar_forward_hybrid_masked_kernel<true, true>, B, hl, s, ha, nmask)
-                                   : launch(nastar_forward_hybrid_masked_kernel<false, true>, B, hl, s, ha, nmask);
-            else rc2 = fd ? launch(nastar_forward_hybrid_masked_kernel<true, false>, B, hl, s, ha, nmask)
-                          : launch(nastar_forward_hybrid_masked_kernel<false, false>, B, hl, s, ha, nmask);
-        } else if (lockstep) rc2 = fd ? launch(nastar_forward_hybrid_kernel<true, true>, B, hl, s, ha) : launch(nastar_forward_hybrid_kernel<false, true>, B, hl, s, ha);
-        else rc2 = fd ? launch(nastar_forward_hybrid_kernel<true, false>, B, hl, s, ha) : launch(nastar_forward_hybrid_kernel<false, false>, B, hl, s, ha);
-        if (rc2) return rc2;
-        if (!ha.bitmap) hipLaunchKernelGGL(nastar_hybrid_store_kernel, grid2, dim3(256), 0, s, ha);  // (a probe launch has no outputs)
-        hipError_t he = hipGetLastError();
-        if (he != hipSuccess) return hip_fail(he, "kernel launch");
-        return NASTAR_OK;
-    }
-    {
-        FwdCArgs c;
-        int rc = make_cdims(B, H, W, max_iters, g_ratio, c.d);
+    if (c.d.W == 32) return launch(&nastar_forward_unit_kernel<5, false>, c.B, lds, s, c, rcp);
+    if (c.flags & NASTAR_FLAG_NO_DIVE) return launch(&nastar_forward_unit_kernel<6, false>, c.B, lds, s, c, rcp);
+    return launch(&nastar_forward_unit_kernel<6, true>, c.B, lds, s, c, rcp);
+}
+
+// maps whose state fits LDS: the unit-cost layout or the compact state (nastar_search_compact.hip.h)
+static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
+{
+    FwdCArgs c;
+    int rc = make_cdims(f.B, f.H, f.W, f.max_iters, f.g_ratio, c.d);
+    if (rc) return rc;
+    const size_t lds = compact_lds_bytes(c.d.HWp, c.d.NCp);
+    if (lds > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
+    hipStream_t s = reinterpret_cast<hipStream_t>(f.stream);
+    c.cost = f.cost; c.start = f.start; c.goal = f.goal; c.passable = f.passable;
+    c.hist = f.histories_out; c.paths = reinterpret_cast<long long*>(f.paths_out);
+    c.sel_log = f.sel_log_out; c.iters = f.iters_out; c.status = f.status_out; c.max_iters = f.max_iters;
+    c.packed = nullptr;
+    c.order = f.order;
+    c.order_out = f.order_out;  // (decided below: in-kernel completion order, or a rank of the step counts after the launch)
+    c.summary = f.summary;
+    c.done_counter = f.summary ? f.done_counter : nullptr;
+    c.order_bad = nullptr;
+    c.marks_out = marks_out;
+    c.marks = f.lock.marks; c.t_end = f.lock.t_end; c.bitmap = f.lock.bitmap; c.bitmap_words = f.lock.bitmap_words;
+    if (f.order && (f.flags & NASTAR_FLAG_CHECK_ORDER)) {
+        rc = check_order(f.order, f.B, f.workspace, f.workspace_bytes, ws_layout(f.B, f.H, f.W, f.flags).chk_off + kOrderCheckBytes, f.summary, s,
+                         &c.order_bad);
         if (rc) return rc;
-        const size_t lds = compact_lds_bytes(c.d.HWp, c.d.NCp);
-        if (lds > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
-        c.cost = cost; c.start = start; c.goal = goal; c.passable = passable;
-        c.hist = histories_out; c.paths = reinterpret_cast<long long*>(paths_out);
-        c.sel_log = sel_log_out; c.iters = iters_out; c.status = status_out; c.max_iters = max_iters;
-        c.packed = nullptr;
-        c.order = order;
-        c.order_out = order_out;  // (decided below: in-kernel completion order, or a rank of the step counts after the launch)
-        c.summary = summary;
-        c.done_counter = summary ? done_counter : nullptr;
-        c.order_bad = nullptr;
-        c.marks_out = marks_out;
-        c.marks = lock ? lock->marks : nullptr; c.t_end = lock ? lock->t_end : nullptr;
-        c.bitmap = lock ? lock->bitmap : nullptr; c.bitmap_words = lock ? lock->bitmap_words : 0;
-        if (order && (flags & NASTAR_FLAG_CHECK_ORDER)) {
-            rc = check_order(order, B, workspace, workspace_bytes, wl.chk_off + kOrderCheckBytes, summary, s, &c.order_bad);
-            if (rc) return rc;
-        }
-        c.flags = flags;
-        const bool vec4 = (W % 4 == 0) && aligned16(cost) && aligned16(start) && aligned16(goal) && aligned16(passable) &&
-                          aligned16(histories_out) && aligned16(paths_out);
-        if (packed_out && vec4 && (c.d.HW % 8 == 0)) {  // fused emission of the bit-packed masks
-            c.packed = packed_out;
-            *packed_done = true;
-        }
-        const float rcp = 1.0f / c.d.sqrtW;
-        const bool fast = fastdiv_verified(W);
-        const bool lg = sel_log_out != nullptr;
-        void (*kern)(const FwdCArgs, const float) = nullptr;
-        c.B = B;
-        if (masked) {
-            // a neighbor_filter: the compiled step loops with the mask (never the hand-scheduled streams or the unit-cost layout, whose
-            // instruction streams hard-wire the Moore-8 stencil), same size ladder as below
-            void (*mk)(const FwdCArgs, const float, const uint32_t) = nullptr;
-#define NASTAR_MPICK(V4, LW, LH, CPL, FD) \
-    mk = lg ? &nastar_forward_compact_masked_kernel<V4, LW, LH, CPL, FD, true> : &nastar_forward_compact_masked_kernel<V4, LW, LH, CPL, FD, false>
-            if (vec4 && fast && H == 32 && W == 32) { NASTAR_MPICK(true, 5, 5, 1, true); }
-            else if (vec4 && fast && H == 64 && W == 64) { NASTAR_MPICK(true, 6, 6, 4, true); }
-            else if (vec4 && fast && H == 16 && W == 16) { NASTAR_MPICK(true, 4, 4, 1, true); }
-            else if (vec4 && fast && c.d.CPL == 1) { NASTAR_MPICK(true, 0, 0, 1, true); }
-            else if (vec4 && fast) { NASTAR_MPICK(true, 0, 0, 0, true); }
-            else if (vec4) { NASTAR_MPICK(true, 0, 0, 0, false); }
-            else if (fast) { NASTAR_MPICK(false, 0, 0, 0, true); }
-            else { NASTAR_MPICK(false, 0, 0, 0, false); }
-#undef NASTAR_MPICK
-            const bool rank_after = order_out && (long long)B > resident_capacity(lds);
-            if (rank_after) c.order_out = nullptr;
-            const int mrc = launch(mk, B, lds, s, c, rcp, nmask);
-            return (mrc == NASTAR_OK && rank_after) ? rank_order_after(iters_out, B, order_out, s) : mrc;
-        }
-#define NASTAR_CPICK(V4, LW, LH, CPL, FD) \
-    kern = lg ? &nastar_forward_compact_kernel<V4, LW, LH, CPL, FD, true> : &nastar_forward_compact_kernel<V4, LW, LH, CPL, FD, false>
-        const bool use_asm = !(flags & (NASTAR_FLAG_NO_ASM | NASTAR_FLAG_LOCKSTEP));  // (lock-step mode lives in the compiled step loops)
-        // unit-cost layout: the caller promises cost == passable with values in {0, 1} (checked per map by the kernel); taken when the
-        // promise can hold at all (ONE tensor), no selection log is wanted and the hand-scheduled stream exists for the size
-        if ((flags & NASTAR_FLAG_UNIT_COST) && cost == passable && use_asm && !(flags & (NASTAR_FLAG_ASM_V2 | NASTAR_FLAG_ASM_V3)) && !lg && vec4 && fast &&
-            g_ratio >= 0.0 && g_ratio <= 1.0 && H == W && (W == 32 || W == 64)) {
-            const size_t ulds = W == 32 ? (size_t)AsmLayoutUnit<5>::BYTES : (size_t)AsmLayoutUnit<6>::BYTES;
-            const bool rank_after = order_out && (long long)B > resident_capacity(ulds);
-            if (rank_after) c.order_out = nullptr;
-            if (marks_out) {  // unit costs are never in the batch-coupled class (f(n) - f(goal) >= 1.001 - 0.001 g_ratio > 0 with every cost 1)
-                hipError_t me = hipMemsetAsync(marks_out, 0, (size_t)B * 4, s);
-                if (me != hipSuccess) return hip_fail(me, "hipMemsetAsync");
-            }
-            int urc;
-            if (W == 32) urc = launch(&nastar_forward_unit_kernel<5, false>, B, ulds, s, c, rcp);
-            else if (flags & NASTAR_FLAG_NO_DIVE) urc = launch(&nastar_forward_unit_kernel<6, false>, B, ulds, s, c, rcp);
-            else urc = launch(&nastar_forward_unit_kernel<6, true>, B, ulds, s, c, rcp);
-            return (urc == NASTAR_OK && rank_after) ? rank_order_after(iters_out, B, order_out, s) : urc;
-        }
-        if (use_asm && vec4 && fast && H == 32 && W == 32)
-            kern = lg ? &nastar_forward_compact_kernel<true, 5, 5, 1, true, true, true> : &nastar_forward_compact_kernel<true, 5, 5, 1, true, false, true>;
-        else if (use_asm && vec4 && fast && H == 16 && W == 16)
-            kern = lg ? &nastar_forward_compact_kernel<true, 4, 4, 1, true, true, true> : &nastar_forward_compact_kernel<true, 4, 4, 1, true, false, true>;
-        else if (use_asm && vec4 && fast && H == 64 && W == 64)
-            kern = lg ? &nastar_forward_compact_kernel<true, 6, 6, 4, true, true, true> : &nastar_forward_compact_kernel<true, 6, 6, 4, true, false, true>;
-        else if (vec4 && fast && H == 32 && W == 32) { NASTAR_CPICK(true, 5, 5, 1, true); }
-        else if (vec4 && fast && H == 64 && W == 64) { NASTAR_CPICK(true, 6, 6, 4, true); }
-        else if (vec4 && fast && H == 16 && W == 16) { NASTAR_CPICK(true, 4, 4, 1, true); }
-        else if (vec4 && fast && c.d.CPL == 1) { NASTAR_CPICK(true, 0, 0, 1, true); }
-        else if (vec4 && fast) { NASTAR_CPICK(true, 0, 0, 0, true); }
-        else if (vec4) { NASTAR_CPICK(true, 0, 0, 0, false); }
-        else if (fast) { NASTAR_CPICK(false, 0, 0, 0, true); }
-        else { NASTAR_CPICK(false, 0, 0, 0, false); }
-#undef NASTAR_CPICK
-        // order_out: a launch whose maps are all resident at once ranks them by completion (one atomic per map, in the kernel); with
-        // several rounds of workgroups completion time says when a map was STARTED, not how long its search was -- rank the step counts
-        const bool rank_after = order_out && (long long)B > resident_capacity(lds);
-        if (rank_after) c.order_out = nullptr;
-        const int krc = launch(kern, B, lds, s, c, rcp);
-        return (krc == NASTAR_OK && rank_after) ? rank_order_after(iters_out, B, order_out, s) : krc;
     }
+    c.flags = f.flags;
+    c.B = f.B;
+    const bool vec4 = (f.W % 4 == 0) && aligned16(f.cost) && aligned16(f.start) && aligned16(f.goal) && aligned16(f.passable) &&
+                      aligned16(f.histories_out) && aligned16(f.paths_out);
+    if (f.packed_out && vec4 && (c.d.HW % 8 == 0)) {  // fused emission of the bit-packed masks
+        c.packed = f.packed_out;
+        packed_done = true;
+    }
+    const float rcp = 1.0f / c.d.sqrtW;
+    const bool fast = fastdiv_verified(f.W);
+    // the hand-scheduled streams: Moore-8 only, and lock-step mode lives in the compiled step loops
+    const bool use_asm = !f.nb.masked && !(f.flags & (NASTAR_FLAG_NO_ASM | NASTAR_FLAG_LOCKSTEP));
+    // unit-cost layout: the caller promises cost == passable with values in {0, 1} (checked per map by the kernel); taken when the promise can
+    // hold at all (ONE tensor), no selection log is wanted and the hand-scheduled stream exists for the size
+    const bool unit = (f.flags & NASTAR_FLAG_UNIT_COST) && f.cost == f.passable && use_asm && !(f.flags & (NASTAR_FLAG_ASM_V2 | NASTAR_FLAG_ASM_V3)) &&
+                      !f.sel_log_out && vec4 && fast && f.g_ratio >= 0.0 && f.g_ratio <= 1.0 && f.H == f.W && (f.W == 32 || f.W == 64);
+    const size_t kernel_lds = !unit ? lds : f.W == 32 ? (size_t)AsmLayoutUnit<5>::BYTES : (size_t)AsmLayoutUnit<6>::BYTES;
+    // order_out: a launch whose maps are all resident at once ranks them by completion (one atomic per map, in the kernel); with several
+    // rounds of workgroups completion time says when a map was STARTED, not how long its search was -- rank the step counts after the launch
+    // (longest first; the trailing counter cell is not used and stays 0)
+    const bool rank_after = f.order_out && (long long)f.B > resident_capacity(kernel_lds);
+    if (rank_after) c.order_out = nullptr;
+    if (unit) rc = forward_unit(c, marks_out, kernel_lds, rcp, s);
+    else rc = with_bools([&](auto masked, auto lg) {
+        const auto kern = compact_kernel<masked, lg>(c.d, vec4, fast, use_asm);
+        if constexpr (masked) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask);
+        else return launch(kern, f.B, lds, s, c, rcp);
+    }, f.nb.masked, f.sel_log_out != nullptr);
+    return (rc == NASTAR_OK && rank_after) ? nastar_placement_from_levels(f.iters_out, f.B, f.order_out, f.stream) : rc;
+}
+
+// every forward entry point: the launch, then the bit-packed masks for shapes whose kernel does not emit them
+static int forward(const FwdLaunch& f)
+{
+    if ((f.order || f.order_out) && f.B > 0 && f.H > 0 && f.W > 0 && needs_global_state(f.H, f.W)) return NASTAR_ERR_UNSUPPORTED;  // LDS-resident searches only
+    if (!f.cost || !f.start || !f.goal || !f.passable || !f.histories_out || !f.paths_out || !f.iters_out || !f.status_out)
+        return NASTAR_ERR_NULL;
+    if (f.flags & ~kKnownFlags) return NASTAR_ERR_UNSUPPORTED;  // (A/B switches of the development build: make dev, csrc/nastar_dev_flags.h)
+    if (f.B <= 0 || f.H <= 0 || f.W <= 0 || f.max_iters <= 0) return NASTAR_ERR_BAD_SHAPE;
+    if ((long long)f.H * f.W > kMaxGlobalCells) return NASTAR_ERR_UNSUPPORTED;
+    const WsLayout wl = ws_layout(f.B, f.H, f.W, f.flags);
+    if (wl.total > 0) {
+        if (!f.workspace) return NASTAR_ERR_NULL;
+        if (f.workspace_bytes < wl.total) return NASTAR_ERR_WORKSPACE;
+    }
+    int* marks_out = (!(f.flags & NASTAR_FLAG_LOCKSTEP) && (f.flags & NASTAR_FLAG_MARK_COUPLED))
+                         ? reinterpret_cast<int*>(static_cast<unsigned char*>(f.workspace) + wl.marks_off) : nullptr;
+    bool packed_done = false;
+    const int rc = needs_global_state(f.H, f.W) ? forward_hybrid(f, marks_out) : forward_lds(f, marks_out, packed_done);
+    if (rc != NASTAR_OK || packed_done || !f.packed_out) return rc;
+    return nastar_pack_outputs(f.histories_out, f.paths_out, f.B, f.H, f.W, f.packed_out, f.stream);
 }
 
 int nastar_forward(const float* cost, const float* start, const float* goal, const float* passable, int B, int H,
@@ -668,9 +680,8 @@ int nastar_forward(const float* cost, const float* start, const float* goal, con
                    int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out, void* workspace,
                    size_t workspace_bytes, int flags, void* stream)
 {
-    bool done;
-    return forward_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out,
-                        iters_out, status_out, workspace, workspace_bytes, flags, stream, nullptr, &done);
+    return forward(FwdLaunch{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out,
+                             status_out, workspace, workspace_bytes, flags, stream});
 }
 
 int nastar_forward_ordered(const float* cost, const float* start, const float* goal, const float* passable, int B, int H,
@@ -678,22 +689,12 @@ int nastar_forward_ordered(const float* cost, const float* start, const float* g
                            int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out, uint8_t* packed_out, void* workspace,
                            size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out, void* stream)
 {
-    return nastar_forward_ex(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out,
-                             status_out, packed_out, workspace, workspace_bytes, flags, order, order_out, nullptr, nullptr, stream);
-}
-
-static int forward_ex_impl(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
-                           int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
-                           uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
-                           int32_t* status_summary, int32_t* completion_counter, void* stream, bool masked, uint32_t nmask)
-{
-    if ((order || order_out) && B > 0 && H > 0 && W > 0 && needs_global_state(H, W)) return NASTAR_ERR_UNSUPPORTED;  // LDS-resident searches only
-    bool done = false;
-    int rc = forward_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out,
-                          iters_out, status_out, workspace, workspace_bytes, flags, stream, packed_out, &done, order, order_out, status_summary,
-                          completion_counter, nullptr, masked, nmask);
-    if (rc != NASTAR_OK || done || !packed_out) return rc;
-    return nastar_pack_outputs(histories_out, paths_out, B, H, W, packed_out, stream);
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, flags, stream};
+    f.packed_out = packed_out;
+    f.order = order;
+    f.order_out = order_out;
+    return forward(f);
 }
 
 int nastar_forward_ex(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
@@ -701,9 +702,14 @@ int nastar_forward_ex(const float* cost, const float* start, const float* goal, 
                       uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
                       int32_t* status_summary, int32_t* completion_counter, void* stream)
 {
-    return forward_ex_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
-                           packed_out, workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, stream, false,
-                           NASTAR_NEIGHBORS_MOORE8);
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, flags, stream};
+    f.packed_out = packed_out;
+    f.order = order;
+    f.order_out = order_out;
+    f.summary = status_summary;
+    f.done_counter = completion_counter;
+    return forward(f);
 }
 
 int nastar_forward_ex_masked(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
@@ -712,54 +718,55 @@ int nastar_forward_ex_masked(const float* cost, const float* start, const float*
                              int32_t* status_summary, int32_t* completion_counter, unsigned neighbor_mask, void* stream)
 {
     if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
-    return forward_ex_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
-                           packed_out, workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, stream, true,
-                           neighbor_mask);
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, flags, stream};
+    f.packed_out = packed_out;
+    f.order = order;
+    f.order_out = order_out;
+    f.summary = status_summary;
+    f.done_counter = completion_counter;
+    f.nb = Neighbourhood{true, neighbor_mask};
+    return forward(f);
 }
 
-static int batchloop_finish_impl(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
-                                 double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
-                                 int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream, bool masked,
-                                 uint32_t nmask)
+static int batchloop_finish(const FwdLaunch& f)
 {
-    if (!cost || !start || !goal || !passable || !histories_out || !paths_out || !iters_out || !status_out || !workspace) return NASTAR_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || max_iters <= 0) return NASTAR_ERR_BAD_SHAPE;
-    if ((long long)H * W > kMaxGlobalCells) return NASTAR_ERR_UNSUPPORTED;
-    if (workspace_bytes < nastar_batchloop_workspace_bytes(B, H, W, max_iters)) return NASTAR_ERR_WORKSPACE;
-    const WsLayout wl = ws_layout(B, H, W, NASTAR_FLAG_MARK_COUPLED | NASTAR_FLAG_CHECK_ORDER);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    LockArgs la;
-    la.marks = reinterpret_cast<const int*>(ws + wl.marks_off);
+    if (!f.cost || !f.start || !f.goal || !f.passable || !f.histories_out || !f.paths_out || !f.iters_out || !f.status_out || !f.workspace)
+        return NASTAR_ERR_NULL;
+    if (f.B <= 0 || f.H <= 0 || f.W <= 0 || f.max_iters <= 0) return NASTAR_ERR_BAD_SHAPE;
+    if ((long long)f.H * f.W > kMaxGlobalCells) return NASTAR_ERR_UNSUPPORTED;
+    if (f.workspace_bytes < nastar_batchloop_workspace_bytes(f.B, f.H, f.W, f.max_iters)) return NASTAR_ERR_WORKSPACE;
+    const WsLayout wl = ws_layout(f.B, f.H, f.W, NASTAR_FLAG_MARK_COUPLED | NASTAR_FLAG_CHECK_ORDER);
+    unsigned char* ws = static_cast<unsigned char*>(f.workspace);
+    const int* marks = reinterpret_cast<const int*>(ws + wl.marks_off);
     int* tcell = reinterpret_cast<int*>(ws + wl.tcell_off);
-    la.bitmap_words = bitmap_words_for(max_iters);
     uint32_t* bitmap = reinterpret_cast<uint32_t*>(ws + wl.total);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    bool done;
+    const int words = bitmap_words_for(f.max_iters);
+    FwdLaunch run = f;  // (its workspace check cannot fail: the lock-step layout is the slabs alone)
+    run.flags = NASTAR_FLAG_LOCKSTEP;
     // 1. PROBE: the marked maps in lock-step mode over the whole budget; which steps select the goal?  (no outputs)
-    la.bitmap = bitmap;
-    int rc = forward_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, nullptr, iters_out, status_out, workspace,
-                          workspace_bytes, NASTAR_FLAG_LOCKSTEP, stream, nullptr, &done, nullptr, nullptr, nullptr, nullptr, &la, masked, nmask);
+    run.sel_log_out = nullptr;
+    run.lock = LockArgs{marks, nullptr, bitmap, words};
+    int rc = forward(run);
     if (rc) return rc;
     // 2. the first step at which EVERY map of the batch selects its goal
-    const int words = la.bitmap_words;
     const int lds_words = words < 16384 ? words : 16384;
-    hipLaunchKernelGGL(nastar_batchloop_tend_kernel, dim3(1), dim3(kTendThreads), (size_t)lds_words * 4, s, iters_out, status_out, la.marks, bitmap, words,
-                       B, max_iters, tcell, lds_words);
+    hipLaunchKernelGGL(nastar_batchloop_tend_kernel, dim3(1), dim3(kTendThreads), (size_t)lds_words * 4, reinterpret_cast<hipStream_t>(f.stream),
+                       f.iters_out, f.status_out, marks, bitmap, words, f.B, f.max_iters, tcell, lds_words);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     // 3. FINAL: the marked maps again, for exactly t_end + 1 steps, with outputs (and their rows of the selection log)
-    la.bitmap = nullptr;
-    la.t_end = tcell;
-    return forward_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out, workspace,
-                        workspace_bytes, NASTAR_FLAG_LOCKSTEP, stream, nullptr, &done, nullptr, nullptr, nullptr, nullptr, &la, masked, nmask);
+    run.sel_log_out = f.sel_log_out;
+    run.lock = LockArgs{marks, tcell, nullptr, words};
+    return forward(run);
 }
 
 int nastar_forward_batchloop_finish(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
                                     double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
                                     int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return batchloop_finish_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out,
-                                 status_out, workspace, workspace_bytes, stream, false, NASTAR_NEIGHBORS_MOORE8);
+    return batchloop_finish(FwdLaunch{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out,
+                                      status_out, workspace, workspace_bytes, 0, stream});
 }
 
 int nastar_forward_batchloop_finish_masked(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
@@ -768,8 +775,10 @@ int nastar_forward_batchloop_finish_masked(const float* cost, const float* start
                                            unsigned neighbor_mask, void* stream)
 {
     if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
-    return batchloop_finish_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out,
-                                 status_out, workspace, workspace_bytes, stream, true, neighbor_mask);
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, 0, stream};
+    f.nb = Neighbourhood{true, neighbor_mask};
+    return batchloop_finish(f);
 }
 
 int nastar_completion_supported(int H, int W)
@@ -831,11 +840,10 @@ int nastar_forward_packed(const float* cost, const float* start, const float* go
                           void* workspace, size_t workspace_bytes, int flags, void* stream)
 {
     if (!packed_out) return NASTAR_ERR_NULL;
-    bool done = false;
-    int rc = forward_impl(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out,
-                          iters_out, status_out, workspace, workspace_bytes, flags, stream, packed_out, &done);
-    if (rc != NASTAR_OK || done) return rc;
-    return nastar_pack_outputs(histories_out, paths_out, B, H, W, packed_out, stream);  // shapes the fused path skips
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, flags, stream};
+    f.packed_out = packed_out;
+    return forward(f);
 }
 
 
@@ -863,7 +871,7 @@ size_t nastar_backward_workspace_bytes(int B, int H, int W, int max_iters)
 static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* start, const float* goal, const float* passable,
                                 const int32_t* sel_log, int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters,
                                 const int32_t* t_batch_dev, float* grad_cost_out, void* workspace, size_t workspace_bytes, void* stream,
-                                int flags = 0, bool masked = false, uint32_t nmask = NASTAR_NEIGHBORS_MOORE8)
+                                int flags, Neighbourhood nb)
 {
     if (!cost || !start || !goal || !passable || !sel_log || !iters || !grad_cost_out || !workspace) return NASTAR_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || max_iters <= 0) return NASTAR_ERR_BAD_SHAPE;
@@ -888,7 +896,6 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
     a.hist = static_cast<double*>(workspace);
     // the kernel indexes the history by step: a search executes at most HW + 1 selections whatever the budget
     const int hlen = bwdr_hist_len(a.d.HW, max_iters);
-    a.max_iters = max_iters;
     a.state = nullptr;
     a.state_stride = 0;
     a.hist_len = hlen;
@@ -899,7 +906,7 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
     if ((flags & ~(kKnownFlags)) != 0) return NASTAR_ERR_UNSUPPORTED;
     const bool wide = bwdr_wide(a.d.HW, max_iters);  // (history stamps are 16-bit otherwise)
     // (the hand-scheduled loop closes every selected cell: a lock-step log, whose goal selections leave the goal open, takes the general loop)
-    if (!masked && (flags & (NASTAR_FLAG_NO_ASM | NASTAR_FLAG_LOCKSTEP)) == 0 && fast && H == W && (W == 32 || W == 16) && aligned16(cost) && aligned16(start) &&
+    if (!nb.masked && (flags & (NASTAR_FLAG_NO_ASM | NASTAR_FLAG_LOCKSTEP)) == 0 && fast && H == W && (W == 32 || W == 16) && aligned16(cost) && aligned16(start) &&
         aligned16(goal) && aligned16(passable) && aligned16(grad_cost_out) && bwdr_asm_lds_bytes(a.d.HW, max_steps) <= kMaxLdsBytes) {
         // hand-scheduled replay loop (nastar_backward_replay_asm.hip.h): the reference's training sizes
         const size_t lds = bwdr_asm_lds_bytes(a.d.HW, max_steps);
@@ -910,16 +917,11 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
         // history in LDS as long as at least 2 maps (or what the state alone allows) stay resident per CU
         const size_t st = bwdr_state_bytes(a.d.HWp), with_hist = st + (size_t)hlen * 16;
         const bool hist_lds = with_hist <= kMaxLdsBytes && (kMaxLdsBytes / with_hist >= 2 || kMaxLdsBytes / st < 2);
-        if (masked) {  // (nastar_backward_replay_ordered_masked: the open sets of a neighbor_filter's search)
-            if (hist_lds) return fast ? launch(nastar_backward_replay_masked_kernel<false, true, true>, B, with_hist, s, a, rcp, nmask)
-                                      : launch(nastar_backward_replay_masked_kernel<false, true, false>, B, with_hist, s, a, rcp, nmask);
-            return fast ? launch(nastar_backward_replay_masked_kernel<false, false, true>, B, st, s, a, rcp, nmask)
-                        : launch(nastar_backward_replay_masked_kernel<false, false, false>, B, st, s, a, rcp, nmask);
-        }
-        if (hist_lds) return fast ? launch(nastar_backward_replay_kernel<false, true, true>, B, with_hist, s, a, rcp)
-                                  : launch(nastar_backward_replay_kernel<false, true, false>, B, with_hist, s, a, rcp);
-        return fast ? launch(nastar_backward_replay_kernel<false, false, true>, B, st, s, a, rcp)
-                    : launch(nastar_backward_replay_kernel<false, false, false>, B, st, s, a, rcp);
+        return with_bools([&](auto hl, auto fd, auto masked) {
+            const size_t lds = hl ? with_hist : st;
+            if constexpr (masked) return launch(nastar_backward_replay_masked_kernel<false, hl, fd>, B, lds, s, a, rcp, nb.mask);
+            else return launch(nastar_backward_replay_kernel<false, hl, fd>, B, lds, s, a, rcp);
+        }, hist_lds, fast, nb.masked);
     }
     // state in the HBM workspace: FILL (all CUs: slab, zeroed gradient, start / goal cells into the slab's header), REPLAY (one wavefront per map:
     // O(steps)), SWEEP (all CUs: the cells still open at the end) -- nastar_backward_replay.hip.h
@@ -928,30 +930,16 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
     // headers (start / goal cell per map) to -1: the fill launch raises them with atomicMax (the forward's header kernel: same layout of two ints)
     hipLaunchKernelGGL(nastar_hybrid_header_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, a.state, a.state_stride,
                        bwdr_header_offset(a.d.HWp, wide), B);
-    hipError_t he;
     const unsigned per_map = (unsigned)((a.d.HW + 255) / 256);
     const dim3 grid2(per_map < 64u ? per_map : 64u, (unsigned)B);
-    if (wide) hipLaunchKernelGGL(nastar_bwdr_fill_kernel<true>, grid2, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(nastar_bwdr_fill_kernel<false>, grid2, dim3(256), 0, s, a);
-    int rc2;
-    if (masked) {
-        if (wide) rc2 = fast ? launch(nastar_backward_replay_masked_kernel<true, false, true, true>, B, 64, s, a, rcp, nmask)
-                             : launch(nastar_backward_replay_masked_kernel<true, false, false, true>, B, 64, s, a, rcp, nmask);
-        else rc2 = fast ? launch(nastar_backward_replay_masked_kernel<true, false, true>, B, 64, s, a, rcp, nmask)
-                        : launch(nastar_backward_replay_masked_kernel<true, false, false>, B, 64, s, a, rcp, nmask);
-    } else if (wide) rc2 = fast ? launch(nastar_backward_replay_kernel<true, false, true, true>, B, 64, s, a, rcp)
-                         : launch(nastar_backward_replay_kernel<true, false, false, true>, B, 64, s, a, rcp);
-    else rc2 = fast ? launch(nastar_backward_replay_kernel<true, false, true>, B, 64, s, a, rcp)
-                    : launch(nastar_backward_replay_kernel<true, false, false>, B, 64, s, a, rcp);
-    if (rc2 != NASTAR_OK) return rc2;
-    if (wide) {
-        if (fast) hipLaunchKernelGGL((nastar_bwdr_sweep_kernel<true, true>), grid2, dim3(256), 0, s, a, rcp);
-        else hipLaunchKernelGGL((nastar_bwdr_sweep_kernel<true, false>), grid2, dim3(256), 0, s, a, rcp);
-    } else {
-        if (fast) hipLaunchKernelGGL((nastar_bwdr_sweep_kernel<false, true>), grid2, dim3(256), 0, s, a, rcp);
-        else hipLaunchKernelGGL((nastar_bwdr_sweep_kernel<false, false>), grid2, dim3(256), 0, s, a, rcp);
-    }
-    he = hipGetLastError();
+    with_bools([&](auto w) { hipLaunchKernelGGL(nastar_bwdr_fill_kernel<w>, grid2, dim3(256), 0, s, a); }, wide);
+    const int rc = with_bools([&](auto fd, auto w, auto masked) {
+        if constexpr (masked) return launch(nastar_backward_replay_masked_kernel<true, false, fd, w>, B, 64, s, a, rcp, nb.mask);
+        else return launch(nastar_backward_replay_kernel<true, false, fd, w>, B, 64, s, a, rcp);
+    }, fast, wide, nb.masked);
+    if (rc != NASTAR_OK) return rc;
+    with_bools([&](auto w, auto fd) { hipLaunchKernelGGL((nastar_bwdr_sweep_kernel<w, fd>), grid2, dim3(256), 0, s, a, rcp); }, wide, fast);
+    hipError_t he = hipGetLastError();
     if (he != hipSuccess) return hip_fail(he, "kernel launch");
     return NASTAR_OK;
 }
@@ -967,7 +955,7 @@ int nastar_backward_replay(const float* grad_histories, const float* cost, const
     a.order = nullptr;
     a.order_bad = nullptr;
     return backward_replay_impl(a, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_iters, iters, t_batch_dev,
-                                grad_cost_out, workspace, workspace_bytes, stream, flags);
+                                grad_cost_out, workspace, workspace_bytes, stream, flags, Neighbourhood{});
 }
 
 int nastar_backward_l1_replay(const float* histories, const float* opt_trajs, const float* grad_loss_dev, const float* cost,
@@ -983,14 +971,14 @@ int nastar_backward_l1_replay(const float* histories, const float* opt_trajs, co
     a.order = nullptr;
     a.order_bad = nullptr;
     return backward_replay_impl(a, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_iters, iters, t_batch_dev,
-                                grad_cost_out, workspace, workspace_bytes, stream);
+                                grad_cost_out, workspace, workspace_bytes, stream, 0, Neighbourhood{});
 }
 
 static int backward_replay_ordered_impl(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
                                         const float* cost, const float* start, const float* goal, const float* passable, const int32_t* sel_log,
                                         int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters, const int32_t* t_batch_dev,
-                                        float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, void* stream,
-                                        bool masked, uint32_t nmask)
+                                        float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order,
+                                        Neighbourhood nb, void* stream)
 {
     if (!grad_histories && (!histories || !opt_trajs)) return NASTAR_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0) return NASTAR_ERR_BAD_SHAPE;
@@ -1009,7 +997,7 @@ static int backward_replay_ordered_impl(const float* grad_histories, const float
         if (rc) return rc;
     }
     return backward_replay_impl(a, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_iters, iters, t_batch_dev,
-                                grad_cost_out, workspace, workspace_bytes, stream, flags, masked, nmask);
+                                grad_cost_out, workspace, workspace_bytes, stream, flags, nb);
 }
 
 int nastar_backward_replay_ordered(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
@@ -1018,8 +1006,8 @@ int nastar_backward_replay_ordered(const float* grad_histories, const float* his
                                    float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, void* stream)
 {
     return backward_replay_ordered_impl(grad_histories, histories, opt_trajs, grad_loss_dev, cost, start, goal, passable, sel_log, B, H, W, g_ratio,
-                                        max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order, stream, false,
-                                        NASTAR_NEIGHBORS_MOORE8);
+                                        max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order,
+                                        Neighbourhood{}, stream);
 }
 
 int nastar_backward_replay_ordered_masked(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
@@ -1030,8 +1018,8 @@ int nastar_backward_replay_ordered_masked(const float* grad_histories, const flo
 {
     if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
     return backward_replay_ordered_impl(grad_histories, histories, opt_trajs, grad_loss_dev, cost, start, goal, passable, sel_log, B, H, W, g_ratio,
-                                        max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order, stream, true,
-                                        neighbor_mask);
+                                        max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order,
+                                        Neighbourhood{true, neighbor_mask}, stream);
 }
 
 int nastar_pack_outputs(const float* histories, const int64_t* paths, int B, int H, int W, uint8_t* packed_out, void* stream)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "../../include/nastar.h"
 
@@ -42,6 +43,19 @@ inline int launch(K kernel, int B, size_t lds, hipStream_t stream, const A&... a
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// f(std::bool_constant<b>{}...) for the runtime values b...: turns the flags that pick a kernel's instantiation into its template arguments
+template <typename F>
+inline auto with_bools(F&& f)
+{
+    return f();
+}
+template <typename F, typename... Bools>
+inline auto with_bools(F&& f, bool b, Bools... rest)
+{
+    if (b) return with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+    return with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
 
 
 }  // namespace nastar

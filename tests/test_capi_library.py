@@ -79,6 +79,23 @@ def test_argument_validation_needs_no_gpu():
         assert lib.nastar_forward(one, one, one, one, 1, 8, 8, 0.5, 64, one, one, None, one, one, None, 0, bit, None) == _native.NASTAR_ERR_UNSUPPORTED, bit
     assert lib.nastar_forward_batchloop_finish(one, one, one, one, 2, 8, 8, 0.5, 64, one, one, None, one, one, None, 0, None) == _native.NASTAR_ERR_NULL
     assert lib.nastar_forward_batchloop_finish(one, one, one, one, 2, 8, 8, 0.5, 64, one, one, None, one, one, one, 16, None) == _native.NASTAR_ERR_WORKSPACE
+    # the masked entry points (0.7.0): an invalid neighbor_mask (bits outside the 3x3 cells, or the centre) is refused before any other check
+    vn = 0x0AA  # NASTAR_NEIGHBORS_VON_NEUMANN
+    for bad in (0x10, 0x1FF, 0x200):
+        assert lib.nastar_forward_ex_masked(None, one, one, one, 1, 8, 8, 0.5, 64, one, one, None, one, one, None, None, 0, 0, None, None, None, None, bad, None) == _native.NASTAR_ERR_UNSUPPORTED, bad
+        assert lib.nastar_forward_batchloop_finish_masked(None, one, one, one, 2, 8, 8, 0.5, 64, one, one, None, one, one, None, 0, bad, None) == _native.NASTAR_ERR_UNSUPPORTED, bad
+        assert lib.nastar_backward_replay_ordered_masked(None, None, None, None, one, one, one, one, one, 1, 8, 8, 0.5, 64, one, None, one, one, 1 << 20, 0, None, bad, None) == _native.NASTAR_ERR_UNSUPPORTED, bad
+    assert lib.nastar_forward_ex_masked(None, one, one, one, 1, 8, 8, 0.5, 64, one, one, None, one, one, None, None, 0, 0, None, None, None, None, vn, None) == _native.NASTAR_ERR_NULL
+    assert lib.nastar_forward_ex_masked(one, one, one, one, 0, 8, 8, 0.5, 64, one, one, None, one, one, None, None, 0, 0, None, None, None, None, vn, None) == _native.NASTAR_ERR_BAD_SHAPE
+    assert lib.nastar_forward_ex_masked(one, one, one, one, 1, 200, 150, 0.5, 64, one, one, None, one, one, None, one, 1 << 30, 0, one, None, None, None, vn, None) == _native.NASTAR_ERR_UNSUPPORTED
+    assert lib.nastar_forward_ex_masked(one, one, one, one, 4, 32, 32, 0.5, 64, one, one, None, one, one, None, one, 8, 256, one, None, None, None, vn, None) == _native.NASTAR_ERR_WORKSPACE
+    assert lib.nastar_forward_batchloop_finish_masked(None, one, one, one, 2, 8, 8, 0.5, 64, one, one, None, one, one, one, 1 << 20, vn, None) == _native.NASTAR_ERR_NULL
+    assert lib.nastar_forward_batchloop_finish_masked(one, one, one, one, 2, 8, 8, 0.5, 64, one, one, None, one, one, None, 0, vn, None) == _native.NASTAR_ERR_NULL
+    assert lib.nastar_forward_batchloop_finish_masked(one, one, one, one, 2, 8, 8, 0.5, 64, one, one, None, one, one, one, 16, vn, None) == _native.NASTAR_ERR_WORKSPACE
+    assert lib.nastar_backward_replay_ordered_masked(None, None, None, None, one, one, one, one, one, 1, 8, 8, 0.5, 64, one, None, one, one, 1 << 20, 0, None, vn, None) == _native.NASTAR_ERR_NULL
+    assert lib.nastar_backward_replay_ordered_masked(one, None, None, None, None, one, one, one, one, 1, 8, 8, 0.5, 64, one, None, one, one, 1 << 20, 0, None, vn, None) == _native.NASTAR_ERR_NULL
+    assert lib.nastar_backward_replay_ordered_masked(one, None, None, None, one, one, one, one, one, 0, 8, 8, 0.5, 64, one, None, one, one, 1 << 20, 0, None, vn, None) == _native.NASTAR_ERR_BAD_SHAPE
+    assert lib.nastar_backward_replay_ordered_masked(one, None, None, None, one, one, one, one, one, 1, 8, 8, 0.5, 64, one, None, one, one, 16, 0, None, vn, None) == _native.NASTAR_ERR_WORKSPACE
     for sym in ("nastar_backward", "nastar_backward_l1", "nastar_has_dev_kernels"):  # rounds 1-3 legacy entry points: gone in 0.4.0
         assert not hasattr(lib, sym), sym
     assert lib.nastar_heuristic(None, 1, 8, 8, one, None) == _native.NASTAR_ERR_NULL
