@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- forward DifferentiableAstar throughput on MI355X (the BASELINE.json metric), through the reference's own API.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is ONE call of the hot path the way a user of the reference makes it -- ``VanillaAstar.forward(map_designs, start_maps, goal_maps)``
 (reference planner/astar.py:73-102) with the default same-call solvability verdict -- over one batch of B = 4096 synthetic 32x32 Moore-8 maps
@@ -13,9 +13,12 @@ on preallocated outputs -- rounds 1-5's headline -- is reported beside it (``bar
 (weak scaling) and the bit-packed ``AstarOutput`` of all ranks is collated with ONE RCCL all-gather per 16 steps (``--collate-bucket``; emitted by
 the search launch itself, the tail bucket flushed inside the timed region), overlapped with the following steps' searches.  Rank 0 prints ONE JSON line.
 
-The line's core (headline, roofline, cpu_baseline) is computed first; every secondary experiment (other workloads, batches in flight, encoders,
-training steps, the reference run on this GPU) lives in ``bench_extras.py`` and runs in a CHILD process with a time limit: whatever happens
-there, the one line that matters is printed.
+A plain run does only what the headline needs: it synthesises the inputs, runs the W + K steps once as they come (``contract_exact_no_prewarm``),
+pre-warms the clocks, runs the timed W + K steps of the headline, writes ``--dump-outputs`` and prints the line.  ``--full`` adds everything else
+the line used to carry: the comparison passes (``natural_order``, ``bare_launch``), the per-launch kernel timings behind ``roofline`` and
+``issue_model``, the parity sample against the CPU oracle, the CPU baselines (``cpu_baseline``) and the secondary experiments (other workloads,
+batches in flight, encoders, training steps, the reference run on this GPU), which live in ``bench_extras.py`` and run in a CHILD process with a
+time limit: whatever happens there, the one line that matters is printed.
 
 Workload (``config.workload``): ``maze32`` = seeded maze-like stand-in for the absent ``mazes_032_moore_c8.npz``
 (SURVEY.md section 8d-ii), VanillaAstar convention cost = map, g_ratio 0.5, eval mode (search runs to the goal).
@@ -66,13 +69,35 @@ def _synth(kind: str, B: int, seed: int):
     raise ValueError(kind)
 
 
+CACHE_ENV = "NASTAR_BENCH_CACHE"
+
+
+def _cache_dir() -> str:
+    """The directory of THIS run's synthesised batches: made by the first process of a run that needs it, inherited by the processes it
+    starts (the ranks of `--gpus N`, bench_extras.py) through the environment, removed when that process exits.  No run reads what an
+    earlier one wrote."""
+    d = os.environ.get(CACHE_ENV)
+    if d and os.path.isdir(d):
+        return d
+    import atexit
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="nastar_bench_")
+    os.environ[CACHE_ENV] = d
+    atexit.register(shutil.rmtree, d, True)
+    return d
+
+
 def make_problem(kind: str, B: int, seed: int, wait: bool = True):
-    """One seeded synthetic batch, cached under /tmp.  Several ranks of one node may ask for the same batch at once (strong
-    scaling: every rank touches chunks of ONE global batch): an exclusive file lock makes exactly one of them synthesise it, the
-    others load the finished file.  wait=False: return None instead of waiting when another process is building it."""
+    """One seeded synthetic batch, cached for the rest of the run (_cache_dir).  Several ranks of one node may ask for the same batch
+    at once (strong scaling: every rank touches chunks of ONE global batch): an exclusive file lock makes exactly one of them synthesise
+    it, the others load the finished file.  wait=False: return None instead of waiting when another process is building it."""
     import fcntl
     from neural_astar.utils import synthetic as syn
-    cache = os.path.join("/tmp", f"nastar_bench_{kind}_{B}_{seed}.npz")
+    try:
+        cache = os.path.join(_cache_dir(), f"{kind}_{B}_{seed}.npz")
+    except OSError:  # no writable temporary directory: no cache, every caller synthesises
+        return _synth(kind, B, seed)
 
     def load():
         z = np.load(cache)
@@ -81,7 +106,7 @@ def make_problem(kind: str, B: int, seed: int, wait: bool = True):
         return load()
     try:
         lock = open(cache + ".lock", "w")
-    except OSError:  # /tmp not writable: no cache, every caller synthesises
+    except OSError:  # cache directory not writable: no cache, every caller synthesises
         return _synth(kind, B, seed)
     try:
         try:
@@ -128,6 +153,20 @@ def make_problem_rows(kind: str, total: int, seed: int, rows: np.ndarray, rank: 
         sel = rows[(rows // CH) == c] - c * CH
         parts.append(tuple(x[sel] for x in pr))
     return syn.Problems(*(np.concatenate([p[k] for p in parts]) for k in range(3)))
+
+
+def make_problems(specs):
+    """make_problem(*spec) for every (kind, B, seed) of `specs`: this process synthesises the first, fresh child processes (spawned, not
+    forked: they never inherit a GPU context) the others meanwhile -- the maze generator is a Python loop, seconds per 4096 maps."""
+    import concurrent.futures
+    import multiprocessing
+    if len(specs) < 2:
+        return [make_problem(*s) for s in specs]
+    _cache_dir()  # (made here, so that the children cache into the same directory as this process)
+    with concurrent.futures.ProcessPoolExecutor(len(specs) - 1, mp_context=multiprocessing.get_context("spawn")) as ex:
+        futs = [ex.submit(make_problem, *s) for s in specs[1:]]
+        first = make_problem(*specs[0])
+        return [first] + [f.result() for f in futs]
 
 
 class Runner:
@@ -686,11 +725,14 @@ def main():
     ap.add_argument("--placement", default="dataset", choices=["dataset", "natural"],
                     help="dataset (default): every timed step searches a NEVER-SEARCHED batch that carries its loader's placement hint (counting sort of "
                          "the start cells' optimal distances, computed INSIDE the timed step); natural: no hint, workgroup i = map i")
-    ap.add_argument("--no-natural", action="store_true", help="skip the comparison passes (natural order, bare launches): clean kernel profiles")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything else the line can carry: comparison passes, per-launch kernel timings (roofline, "
+                         "issue_model), the oracle parity sample, CPU baselines and the secondary experiments (bench_extras.py)")
+    ap.add_argument("--no-natural", action="store_true", help="--full: skip the comparison passes (natural order, bare launches): clean kernel profiles")
     ap.add_argument("--no-prewarm", action="store_true", help="skip the untimed clock pre-warm launches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip bench_extras.py (the secondary experiments)")
-    ap.add_argument("--extras-timeout", type=float, default=420.0, help="time limit of the bench_extras.py child process, seconds")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip bench_extras.py (the secondary experiments)")
+    ap.add_argument("--extras-timeout", type=float, default=420.0, help="--full: time limit of the bench_extras.py child process, seconds")
     ap.add_argument("--no-collate", action="store_true", help="N>1: skip the all-gather of AstarOutput")
     ap.add_argument("--collate-bucket", type=int, default=16, help="N>1: steps per all-gather (parallel.BucketedCollator)")
     ap.add_argument("--force-collate", action="store_true", help="dev: run the N>1 collation path (pack kernel + all-gather) in a 1-rank RCCL group")
@@ -714,6 +756,7 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as plain `python bench.py --gpus N`: re-launch one rank per GPU the way the driver does
         import subprocess
+        _cache_dir()  # (the ranks share this run's synthesised batches)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", os.environ.get("MASTER_PORT", "29533"), os.path.abspath(__file__)] + sys.argv[1:]
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
@@ -760,7 +803,8 @@ def main():
         prs = [make_problem_rows(args.workload, args.global_batch, 1234 + 1000 * k, rows, rank, n_gpus) for k in range(N_ROTATE)]
     else:
         b_rank = B_PER_GPU
-        prs = [make_problem(args.workload, B_PER_GPU, seed=1234 + rank + 1000 * k) for k in range(N_ROTATE)]
+        specs = [(args.workload, B_PER_GPU, 1234 + rank + 1000 * k) for k in range(N_ROTATE)]
+        prs = make_problems(specs) if world == 1 else [make_problem(*s) for s in specs]  # (N > 1: the ranks synthesise side by side)
     pr = prs[0]
     # the resident pool (maps, goals, distance-to-goal maps: a planning-datasets split) the loader-style batches are drawn from
     pool = FreshBatches(args.workload, dev, prs, seed=4321 + rank)
@@ -824,7 +868,7 @@ def main():
     total_maps = n_gpus * b_rank * args.steps
     value = total_maps / dt
     comp = {}
-    if not args.no_natural and collate is None:
+    if args.full and not args.no_natural and collate is None:
         # beside the headline, the same W + K steps: (a) through the API without a hint, (b) BARE C-ABI launches on preallocated outputs with the
         # order computed at batch assembly -- outside the timed region: the headline of rounds 1-5 --, (c) bare launches in the natural order
         fresh2 = sets[:per_pass] if n_fresh else sets
@@ -837,32 +881,6 @@ def main():
             del r2
 
     if rank == 0:
-        # parity sample on the pool's seeded batch 0 (the generator's own starts), through the SAME API call
-        chk = ApiRunner([pool.fixed(0, b_rank)], dev, placement=args.placement)
-        chk.step()
-        torch.cuda.synchronize(dev)
-        hist = chk.out.histories[:, 0].cpu().numpy()
-        paths = chk.out.paths[:, 0].cpu().numpy()
-        # the dominant kernel's duration: HIP events around single launches on the launch stream, same placement as the headline
-        krun = Runner(sets[:per_pass] if n_fresh else sets, dev, placement=args.placement)
-        avg_ms, med_ms, min_ms = kernel_launch_ms(krun, min(args.steps, 100), dev)
-        nat_ms = None
-        if not args.no_natural:  # (--no-natural: a kernel profile of this run must hold ONE placement)
-            krun_n = Runner(sets[:per_pass] if n_fresh else sets, dev, placement="natural")
-            nat_ms = kernel_launch_ms(krun_n, min(args.steps, 100), dev)[0]
-            del krun_n
-        del krun
-        achieved = bytes_moved_per_map * b_rank / (avg_ms * 1e-3) / 1e9
-        traffic = None
-        tp = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tp):
-            with open(tp) as f:
-                traffic = json.load(f).get(args.workload, {}).get("bytes_per_launch")
-        kprof = None  # the committed rocprofv3 average of the same kernel on the same command: `frac` is reproducible from one file
-        kp = os.path.join(ROOT, "profiles", "kernel_profile.json")
-        if os.path.exists(kp):
-            with open(kp) as f:
-                kprof = json.load(f).get(args.workload)
         placement_note = {
             "dataset": ("dataset: the batch carries its loader's hint (start_maps.placement_order) -- workgroup i searches map order[i], order = counting sort "
                         "(longest first) of |opt_dist[start]|, the optimal distance of each sample's start cell, which the reference's maze files carry and "
@@ -895,34 +913,6 @@ def main():
                        "first_visit_note": (f"headline pass = batches #{first_fresh}..#{first_fresh + per_pass - 1} of {n_fresh} assembled; none was searched before its step"
                                             if all_first_visits else "batches recur (see workload)")},
             "value_is": "maps/s a caller of the reference's forward() signature gets (VERDICT r5 item 3): placement sort + allocation + launch + same-call verdict per step",
-            "natural_order": comp.get("api_natural_order"),
-            "value_natural_order": comp.get("api_natural_order", {}).get("value"),
-            "bare_launch": ({"dataset_order": comp.get("bare_dataset_order"), "natural_order": comp.get("bare_natural_order"),
-                             "note": "nastar_forward_ex back to back through ctypes on preallocated outputs, no verdict read, the order computed at batch "
-                                     "assembly OUTSIDE the timed region: the headline of rounds 1-5, what no host shim can beat"} if comp else None),
-            "value_bare_launch": comp.get("bare_dataset_order", {}).get("value"),
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "bytes_note": "achieved / frac on the bytes this call MUST move: 24 B/cell (VanillaAstar hands ONE tensor over as cost and passable "
-                                       "map, reference astar.py:93-94; reads 3 x 4 B, writes fp32 histories + int64 paths); SURVEY 8(d)'s 28 B/cell "
-                                       "(DifferentiableAstar boundary, four distinct inputs) beside it",
-                         "algorithmic_bytes_per_launch": bytes_moved_per_map * b_rank,
-                         "frac_28B_per_cell": bytes_per_map * b_rank / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "frac_of_whole_step": bytes_moved_per_map * b_rank / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                         "traffic": traffic,
-                         "traffic_source": "committed constant: profiles/hbm_traffic.json (rocprofv3 FETCH_SIZE / WRITE_SIZE passes of the same command, same kernel and batch shape; see its note), NOT measured in this run",
-                         "kernel": "nastar_forward_compact_kernel (hand-scheduled step loop: nastar_search_asm4.hip.h)",
-                         "launch_ms_avg": avg_ms, "launch_ms_median": med_ms, "launch_ms_min": min_ms,
-                         "launch_ms_avg_natural_order": nat_ms,
-                         "frac_natural_order": (bytes_moved_per_map * b_rank / (nat_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if nat_ms else None,
-                         "launch_ms_note": "HIP events around single bare launches (C ABI, preallocated outputs) on the launch stream, measured in THIS run on the headline pass's batches, placement as the headline",
-                         "committed_kernel_profile_us": kprof["avg_us"] if kprof else None,
-                         "committed_kernel_profile_source": kprof["source"] if kprof else None,
-                         "committed_frac_from_kernel_profile": (bytes_moved_per_map * b_rank / (kprof["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS) if kprof else None},
-            # the search is a serial chain of select + update steps with all state on-chip, so next to the HBM fraction the line
-            # carries what the launch costs the CU's pipes and what its longest chain alone costs (pipe_model above)
-            "issue_model": (pipe_model(float(iters.sum()), avg_ms * 1e3, int(iters.max()), LONE_STEP_NS, FIXED_US)
-                            if (Hh, Ww) == (32, 32) and not strong else None),
             "contract_exact_no_prewarm": {"value": total_maps / dt_cold, "ms_per_step": dt_cold / args.steps * 1e3,
                                           "note": "the same W warm-up + K timed steps run FIRST (on never-searched batches of their own), without the untimed "
                                                   "pre-warm launches: the headline `value` is the second pass (clocks out of their idle state)"},
@@ -930,26 +920,84 @@ def main():
             "mean_iters_per_map": float(iters.mean()), "max_iters_per_map": int(iters.max()),
             "device_ms_per_step": dev_ms / args.steps,
         }
+        if args.full:
+            # parity sample on the pool's seeded batch 0 (the generator's own starts), through the SAME API call
+            chk = ApiRunner([pool.fixed(0, b_rank)], dev, placement=args.placement)
+            chk.step()
+            torch.cuda.synchronize(dev)
+            hist = chk.out.histories[:, 0].cpu().numpy()
+            paths = chk.out.paths[:, 0].cpu().numpy()
+            # the dominant kernel's duration: HIP events around single launches on the launch stream, same placement as the headline
+            krun = Runner(sets[:per_pass] if n_fresh else sets, dev, placement=args.placement)
+            avg_ms, med_ms, min_ms = kernel_launch_ms(krun, min(args.steps, 100), dev)
+            nat_ms = None
+            if not args.no_natural:  # (--no-natural: a kernel profile of this run must hold ONE placement)
+                krun_n = Runner(sets[:per_pass] if n_fresh else sets, dev, placement="natural")
+                nat_ms = kernel_launch_ms(krun_n, min(args.steps, 100), dev)[0]
+                del krun_n
+            del krun
+            achieved = bytes_moved_per_map * b_rank / (avg_ms * 1e-3) / 1e9
+            traffic = None
+            tp = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+            if os.path.exists(tp):
+                with open(tp) as f:
+                    traffic = json.load(f).get(args.workload, {}).get("bytes_per_launch")
+            kprof = None  # the committed rocprofv3 average of the same kernel on the same command: `frac` is reproducible from one file
+            kp = os.path.join(ROOT, "profiles", "kernel_profile.json")
+            if os.path.exists(kp):
+                with open(kp) as f:
+                    kprof = json.load(f).get(args.workload)
+            out.update({
+                "natural_order": comp.get("api_natural_order"),
+                "value_natural_order": comp.get("api_natural_order", {}).get("value"),
+                "bare_launch": ({"dataset_order": comp.get("bare_dataset_order"), "natural_order": comp.get("bare_natural_order"),
+                                 "note": "nastar_forward_ex back to back through ctypes on preallocated outputs, no verdict read, the order computed at batch "
+                                         "assembly OUTSIDE the timed region: the headline of rounds 1-5, what no host shim can beat"} if comp else None),
+                "value_bare_launch": comp.get("bare_dataset_order", {}).get("value"),
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS,
+                             "bytes_note": "achieved / frac on the bytes this call MUST move: 24 B/cell (VanillaAstar hands ONE tensor over as cost and passable "
+                                           "map, reference astar.py:93-94; reads 3 x 4 B, writes fp32 histories + int64 paths); SURVEY 8(d)'s 28 B/cell "
+                                           "(DifferentiableAstar boundary, four distinct inputs) beside it",
+                             "algorithmic_bytes_per_launch": bytes_moved_per_map * b_rank,
+                             "frac_28B_per_cell": bytes_per_map * b_rank / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "frac_of_whole_step": bytes_moved_per_map * b_rank / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+                             "traffic": traffic,
+                             "traffic_source": "committed constant: profiles/hbm_traffic.json (rocprofv3 FETCH_SIZE / WRITE_SIZE passes of the same command, same kernel and batch shape; see its note), NOT measured in this run",
+                             "kernel": "nastar_forward_compact_kernel (hand-scheduled step loop: nastar_search_asm4.hip.h)",
+                             "launch_ms_avg": avg_ms, "launch_ms_median": med_ms, "launch_ms_min": min_ms,
+                             "launch_ms_avg_natural_order": nat_ms,
+                             "frac_natural_order": (bytes_moved_per_map * b_rank / (nat_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if nat_ms else None,
+                             "launch_ms_note": "HIP events around single bare launches (C ABI, preallocated outputs) on the launch stream, measured in THIS run on the headline pass's batches, placement as the headline",
+                             "committed_kernel_profile_us": kprof["avg_us"] if kprof else None,
+                             "committed_kernel_profile_source": kprof["source"] if kprof else None,
+                             "committed_frac_from_kernel_profile": (bytes_moved_per_map * b_rank / (kprof["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS) if kprof else None},
+                # the search is a serial chain of select + update steps with all state on-chip, so next to the HBM fraction the line
+                # carries what the launch costs the CU's pipes and what its longest chain alone costs (pipe_model above)
+                "issue_model": (pipe_model(float(iters.sum()), avg_ms * 1e3, int(iters.max()), LONE_STEP_NS, FIXED_US)
+                                if (Hh, Ww) == (32, 32) and not strong else None),
+            })
         if args.dump_outputs:  # (after every timed pass of this process)
             out["dump_outputs"] = dump_outputs(args.dump_outputs, {"histories": last_out.histories, "paths": last_out.paths})
         del last_out
-        if n_gpus == 1 and not args.no_cpu_baseline:
-            _log("cpu baseline")
-            out["cpu_baseline"] = cpu_baseline(pr, hist, paths)
-        else:
-            out["gpu_matches_oracle_on_sample"] = oracle_check(pr, hist, paths, 256)
-        if n_gpus == 1 and not args.no_secondary:
-            _log("secondary experiments: bench_extras.py (child process)")
-            del run, warm, chk, sets
-            torch.cuda.empty_cache()
-            try:
-                out.update(run_extras(args, args.extras_timeout))
-            except Exception as e:  # noqa: BLE001 - never sinks the line
-                out["extras_note"] = f"bench_extras.py failed to run: {type(e).__name__}: {str(e)[:300]}"
-        if n_gpus == 1 and not args.no_cpu_baseline:
-            # strictly LAST and alone: 256 ATen threads on [B,32,32] maps starve the GPU launch thread of anything timed beside them
-            _log("cpu baseline in BASELINE.md's exact configuration (hard limit 45 s)")
-            out["cpu_baseline"]["spec_config"] = cpu_baseline_spec_collect(cpu_baseline_spec_start(pr, hist, paths), timeout_s=45.0)
+        if args.full:
+            if n_gpus == 1 and not args.no_cpu_baseline:
+                _log("cpu baseline")
+                out["cpu_baseline"] = cpu_baseline(pr, hist, paths)
+            else:
+                out["gpu_matches_oracle_on_sample"] = oracle_check(pr, hist, paths, 256)
+            if n_gpus == 1 and not args.no_secondary:
+                _log("secondary experiments: bench_extras.py (child process)")
+                del run, warm, chk, sets
+                torch.cuda.empty_cache()
+                try:
+                    out.update(run_extras(args, args.extras_timeout))
+                except Exception as e:  # noqa: BLE001 - never sinks the line
+                    out["extras_note"] = f"bench_extras.py failed to run: {type(e).__name__}: {str(e)[:300]}"
+            if n_gpus == 1 and not args.no_cpu_baseline:
+                # strictly LAST and alone: 256 ATen threads on [B,32,32] maps starve the GPU launch thread of anything timed beside them
+                _log("cpu baseline in BASELINE.md's exact configuration (hard limit 45 s)")
+                out["cpu_baseline"]["spec_config"] = cpu_baseline_spec_collect(cpu_baseline_spec_start(pr, hist, paths), timeout_s=45.0)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if world > 1 or args.force_collate:

@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -24,7 +25,7 @@ def test_bench_refuses_to_run_without_a_hip_device():
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--no-secondary"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -65,11 +66,55 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_measures_the_headline_alone():
+    """without --full the run sets up, warms up, times the K steps and prints the line: the headline keys mean what they mean under --full,
+    the comparison passes, kernel timings, baselines and secondary experiments are absent, and little time goes outside the steps"""
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2"], capture_output=True,
+                       text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["metric"] == "map-instances/s (forward A*) 32x32 Moore-8 @batch 4096" and j["unit"] == "maps/s" and j["dtype"] == "f32"
+    assert j["higher_is_better"] is True and j["n_gpus"] == 1 and j["steps"] == 4 and j["warmup"] == 2 and j["scaling"] == "weak"
+    assert abs(j["value"] - 4096 * 4 / (j["ms_per_step"] * 4e-3)) < 1e-6 * j["value"]
+    assert j["config"]["placement"].startswith("dataset") and j["config"]["every_timed_step_is_a_first_visit"] is True
+    for k in ("roofline", "issue_model", "natural_order", "bare_launch", "cpu_baseline", "extras_note", "gpu_matches_oracle_on_sample"):
+        assert k not in j, k
+    assert wall - 6 * j["ms_per_step"] * 1e-3 < 60.0, wall  # (a plain run is meant to stay well inside 30 s outside its steps)
+
+
+def test_synthesised_batches_live_as_long_as_the_run():
+    """make_problems: the first batch in this process, the others in spawned children, all equal to the generator's own output; they are
+    cached in a directory of the run's own that is gone once the run has exited, so no run reads what an earlier one wrote"""
+    code = ("import json, os, sys; sys.path[:0] = [%r, %r]\n"
+            "import numpy as np, bench\n"
+            "from neural_astar.utils import synthetic as syn\n"
+            "specs = [('maze32', 48, 7 + k) for k in range(3)]\n"
+            "prs = bench.make_problems(specs)\n"
+            "same = all(np.array_equal(a, b) and a.dtype == b.dtype for (_, B, s), pr in zip(specs, prs) for a, b in zip(pr, syn.maze_maps(B, 32, seed=s)))\n"
+            "d = os.environ[bench.CACHE_ENV]\n"
+            "print(json.dumps({'same': same, 'dir': d, 'files': sorted(f for f in os.listdir(d) if f.endswith('.npz'))}))\n"
+            % (os.path.join(ROOT, "neural-astar_amd"), ROOT))
+    dirs = []
+    for _ in range(2):
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads(r.stdout.strip().splitlines()[-1])
+        assert j["same"] and j["files"] == ["maze32_48_7.npz", "maze32_48_8.npz", "maze32_48_9.npz"]
+        assert not os.path.exists(j["dir"])
+        dirs.append(j["dir"])
+    assert dirs[0] != dirs[1]
+
+
+@pytest.mark.gpu
 def test_bench_line_survives_its_secondary_experiments():
     """the secondary experiments run in a CHILD process (bench_extras.py) with a time limit: cut off after a few seconds here, the line is still
     printed, says so, and carries the sections the child had finished"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--extras-timeout", "25"],
-                       capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
+                        "--extras-timeout", "25"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines

@@ -16,7 +16,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # (--no-natural: the default bench line also times the natural-order placement beside the hinted one; a kernel average must not mix the two)
 # (--no-prewarm: the pre-warm launches are bare dataset-placed launches and would dominate the kernel's call count)
-B="python $R/bench.py --no-cpu-baseline --no-secondary --no-natural --no-prewarm"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary --no-natural --no-prewarm"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- $B --steps 200 --warmup 20 > $OUT/bench_under_rocprof.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace_natural -o bench --output-format csv -- $B --placement natural --steps 200 --warmup 20 > $OUT/bench_natural_under_rocprof.log 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do

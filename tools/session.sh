@@ -16,13 +16,13 @@ r06_final)
   O=gpurun_out/r06/final; mkdir -p $O
   python -m pytest tests -q -m gpu > $O/gpu_tests_final.log 2>&1; echo "suite rc=$?"; tail -6 $O/gpu_tests_final.log
   python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_command.json 2> $O/bench_n1_driver_command.err; echo "bench rc=$?"
-  python bench.py --steps 200 --warmup 20 --no-secondary --no-cpu-baseline > $O/bench_n1_steps200.json 2>/dev/null
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_command.json 2> $O/bench_n1_driver_command.err; echo "bench rc=$?"
+  python bench.py --full --steps 200 --warmup 20 --no-secondary --no-cpu-baseline > $O/bench_n1_steps200.json 2>/dev/null
   bash tools/profile_round.sh r06 > $O/profile_round.log 2>&1; tail -c 400 $O/profile_round.log
   python tools/probe_boundary.py > $O/probe_boundary.jsonl 2> $O/probe_boundary.err
   NASTAR_FASTLANE=0 python tools/probe_boundary.py 2>/dev/null | head -1 > $O/probe_boundary_python_lane.jsonl
-  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 8 --steps 10 --warmup 2 --dist-backend gloo --share-gpu --no-cpu-baseline --no-secondary > $O/world8_maze32_weak.json 2> $O/world8.err; echo "world8 rc=$?"
-  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --force-collate --steps 50 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_force_collate_rccl1.json 2> $O/rccl1.err; echo "rccl1 rc=$?"
+  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 8 --steps 10 --warmup 2 --dist-backend gloo --share-gpu --no-cpu-baseline --no-secondary > $O/world8_maze32_weak.json 2> $O/world8.err; echo "world8 rc=$?"
+  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python bench.py --full --force-collate --steps 50 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_force_collate_rccl1.json 2> $O/rccl1.err; echo "rccl1 rc=$?"
   python - <<'P'
 import json
 for f in ("bench_n1_driver_command", "bench_n1_steps200", "world8_maze32_weak", "bench_force_collate_rccl1"):
@@ -65,7 +65,7 @@ r04_c)
   python tools/probe_streams.py --workloads maze32,rand32,rand64 --flags 0,128,64 --streams 1,2,4,6,8 --bigb 4,8 > $O/streams.jsonl 2> $O/streams.err
   cat $O/streams.jsonl; tail -n 3 $O/streams.err
   for f in 0 128 64; do for w in maze32 rand32 rand64; do
-    NASTAR_FORWARD_FLAGS=$f python bench.py --no-cpu-baseline --no-secondary --steps 200 --warmup 10 --workload $w > $O/serial_${w}_f$f.json 2>> $O/serial.err
+    NASTAR_FORWARD_FLAGS=$f python bench.py --full --no-cpu-baseline --no-secondary --steps 200 --warmup 10 --workload $w > $O/serial_${w}_f$f.json 2>> $O/serial.err
   done; done
   python - <<'P'
 import json
@@ -83,7 +83,7 @@ r04_prof)
   bash tools/profile_round.sh r04 > $O/profile_round.log 2>&1; tail -c 3000 $O/profile_round.log
   python tools/probe_latency.py > $O/lat_asm4.txt 2>&1; NASTAR_FORWARD_FLAGS=128 python tools/probe_latency.py > $O/lat_asm3.txt 2>&1
   head -4 $O/lat_asm4.txt $O/lat_asm3.txt
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_command.json 2> $O/bench_n1_driver_command.err; echo "bench rc=$?"
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_command.json 2> $O/bench_n1_driver_command.err; echo "bench rc=$?"
   tail -n 5 $O/bench_n1_driver_command.err; head -c 1500 $O/bench_n1_driver_command.json
   ;;
 r04_d)
@@ -93,7 +93,7 @@ r04_d)
   python -m pytest tests/test_trainloop_golden_gpu.py tests/test_encoder_train_gpu.py tests/test_distributed_training.py tests/test_unet_gpu.py tests/test_trainstep_golden_gpu.py -q -s -m gpu > $O/tests.log 2>&1; echo "tests rc=$?"
   grep -a "TRAINLOOP\|GRADERR unet\|ambiguous-only\|passed\|failed\|^E  " $O/tests.log | cut -c1-900 | tail -40
   run8() { name=$1; shift; port=$((29600 + RANDOM % 300)); t0=$(date +%s)
-    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 8 --steps 20 --warmup 5 --dist-backend gloo --share-gpu "$@" > $O/world8_$name.json 2> $O/world8_$name.err
+    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus 8 --steps 20 --warmup 5 --dist-backend gloo --share-gpu "$@" > $O/world8_$name.json 2> $O/world8_$name.err
     echo "world8 $name rc=$? $(( $(date +%s) - t0 )) s: $(head -c 300 $O/world8_$name.json)"; }
   run8 maze32_weak
   run8 rand64_contiguous --workload rand64 --global-batch 32768
@@ -125,7 +125,7 @@ r04_f)
   python -m pytest tests/test_trainloop_golden_gpu.py tests/test_bench_contract.py -q -s -m gpu > $O/trainloop.log 2>&1; echo "trainloop rc=$?"
   grep -a "TRAINLOOP\|passed\|failed" $O/trainloop.log | cut -c1-2500 | tail -8
   for rep in 1 2; do for f in 0 32 64 96; do for w in maze32 rand32; do
-    NASTAR_FORWARD_FLAGS=$f python bench.py --no-cpu-baseline --no-secondary --steps 200 --warmup 10 --workload $w > $O/serial_${w}_f${f}_$rep.json 2>> $O/serial.err
+    NASTAR_FORWARD_FLAGS=$f python bench.py --full --no-cpu-baseline --no-secondary --steps 200 --warmup 10 --workload $w > $O/serial_${w}_f${f}_$rep.json 2>> $O/serial.err
   done; done; done
   python - <<'P'
 import json
@@ -143,7 +143,7 @@ r04_final)
   python -m pytest tests -q -m gpu > $O/all_gpu_tests.log 2>&1; echo "suite rc=$?"; tail -4 $O/all_gpu_tests.log
   python __graft_entry__.py smoke 2>&1 | tail -1
   bash tools/profile_round.sh r04 > $O/profile_round.log 2>&1
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_command.json 2> $O/bench_n1_driver_command.err; echo "bench rc=$?"
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_command.json 2> $O/bench_n1_driver_command.err; echo "bench rc=$?"
   tail -n 3 $O/bench_n1_driver_command.err; head -c 600 $O/bench_n1_driver_command.json
   ;;
 r04_tp)
@@ -205,7 +205,7 @@ r04_spec)
   O=gpurun_out/r04/spec${2:-}; mkdir -p $O
   python -m pytest tests/test_gpu_parity.py -q -m gpu -x -k "instruction_streams" > $O/parity.log 2>&1; echo "parity rc=$?"; tail -5 $O/parity.log
   for f in 0 8 256 512; do for w in maze32 rand32; do
-    NASTAR_FORWARD_FLAGS=$f python bench.py --no-cpu-baseline --no-secondary --steps 200 --warmup 10 --workload $w > $O/serial_${w}_f$f.json 2>> $O/serial.err
+    NASTAR_FORWARD_FLAGS=$f python bench.py --full --no-cpu-baseline --no-secondary --steps 200 --warmup 10 --workload $w > $O/serial_${w}_f$f.json 2>> $O/serial.err
   done; done
   python - <<P
 import json
@@ -228,7 +228,7 @@ r04_order2)
   O=gpurun_out/r04/order2${2:-}; mkdir -p $O
   python -m pytest tests/test_gpu_parity.py -q -m gpu -x -k "placement" > $O/parity.log 2>&1; echo "parity rc=$?"; tail -5 $O/parity.log
   python tools/probe_latency.py > $O/lat.txt 2>&1; tail -4 $O/lat.txt
-  python bench.py --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
   python - <<P
 import json
 j = json.load(open("$O/bench_driver_command.json"))
@@ -246,7 +246,7 @@ r04_final2)
   python tools/probe_latency.py > $O/lat_working_clocks.txt 2>&1; tail -8 $O/lat_working_clocks.txt
   python tools/probe_order_train.py > $O/order_train_pair.json 2> $O/order_train_pair.err; cat $O/order_train_pair.json
   python tools/probe_order.py maze32,rand32,rand64 0 > $O/order_placements_probe.jsonl 2>/dev/null
-  python bench.py --steps 20 --warmup 5 > $O/bench_n1_driver_command.json 2> $O/bench.err; echo "bench rc=$?"
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_n1_driver_command.json 2> $O/bench.err; echo "bench rc=$?"
   bash tools/profile_round.sh r04 > $O/profile_round.log 2>&1; tail -c 600 $O/profile_round.log
   ;;
 r05_a)
@@ -255,7 +255,7 @@ r05_a)
   O=gpurun_out/r05/a; mkdir -p $O
   python -m pytest tests/test_boundary_gpu.py -q -x -m gpu > $O/boundary.log 2>&1; echo "boundary rc=$?"
   tail -30 $O/boundary.log
-  python bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 5 > $O/bench_short.json 2> $O/bench_short.err; echo "bench rc=$?"
+  python bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 5 > $O/bench_short.json 2> $O/bench_short.err; echo "bench rc=$?"
   tail -5 $O/bench_short.err
   python - <<'P'
 import json
@@ -264,7 +264,7 @@ print("value", round(j["value"]/1e6,2), "M maps/s  ms/step", round(j["ms_per_ste
 print("roofline", {k: j["roofline"][k] for k in ("frac","frac_28B_per_cell","launch_ms_avg","launch_ms_median","launch_ms_min")})
 print("first visits:", j["config"]["every_timed_step_is_a_first_visit"], j["config"]["first_visit_note"])
 P
-  (cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/trace -o bench --output-format csv -- python $R/bench.py --no-cpu-baseline --no-secondary --no-natural --no-prewarm --steps 200 --warmup 20 > $R/$O/bench_under_rocprof.json 2> $R/$O/bench_under_rocprof.err)
+  (cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/trace -o bench --output-format csv -- python $R/bench.py --full --no-cpu-baseline --no-secondary --no-natural --no-prewarm --steps 200 --warmup 20 > $R/$O/bench_under_rocprof.json 2> $R/$O/bench_under_rocprof.err)
   find $O/trace -name "*kernel_stats.csv" -exec cp {} $O/first_visit_kernel_stats.csv \;
   head -5 $O/first_visit_kernel_stats.csv
   python -m pytest tests -q -m gpu -x > $O/all_gpu_tests.log 2>&1; echo "suite rc=$?"
@@ -275,7 +275,7 @@ r05_b)
   O=gpurun_out/r05/b; mkdir -p $O
   python -m pytest tests/test_boundary_gpu.py -q -m gpu > $O/boundary.log 2>&1; echo "boundary rc=$?"; tail -5 $O/boundary.log
   python -m pytest tests -q -m gpu > $O/all_gpu_tests.log 2>&1; echo "suite rc=$?"; tail -8 $O/all_gpu_tests.log
-  python bench.py --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err
   python - <<'P'
 import json
 j=json.load(open("gpurun_out/r05/b/bench_driver_command.json"))
@@ -306,8 +306,8 @@ r05_e)
   O=gpurun_out/r05/e; mkdir -p $O
   python -m pytest tests -q -m gpu > $O/all_gpu_tests.log 2>&1; echo "suite rc=$?"; tail -12 $O/all_gpu_tests.log | cut -c1-300
   python tools/probe_large.py > $O/probe_large.jsonl 2> $O/probe_large.err; echo "large rc=$?"; cat $O/probe_large.jsonl
-  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 8 --steps 10 --warmup 3 --dist-backend gloo --share-gpu --no-secondary --no-cpu-baseline > $O/world8_maze32_weak.json 2> $O/world8_maze32_weak.err; echo "world8 weak rc=$?"; tail -2 $O/world8_maze32_weak.err; cut -c1-600 $O/world8_maze32_weak.json
-  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 8 --steps 10 --warmup 3 --dist-backend gloo --share-gpu --no-secondary --no-cpu-baseline --workload rand64 --global-batch 32768 --shard interleaved > $O/world8_rand64_interleaved.json 2> $O/world8_rand64_interleaved.err; echo "world8 rand64 rc=$?"; tail -2 $O/world8_rand64_interleaved.err; cut -c1-600 $O/world8_rand64_interleaved.json
+  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 8 --steps 10 --warmup 3 --dist-backend gloo --share-gpu --no-secondary --no-cpu-baseline > $O/world8_maze32_weak.json 2> $O/world8_maze32_weak.err; echo "world8 weak rc=$?"; tail -2 $O/world8_maze32_weak.err; cut -c1-600 $O/world8_maze32_weak.json
+  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29542 bench.py --full --gpus 8 --steps 10 --warmup 3 --dist-backend gloo --share-gpu --no-secondary --no-cpu-baseline --workload rand64 --global-batch 32768 --shard interleaved > $O/world8_rand64_interleaved.json 2> $O/world8_rand64_interleaved.err; echo "world8 rand64 rc=$?"; tail -2 $O/world8_rand64_interleaved.err; cut -c1-600 $O/world8_rand64_interleaved.json
   ;;
 r05_prof)
   # the record of round 5 on the final tree: GPU suite + smoke, the driver's bench command, a clean FIRST-VISIT kernel profile (every launch of the
@@ -316,8 +316,8 @@ r05_prof)
   O=gpurun_out/r05/prof; mkdir -p $O
   python -m pytest tests -q -m gpu > $O/gpu_tests_final.log 2>&1; echo "suite rc=$?"; tail -3 $O/gpu_tests_final.log | cut -c1-200
   python __graft_entry__.py smoke 2>&1 | tail -1
-  python bench.py --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
-  B="python $R/bench.py --no-cpu-baseline --no-secondary --no-natural --no-prewarm"
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
+  B="python $R/bench.py --full --no-cpu-baseline --no-secondary --no-natural --no-prewarm"
   (cd /tmp && export TMPDIR=/tmp
    timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/trace -o bench --output-format csv -- $B --steps 200 --warmup 20 > $R/$O/bench_under_rocprof.json 2> $R/$O/bench_under_rocprof.err
    timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/trace_natural -o bench --output-format csv -- $B --placement natural --steps 200 --warmup 20 > $R/$O/bench_natural_under_rocprof.json 2> $R/$O/bench_natural_under_rocprof.err
@@ -363,7 +363,7 @@ r05_g)
   # final tree: whole GPU suite (incl. the status-verdict stress test), the collated path in a 1-rank RCCL group, both training benches
   O=gpurun_out/r05/g; mkdir -p $O
   python -m pytest tests -q -m gpu > $O/gpu_tests_final.log 2>&1; echo "suite rc=$?"; tail -3 $O/gpu_tests_final.log | cut -c1-200
-  python bench.py --force-collate --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_force_collate.json 2> $O/bench_force_collate.err; echo "collate rc=$?"; tail -2 $O/bench_force_collate.err; cut -c1-300 $O/bench_force_collate.json
+  python bench.py --full --force-collate --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_force_collate.json 2> $O/bench_force_collate.err; echo "collate rc=$?"; tail -2 $O/bench_force_collate.err; cut -c1-300 $O/bench_force_collate.json
   for c in maze warcraft; do
     python bench.py --mode train --config $c --steps 20 --warmup 5 --no-cpu-baseline > $O/train_$c.json 2> $O/train_$c.err; echo "train $c rc=$?"; cut -c1-260 $O/train_$c.json
   done
@@ -381,7 +381,7 @@ r05_final)
   O=gpurun_out/r05/final; mkdir -p $O
   python -m pytest tests -q -m gpu > $O/gpu_tests_final.log 2>&1; echo "suite rc=$?"; tail -3 $O/gpu_tests_final.log | cut -c1-200
   python __graft_entry__.py smoke 2>&1 | tail -1
-  python bench.py --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
   python - <<'P'
 import json
 j = json.load(open("gpurun_out/r05/final/bench_driver_command.json"))
@@ -425,7 +425,7 @@ r05_final2)
   O=gpurun_out/r05/final2; mkdir -p $O
   timeout 240 python -m pytest tests -q -m gpu > $O/gpu_tests_final.log 2>&1; echo "suite rc=$?"; tail -3 $O/gpu_tests_final.log | cut -c1-200
   timeout 60 python __graft_entry__.py smoke 2>&1 | tail -1
-  timeout 110 python bench.py --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
+  timeout 110 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench.err; echo "bench rc=$?"; tail -2 $O/bench.err
   python - <<'P'
 import json
 try:
