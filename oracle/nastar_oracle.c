@@ -28,6 +28,10 @@
  *      updates, per-map early exit, walk-to-start backtrack.  This is the algorithm the HIP kernel implements; the CPU tests prove (1)==(2)
  *      on the golden vectors so that kernel-vs-(1) failures can be told apart from algorithmic ones.
  *
+ * Neighbourhood: every entry point has a *_masked twin that takes the reference's neighbor_filter as a 9-bit mask (bit r*3+c set <=>
+ * filter cell (r, c) is 1, as in include/nastar.h); the gate is derived from the definition of conv2d in expand_dense, independently of
+ * the device code.  The entry points without a mask search Moore-8 (0x1EF).
+ *
  * Build: see oracle/Makefile (gcc -O2 -ffp-contract=off -fopenmp).
  */
 #include <math.h>
@@ -57,15 +61,20 @@ static float heuristic0(int r, int c, int gr, int gc, float tb)
 }
 
 /* dense 3x3 stencil, zero centre, zero padding == F.conv2d(x, neighbor_filter, padding=1)
- * (differentiable_astar.py:77-93, filter at :140-141).  Accumulation order = kernel raster order. */
-static void expand_dense(const float* x, float* y, int H, int W)
+ * (differentiable_astar.py:77-93, filter at :140-141).  Accumulation order = kernel raster order.
+ * neighbor_mask: bit r*3+c set <=> filter cell (r, c) is 1 (include/nastar.h).  By the definition of conv2d (a cross-correlation,
+ * y[r][c] = sum_{a,b} w[a][b] * x[r + a - 1][c + b - 1]) the term that reads x at (r + dr, c + dc) carries filter cell (1 + dr, 1 + dc);
+ * a zero weight contributes fl(0 * x) = +0, which leaves the fp32 sum unchanged, so the term is skipped. */
+static int filter_cell(unsigned neighbor_mask, int a, int b) { return (neighbor_mask >> (a * 3 + b)) & 1u; }
+
+static void expand_dense(const float* x, float* y, int H, int W, unsigned neighbor_mask)
 {
     for (int r = 0; r < H; ++r)
         for (int c = 0; c < W; ++c) {
             float acc = 0.0f;
             for (int dr = -1; dr <= 1; ++dr)
                 for (int dc = -1; dc <= 1; ++dc) {
-                    if (dr == 0 && dc == 0) continue;
+                    if (!filter_cell(neighbor_mask, 1 + dr, 1 + dc)) continue;
                     int rr = r + dr, cc = c + dc;
                     if (rr < 0 || rr >= H || cc < 0 || cc >= W) continue;
                     acc += x[rr * W + cc];
@@ -97,7 +106,7 @@ static float clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); 
  * softmax y_t (needed by the backward) is copied there; *pass_goal gets the clamp-backward mask. */
 static int dense_step(dense_map_t* m, const float* cost, const float* goal, const float* passable,
                       int H, int W, float gr, float omg, float sqrtW, int* sel_idx,
-                      float* y_out, unsigned char* passmask_out)
+                      float* y_out, unsigned char* passmask_out, unsigned neighbor_mask)
 {
     const int HW = H * W;
     /* :206  f = g_ratio * g + (1 - g_ratio) * h */
@@ -141,11 +150,11 @@ static int dense_step(dense_map_t* m, const float* cost, const float* goal, cons
         m->open[i] = clamp01(m->open[i] - unsolved * m->sel[i]);
     }
     /* :228-229 neighbor_nodes = expand(sel) * obstacles_maps */
-    expand_dense(m->sel, m->nb, H, W);
+    expand_dense(m->sel, m->nb, H, W, neighbor_mask);
     for (int i = 0; i < HW; ++i) m->nb[i] = m->nb[i] * passable[i];
     /* :234 g2 = expand((g + cost) * sel) */
     for (int i = 0; i < HW; ++i) m->tmp[i] = (m->g[i] + cost[i]) * m->sel[i];
-    expand_dense(m->tmp, m->g2, H, W);
+    expand_dense(m->tmp, m->g2, H, W, neighbor_mask);
     /* :235-243 idx, g, open */
     for (int i = 0; i < HW; ++i) {
         float gt = (m->g[i] > m->g2[i]) ? 1.0f : 0.0f;
@@ -219,10 +228,10 @@ static void backtrack_dense(const float* goal, const float* par, int HW, int t, 
  * or the number of executed steps if it never did; t_batch_out = last executed loop index `t`.
  * max_iters = int(Tmax_eff * W * W) (differentiable_astar.py:200-202).
  */
-int nastar_oracle_forward_dense(const float* cost, const float* start, const float* goal,
-                                const float* passable, int B, int H, int W, double g_ratio,
-                                int max_iters, float* histories, int64_t* paths, int32_t* sel_log,
-                                int32_t* iters_out, int32_t* t_batch_out)
+int nastar_oracle_forward_dense_masked(const float* cost, const float* start, const float* goal,
+                                       const float* passable, int B, int H, int W, double g_ratio,
+                                       int max_iters, float* histories, int64_t* paths, int32_t* sel_log,
+                                       int32_t* iters_out, int32_t* t_batch_out, unsigned neighbor_mask)
 {
     if (B <= 0 || H <= 0 || W <= 0 || max_iters <= 0) return ORACLE_ERR_ARG;
     const int HW = H * W;
@@ -244,7 +253,7 @@ int nastar_oracle_forward_dense(const float* cost, const float* start, const flo
         for (int b = 0; b < B; ++b) {
             int ind = -1;
             int u = dense_step(&maps[b], cost + (size_t)b * HW, goal + (size_t)b * HW,
-                               passable + (size_t)b * HW, H, W, gr, omg, sqrtW, &ind, NULL, NULL);
+                               passable + (size_t)b * HW, H, W, gr, omg, sqrtW, &ind, NULL, NULL, neighbor_mask);
             if (u < 0) { bad = 1; continue; }
             if (sel_log) sel_log[(size_t)b * max_iters + t] = ind;
             if (!u && maps[b].solved_step < 0) maps[b].solved_step = t;
@@ -266,6 +275,18 @@ done:
     return rc;
 }
 
+/* the reference's default neighbor_filter (Moore-8: every cell but the centre) */
+#define ORACLE_MOORE8 0x1EFu
+
+int nastar_oracle_forward_dense(const float* cost, const float* start, const float* goal,
+                                const float* passable, int B, int H, int W, double g_ratio,
+                                int max_iters, float* histories, int64_t* paths, int32_t* sel_log,
+                                int32_t* iters_out, int32_t* t_batch_out)
+{
+    return nastar_oracle_forward_dense_masked(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories, paths,
+                                              sel_log, iters_out, t_batch_out, ORACLE_MOORE8);
+}
+
 /*
  * Literal reverse-mode restatement of what autograd does for `histories` -> `cost_maps`
  * (SURVEY.md 8a-8).  Per map: re-run the forward keeping y_t and the clamp pass-mask of every
@@ -274,9 +295,9 @@ done:
  *     grad_cost += (1-g_ratio) * (-1/sqrt(W)) * y_t * (G - <G, y_t>) ;  G_hist(t) = G
  * Accumulations are done in double; the reference's own fp32 accumulation order is ATen's.
  */
-int nastar_oracle_backward_dense(const float* grad_hist, const float* cost, const float* start,
-                                 const float* goal, const float* passable, int B, int H, int W,
-                                 double g_ratio, int max_iters, float* grad_cost)
+int nastar_oracle_backward_dense_masked(const float* grad_hist, const float* cost, const float* start,
+                                        const float* goal, const float* passable, int B, int H, int W,
+                                        double g_ratio, int max_iters, float* grad_cost, unsigned neighbor_mask)
 {
     if (B <= 0 || H <= 0 || W <= 0 || max_iters <= 0) return ORACLE_ERR_ARG;
     const int HW = H * W;
@@ -289,8 +310,8 @@ int nastar_oracle_backward_dense(const float* grad_hist, const float* cost, cons
         float* hist = (float*)malloc(sizeof(float) * (size_t)B * HW);
         int64_t* paths = (int64_t*)malloc(sizeof(int64_t) * (size_t)B * HW);
         if (!hist || !paths) { free(hist); free(paths); return ORACLE_ERR_ALLOC; }
-        int rc = nastar_oracle_forward_dense(cost, start, goal, passable, B, H, W, g_ratio, max_iters,
-                                             hist, paths, NULL, NULL, &t_batch);
+        int rc = nastar_oracle_forward_dense_masked(cost, start, goal, passable, B, H, W, g_ratio, max_iters,
+                                                    hist, paths, NULL, NULL, &t_batch, neighbor_mask);
         free(hist); free(paths);
         if (rc) return rc;
     }
@@ -309,7 +330,7 @@ int nastar_oracle_backward_dense(const float* grad_hist, const float* cost, cons
         for (int t = 0; t < T; ++t) {
             int ind;
             dense_step(&m, cb, goal + (size_t)b * HW, passable + (size_t)b * HW, H, W, gr, omg, sqrtW,
-                       &ind, ys + (size_t)t * HW, pm + (size_t)t * HW);
+                       &ind, ys + (size_t)t * HW, pm + (size_t)t * HW, neighbor_mask);
         }
         for (int i = 0; i < HW; ++i) G[i] = grad_hist[(size_t)b * HW + i];
         const double k = (double)omg * (-1.0 / (double)sqrtW);
@@ -326,13 +347,21 @@ int nastar_oracle_backward_dense(const float* grad_hist, const float* cost, cons
     return rc_all;
 }
 
+int nastar_oracle_backward_dense(const float* grad_hist, const float* cost, const float* start,
+                                 const float* goal, const float* passable, int B, int H, int W,
+                                 double g_ratio, int max_iters, float* grad_cost)
+{
+    return nastar_oracle_backward_dense_masked(grad_hist, cost, start, goal, passable, B, H, W, g_ratio, max_iters, grad_cost,
+                                               ORACLE_MOORE8);
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* (2) state-machine reading (SURVEY.md 8a "Forward state machine"), one map at a time.        */
 /* ------------------------------------------------------------------------------------------ */
-int nastar_oracle_forward_sm(const float* cost, const float* start, const float* goal,
-                             const float* passable, int B, int H, int W, double g_ratio,
-                             int max_iters, float* histories, int64_t* paths, int32_t* sel_log,
-                             int32_t* iters_out, int32_t* status_out)
+int nastar_oracle_forward_sm_masked(const float* cost, const float* start, const float* goal,
+                                    const float* passable, int B, int H, int W, double g_ratio,
+                                    int max_iters, float* histories, int64_t* paths, int32_t* sel_log,
+                                    int32_t* iters_out, int32_t* status_out, unsigned neighbor_mask)
 {
     if (B <= 0 || H <= 0 || W <= 0 || max_iters <= 0) return ORACLE_ERR_ARG;
     const int HW = H * W;
@@ -376,7 +405,8 @@ int nastar_oracle_forward_sm(const float* cost, const float* start, const float*
             int r = s / W, c = s % W;
             for (int dr = -1; dr <= 1; ++dr)
                 for (int dc = -1; dc <= 1; ++dc) {
-                    if (!dr && !dc) continue;
+                    /* s reaches n = s + (dr, dc) when expand() at n reads s, i.e. through filter cell (1 - dr, 1 - dc) (see expand_dense) */
+                    if (!filter_cell(neighbor_mask, 1 - dr, 1 - dc)) continue;
                     int rr = r + dr, cc = c + dc;
                     if (rr < 0 || rr >= H || cc < 0 || cc >= W) continue;
                     int n = rr * W + cc;
@@ -407,6 +437,15 @@ int nastar_oracle_forward_sm(const float* cost, const float* start, const float*
         free(g); free(hh); free(key); free(par); free(st);
     }
     return any_unsolvable ? ORACLE_ERR_UNSOLVABLE : ORACLE_OK;
+}
+
+int nastar_oracle_forward_sm(const float* cost, const float* start, const float* goal,
+                             const float* passable, int B, int H, int W, double g_ratio,
+                             int max_iters, float* histories, int64_t* paths, int32_t* sel_log,
+                             int32_t* iters_out, int32_t* status_out)
+{
+    return nastar_oracle_forward_sm_masked(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories, paths, sel_log,
+                                           iters_out, status_out, ORACLE_MOORE8);
 }
 
 /* heuristic table for spot checks against SURVEY.md 8(c) known values */

@@ -47,6 +47,13 @@ def _load():
         _lib.nastar_oracle_backward_dense.restype = ci
         _lib.nastar_oracle_forward_sm.argtypes = [fp, fp, fp, fp, ci, ci, ci, cd, ci, fp, i64p, i32p, i32p, i32p]
         _lib.nastar_oracle_forward_sm.restype = ci
+        cu = ctypes.c_uint
+        _lib.nastar_oracle_forward_dense_masked.argtypes = _lib.nastar_oracle_forward_dense.argtypes + [cu]
+        _lib.nastar_oracle_forward_dense_masked.restype = ci
+        _lib.nastar_oracle_backward_dense_masked.argtypes = _lib.nastar_oracle_backward_dense.argtypes + [cu]
+        _lib.nastar_oracle_backward_dense_masked.restype = ci
+        _lib.nastar_oracle_forward_sm_masked.argtypes = _lib.nastar_oracle_forward_sm.argtypes + [cu]
+        _lib.nastar_oracle_forward_sm_masked.restype = ci
         _lib.nastar_oracle_heuristic.argtypes = [ci, ci, ci, ci, fp]
         _lib.nastar_oracle_heuristic.restype = None
     return _lib
@@ -59,6 +66,7 @@ class OracleOutput(NamedTuple):
     iters: np.ndarray  # [B] int32
     t_batch: int  # last executed loop index of the whole batch (dense) / max(iters)-1 (sm)
     status: int
+    map_status: Optional[np.ndarray] = None  # [B] int32 per-map status (sm only): 0, or ERR_UNSOLVABLE when its open list ran empty
 
 
 def _f32(a):
@@ -80,8 +88,24 @@ def max_iters_for(W: int, Tmax: float = 1.0, training: bool = False) -> int:
     return int(t * W * W)
 
 
+MOORE8 = 0x1EF  # the reference's default neighbor_filter [[1,1,1],[1,0,1],[1,1,1]]
+
+
+def _entry(lib, name: str, neighbor_mask: Optional[int]):
+    """the C entry point `name` searching the neighbourhood of `neighbor_mask` (bit r*3+c <=> neighbor_filter cell (r, c) is 1, as in
+    include/nastar.h); None = the entry point without a mask argument (Moore-8)"""
+    if neighbor_mask is None:
+        return getattr(lib, name)
+    m = int(neighbor_mask)
+    if m & ~0x1FF or m & 0x10:
+        raise ValueError(f"neighbor_mask {m:#x}: 9 bits, centre (bit 4) clear")
+    f = getattr(lib, name + "_masked")
+    return lambda *args: f(*args, m)
+
+
 def forward(cost, start, goal, passable, g_ratio: float = 0.5, max_iters: Optional[int] = None,
-            mode: str = "dense", want_log: bool = False) -> OracleOutput:
+            mode: str = "dense", want_log: bool = False, neighbor_mask: Optional[int] = MOORE8) -> OracleOutput:
+    """``neighbor_mask``: the search neighbourhood as a 9-bit neighbor_filter mask (None: the entry points without a mask)"""
     lib = _load()
     cost, start, goal, passable = map(_f32, (cost, start, goal, passable))
     B, H, W = cost.shape
@@ -94,7 +118,7 @@ def forward(cost, start, goal, passable, g_ratio: float = 0.5, max_iters: Option
     logp = _p(log, ctypes.c_int32) if want_log else None
     if mode == "dense":
         tb = ctypes.c_int32(0)
-        rc = lib.nastar_oracle_forward_dense(
+        rc = _entry(lib, "nastar_oracle_forward_dense", neighbor_mask)(
             _p(cost, ctypes.c_float), _p(start, ctypes.c_float), _p(goal, ctypes.c_float),
             _p(passable, ctypes.c_float), B, H, W, float(g_ratio), int(max_iters),
             _p(hist, ctypes.c_float), _p(paths, ctypes.c_int64), logp, _p(iters, ctypes.c_int32),
@@ -102,7 +126,7 @@ def forward(cost, start, goal, passable, g_ratio: float = 0.5, max_iters: Option
         t_batch = int(tb.value)
     elif mode == "sm":
         status = np.empty((B,), np.int32)
-        rc = lib.nastar_oracle_forward_sm(
+        rc = _entry(lib, "nastar_oracle_forward_sm", neighbor_mask)(
             _p(cost, ctypes.c_float), _p(start, ctypes.c_float), _p(goal, ctypes.c_float),
             _p(passable, ctypes.c_float), B, H, W, float(g_ratio), int(max_iters),
             _p(hist, ctypes.c_float), _p(paths, ctypes.c_int64), logp, _p(iters, ctypes.c_int32),
@@ -110,18 +134,18 @@ def forward(cost, start, goal, passable, g_ratio: float = 0.5, max_iters: Option
         t_batch = int(iters.max()) - 1
     else:
         raise ValueError(mode)
-    return OracleOutput(hist, paths, log, iters, t_batch, rc)
+    return OracleOutput(hist, paths, log, iters, t_batch, rc, status if mode == "sm" else None)
 
 
 def backward(grad_hist, cost, start, goal, passable, g_ratio: float = 0.5,
-             max_iters: Optional[int] = None) -> np.ndarray:
+             max_iters: Optional[int] = None, neighbor_mask: Optional[int] = MOORE8) -> np.ndarray:
     lib = _load()
     grad_hist, cost, start, goal, passable = map(_f32, (grad_hist, cost, start, goal, passable))
     B, H, W = cost.shape
     if max_iters is None:
         max_iters = W * W
     out = np.zeros((B, H, W), np.float32)
-    rc = lib.nastar_oracle_backward_dense(
+    rc = _entry(lib, "nastar_oracle_backward_dense", neighbor_mask)(
         _p(grad_hist, ctypes.c_float), _p(cost, ctypes.c_float), _p(start, ctypes.c_float),
         _p(goal, ctypes.c_float), _p(passable, ctypes.c_float), B, H, W, float(g_ratio),
         int(max_iters), _p(out, ctypes.c_float))

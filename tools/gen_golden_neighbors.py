@@ -26,6 +26,11 @@ OUT = os.path.join(ROOT, "tests", "golden", "neighbors")
 VON_NEUMANN = [[0, 1, 0], [1, 0, 1], [0, 1, 0]]
 DOWN_RIGHT = [[1, 1, 0], [1, 0, 0], [0, 0, 0]]  # the issue's "down / right moves only": opens offsets (+1,+1), (+1,0), (0,+1)
 ASYM = [[1, 1, 0], [1, 0, 1], [0, 1, 0]]        # von Neumann + the down-right diagonal (filter cell (0,0) opens offset (+1,+1))
+# filters that set cells (0,2), (2,0), (2,2) -- bits 2, 6, 8, the offsets (+1,-1), (-1,+1), (-1,-1) -- without being Moore-8
+UP_LEFT = [[0, 0, 0], [0, 0, 1], [0, 1, 1]]     # up, left and the up-left diagonal only: offsets (-1,0), (0,-1), (-1,-1)
+MOORE_NO_DR = [[0, 1, 1], [1, 0, 1], [1, 1, 1]]  # Moore-8 without the down-right diagonal (filter cell (0,0))
+MOORE_NO_DL = [[1, 1, 0], [1, 0, 1], [1, 1, 1]]  # Moore-8 without the down-left diagonal (filter cell (0,2)): cell (2,0) without (0,2)
+ANTI = [[0, 0, 1], [0, 0, 1], [0, 1, 0]]        # directed: (+1,-1), (0,-1), (-1,0) -- cell (0,2) without (2,0)
 
 
 def load_reference(checkout: str):
@@ -104,6 +109,9 @@ def fixture(B=1):
     return m, s, g
 
 
+ONLY = None  # --only: the names to (re)write; every other case is still run (its asserts hold) but its file is left as it is
+
+
 def run(ref, name, filt, maps, start, goal, cost=None, g_ratio=0.5, Tmax=1.0, training=False, target=None, store=False):
     B, _, H, W = maps.shape
     m = ref.DifferentiableAstar(g_ratio=g_ratio, Tmax=Tmax)
@@ -134,6 +142,8 @@ def run(ref, name, filt, maps, start, goal, cost=None, g_ratio=0.5, Tmax=1.0, tr
         loss.backward()
         d["target_bits"] = pack(target)
         d["grad_cost"] = c.grad.detach().numpy().astype(np.float32)
+    if ONLY is not None and name not in ONLY:
+        return d
     np.savez_compressed(os.path.join(OUT, name + ".npz"), **d)
     print(f"{name}: B={B} {H}x{W} g_ratio={g_ratio} filter={np.asarray(filt).reshape(-1).tolist()} t_batch={sel.shape[1] - 1} "
           f"hist_sum[:4]={d['hist_sum'][:4]} path_sum[:4]={d['path_sum'][:4]}")
@@ -143,7 +153,10 @@ def run(ref, name, filt, maps, start, goal, cost=None, g_ratio=0.5, Tmax=1.0, tr
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--reference", required=True, help="root of a reference checkout (holds src/neural_astar/planner/differentiable_astar.py)")
+    ap.add_argument("--only", nargs="+", help="write only these vectors (the others stay byte-identical)")
     args = ap.parse_args()
+    global ONLY
+    ONLY = set(args.only) if args.only else None
     ref = load_reference(args.reference)
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -181,6 +194,21 @@ def main():
     pr = random_problems(2, 120, 120, VON_NEUMANN, seed=707, max_dist=10)
     tgt = (rng.random((2, 1, 120, 120)) < 0.02).astype(np.float32)
     run(ref, "grad_rand120_vn_train_T025", VON_NEUMANN, *pr, cost=rng.random((2, 1, 120, 120)).astype(np.float32), Tmax=0.25, training=True,
+        target=tgt)
+    # 6. the filter cells no filter above sets (0,2), (2,0), (2,2): small maps, U(0,1) costs (an RNG of its own: the vectors above stay as they are)
+    rng = np.random.Generator(np.random.PCG64(808))
+    pr = random_problems(6, 16, 16, UP_LEFT, seed=809)
+    run(ref, "rand16_upleft_ucost_g050", UP_LEFT, *pr, cost=rng.random((6, 1, 16, 16)).astype(np.float32))
+    pr = random_problems(6, 24, 20, MOORE_NO_DR, seed=810)
+    run(ref, "rand24x20_moorenodr_ucost_g050", MOORE_NO_DR, *pr, cost=rng.random((6, 1, 24, 20)).astype(np.float32))
+    pr = random_problems(6, 20, 20, ANTI, seed=811)
+    run(ref, "rand20_antidl_ucost_g050", ANTI, *pr, cost=rng.random((6, 1, 20, 20)).astype(np.float32))
+    # ... and g_ratio 0.8 with costs up to 10
+    pr = random_problems(6, 18, 22, MOORE_NO_DL, seed=812)
+    run(ref, "rand18x22_moorenodl_u10cost_g080", MOORE_NO_DL, *pr, cost=(10.0 * rng.random((6, 1, 18, 22))).astype(np.float32), g_ratio=0.8)
+    pr = random_problems(4, 16, 16, UP_LEFT, seed=813)
+    tgt = (rng.random((4, 1, 16, 16)) < 0.2).astype(np.float32)
+    run(ref, "grad_rand16_upleft_train_T050", UP_LEFT, *pr, cost=rng.random((4, 1, 16, 16)).astype(np.float32), Tmax=0.5, training=True,
         target=tgt)
 
 
