@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define NASTAR_VERSION 700 /* 0.7.0: the masked entry points nastar_forward_ex_masked / nastar_forward_batchloop_finish_masked / nastar_backward_replay_ordered_masked (DifferentiableAstar.neighbor_filter, NASTAR_NEIGHBORS_*); 0.6.0: nastar_forward_batchloop_finish (the reference's batch loop to the letter, any size, no host round trip), NASTAR_FLAG_MARK_COUPLED; the A/B flags left the ABI; 0.5.0: nastar_forward_ex (status summary, checked placement), nastar_placement_from_levels; 0.4.1: nastar_forward_ordered (placement); 0.4.0: round-4 search instruction stream, unit-cost LDS layout */
+#define NASTAR_VERSION 800 /* 0.8.0: the entry points with a caller-supplied heuristic nastar_forward_ex_heuristic / nastar_forward_batchloop_finish_heuristic / nastar_backward_replay_ordered_heuristic, NASTAR_ERR_BAD_HEURISTIC; 0.7.0: the masked entry points nastar_forward_ex_masked / nastar_forward_batchloop_finish_masked / nastar_backward_replay_ordered_masked (DifferentiableAstar.neighbor_filter, NASTAR_NEIGHBORS_*); 0.6.0: nastar_forward_batchloop_finish (the reference's batch loop to the letter, any size, no host round trip), NASTAR_FLAG_MARK_COUPLED; the A/B flags left the ABI; 0.5.0: nastar_forward_ex (status summary, checked placement), nastar_placement_from_levels; 0.4.1: nastar_forward_ordered (placement); 0.4.0: round-4 search instruction stream, unit-cost LDS layout */
 
 /* status codes (function return values) */
 #define NASTAR_OK 0
@@ -55,6 +55,8 @@ extern "C" {
 #define NASTAR_ERR_WORKSPACE 6   /* workspace_bytes smaller than nastar_workspace_bytes()            */
 #define NASTAR_ERR_NOT_UNIT_COST 7 /* per-map status only: NASTAR_FLAG_UNIT_COST was passed but this map holds a value other than 0.0 / 1.0;
                                       its outputs are all-zero -- run it again without the flag */
+#define NASTAR_ERR_BAD_HEURISTIC 8 /* per-map status only (the _heuristic entry points): this map's heuristic holds a NaN or an infinite value; the
+                                      map is not searched, the other maps of the batch are */
 
 /* flags for nastar_workspace_bytes / nastar_forward* / nastar_backward_replay*.  (The A/B switches of earlier rounds -- older instruction
  * streams, the compiler-generated step, variants of the large-map kernel -- are not part of this ABI any more: they exist in the development
@@ -188,6 +190,21 @@ int nastar_forward_ex_masked(const float* cost, const float* start, const float*
                              int flags, const int32_t* order, int32_t* order_out, int32_t* status_summary, int32_t* completion_counter,
                              unsigned neighbor_mask, void* stream);
 
+/* nastar_forward_ex_masked with a CALLER-SUPPLIED HEURISTIC: `h0` [B, H, W] fp32 device takes the place of the reference's get_heuristic
+ * (:191 h = h0 + cost) -- zero (Dijkstra), weighted, Manhattan, a network's output; any finite values, negative ones included, and h0(goal)
+ * need not be 0.  Exactly the reference run with `get_heuristic = lambda goal_maps: h0`.  neighbor_mask as above (NASTAR_NEIGHBORS_MOORE8 for
+ * the default filter); NULL `h0` is NASTAR_ERR_NULL.  A map whose heuristic holds a NaN or an infinite value ends with the per-map status
+ * NASTAR_ERR_BAD_HEURISTIC (status_summary cell 8) and is not searched; the other maps are.  LDS-resident sizes keep
+ * fl((1-g_ratio) fl(h0 + cost)) per cell in LDS (13 B per cell), the large-map kernel reads h0 beside the cost.  With a free heuristic a
+ * finished map is often NOT at a fixed point of the reference's batch loop, whatever g_ratio: a caller that wants the batch run passes
+ * NASTAR_FLAG_MARK_COUPLED and calls nastar_forward_batchloop_finish_heuristic.  Gradient: dL/dh0 == dL/dcost, the tensor
+ * nastar_backward_replay_ordered_heuristic writes (g is detached every step, :239: the loss sees both only through h0 + cost). */
+int nastar_forward_ex_heuristic(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
+                                double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
+                                int32_t* iters_out, int32_t* status_out, uint8_t* packed_out, void* workspace, size_t workspace_bytes,
+                                int flags, const int32_t* order, int32_t* order_out, int32_t* status_summary, int32_t* completion_counter,
+                                unsigned neighbor_mask, const float* h0, void* stream);
+
 /*
  * The reference's BATCH LOOP to the letter (differentiable_astar.py:203-252, :219-225, :251-252), for the class of inputs in which it matters.
  * The reference steps EVERY map until all maps of the batch select their goal in the same step; a finished map keeps its goal on the open
@@ -215,6 +232,11 @@ int nastar_forward_batchloop_finish_masked(const float* cost, const float* start
                                            int W, double g_ratio, int max_iters, float* histories_out, int64_t* paths_out,
                                            int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out, void* workspace,
                                            size_t workspace_bytes, unsigned neighbor_mask, void* stream);
+/* ... after a nastar_forward_ex_heuristic launch: the SAME neighbor_mask and h0 */
+int nastar_forward_batchloop_finish_heuristic(const float* cost, const float* start, const float* goal, const float* passable, int B, int H,
+                                              int W, double g_ratio, int max_iters, float* histories_out, int64_t* paths_out,
+                                              int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out, void* workspace,
+                                              size_t workspace_bytes, unsigned neighbor_mask, const float* h0, void* stream);
 /* Spin (pause loop, at most timeout_us) until *word_host != 0; returns 1 when it is, 0 on timeout.  HOST pointer (pinned memory). */
 int nastar_host_wait_nonzero(const volatile int32_t* word_host, int timeout_us);
 
@@ -268,6 +290,14 @@ int nastar_backward_replay_ordered_masked(const float* grad_histories, const flo
                                           int max_iters, const int32_t* iters, const int32_t* t_batch_dev, float* grad_cost_out,
                                           void* workspace, size_t workspace_bytes, int flags, const int32_t* order,
                                           unsigned neighbor_mask, void* stream);
+/* ... for the log of a nastar_forward_ex_heuristic search: the keys are rebuilt from the SAME h0 (and neighbor_mask); grad_cost_out is
+ * dL/dcost AND dL/dh0 (the compiled replay loop, every size) */
+int nastar_backward_replay_ordered_heuristic(const float* grad_histories, const float* histories, const float* opt_trajs,
+                                             const float* grad_loss_dev, const float* cost, const float* start, const float* goal,
+                                             const float* passable, const int32_t* sel_log, int B, int H, int W, double g_ratio,
+                                             int max_iters, const int32_t* iters, const int32_t* t_batch_dev, float* grad_cost_out,
+                                             void* workspace, size_t workspace_bytes, int flags, const int32_t* order,
+                                             unsigned neighbor_mask, const float* h0, void* stream);
 
 /*
  * Backward of `histories` w.r.t. `cost` (paths carry no gradient):

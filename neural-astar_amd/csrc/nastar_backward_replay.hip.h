@@ -140,8 +140,9 @@ __global__ __launch_bounds__(256) void nastar_bwdr_fill_kernel(const BwdRArgs a)
 }
 
 // cells still on the open list when the replay ended: their intervals close at the final (A, B) the replay left in the header
-template <bool kWide, bool kFastDiv>
-__global__ __launch_bounds__(256) void nastar_bwdr_sweep_kernel(const BwdRArgs a, const float rcp_sqrtW)
+// kHeur (nastar_bwdr_sweep_heuristic_kernel below): h0 is read from the caller's heuristic maps `h0p`
+template <bool kWide, bool kFastDiv, bool kHeur>
+__device__ __forceinline__ void bwdr_sweep(const BwdRArgs& a, const float rcp_sqrtW, const float* __restrict__ h0p)
 {
     using stamp_t = typename std::conditional<kWide, uint32_t, unsigned short>::type;
     const int b = blockIdx.y;
@@ -164,12 +165,26 @@ __global__ __launch_bounds__(256) void nastar_bwdr_sweep_kernel(const BwdRArgs a
             const int ti = (int)t0[i];
             const double A0 = hist[2 * ti], B0 = hist[2 * ti + 1];
             const int ri = i / d.W, ci = i - ri * d.W;
-            const float h0v = kWide ? heuristic0(ri, ci, goal_r, goal_c) : heuristic0_fast(ri, ci, goal_r, goal_c);
+            float h0v;
+            if constexpr (kHeur) h0v = h0p[(size_t)b * (size_t)d.HW + i];
+            else h0v = kWide ? heuristic0(ri, ci, goal_r, goal_c) : heuristic0_fast(ri, ci, goal_r, goal_c);
             const float v = bwdr_v<kFastDiv>(d, gi, d.omg * (h0v + cst[i]), rcp_sqrtW);
             const float dA = (float)(A - A0), dB = (float)(B - B0);
             gout[i] += (a.kfac * v) * (G[i] * dA - dB);  // (the replay's atomics are over: one thread per cell)
         }
     }
+}
+
+template <bool kWide, bool kFastDiv>
+__global__ __launch_bounds__(256) void nastar_bwdr_sweep_kernel(const BwdRArgs a, const float rcp_sqrtW)
+{
+    bwdr_sweep<kWide, kFastDiv, false>(a, rcp_sqrtW, nullptr);
+}
+
+template <bool kWide, bool kFastDiv>
+__global__ __launch_bounds__(256) void nastar_bwdr_sweep_heuristic_kernel(const BwdRArgs a, const float rcp_sqrtW, const float* __restrict__ h0p)
+{
+    bwdr_sweep<kWide, kFastDiv, true>(a, rcp_sqrtW, h0p);
 }
 
 // kHistLds: the (A, B) history lives in LDS behind the state (16 B per executed step): no global round trip inside the loop
@@ -181,15 +196,28 @@ __global__ __launch_bounds__(256) void nastar_bwdr_sweep_kernel(const BwdRArgs a
 template <bool kGlobal, bool kHistLds, bool kFastDiv, bool kWide = false>
 __global__ __launch_bounds__(64) void nastar_backward_replay_kernel(const BwdRArgs a, const float rcp_sqrtW)
 {
-    constexpr bool kMasked = false;
+    constexpr bool kMasked = false, kHeur = false;
     constexpr uint32_t nmask = 0x1EFu;  // (NASTAR_NEIGHBORS_MOORE8; never read)
+    constexpr const float* h0p = nullptr;
 #include "nastar_backward_replay_body.inc"
 }
 
 template <bool kGlobal, bool kHistLds, bool kFastDiv, bool kWide = false>
 __global__ __launch_bounds__(64) void nastar_backward_replay_masked_kernel(const BwdRArgs a, const float rcp_sqrtW, const uint32_t nmask)
 {
-    constexpr bool kMasked = true;
+    constexpr bool kMasked = true, kHeur = false;
+    constexpr const float* h0p = nullptr;
+#include "nastar_backward_replay_body.inc"
+}
+
+// the replay of a search that ran with a caller-supplied heuristic (nastar_backward_replay_ordered_heuristic): the keys are rebuilt from
+// `h0p`, the tensor the forward searched with; it always takes the neighbourhood mask.  dL/dh0 is the tensor this kernel writes for the
+// cost (the loss sees both only through h = h0 + cost: g is detached every step, differentiable_astar.py:239).
+template <bool kGlobal, bool kHistLds, bool kFastDiv, bool kWide = false>
+__global__ __launch_bounds__(64) void nastar_backward_replay_heuristic_kernel(const BwdRArgs a, const float rcp_sqrtW, const uint32_t nmask,
+                                                                              const float* __restrict__ h0p)
+{
+    constexpr bool kMasked = true, kHeur = true;
 #include "nastar_backward_replay_body.inc"
 }
 

@@ -1,9 +1,8 @@
 // nastar_backward_replay_body.inc -- the body of nastar_backward_replay_kernel and nastar_backward_replay_masked_kernel
 // (nastar_backward_replay.hip.h), included INSIDE each kernel so that the kernel without a mask keeps its instruction stream (see
-// nastar_forward_compact_body.inc).  In scope: kGlobal, kHistLds, kFastDiv, kWide, `a`, `rcp_sqrtW`, and `constexpr bool kMasked` / `nmask`.
+// nastar_forward_compact_body.inc).  In scope: kGlobal, kHistLds, kFastDiv, kWide, `a`, `rcp_sqrtW`, and `constexpr bool kMasked` / `nmask`, `constexpr bool kHeur` / `h0p`.
     static_assert(!kWide || kGlobal, "wide stamps exist for the HBM state only");
     using stamp_t = typename std::conditional<kWide, uint32_t, unsigned short>::type;
-    auto h0 = [](int r, int c, int gr, int gc) { return kWide ? heuristic0(r, c, gr, gc) : heuristic0_fast(r, c, gr, gc); };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = (a.order == nullptr || (a.order_bad != nullptr && *a.order_bad != 0)) ? (int)blockIdx.x : a.order[blockIdx.x];
     if ((unsigned)b >= (unsigned)a.B_total) return;  // not a permutation: never touch memory outside the batch
@@ -16,6 +15,13 @@
     stamp_t* t0 = reinterpret_cast<stamp_t*>(G + d.HWp);  // [HWp] history index at which the cell was (re)opened
     double* sd = reinterpret_cast<double*>(smem + (kGlobal ? 0 : (size_t)d.HWp * 14));  // S, D: always in LDS
     const size_t off = (size_t)b * (size_t)d.HW;
+    // h0 of cell `i` at (r, c): the built-in heuristic from the coordinates, or (kHeur: nastar_backward_replay_heuristic_kernel, `h0p` = the
+    // caller's heuristic maps) the value the forward searched with, read from the tensor
+    const float* const h0m = kHeur ? h0p + off : nullptr;
+    auto h0 = [=](int i, int r, int c, int gr, int gc) {
+        if constexpr (kHeur) return h0m[i];
+        else return kWide ? heuristic0(r, c, gr, gc) : heuristic0_fast(r, c, gr, gc);
+    };
     static_assert(!(kGlobal && kHistLds), "a map too large for LDS keeps its history in the workspace as well");
     double* hist = kHistLds ? reinterpret_cast<double*>(smem + (size_t)d.HWp * 14 + 16) : a.hist + (size_t)b * (size_t)a.hist_len * 2;
     float* gout = a.grad_cost + off;
@@ -75,7 +81,7 @@
         if (goal_zeroed) st_st<kGlobal>(&G[gidx], 0.f);
         // open list = {start} (:187), g[start] = 0 (:193): the start is open from history index 0
         const int r = sidx / d.W, c = sidx - r * d.W;
-        const float hh = d.omg * (h0(r, c, goal_r, goal_c) + st_ld<kGlobal>(&cst[sidx]));
+        const float hh = d.omg * (h0(sidx, r, c, goal_r, goal_c) + st_ld<kGlobal>(&cst[sidx]));
         const float v = bwdr_v<kFastDiv>(d, 0.0f, hh, rcp_sqrtW);
         st_st<kGlobal>(&g[sidx], 0.0f);
         sd[0] = (double)v;
@@ -127,7 +133,7 @@
         const float Gl = st_ld<kGlobal>(&G[il]);
         const int tl = (int)st_ld<kGlobal>(&t0[il]);
         const int rl = il / d.W, cc = il - rl * d.W;
-        const float hh = d.omg * (h0(rl, cc, goal_r, goal_c) + cl);
+        const float hh = d.omg * (h0(il, rl, cc, goal_r, goal_c) + cl);
         const float g2 = gs + cs;
         const bool upd = inb & (gl > g2);
         const bool was_open = fabsf(gl) < NASTAR_POS_INF;
@@ -202,7 +208,7 @@
             const double A0 = hist_ld<kHistLds>(&hist[2 * ti]);
             const double B0 = hist_ld<kHistLds>(&hist[2 * ti + 1]);
             const int ri = i / d.W, ci = i - ri * d.W;
-            const float hh = d.omg * (h0(ri, ci, goal_r, goal_c) + st_ld<kGlobal>(&cst[i]));
+            const float hh = d.omg * (h0(i, ri, ci, goal_r, goal_c) + st_ld<kGlobal>(&cst[i]));
             const float v = bwdr_v<kFastDiv>(d, gi, hh, rcp_sqrtW);
             const float dA = (float)(A - A0), dB = (float)(B - B0);
             unsafeAtomicAdd(&gout[i], (a.kfac * v) * (st_ld<kGlobal>(&G[i]) * dA - dB));

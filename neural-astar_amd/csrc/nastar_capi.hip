@@ -115,8 +115,9 @@ __global__ __launch_bounds__(1024) void nastar_order_check_kernel(const int* __r
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, bool kAsm = false>
 __global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCArgs a, const float rcp_sqrtW)
 {
-    constexpr bool kMasked = false;
+    constexpr bool kMasked = false, kHeur = false;
     constexpr uint32_t nmask = NASTAR_NEIGHBORS_MOORE8;
+    constexpr const float* h0 = nullptr;
 #include "nastar_forward_compact_body.inc"
 }
 
@@ -124,7 +125,19 @@ __global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCAr
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 __global__ __launch_bounds__(64) void nastar_forward_compact_masked_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask)
 {
-    constexpr bool kAsm = false, kMasked = true;
+    constexpr bool kAsm = false, kMasked = true, kHeur = false;
+    constexpr const float* h0 = nullptr;
+#include "nastar_forward_compact_body.inc"
+}
+
+// the compiled step loop with a caller-supplied heuristic (nastar_forward_ex_heuristic): h0 = the heuristic maps [B, H, W].  Load time
+// stores hh = fl((1-g_ratio) fl(h0 + cost)) per cell in a third LDS array (13 B per cell, compact_heur_lds_bytes); the step reads it
+// beside (g, cost) and computes no heuristic.  It always takes the neighbourhood mask (NASTAR_NEIGHBORS_MOORE8 for the default filter).
+template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
+__global__ __launch_bounds__(64) void nastar_forward_compact_heuristic_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask,
+                                                                              const float* __restrict__ h0)
+{
+    constexpr bool kAsm = false, kMasked = true, kHeur = true;
 #include "nastar_forward_compact_body.inc"
 }
 
@@ -204,6 +217,26 @@ __global__ __launch_bounds__(64) void nastar_heuristic_kernel(const float* goal,
     const int gr = (int)div_magic((uint32_t)gidx, magicW), gc = gidx - gr * W;
     for (int i = lane; i < HW; i += 64) {
         int r = (int)div_magic((uint32_t)i, magicW), c = i - r * W;
+        out[(size_t)b * HW + i] = heuristic0(r, c, gr, gc);
+    }
+}
+
+// ... for maps above 65,535 cells (the large-map kernel's sizes): rows by integer division, the goal cell found by all lanes of a workgroup per map
+__global__ __launch_bounds__(256) void nastar_heuristic_large_kernel(const float* goal, float* out, int H, int W)
+{
+    __shared__ int s_goal;
+    const int b = blockIdx.x, HW = H * W;
+    const float* gm = goal + (size_t)b * HW;
+    if (threadIdx.x == 0) s_goal = 0;
+    __syncthreads();
+    int gidx = -1;
+    for (int i = threadIdx.x; i < HW; i += 256)
+        if (gm[i] != 0.f) gidx = i;
+    if (gidx >= 0) atomicMax(&s_goal, gidx);
+    __syncthreads();
+    const int gr = s_goal / W, gc = s_goal - gr * W;
+    for (int i = threadIdx.x; i < HW; i += 256) {
+        const int r = i / W, c = i - r * W;
         out[(size_t)b * HW + i] = heuristic0(r, c, gr, gc);
     }
 }
@@ -432,9 +465,11 @@ static bool neighbor_mask_valid(unsigned m) { return (m & ~0x1FFu) == 0u && (m &
 
 // the neighbourhood of a launch: the Moore-8 stencil of the plain kernels, or (the _masked entry points) a neighbor_filter's mask, searched by
 // the masked twin of each kernel for EVERY mask, Moore-8 included
+// h0: the caller's heuristic maps (the _heuristic entry points; they always take a mask), searched by the third twin of each kernel
 struct Neighbourhood {
     bool masked = false;
     uint32_t mask = NASTAR_NEIGHBORS_MOORE8;
+    const float* h0 = nullptr;
 };
 
 // map widths for which the FMA-based division by fl32(sqrt(W)) was verified bit-exact against IEEE division for
@@ -448,31 +483,33 @@ static bool fastdiv_verified(int W)
     return false;
 }
 
-template <bool kMasked, bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
+// kKind: 0 = Moore-8, 1 = masked, 2 = masked with a caller-supplied heuristic
+template <int kKind, bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 static auto compiled_compact_kernel()
 {
-    if constexpr (kMasked) return &nastar_forward_compact_masked_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
+    if constexpr (kKind == 2) return &nastar_forward_compact_heuristic_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
+    else if constexpr (kKind == 1) return &nastar_forward_compact_masked_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
     else return &nastar_forward_compact_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
 }
 
 // the compact-state kernel for a map: a hand-scheduled stream where one exists (Moore-8 only: the streams hard-wire the stencil), else the
 // compiled step loop -- compile-time sizes for 16x16, 32x32 and 64x64, one chunk minimum per lane, or runtime sizes
-template <bool kMasked, bool kLog>
+template <int kKind, bool kLog>
 static auto compact_kernel(const CompactDims& d, bool vec4, bool fast, bool use_asm)
 {
-    if constexpr (!kMasked) {
+    if constexpr (kKind == 0) {
         if (use_asm && vec4 && fast && d.H == 32 && d.W == 32) return &nastar_forward_compact_kernel<true, 5, 5, 1, true, kLog, true>;
         if (use_asm && vec4 && fast && d.H == 16 && d.W == 16) return &nastar_forward_compact_kernel<true, 4, 4, 1, true, kLog, true>;
         if (use_asm && vec4 && fast && d.H == 64 && d.W == 64) return &nastar_forward_compact_kernel<true, 6, 6, 4, true, kLog, true>;
     }
-    if (vec4 && fast && d.H == 32 && d.W == 32) return compiled_compact_kernel<kMasked, true, 5, 5, 1, true, kLog>();
-    if (vec4 && fast && d.H == 64 && d.W == 64) return compiled_compact_kernel<kMasked, true, 6, 6, 4, true, kLog>();
-    if (vec4 && fast && d.H == 16 && d.W == 16) return compiled_compact_kernel<kMasked, true, 4, 4, 1, true, kLog>();
-    if (vec4 && fast && d.CPL == 1) return compiled_compact_kernel<kMasked, true, 0, 0, 1, true, kLog>();
-    if (vec4 && fast) return compiled_compact_kernel<kMasked, true, 0, 0, 0, true, kLog>();
-    if (vec4) return compiled_compact_kernel<kMasked, true, 0, 0, 0, false, kLog>();
-    if (fast) return compiled_compact_kernel<kMasked, false, 0, 0, 0, true, kLog>();
-    return compiled_compact_kernel<kMasked, false, 0, 0, 0, false, kLog>();
+    if (vec4 && fast && d.H == 32 && d.W == 32) return compiled_compact_kernel<kKind, true, 5, 5, 1, true, kLog>();
+    if (vec4 && fast && d.H == 64 && d.W == 64) return compiled_compact_kernel<kKind, true, 6, 6, 4, true, kLog>();
+    if (vec4 && fast && d.H == 16 && d.W == 16) return compiled_compact_kernel<kKind, true, 4, 4, 1, true, kLog>();
+    if (vec4 && fast && d.CPL == 1) return compiled_compact_kernel<kKind, true, 0, 0, 1, true, kLog>();
+    if (vec4 && fast) return compiled_compact_kernel<kKind, true, 0, 0, 0, true, kLog>();
+    if (vec4) return compiled_compact_kernel<kKind, true, 0, 0, 0, false, kLog>();
+    if (fast) return compiled_compact_kernel<kKind, false, 0, 0, 0, true, kLog>();
+    return compiled_compact_kernel<kKind, false, 0, 0, 0, false, kLog>();
 }
 
 }  // namespace nastar
@@ -567,17 +604,24 @@ static int forward_hybrid(const FwdLaunch& f, int* marks_out)
     hd.rcp_sqrtW = 1.0f / hd.sqrtW;
     hd.inv_W = 1.0f / (float)f.W;
     // headers (start / goal cell per map) to -1: the fill launch raises them with atomicMax
-    hipLaunchKernelGGL(nastar_hybrid_header_kernel, dim3((unsigned)((f.B + 255) / 256)), dim3(256), 0, s, ha.workspace, slab,
-                       hybrid_header_offset(hd.HW), f.B);
     const unsigned per_map = (unsigned)((hd.nchunks * 64 + 255) / 256);
     const dim3 grid2(per_map < 64u ? per_map : 64u, (unsigned)f.B);
-    hipLaunchKernelGGL(nastar_hybrid_fill_kernel, grid2, dim3(256), 0, s, ha);
+    if (f.nb.h0) {  // (the fill launch also looks at every heuristic value once: a NaN / infinite one marks its map in the header)
+        hipLaunchKernelGGL(nastar_hybrid_header_heuristic_kernel, dim3((unsigned)((f.B + 255) / 256)), dim3(256), 0, s, ha.workspace, slab,
+                           hybrid_header_offset(hd.HW), f.B);
+        hipLaunchKernelGGL(nastar_hybrid_fill_heuristic_kernel, grid2, dim3(256), 0, s, ha, f.nb.h0);
+    } else {
+        hipLaunchKernelGGL(nastar_hybrid_header_kernel, dim3((unsigned)((f.B + 255) / 256)), dim3(256), 0, s, ha.workspace, slab,
+                           hybrid_header_offset(hd.HW), f.B);
+        hipLaunchKernelGGL(nastar_hybrid_fill_kernel, grid2, dim3(256), 0, s, ha);
+    }
     const size_t hl = hybrid_lds_bytes(hd.HW);
     if (hl > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
-    const int rc = with_bools([&](auto fd, auto lk, auto masked) {
-        if constexpr (masked) return launch(nastar_forward_hybrid_masked_kernel<fd, lk>, f.B, hl, s, ha, f.nb.mask);
+    const int rc = with_bools([&](auto fd, auto lk, auto masked, auto heur) {
+        if constexpr (heur) return launch(nastar_forward_hybrid_heuristic_kernel<fd, lk>, f.B, hl, s, ha, f.nb.mask, f.nb.h0);
+        else if constexpr (masked) return launch(nastar_forward_hybrid_masked_kernel<fd, lk>, f.B, hl, s, ha, f.nb.mask);
         else return launch(nastar_forward_hybrid_kernel<fd, lk>, f.B, hl, s, ha);
-    }, fastdiv_verified(f.W), (f.flags & NASTAR_FLAG_LOCKSTEP) != 0, f.nb.masked);
+    }, fastdiv_verified(f.W), (f.flags & NASTAR_FLAG_LOCKSTEP) != 0, f.nb.masked, f.nb.h0 != nullptr);
     if (rc) return rc;
     if (!ha.bitmap) hipLaunchKernelGGL(nastar_hybrid_store_kernel, grid2, dim3(256), 0, s, ha);  // (a probe launch has no outputs)
     hipError_t he = hipGetLastError();
@@ -603,7 +647,7 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     FwdCArgs c;
     int rc = make_cdims(f.B, f.H, f.W, f.max_iters, f.g_ratio, c.d);
     if (rc) return rc;
-    const size_t lds = compact_lds_bytes(c.d.HWp, c.d.NCp);
+    const size_t lds = f.nb.h0 ? compact_heur_lds_bytes(c.d.HWp, c.d.NCp) : compact_lds_bytes(c.d.HWp, c.d.NCp);
     if (lds > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(f.stream);
     c.cost = f.cost; c.start = f.start; c.goal = f.goal; c.passable = f.passable;
@@ -625,7 +669,7 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     c.flags = f.flags;
     c.B = f.B;
     const bool vec4 = (f.W % 4 == 0) && aligned16(f.cost) && aligned16(f.start) && aligned16(f.goal) && aligned16(f.passable) &&
-                      aligned16(f.histories_out) && aligned16(f.paths_out);
+                      aligned16(f.histories_out) && aligned16(f.paths_out) && aligned16(f.nb.h0);
     if (f.packed_out && vec4 && (c.d.HW % 8 == 0)) {  // fused emission of the bit-packed masks
         c.packed = f.packed_out;
         packed_done = true;
@@ -645,11 +689,12 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     const bool rank_after = f.order_out && (long long)f.B > resident_capacity(kernel_lds);
     if (rank_after) c.order_out = nullptr;
     if (unit) rc = forward_unit(c, marks_out, kernel_lds, rcp, s);
-    else rc = with_bools([&](auto masked, auto lg) {
-        const auto kern = compact_kernel<masked, lg>(c.d, vec4, fast, use_asm);
-        if constexpr (masked) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask);
+    else rc = with_bools([&](auto masked, auto heur, auto lg) {
+        const auto kern = compact_kernel<(heur ? 2 : masked ? 1 : 0), lg>(c.d, vec4, fast, use_asm);
+        if constexpr (heur) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask, f.nb.h0);
+        else if constexpr (masked) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask);
         else return launch(kern, f.B, lds, s, c, rcp);
-    }, f.nb.masked, f.sel_log_out != nullptr);
+    }, f.nb.masked, f.nb.h0 != nullptr, f.sel_log_out != nullptr);
     return (rc == NASTAR_OK && rank_after) ? nastar_placement_from_levels(f.iters_out, f.B, f.order_out, f.stream) : rc;
 }
 
@@ -729,6 +774,24 @@ int nastar_forward_ex_masked(const float* cost, const float* start, const float*
     return forward(f);
 }
 
+int nastar_forward_ex_heuristic(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
+                                int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
+                                uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
+                                int32_t* status_summary, int32_t* completion_counter, unsigned neighbor_mask, const float* h0, void* stream)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    if (!h0) return NASTAR_ERR_NULL;
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, flags, stream};
+    f.packed_out = packed_out;
+    f.order = order;
+    f.order_out = order_out;
+    f.summary = status_summary;
+    f.done_counter = completion_counter;
+    f.nb = Neighbourhood{true, neighbor_mask, h0};
+    return forward(f);
+}
+
 static int batchloop_finish(const FwdLaunch& f)
 {
     if (!f.cost || !f.start || !f.goal || !f.passable || !f.histories_out || !f.paths_out || !f.iters_out || !f.status_out || !f.workspace)
@@ -778,6 +841,19 @@ int nastar_forward_batchloop_finish_masked(const float* cost, const float* start
     FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
                 workspace, workspace_bytes, 0, stream};
     f.nb = Neighbourhood{true, neighbor_mask};
+    return batchloop_finish(f);
+}
+
+int nastar_forward_batchloop_finish_heuristic(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
+                                              double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
+                                              int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes,
+                                              unsigned neighbor_mask, const float* h0, void* stream)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    if (!h0) return NASTAR_ERR_NULL;
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, 0, stream};
+    f.nb = Neighbourhood{true, neighbor_mask, h0};
     return batchloop_finish(f);
 }
 
@@ -917,11 +993,12 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
         // history in LDS as long as at least 2 maps (or what the state alone allows) stay resident per CU
         const size_t st = bwdr_state_bytes(a.d.HWp), with_hist = st + (size_t)hlen * 16;
         const bool hist_lds = with_hist <= kMaxLdsBytes && (kMaxLdsBytes / with_hist >= 2 || kMaxLdsBytes / st < 2);
-        return with_bools([&](auto hl, auto fd, auto masked) {
+        return with_bools([&](auto hl, auto fd, auto masked, auto heur) {
             const size_t lds = hl ? with_hist : st;
-            if constexpr (masked) return launch(nastar_backward_replay_masked_kernel<false, hl, fd>, B, lds, s, a, rcp, nb.mask);
+            if constexpr (heur) return launch(nastar_backward_replay_heuristic_kernel<false, hl, fd>, B, lds, s, a, rcp, nb.mask, nb.h0);
+            else if constexpr (masked) return launch(nastar_backward_replay_masked_kernel<false, hl, fd>, B, lds, s, a, rcp, nb.mask);
             else return launch(nastar_backward_replay_kernel<false, hl, fd>, B, lds, s, a, rcp);
-        }, hist_lds, fast, nb.masked);
+        }, hist_lds, fast, nb.masked, nb.h0 != nullptr);
     }
     // state in the HBM workspace: FILL (all CUs: slab, zeroed gradient, start / goal cells into the slab's header), REPLAY (one wavefront per map:
     // O(steps)), SWEEP (all CUs: the cells still open at the end) -- nastar_backward_replay.hip.h
@@ -933,12 +1010,16 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
     const unsigned per_map = (unsigned)((a.d.HW + 255) / 256);
     const dim3 grid2(per_map < 64u ? per_map : 64u, (unsigned)B);
     with_bools([&](auto w) { hipLaunchKernelGGL(nastar_bwdr_fill_kernel<w>, grid2, dim3(256), 0, s, a); }, wide);
-    const int rc = with_bools([&](auto fd, auto w, auto masked) {
-        if constexpr (masked) return launch(nastar_backward_replay_masked_kernel<true, false, fd, w>, B, 64, s, a, rcp, nb.mask);
+    const int rc = with_bools([&](auto fd, auto w, auto masked, auto heur) {
+        if constexpr (heur) return launch(nastar_backward_replay_heuristic_kernel<true, false, fd, w>, B, 64, s, a, rcp, nb.mask, nb.h0);
+        else if constexpr (masked) return launch(nastar_backward_replay_masked_kernel<true, false, fd, w>, B, 64, s, a, rcp, nb.mask);
         else return launch(nastar_backward_replay_kernel<true, false, fd, w>, B, 64, s, a, rcp);
-    }, fast, wide, nb.masked);
+    }, fast, wide, nb.masked, nb.h0 != nullptr);
     if (rc != NASTAR_OK) return rc;
-    with_bools([&](auto w, auto fd) { hipLaunchKernelGGL((nastar_bwdr_sweep_kernel<w, fd>), grid2, dim3(256), 0, s, a, rcp); }, wide, fast);
+    with_bools([&](auto w, auto fd, auto heur) {
+        if constexpr (heur) hipLaunchKernelGGL((nastar_bwdr_sweep_heuristic_kernel<w, fd>), grid2, dim3(256), 0, s, a, rcp, nb.h0);
+        else hipLaunchKernelGGL((nastar_bwdr_sweep_kernel<w, fd>), grid2, dim3(256), 0, s, a, rcp);
+    }, wide, fast, nb.h0 != nullptr);
     hipError_t he = hipGetLastError();
     if (he != hipSuccess) return hip_fail(he, "kernel launch");
     return NASTAR_OK;
@@ -1022,6 +1103,19 @@ int nastar_backward_replay_ordered_masked(const float* grad_histories, const flo
                                         Neighbourhood{true, neighbor_mask}, stream);
 }
 
+int nastar_backward_replay_ordered_heuristic(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
+                                             const float* cost, const float* start, const float* goal, const float* passable, const int32_t* sel_log,
+                                             int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters, const int32_t* t_batch_dev,
+                                             float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order,
+                                             unsigned neighbor_mask, const float* h0, void* stream)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    if (!h0) return NASTAR_ERR_NULL;
+    return backward_replay_ordered_impl(grad_histories, histories, opt_trajs, grad_loss_dev, cost, start, goal, passable, sel_log, B, H, W, g_ratio,
+                                        max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order,
+                                        Neighbourhood{true, neighbor_mask, h0}, stream);
+}
+
 int nastar_pack_outputs(const float* histories, const int64_t* paths, int B, int H, int W, uint8_t* packed_out, void* stream)
 {
     if (!histories || !paths || !packed_out) return NASTAR_ERR_NULL;
@@ -1070,10 +1164,14 @@ int nastar_heuristic(const float* goal, int B, int H, int W, float* h0_out, void
 {
     if (!goal || !h0_out) return NASTAR_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0) return NASTAR_ERR_BAD_SHAPE;
-    if ((long long)H * W > 65535) return NASTAR_ERR_UNSUPPORTED;
-    const uint32_t magicW = (uint32_t)((1ull << 32) / (unsigned)W) + 1u;
-    hipLaunchKernelGGL(nastar_heuristic_kernel, dim3((unsigned)B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                       goal, h0_out, H, W, magicW);
+    if ((long long)H * W > kMaxGlobalCells) return NASTAR_ERR_UNSUPPORTED;
+    if ((long long)H * W > 65535) {
+        hipLaunchKernelGGL(nastar_heuristic_large_kernel, dim3((unsigned)B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), goal, h0_out, H, W);
+    } else {
+        const uint32_t magicW = (uint32_t)((1ull << 32) / (unsigned)W) + 1u;
+        hipLaunchKernelGGL(nastar_heuristic_kernel, dim3((unsigned)B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                           goal, h0_out, H, W, magicW);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return NASTAR_OK;

@@ -2,6 +2,8 @@
 // included INSIDE each kernel: the kernel without a mask keeps, token for token, the body it had before the masked one existed, so its
 // instruction stream is unchanged (a shared __device__ function changes how the optimiser sees the body and with it the register allocation).
 // In scope: the kernel's template parameters, `a`, `rcp_sqrtW`, and `constexpr bool kMasked` / `nmask` (the neighbor_filter mask, an SGPR).
+// nastar_forward_compact_heuristic_kernel shares it too: `constexpr bool kHeur` / `h0` (the caller's heuristic maps, [B, H, W]); every
+// kHeur branch below is discarded in the other two kernels.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = placed_map(a.order, a.order_bad, a.B);
     if ((unsigned)b >= (unsigned)a.B) return;  // not a permutation (and not checked: NASTAR_FLAG_CHECK_ORDER): never read or write outside the batch
@@ -33,6 +35,12 @@
 #else
     const bool raw = kAsm && !any_signed && d.gr >= 0.f && d.omg >= 0.f;
 #endif
+    float* hhv = nullptr;  // kHeur: fl(omg * fl(h0 + cost)) per cell, behind the compact state
+    bool bad_h0 = false;
+    if constexpr (kHeur) {
+        hhv = reinterpret_cast<float*>(l.pdir + d.HWp);
+        bad_h0 = compact_load_heuristic<kVec4>(d, l, hhv, h0 + off, lane);
+    }
     const int gi = goal_idx < 0 ? 0 : goal_idx;
     const int goal_r = (int)div_magic((uint32_t)gi, d.magicW);
     const int goal_c = gi - goal_r * d.W;
@@ -46,7 +54,9 @@
     const int budget = (lockstep && a.t_end != nullptr) ? __builtin_amdgcn_readfirstlane(*a.t_end + 1) : a.max_iters;
     uint32_t bits = 0u;  // probe: goal selections of the current 32 steps
     uint32_t* const bm = probe ? a.bitmap + (size_t)b * (size_t)a.bitmap_words : nullptr;
-    if (start_idx < 0 || goal_idx < 0) {
+    if (kHeur && bad_h0) {
+        status = NASTAR_ERR_BAD_HEURISTIC;  // a NaN / infinite heuristic value: this map is not searched (empty outputs)
+    } else if (start_idx < 0 || goal_idx < 0) {
         status = NASTAR_ERR_UNSOLVABLE;  // not a one-hot start/goal map
     } else {
         // round-4 stream (nastar_search_asm4.hip.h) wherever raw-bit keys apply (costs >= +0, 0 <= g_ratio <= 1: every priority is >= +0); a map with a
@@ -60,6 +70,14 @@
         const bool asm4 = raw;
 #endif
         const bool half = asm4 && d.gr == 0.5f && d.omg == 0.5f;
+        if constexpr (kHeur) {  // open list = {start} (:187), g[start] = 0 (:193), keyed by the stored hh
+            if (lane == 0) {
+                l.gc[start_idx].x = 0.0f;
+                l.cmin[start_idx >> CCL] = cmin_entry(compact_key<kFastDiv>(d, 0.0f, hhv[start_idx], rcp_sqrtW), (uint32_t)start_idx);
+                l.pdir[start_idx] = (uint8_t)(PARENT_UNSET | P_PASS);
+            }
+            wave_sync();
+        } else
         compact_open_start<kFastDiv>(d, l, lane, start_idx, goal_r, goal_c, rcp_sqrtW, raw, half);
         int s = 0;
         if constexpr (kAsm) {
@@ -105,6 +123,8 @@
             // lock-step mode: the reference's loop to the letter -- a selected goal is expanded like any cell, stays open, and the map is stepped
             // on (it may wander: NASTAR_SUMMARY_COUPLED) until the caller's step count is reached
             goal_hit |= s == goal_idx;
+            if constexpr (kHeur) compact_expand<LOGW, kFastDiv, CPL_T, true>(d, l, lc, lane, s, goal_r, goal_c, rcp_sqrtW, mine, s == goal_idx, hhv);
+            else
             compact_expand<LOGW, kFastDiv, CPL_T>(d, l, lc, lane, s, goal_r, goal_c, rcp_sqrtW, mine, s == goal_idx);
         }
         if (probe) {  // the words this map's search did not reach say "no goal selection"; nothing else is written
@@ -135,8 +155,14 @@
                     const int n = inb ? s + lc.off : s;
                     const float2 gg = l.gc[s], gn = l.gc[n];
                     const float g2 = gg.x + gg.y;
-                    const uint32_t kn = compact_key<kFastDiv>(d, g2, d.omg * (heuristic0_fast(nr, nc, goal_r, goal_c) + gn.y), rcp_sqrtW);
-                    const uint32_t kg = compact_key<kFastDiv>(d, gg.x, d.omg * (heuristic0_fast(goal_r, goal_c, goal_r, goal_c) + gg.y), rcp_sqrtW);
+                    uint32_t kn, kg;
+                    if constexpr (kHeur) {  // the stored values, for the neighbour AND the goal (h0(goal) need not be 0)
+                        kn = compact_key<kFastDiv>(d, g2, hhv[n], rcp_sqrtW);
+                        kg = compact_key<kFastDiv>(d, gg.x, hhv[s], rcp_sqrtW);
+                    } else {
+                    kn = compact_key<kFastDiv>(d, g2, d.omg * (heuristic0_fast(nr, nc, goal_r, goal_c) + gn.y), rcp_sqrtW);
+                    kg = compact_key<kFastDiv>(d, gg.x, d.omg * (heuristic0_fast(goal_r, goal_c, goal_r, goal_c) + gg.y), rcp_sqrtW);
+                    }
                     const bool beats = inb & (gn.x > g2) & ((kn < kg) | ((kn == kg) & (n < s)));
                     coupled = __ballot(beats) != 0ull;
                     if (coupled && a.summary != nullptr && lane == 0) a.summary[NASTAR_SUMMARY_COUPLED] = 1;
@@ -159,6 +185,6 @@
         // (the COUPLED note above is a summary cell like any other: it must be visible before this search counts itself -- ADVICE r5)
         if (a.done_counter) note_done(a.done_counter, a.summary, a.B, status != NASTAR_OK || coupled);
     }
-    if (goal_idx >= 0) compact_backtrack<(LOGW == LOGH ? LOGW : 0)>(d, l, lane, start_idx, goal_idx, solved ? d.HW : iters - 1);
+    if (goal_idx >= 0 && !(kHeur && bad_h0)) compact_backtrack<(LOGW == LOGH ? LOGW : 0)>(d, l, lane, start_idx, goal_idx, solved ? d.HW : iters - 1);
     compact_store_outputs<kVec4, false>(d, l, lane, a.hist + off, a.paths + off,
                                         a.packed ? a.packed + (size_t)b * (size_t)(d.HW >> 2) : nullptr);

@@ -1,6 +1,8 @@
 // nastar_forward_hybrid_body.inc -- the body of nastar_forward_hybrid_kernel and nastar_forward_hybrid_masked_kernel (nastar_search_hybrid.hip.h),
 // included INSIDE each kernel so that the kernel without a mask keeps its instruction stream (see nastar_forward_compact_body.inc).
 // In scope: kFastDiv, kLock, `a`, and `constexpr bool kMasked` / `nmask` (the neighbor_filter mask, an SGPR).
+// nastar_forward_hybrid_heuristic_kernel shares it too: `constexpr bool kHeur` / `h0` (the caller's heuristic maps, [B, H, W], read cell by
+// cell next to the cost in the step's one HBM round trip); every kHeur branch is discarded in the other two kernels.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x;
     if constexpr (kLock) {
@@ -17,6 +19,7 @@
     const int* const hdr = reinterpret_cast<const int*>(slab + hybrid_header_offset(d.HW));
     const size_t off = (size_t)b * (size_t)d.HW;
     const float* cost = a.cost + off;
+    const float* const h0m = kHeur ? h0 + off : nullptr;
     const bool probe = kLock && a.bitmap != nullptr;
     const int budget = (kLock && a.t_end != nullptr) ? __builtin_amdgcn_readfirstlane(*a.t_end + 1) : a.max_iters;
 
@@ -32,6 +35,8 @@
     if (sidx >= 0) {
         int sc;
         const int sr = hybrid_row(sidx, d, sc);
+        if constexpr (kHeur) h_start = h0m[sidx] + cost[sidx];
+        else
         h_start = heuristic0(sr, sc, goal_r, goal_c) + cost[sidx];
     }
     if (lane == 0 && sidx >= 0) {  // open list = {start} (:187), g[start] = 0 (:193); the start is expanded even on an obstacle
@@ -52,7 +57,9 @@
     bool solved = false, goal_hit = false, coupled = false;
     uint32_t bits = 0u;  // probe: goal selections of the current 32 steps
     uint32_t* const bm = probe ? a.bitmap + (size_t)b * (size_t)a.bitmap_words : nullptr;
-    if (sidx < 0 || gidx < 0) {
+    if (kHeur && __builtin_amdgcn_readfirstlane(hdr[2]) != 0) {
+        status = NASTAR_ERR_BAD_HEURISTIC;  // the fill launch met a NaN / infinite heuristic value: this map is not searched
+    } else if (sidx < 0 || gidx < 0) {
         status = NASTAR_ERR_UNSOLVABLE;  // not a one-hot start / goal map
     } else {
         // (key << 32 | cell) of the next selection, wave-uniform in scalar registers; ~0 = open list empty
@@ -81,6 +88,8 @@
                 // :219-220,:251 every later step of the reference is a fixed point -- unless the goal's own expansion would open a cell that beats
                 // it (nastar_capi.hip, same test): reported as summary[NASTAR_SUMMARY_COUPLED] and, per map, in marks[]
                 if (a.summary != nullptr || a.marks_out != nullptr) {
+                    if constexpr (kHeur) coupled = hybrid_goal_beaten_heuristic<kFastDiv>(d, g, cost, h0m, s, nb_on, dr, dc);
+                    else
                     if constexpr (kMasked) coupled = hybrid_goal_beaten_gated<kFastDiv>(d, g, cost, s, nb_on, dr, dc, goal_r, goal_c);
                     else coupled = hybrid_goal_beaten<kFastDiv>(d, g, cost, s, lane, dr, dc, goal_r, goal_c);
                 }
@@ -112,6 +121,11 @@
             const float cs = cost[s];
             const float cn = cost[n];
             const float cc = cost[icv ? ic : 0];
+            float hn, hc;
+            if constexpr (kHeur) {
+                hn = h0m[n];
+                hc = h0m[icv ? ic : 0];
+            }
             // ---- in the shadow of that round trip: nothing below needs a loaded value until `g2` -------------------------
             // rest of the super-chunk of s* (its 64 chunk entries but the one of s*) and rest of the map (every other super-chunk): entries
             // ascend with the lane, so the first lane that holds the minimal key holds the first minimal entry
@@ -121,13 +135,15 @@
             wave_min_scalar_u32x2(kS, kE, mS, mE);
             const uint32_t cS = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)ev, __builtin_ctzll(__ballot(kS == mS)));
             const uint32_t cE = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)e0, __builtin_ctzll(__ballot(kE == mE)));
+            if constexpr (!kHeur) {
             int icc;
             const int icr = hybrid_row_nb(icv ? ic : 0, d, icc);
-            float hn = heuristic0(nr, nc, goal_r, goal_c);
-            float hc = heuristic0(icr, icc, goal_r, goal_c);
+            hn = heuristic0(nr, nc, goal_r, goal_c);
+            hc = heuristic0(icr, icc, goal_r, goal_c);
             // (the compiler otherwise sinks both heuristics below the first use of a loaded value, into regions predicated on `upd` / `open_c`:
             //  a lone wavefront pays for predicated-off lanes anyway, and there they sit behind the round trip instead of inside it)
             asm volatile("" : "+v"(hn), "+v"(hc) : : "memory");
+            }
             // ---- the loaded values ------------------------------------------------------------------------------------------
             const float g2 = gs + cs;                                              // :234 step cost of the node being LEFT
             const bool upd = inb & (gn > g2);                                      // :229,:235
@@ -194,7 +210,7 @@
     }
 
     // ---- backtrack (:96-125): walk to the start, cap = this map's own step count in the budget-truncated case ----------
-    if (gidx >= 0 && lane == 0) {
+    if (gidx >= 0 && lane == 0 && !(kHeur && status == NASTAR_ERR_BAD_HEURISTIC)) {
         const int cap = solved ? d.HW : iters - 1;
         uint32_t m = pdir[gidx];
         pdir[gidx] = (uint8_t)(m | P_PATH);

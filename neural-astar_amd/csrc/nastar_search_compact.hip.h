@@ -47,6 +47,9 @@ struct CompactLds {
 
 __host__ __device__ inline size_t compact_lds_bytes(int HWp, int NCp) { return (size_t)HWp * 9 + (size_t)NCp * 8 + 256; }
 
+// the kernels with a caller-supplied heuristic keep hh = fl((1-g_ratio) fl(h0 + cost)) per cell behind the compact state: 13 B per cell
+__host__ __device__ inline size_t compact_heur_lds_bytes(int HWp, int NCp) { return compact_lds_bytes(HWp, NCp) + (size_t)HWp * 4; }
+
 __device__ __forceinline__ CompactLds carve_compact_lds(unsigned char* smem, const CompactDims& d)
 {
     CompactLds l;
@@ -183,6 +186,40 @@ __device__ __forceinline__ void compact_load_map(const CompactDims& d, const Com
     wave_sync();
 }
 
+// caller-supplied heuristic h0 (one map, after compact_load_map has put the costs into l.gc): hhv[i] = fl(omg * fl(h0[i] + cost[i])), the
+// two roundings the step makes from the built-in heuristic (:191-192, :206).  Returns whether some h0 value is NaN or infinite (wave-uniform).
+template <bool kVec4>
+__device__ __forceinline__ bool compact_load_heuristic(const CompactDims& d, const CompactLds& l, float* hhv, const float* __restrict__ h0, int lane)
+{
+    bool bad = false;
+    if constexpr (kVec4) {
+        const float4* h4 = reinterpret_cast<const float4*>(h0);
+        const int n4 = d.HW >> 2;
+        for (int q = lane; q < n4; q += 64) {
+            const float4 hv = h4[q];
+            const float4 lo = *reinterpret_cast<const float4*>(l.gc + (q << 2));
+            const float4 hi = *reinterpret_cast<const float4*>(l.gc + (q << 2) + 2);
+            bad = bad || !(fabsf(hv.x) < NASTAR_POS_INF) || !(fabsf(hv.y) < NASTAR_POS_INF) || !(fabsf(hv.z) < NASTAR_POS_INF) || !(fabsf(hv.w) < NASTAR_POS_INF);
+            float4 o;
+            o.x = d.omg * (hv.x + lo.y);
+            o.y = d.omg * (hv.y + lo.w);
+            o.z = d.omg * (hv.z + hi.y);
+            o.w = d.omg * (hv.w + hi.w);
+            *reinterpret_cast<float4*>(hhv + (q << 2)) = o;
+        }
+    } else {
+        for (int i = lane; i < d.HW; i += 64) {
+            const float hv = h0[i];
+            bad |= !(fabsf(hv) < NASTAR_POS_INF);
+            hhv[i] = d.omg * (hv + l.gc[i].y);
+        }
+    }
+    for (int i = d.HW + lane; i < d.HWp; i += 64) hhv[i] = 0.f;  // tail of the last chunk: never open
+    const bool any_bad = __ballot(bad) != 0ull;
+    wave_sync();
+    return any_bad;
+}
+
 // open list = {start} (:187), g[start] = 0 (:193).  raw_key: the key is the bit pattern of q itself (nastar_search_asm3.hip.h, q >= +0)
 // half_key: g_ratio == 0.5 form of the round-4 stream -- the key of q' = fl(fl(g + h) / sqrt(W)) = 2 q (nastar_search_asm4.hip.h)
 template <bool kFastDiv>
@@ -261,9 +298,12 @@ __device__ __forceinline__ CompactLane make_compact_lane(const CompactDims& d, i
 // CPL_T == 1: `mine` is this lane's own cmin entry as read by compact_select (nothing has touched it since).
 // keep_open (lock-step mode, NASTAR_FLAG_LOCKSTEP): s* is the goal -- the reference expands it like any cell but leaves it on the open list
 // (:224 open_maps - is_unsolved * selected) while histories records it (:222-223); the caller keeps that flag
-template <int LOGW, bool kFastDiv, int CPL_T>
+// kHeur (the kernels with a caller-supplied heuristic): hh = fl((1-g_ratio) fl(h0 + cost)) of every cell was stored in `hhv` at load time
+// (compact_load_heuristic) and is read beside (g, cost); no coordinates, no square root in the step
+template <int LOGW, bool kFastDiv, int CPL_T, bool kHeur = false>
 __device__ __forceinline__ void compact_expand(const CompactDims& d, const CompactLds& l, const CompactLane& lc, int lane, int s,
-                                               int goal_r, int goal_c, float rcp_sqrtW, const uint2 mine, const bool keep_open = false)
+                                               int goal_r, int goal_c, float rcp_sqrtW, const uint2 mine, const bool keep_open = false,
+                                               const float* hhv = nullptr)
 {
     int r, c;
     if constexpr (LOGW) {
@@ -281,6 +321,10 @@ __device__ __forceinline__ void compact_expand(const CompactDims& d, const Compa
     // one batch of LDS reads: (g, cost) of s* (broadcast) and of this lane's cell
     const float2 gs = l.gc[s];
     const float2 gl = l.gc[il];
+    float hh;
+    if constexpr (kHeur) {
+        hh = hhv[il];
+    } else {
     // position of il (independent of the reads: overlaps their latency)
     int rl, cl;
     if constexpr (LOGW) {
@@ -291,7 +335,8 @@ __device__ __forceinline__ void compact_expand(const CompactDims& d, const Compa
         cl = il - rl * d.W;
     }
     const float h0 = heuristic0_fast(rl, cl, goal_r, goal_c);
-    const float hh = d.omg * (h0 + gl.y);  // :191-192 h = h0 + cost ; :206 (1-g_ratio)*h
+    hh = d.omg * (h0 + gl.y);  // :191-192 h = h0 + cost ; :206 (1-g_ratio)*h
+    }
     // g2 = g[s*] + cost[s*]  (:234: expand((g + cost_maps) * selected)) -- step cost of the node being LEFT
     const float g2 = gs.x + gs.y;
     // :229,:235  neighbour is passable, not closed, and (not open, or open with g > g2)   <=>   g[n] > g2

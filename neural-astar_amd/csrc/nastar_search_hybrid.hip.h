@@ -240,20 +240,91 @@ __device__ __forceinline__ bool hybrid_goal_beaten_gated(const HybridDims& d, co
     return __ballot(beats) != 0ull;
 }
 
-// kMasked: the neighbourhood of DifferentiableAstar.neighbor_filter (nmask, see neighbour_enabled) instead of the Moore-8 stencil.  Both
-// kernels share one body, nastar_forward_hybrid_body.inc.
+// the same test with a caller-supplied heuristic: h0 of the neighbour and of the goal itself are loaded (h0(goal) need not be 0)
+template <bool kFastDiv>
+__device__ __forceinline__ bool hybrid_goal_beaten_heuristic(const HybridDims& d, const float* g, const float* cost, const float* h0m, int s,
+                                                             bool nb, int dr, int dc)
+{
+    int gc0;
+    const int gr0 = hybrid_row_nb(s, d, gc0);
+    const int nr = gr0 + dr, nc = gc0 + dc;
+    const bool inb = nb & ((unsigned)nr < (unsigned)d.H) & ((unsigned)nc < (unsigned)d.W);
+    const int n = inb ? s + dr * d.W + dc : s;
+    global_step_fence();
+    const float gs = g[s], gn = g[n];
+    const float cs = cost[s], cn = cost[n];
+    const float hs = h0m[s], hn = h0m[n];
+    const float g2 = gs + cs;
+    const uint32_t kn = hybrid_key<kFastDiv>(d, g2, hn + cn);
+    const uint32_t kg = hybrid_key<kFastDiv>(d, gs, hs + cs);
+    const bool beats = inb & (gn > g2) & ((kn < kg) | ((kn == kg) & (n < s)));
+    return __ballot(beats) != 0ull;
+}
+
+// the fill launch of a search with a caller-supplied heuristic: nastar_hybrid_fill_kernel, and every h0 value of the map is looked at
+// once -- hdr[2] (0 on entry: nastar_hybrid_header_heuristic_kernel) becomes 1 when one is NaN or infinite (NASTAR_ERR_BAD_HEURISTIC)
+__global__ __launch_bounds__(256) void nastar_hybrid_fill_heuristic_kernel(const FwdHybridArgs a, const float* __restrict__ h0)
+{
+    const int b = blockIdx.y;
+    if (a.marks != nullptr && a.marks[b] == 0) return;  // lock-step launches touch only the marked maps
+    const HybridDims d = a.d;
+    const int HWp = d.nchunks * 64;
+    unsigned char* const slab = a.workspace + (size_t)b * a.slab_bytes;
+    float* const g = reinterpret_cast<float*>(slab);
+    uint8_t* const pdir = reinterpret_cast<uint8_t*>(g + HWp);
+    int* const hdr = reinterpret_cast<int*>(slab + hybrid_header_offset(d.HW));
+    const size_t off = (size_t)b * (size_t)d.HW;
+    int sidx = -1, gidx = -1;
+    bool bad = false;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HWp; i += gridDim.x * 256) {
+        const bool valid = i < d.HW;
+        if (valid && a.start[off + i] != 0.f) sidx = i;
+        if (valid && a.goal[off + i] != 0.f) gidx = i;
+        if (valid) bad |= !(fabsf(h0[off + i]) < NASTAR_POS_INF);
+        const bool pass = valid && a.passable[off + i] != 0.f;
+        g[i] = pass ? NASTAR_POS_INF : NASTAR_NEG_INF;
+        pdir[i] = (uint8_t)(PARENT_UNSET | (pass ? P_PASS : 0u));
+    }
+    if (sidx >= 0) atomicMax(&hdr[0], sidx);
+    if (gidx >= 0) atomicMax(&hdr[1], gidx);
+    if (bad) atomicMax(&hdr[2], 1);
+}
+
+__global__ __launch_bounds__(256) void nastar_hybrid_header_heuristic_kernel(unsigned char* workspace, size_t slab_bytes, size_t header_off, int B)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b < B) {
+        int* hdr = reinterpret_cast<int*>(workspace + (size_t)b * slab_bytes + header_off);
+        hdr[0] = -1;
+        hdr[1] = -1;
+        hdr[2] = 0;
+    }
+}
+
+// kMasked: the neighbourhood of DifferentiableAstar.neighbor_filter (nmask, see neighbour_enabled) instead of the Moore-8 stencil.
+// kHeur (nastar_forward_hybrid_heuristic_kernel): h0 is the caller's tensor instead of the built-in heuristic; it always takes the mask.
+// All three kernels share one body, nastar_forward_hybrid_body.inc.
 template <bool kFastDiv, bool kLock = false>
 __global__ __launch_bounds__(64) void nastar_forward_hybrid_kernel(const FwdHybridArgs a)
 {
-    constexpr bool kMasked = false;
+    constexpr bool kMasked = false, kHeur = false;
     constexpr uint32_t nmask = 0x1EFu;  // (NASTAR_NEIGHBORS_MOORE8; never read)
+    constexpr const float* h0 = nullptr;
 #include "nastar_forward_hybrid_body.inc"
 }
 
 template <bool kFastDiv, bool kLock>
 __global__ __launch_bounds__(64) void nastar_forward_hybrid_masked_kernel(const FwdHybridArgs a, const uint32_t nmask)
 {
-    constexpr bool kMasked = true;
+    constexpr bool kMasked = true, kHeur = false;
+    constexpr const float* h0 = nullptr;
+#include "nastar_forward_hybrid_body.inc"
+}
+
+template <bool kFastDiv, bool kLock>
+__global__ __launch_bounds__(64) void nastar_forward_hybrid_heuristic_kernel(const FwdHybridArgs a, const uint32_t nmask, const float* __restrict__ h0)
+{
+    constexpr bool kMasked = true, kHeur = true;
 #include "nastar_forward_hybrid_body.inc"
 }
 

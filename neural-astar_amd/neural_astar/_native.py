@@ -23,6 +23,7 @@ NASTAR_ERR_UNSOLVABLE = 3
 NASTAR_ERR_HIP = 4
 NASTAR_ERR_NULL = 5
 NASTAR_ERR_WORKSPACE = 6
+NASTAR_ERR_BAD_HEURISTIC = 8  # per-map status only
 
 _ERR_NAMES = {
     NASTAR_ERR_BAD_SHAPE: "bad shape (B, H, W and max_iters must be positive)",
@@ -43,9 +44,11 @@ EXPORTED_SYMBOLS = (
     "nastar_forward_ordered",
     "nastar_forward_ex",
     "nastar_forward_ex_masked",
+    "nastar_forward_ex_heuristic",
     "nastar_batchloop_workspace_bytes",
     "nastar_forward_batchloop_finish",
     "nastar_forward_batchloop_finish_masked",
+    "nastar_forward_batchloop_finish_heuristic",
     "nastar_completion_supported",
     "nastar_host_wait_nonzero",
     "nastar_placement_from_levels",
@@ -54,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "nastar_backward_replay",
     "nastar_backward_replay_ordered",
     "nastar_backward_replay_ordered_masked",
+    "nastar_backward_replay_ordered_heuristic",
     "nastar_backward_l1_replay",
     "nastar_l1_loss",
     "nastar_policy_rollout",
@@ -230,6 +234,13 @@ def load() -> ctypes.CDLL:
     lib.nastar_forward_batchloop_finish_masked.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, cz, cu, vp]
     lib.nastar_backward_replay_ordered_masked.restype = ci
     lib.nastar_backward_replay_ordered_masked.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, ci, vp, cu, vp]
+    # the entry points with a caller-supplied heuristic: `unsigned neighbor_mask, const float* h0` in front of the stream
+    lib.nastar_forward_ex_heuristic.restype = ci
+    lib.nastar_forward_ex_heuristic.argtypes = lib.nastar_forward_ex_masked.argtypes[:-1] + [vp, vp]
+    lib.nastar_forward_batchloop_finish_heuristic.restype = ci
+    lib.nastar_forward_batchloop_finish_heuristic.argtypes = lib.nastar_forward_batchloop_finish_masked.argtypes[:-1] + [vp, vp]
+    lib.nastar_backward_replay_ordered_heuristic.restype = ci
+    lib.nastar_backward_replay_ordered_heuristic.argtypes = lib.nastar_backward_replay_ordered_masked.argtypes[:-1] + [vp, vp]
     lib.nastar_backward_l1_replay.restype = ci
     lib.nastar_backward_l1_replay.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, vp]
     lib.nastar_l1_loss.restype = ci

@@ -39,6 +39,7 @@ FLAG_CHECK_ORDER = 256  # NASTAR_FLAG_CHECK_ORDER: the launch verifies `order` o
 FLAG_MARK_COUPLED = 32768  # NASTAR_FLAG_MARK_COUPLED: the launch marks the maps of the batch-coupled class for nastar_forward_batchloop_finish
 STATUS_UNSOLVABLE = 3  # NASTAR_ERR_UNSOLVABLE (per-map status)
 STATUS_NOT_UNIT_COST = 7  # NASTAR_ERR_NOT_UNIT_COST (per-map status)
+STATUS_BAD_HEURISTIC = 8  # NASTAR_ERR_BAD_HEURISTIC (per-map status): a NaN / infinite value in this map's heuristic_maps
 SUMMARY_WORDS = 16  # NASTAR_SUMMARY_WORDS
 SUMMARY_BAD_ORDER = 15  # NASTAR_SUMMARY_BAD_ORDER
 SUMMARY_COUPLED = 14  # NASTAR_SUMMARY_COUPLED: a NOTE (a finished map is not at a fixed point of the reference's batch loop), cells 1..13 are errors
@@ -190,7 +191,7 @@ def in_lds(H: int, W: int) -> bool:
 
 
 def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, order, order_out, check_order, summary_ptr, dev,
-                   one_meta=False, stream_ptr=None, out_4d=False, counter_ptr=0, keep=None, exact=False, neighbor_mask=None):
+                   one_meta=False, stream_ptr=None, out_4d=False, counter_ptr=0, keep=None, exact=False, neighbor_mask=None, heuristic=None):
     """allocate the five outputs and issue ONE nastar_forward_ex launch on torch's current stream (shared by the custom ops and the
     no-autograd fast path).  cost / start / goal / passable: contiguous fp32 tensors of B*H*W elements (any leading shape).
     ``keep``: a list that receives the launch's temporaries (its workspace) when the launch goes to ANOTHER stream than the one the
@@ -200,7 +201,9 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
     lock-step mode up to the step at which every map of the batch selects its goal.  No host round trip; nothing happens when no map is
     marked (always so for g_ratio in [0.5, 1) with costs >= 0).
     ``neighbor_mask``: None = the reference's default neighbourhood (Moore-8) on the fastest kernels; an int = the search neighbourhood of a
-    ``neighbor_filter`` (NEIGHBORS_*), searched by the masked entry points (nastar_forward_ex_masked: the compiled step loops, for every mask)."""
+    ``neighbor_filter`` (NEIGHBORS_*), searched by the masked entry points (nastar_forward_ex_masked: the compiled step loops, for every mask).
+    ``heuristic``: None = the reference's get_heuristic, computed by the kernels; a contiguous fp32 [B, H, W] tensor = the caller's heuristic
+    maps (nastar_forward_ex_heuristic; with ``neighbor_mask`` or Moore-8)."""
     shape = (B, 1, H, W) if out_4d else (B, H, W)
     hist = torch.empty(shape, dtype=torch.float32, device=dev)
     paths = torch.empty(shape, dtype=torch.int64, device=dev)
@@ -250,6 +253,12 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
         args = args[:-1] + (int(neighbor_mask), sp)
         if fin is not None:
             fin = fin[:-1] + (int(neighbor_mask), sp)
+    if heuristic is not None:  # ... and with a heuristic: `neighbor_mask, h0` in front of the stream
+        fwd, finish = lib.nastar_forward_ex_heuristic, lib.nastar_forward_batchloop_finish_heuristic
+        tail = (int(neighbor_mask) if neighbor_mask is not None else NEIGHBORS_MOORE8, heuristic.data_ptr(), sp)
+        args = args[:22] + tail
+        if fin is not None:
+            fin = fin[:16] + tail
     if dev.index is None or torch.cuda.current_device() == dev.index:
         rc = fwd(*args)
         if not rc and fin is not None:
@@ -267,17 +276,19 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
 @torch.library.custom_op("nastar::astar_forward", mutates_args=())
 def astar_forward(cost: torch.Tensor, start: torch.Tensor, goal: torch.Tensor, passable: torch.Tensor,
                   g_ratio: float, max_iters: int, want_log: bool, flags: int = 0, summary_ptr: int = 0, exact: bool = False,
-                  neighbor_mask: int = NEIGHBORS_MOORE8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                  neighbor_mask: int = NEIGHBORS_MOORE8,
+                  heuristic: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """Returns (histories [B,H,W] f32, paths [B,H,W] i64, iters [B] i32, status [B] i32, sel_log [B,T] i32 or [0]).
     ``flags``: NASTAR_FLAG_* of include/nastar.h (e.g. ``FLAG_UNIT_COST`` when cost and passable are ONE binary tensor);
     ``summary_ptr``: address of a ``StatusBoard`` row (0 = none) that receives the launch's status summary; ``exact``: see ``_launch_search``;
-    ``neighbor_mask``: the search neighbourhood (NEIGHBORS_*, DifferentiableAstar.neighbor_filter); the backward replays with the same one."""
+    ``neighbor_mask``: the search neighbourhood (NEIGHBORS_*, DifferentiableAstar.neighbor_filter); the backward replays with the same one.
+    ``heuristic``: [B,H,W] fp32 heuristic maps in place of the reference's get_heuristic (None = that one); its gradient is the cost's."""
     _require_device(cost, start, goal, passable)
     lib = _native.load()
     cost, start, goal, passable = (x.contiguous() for x in (cost, start, goal, passable))
     B, H, W = cost.shape
     return _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, None, None, False, summary_ptr, cost.device,
-                          exact=exact, neighbor_mask=_mask_arg(neighbor_mask))
+                          exact=exact, neighbor_mask=_mask_arg(neighbor_mask), heuristic=_heuristic_arg(heuristic, cost))
 
 
 def _mask_arg(neighbor_mask: int) -> Optional[int]:
@@ -285,8 +296,18 @@ def _mask_arg(neighbor_mask: int) -> Optional[int]:
     return None if int(neighbor_mask) == NEIGHBORS_MOORE8 else int(neighbor_mask)
 
 
+def _heuristic_arg(heuristic: Optional[torch.Tensor], cost: torch.Tensor) -> Optional[torch.Tensor]:
+    """the custom ops' `heuristic` -> ``_launch_search``'s: contiguous fp32 [B,H,W] on the device of ``cost``"""
+    if heuristic is None:
+        return None
+    _require_device(heuristic)
+    if heuristic.shape != cost.shape or heuristic.device != cost.device:
+        raise ValueError(f"heuristic must have the shape and device of cost ({tuple(cost.shape)} on {cost.device}), got {tuple(heuristic.shape)} on {heuristic.device}")
+    return heuristic.contiguous()
+
+
 @astar_forward.register_fake
-def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags=0, summary_ptr=0, exact=False, neighbor_mask=NEIGHBORS_MOORE8):
+def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags=0, summary_ptr=0, exact=False, neighbor_mask=NEIGHBORS_MOORE8, heuristic=None):
     B, H, W = cost.shape
     return (cost.new_empty((B, H, W)), cost.new_empty((B, H, W), dtype=torch.int64),
             cost.new_empty((B,), dtype=torch.int32), cost.new_empty((B,), dtype=torch.int32),
@@ -297,7 +318,8 @@ def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags=0, summar
 def astar_forward_ordered(cost: torch.Tensor, start: torch.Tensor, goal: torch.Tensor, passable: torch.Tensor, g_ratio: float,
                           max_iters: int, want_log: bool, flags: int, order: Optional[torch.Tensor],
                           order_out: Optional[torch.Tensor], check_order: bool = True, summary_ptr: int = 0, exact: bool = False,
-                          neighbor_mask: int = NEIGHBORS_MOORE8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                          neighbor_mask: int = NEIGHBORS_MOORE8,
+                          heuristic: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """``astar_forward`` with a placement (include/nastar.h: nastar_forward_ex): workgroup i searches map ``order[i]`` (int32 [B], a
     permutation of 0..B-1, or None = identity).  Same five outputs as ``astar_forward``.  ``order_out`` (int32 [B + 1] from
     ``new_placement_buffer``, or None) receives in [:B] the maps in reverse order of search completion in this launch -- the ``order``
@@ -310,12 +332,12 @@ def astar_forward_ordered(cost: torch.Tensor, start: torch.Tensor, goal: torch.T
     cost, start, goal, passable = (x.contiguous() for x in (cost, start, goal, passable))
     B, H, W = cost.shape
     return _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, order, order_out, check_order,
-                          summary_ptr, cost.device, exact=exact, neighbor_mask=_mask_arg(neighbor_mask))
+                          summary_ptr, cost.device, exact=exact, neighbor_mask=_mask_arg(neighbor_mask), heuristic=_heuristic_arg(heuristic, cost))
 
 
 @astar_forward_ordered.register_fake
 def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags, order, order_out, check_order=True, summary_ptr=0, exact=False,
-      neighbor_mask=NEIGHBORS_MOORE8):
+      neighbor_mask=NEIGHBORS_MOORE8, heuristic=None):
     B, H, W = cost.shape
     return (cost.new_empty((B, H, W)), cost.new_empty((B, H, W), dtype=torch.int64),
             cost.new_empty((B,), dtype=torch.int32), cost.new_empty((B,), dtype=torch.int32),
@@ -326,7 +348,7 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
                   max_iters: int, want_log: bool = False, flags: int = 0, order: Optional[torch.Tensor] = None,
                   order_out: Optional[torch.Tensor] = None, check_order: bool = True, summary_ptr: int = 0, stream_ptr: Optional[int] = None,
                   out_4d: bool = False, counter_ptr: int = 0, keep: Optional[list] = None, exact: bool = False, lib=None,
-                  neighbor_mask: Optional[int] = None):
+                  neighbor_mask: Optional[int] = None, heuristic: Optional[torch.Tensor] = None):
     """The search launch WITHOUT the torch.library dispatch: what ``DifferentiableAstar.forward`` calls when no gradient can flow
     (``torch.no_grad()`` / inputs that do not require one) and nothing is being traced -- the custom-op machinery costs more host time
     than the launch itself at 4096 maps.  Takes the reference's [B,1,H,W] tensors (or [B,H,W]) as they are; same five outputs
@@ -336,7 +358,8 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
     allocated on the CURRENT stream: the caller orders the two streams before anyone reads or frees them, passes contiguous inputs --
     a copy made here would be made on the current stream, after the caller ordered the streams -- and holds ``keep``, the list that
     receives the launch's workspace, until that stream is done).  ``exact``: the reference's batch loop to the letter (``_launch_search``).
-    ``lib``: another build of the C ABI (``_native.load_dev()``: stream-equality tests).  ``neighbor_mask``: see ``_launch_search``."""
+    ``lib``: another build of the C ABI (``_native.load_dev()``: stream-equality tests).  ``neighbor_mask``, ``heuristic`` ([B,1,H,W] or
+    [B,H,W] fp32 on the maps' device; made contiguous here): see ``_launch_search``."""
     if stream_ptr is not None and not (cost_maps.is_contiguous() and start_maps.is_contiguous() and goal_maps.is_contiguous()
                                        and obstacles_maps.is_contiguous()):
         raise ValueError("search_nograd(stream_ptr=...): the maps must be contiguous (make the copies before ordering the streams)")
@@ -361,9 +384,16 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
         start_maps = start_maps.contiguous()
     if not goal_maps.is_contiguous():
         goal_maps = goal_maps.contiguous()
+    if heuristic is not None:
+        if not (heuristic.is_cuda and heuristic.dtype == torch.float32):
+            _require_device(heuristic)
+        if heuristic.numel() != n or heuristic.shape[-2:] != cost_maps.shape[-2:] or heuristic.device != cost_maps.device:
+            raise ValueError("heuristic maps must have the shape and device of the cost maps")
+        if not heuristic.is_contiguous():
+            heuristic = heuristic.contiguous()
     return _launch_search(lib if lib is not None else _native.load(), cost_maps, start_maps, goal_maps, obstacles_maps, B, H, W, g_ratio, max_iters,
                           want_log, flags, order, order_out, check_order, summary_ptr, cost_maps.device, True, stream_ptr, out_4d, counter_ptr, keep, exact,
-                          neighbor_mask)
+                          neighbor_mask, heuristic)
 
 
 def order_from_levels(levels: torch.Tensor) -> torch.Tensor:
@@ -461,12 +491,13 @@ def placement_from_iters(iters: torch.Tensor) -> torch.Tensor:
 def astar_backward_replay(grad_hist: torch.Tensor, cost: torch.Tensor, start: torch.Tensor, goal: torch.Tensor,
                           passable: torch.Tensor, sel_log: torch.Tensor, g_ratio: float, max_iters: int, iters: torch.Tensor,
                           t_batch: Optional[torch.Tensor], order: Optional[torch.Tensor] = None, flags: int = 0,
-                          neighbor_mask: int = NEIGHBORS_MOORE8) -> torch.Tensor:
+                          neighbor_mask: int = NEIGHBORS_MOORE8, heuristic: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dL/dcost by replaying the forward's selection log (csrc/nastar_backward_replay.hip.h): any map size the forward takes
     (1,179,648 cells; 32-bit history stamps above 65519), O(9) accounting work per step.  ``order`` (int32 permutation of 0..B-1): workgroup i replays map order[i] --
     the forward's own completion order (``astar_forward_ordered``'s ``order_out``) puts the longest replays first.  ``flags``:
     ``FLAG_LOCKSTEP`` for the log of an ``exact`` forward (goal selections before the last entry: the general replay loop).
-    ``neighbor_mask``: the neighbourhood the forward searched (NEIGHBORS_*; anything but Moore-8: nastar_backward_replay_ordered_masked)."""
+    ``neighbor_mask``: the neighbourhood the forward searched (NEIGHBORS_*; anything but Moore-8: nastar_backward_replay_ordered_masked).
+    ``heuristic``: the heuristic maps the forward searched with (nastar_backward_replay_ordered_heuristic); the result is then dL/dheuristic too."""
     _require_device(grad_hist, cost, start, goal, passable)
     lib = _native.load()
     grad_hist, cost, start, goal, passable, sel_log = (x.contiguous() for x in (grad_hist, cost, start, goal, passable, sel_log))
@@ -477,8 +508,16 @@ def astar_backward_replay(grad_hist: torch.Tensor, cost: torch.Tensor, start: to
     if ws_bytes == 0:
         raise RuntimeError(f"nastar_backward_replay: unsupported map size {H}x{W}")
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    heuristic = _heuristic_arg(heuristic, cost)
     with torch.cuda.device(dev):
-        if int(neighbor_mask) != NEIGHBORS_MOORE8:
+        if heuristic is not None:
+            rc = lib.nastar_backward_replay_ordered_heuristic(grad_hist.data_ptr(), None, None, None, cost.data_ptr(), start.data_ptr(), goal.data_ptr(),
+                                                              passable.data_ptr(), sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters),
+                                                              iters.data_ptr(), t_batch.data_ptr() if t_batch is not None else None, grad_cost.data_ptr(),
+                                                              ws.data_ptr(), ws_bytes, int(flags),
+                                                              _order_ptr(order, B, dev, True) if order is not None else None, int(neighbor_mask),
+                                                              heuristic.data_ptr(), _stream_ptr(dev))
+        elif int(neighbor_mask) != NEIGHBORS_MOORE8:
             rc = lib.nastar_backward_replay_ordered_masked(grad_hist.data_ptr(), None, None, None, cost.data_ptr(), start.data_ptr(), goal.data_ptr(),
                                                            passable.data_ptr(), sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters),
                                                            iters.data_ptr(), t_batch.data_ptr() if t_batch is not None else None, grad_cost.data_ptr(),
@@ -500,14 +539,19 @@ def astar_backward_replay(grad_hist: torch.Tensor, cost: torch.Tensor, start: to
 
 
 @astar_backward_replay.register_fake
-def _(grad_hist, cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_batch, order=None, flags=0, neighbor_mask=NEIGHBORS_MOORE8):
+def _(grad_hist, cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_batch, order=None, flags=0, neighbor_mask=NEIGHBORS_MOORE8, heuristic=None):
     return torch.empty_like(cost)
 
 
 def _setup_context(ctx, inputs, output):
     cost, start, goal, passable, g_ratio, max_iters = inputs[:6]
     _, _, iters, _, sel_log = output
-    ctx.save_for_backward(cost, start, goal, passable, iters, sel_log)
+    heuristic = inputs[11] if len(inputs) > 11 else None  # the heuristic maps the forward searched with: the replay rebuilds its keys from them
+    ctx.has_heuristic = heuristic is not None
+    if heuristic is not None:
+        ctx.save_for_backward(cost, start, goal, passable, iters, sel_log, heuristic)
+    else:
+        ctx.save_for_backward(cost, start, goal, passable, iters, sel_log)
     ctx.g_ratio = g_ratio
     ctx.max_iters = max_iters
     ctx.lockstep = bool(inputs[9]) if len(inputs) > 9 else False  # `exact`: the log may hold goal selections before its last entry
@@ -517,7 +561,8 @@ def _setup_context(ctx, inputs, output):
 
 
 def _backward(ctx, g_hist, g_paths, g_iters, g_status, g_log):
-    cost, start, goal, passable, iters, sel_log = ctx.saved_tensors
+    cost, start, goal, passable, iters, sel_log = ctx.saved_tensors[:6]
+    heuristic = ctx.saved_tensors[6] if ctx.has_heuristic else None
     if g_hist is None:
         return (None,) * ctx.n_inputs
     # t_batch: the reference's batch-wide loop index (differentiable_astar.py:251-255).  BatchCoupling lets the
@@ -528,7 +573,10 @@ def _backward(ctx, g_hist, g_paths, g_iters, g_status, g_log):
                            "(DifferentiableAstar.forward does whenever cost_maps.requires_grad)")
     grad_cost = torch.ops.nastar.astar_backward_replay(g_hist.contiguous(), cost, start, goal, passable, sel_log,
                                                        ctx.g_ratio, ctx.max_iters, iters, t_batch, None, FLAG_LOCKSTEP if ctx.lockstep else 0,
-                                                       ctx.neighbor_mask)
+                                                       ctx.neighbor_mask, heuristic)
+    if heuristic is not None:
+        # dL/dh0 == dL/dcost: g is detached every step (differentiable_astar.py:239), so the loss sees both only through h = h0 + cost
+        return (grad_cost,) + (None,) * 10 + (grad_cost,) + (None,) * (ctx.n_inputs - 12)
     return (grad_cost,) + (None,) * (ctx.n_inputs - 1)
 
 

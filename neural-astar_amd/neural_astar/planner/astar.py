@@ -11,6 +11,8 @@ a one-line ``.cuda()`` on both to run.
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn as nn
 
@@ -46,18 +48,22 @@ class VanillaAstar(nn.Module):
         self.use_differentiable_astar = use_differentiable_astar
 
     def perform_astar(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
-                      obstacles_maps: torch.Tensor, store_intermediate_results: bool = False) -> AstarOutput:
+                      obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
+                      heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:
+        """``heuristic_maps``: [B,1,H,W] fp32 heuristic in place of the reference's get_heuristic (``DifferentiableAstar.forward``)"""
         if not self.use_differentiable_astar:
             # reference astar.py:57-61 dispatches to pq_astar (CPU numpy + pqdict): a different, non-differentiable
             # algorithm (it charges the NEIGHBOUR's cost, pq_astar.py:138-144) that is outside the hot path.
             raise NotImplementedError(
                 "use_differentiable_astar=False selects the reference's CPU-only pq_astar, which is out of scope for "
                 "the MI355X-native hot path; the HIP DifferentiableAstar kernel has no large-map penalty, use it.")
-        return self.astar(map_designs, start_maps, goal_maps, obstacles_maps, store_intermediate_results)
+        if heuristic_maps is None:
+            return self.astar(map_designs, start_maps, goal_maps, obstacles_maps, store_intermediate_results)
+        return self.astar(map_designs, start_maps, goal_maps, obstacles_maps, store_intermediate_results, heuristic_maps=heuristic_maps)
 
     def forward(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
-                store_intermediate_results: bool = False) -> AstarOutput:
-        return self.perform_astar(map_designs, start_maps, goal_maps, map_designs, store_intermediate_results)
+                store_intermediate_results: bool = False, heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:
+        return self.perform_astar(map_designs, start_maps, goal_maps, map_designs, store_intermediate_results, heuristic_maps)
 
 
 class NeuralAstar(VanillaAstar):
@@ -209,7 +215,7 @@ class NeuralAstar(VanillaAstar):
         return self.encoder(inputs)
 
     def forward(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
-                store_intermediate_results: bool = False) -> AstarOutput:
+                store_intermediate_results: bool = False, heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:
         cost_maps = self.encode(map_designs, start_maps, goal_maps)
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
-        return self.perform_astar(cost_maps, start_maps, goal_maps, obstacles_maps, store_intermediate_results)
+        return self.perform_astar(cost_maps, start_maps, goal_maps, obstacles_maps, store_intermediate_results, heuristic_maps)

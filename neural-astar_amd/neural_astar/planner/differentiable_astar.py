@@ -138,6 +138,10 @@ def _raise_unsolvable(status: torch.Tensor, seq: int = 0, deferred: bool = False
     if nu:
         raise ValueError(f"unit_cost=True, but {len(nu)} map(s) hold values other than 0.0 / 1.0 (batch rows {nu[:16]}"
                          f"{'...' if len(nu) > 16 else ''} of search call #{seq}): their outputs are empty; use unit_cost='auto' or False")
+    bh = torch.nonzero(status == ops.STATUS_BAD_HEURISTIC).flatten().tolist()
+    if bh:
+        raise ValueError(f"non-finite heuristic: heuristic_maps of {len(bh)} map(s) hold a NaN or an infinite value (batch rows {bh[:16]}"
+                         f"{'...' if len(bh) > 16 else ''} of search call #{seq}): those maps were not searched, the others were")
     bad = torch.nonzero(status != 0).flatten().tolist()
     where = f"search call #{seq} of this module" + (" (an EARLIER call: check_solvable='deferred' delivers verdicts late)" if deferred else "")
     raise UnsolvableMapError(
@@ -217,8 +221,9 @@ class DifferentiableAstar(nn.Module):
         self.neighbor_filter = nn.Parameter(nf, requires_grad=False)
         self._nf_key = self._filter_key()
         self._nf_mask: Optional[int] = None  # None = Moore-8
-        # the reference keeps its heuristic as an INSTANCE attribute (:143), i.e. as something a user may replace; the kernels hard-wire that
-        # function (Chebyshev + 0.001 Euclidean): forward() refuses, loudly, to run with anything else in this attribute
+        # the reference keeps its heuristic as an INSTANCE attribute (:143), i.e. as something a user may replace; the kernels compute that
+        # function (Chebyshev + 0.001 Euclidean) themselves or take the heuristic as a TENSOR (forward(..., heuristic_maps=)): forward()
+        # refuses, loudly, to run with anything else in this attribute
         self.get_heuristic = get_heuristic
         self.g_ratio = g_ratio
         assert (Tmax > 0) & (Tmax <= 1), "Tmax must be within (0, 1]"
@@ -498,17 +503,29 @@ class DifferentiableAstar(nn.Module):
         return AstarOutput(hist, paths, [])
 
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
-                obstacles_maps: torch.Tensor, store_intermediate_results: bool = False) -> AstarOutput:
+                obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
+                heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:
+        """``heuristic_maps``: None = the reference's heuristic (today's call, unchanged); a [B,1,H,W] float32 tensor on the device of
+        ``cost_maps`` = exactly the reference run with ``astar.get_heuristic = lambda goal_maps: heuristic_maps[:, 0]`` -- zero (Dijkstra),
+        weighted, Manhattan, a network's output (any finite values; a NaN / infinite one raises ``ValueError`` naming the map).  A tensor, not
+        a callable: a learned heuristic depends on the map, not on the goal alone.  Its gradient is the gradient of ``cost_maps`` (the
+        loss sees both only through h = h0 + cost) and flows when either of the two requires one.  With a free heuristic a finished map is
+        often not at a fixed point of the reference's batch loop, so a batch of more than one map always runs the exact pipeline (DESIGN.md
+        section 2, item 6b).  Composes with ``neighbor_filter``; takes no native host lane, unit-cost layout or hand-scheduled stream."""
         assert cost_maps.ndim == 4
         assert start_maps.ndim == 4
         assert goal_maps.ndim == 4
         assert obstacles_maps.ndim == 4
         if self.get_heuristic is not get_heuristic:
             raise NotImplementedError("DifferentiableAstar.get_heuristic was replaced: the MI355X search kernels hard-wire the reference's heuristic "
-                                      "(Chebyshev + 0.001 x Euclidean, differentiable_astar.py:26-52) and would silently ignore another one")
+                                      "(Chebyshev + 0.001 x Euclidean, differentiable_astar.py:26-52) and would silently ignore another one; "
+                                      "pass the heuristic as a tensor instead: forward(..., heuristic_maps=h0) with h0 of shape [B, 1, H, W]")
+        h0 = None
+        if heuristic_maps is not None:
+            h0 = _checked_heuristic(heuristic_maps, cost_maps)
         self.last_packed = None
         nmask = self.neighbor_mask()  # None: the default (Moore-8) filter -- its kernels, its native host lane, its unit-cost layout
-        if (nmask is None and self.check_solvable is True and not store_intermediate_results and not self._pending and type(cost_maps) is torch.Tensor
+        if (nmask is None and h0 is None and self.check_solvable is True and not store_intermediate_results and not self._pending and type(cost_maps) is torch.Tensor
                 and not (cost_maps.requires_grad and torch.is_grad_enabled())):
             out = self._forward_fast(cost_maps, start_maps, goal_maps, obstacles_maps)
             if out is not None:
@@ -516,7 +533,7 @@ class DifferentiableAstar(nn.Module):
 
         B, _, H, W = cost_maps.shape
         max_iters = ops.max_iters_for(W, self.Tmax, self.training)
-        needs_grad = cost_maps.requires_grad and torch.is_grad_enabled()
+        needs_grad = (cost_maps.requires_grad or (h0 is not None and h0.requires_grad)) and torch.is_grad_enabled()
         # the selection log doubles as the tape of the backward (replayed by nastar_backward_replay): keep it whenever
         # autograd will need it
         want_log = bool(store_intermediate_results) or needs_grad
@@ -530,7 +547,7 @@ class DifferentiableAstar(nn.Module):
         # the unit-cost layout pays with SEVERAL launches in flight (more maps resident per CU); one launch at a time is a serial chain whose
         # length does not depend on the layout (probe_boundary: 117 us unit vs 114 us general per placed 4096-map launch), so forward()
         # takes it only on request -- parallel.InFlightPlanner is where "auto" means "unit-cost first"
-        unit = same and not want_log and self.unit_cost is True and nmask is None
+        unit = same and not want_log and self.unit_cost is True and nmask is None and h0 is None
         in_lds = ops.in_lds(H, W)
         # a recurring batch starts its longest searches first (Placement), a fresh one by its loader's hint; maps whose state lives in HBM take no placement
         if self.placement is None and not hasattr(start_maps, "placement_order"):
@@ -538,8 +555,8 @@ class DifferentiableAstar(nn.Module):
             check_order = False
         else:
             order, order_out, check_order, pl = self.resolve_placement(B, start_maps, in_lds)
-            if nmask is not None and needs_grad:
-                order = order_out = None  # (a neighbor_filter under autograd: the plain differentiable op, no placement)
+            if (nmask is not None or h0 is not None) and needs_grad:
+                order = order_out = None  # (a neighbor_filter / a heuristic under autograd: the plain differentiable op, no placement)
         dev = cost_maps.device
         compiling = torch.compiler.is_compiling()
         # (no status protocol while a hipGraph is captured or torch.compile traces: its host side would run once, at capture / trace time)
@@ -554,16 +571,24 @@ class DifferentiableAstar(nn.Module):
         # batch loop and ONE launch is the whole story; the launch reports the rare exception (negative costs) in its status summary.  Outside
         # that range the class is reachable with ordinary costs: the exact pipeline runs straight away (marks + three launches that do nothing
         # when no map is marked) -- under autograd, with deferred or no checking, inside a hipGraph capture or a trace alike.
-        exact = B > 1 and ops.coupling_possible(self.g_ratio) and not unit
+        # With a caller's heuristic the class is reachable at every g_ratio (the fixed-point proof needs h0(n) >= 1.001 and h0(goal) = 0).
+        exact = B > 1 and (ops.coupling_possible(self.g_ratio) or h0 is not None) and not unit
 
         def launch(exact_now: bool, sptr_now: int, cptr_now: int):
             if not traced:
                 # no gradient can flow and nothing is tracing: straight to the C ABI (no torch.library dispatch)
                 return ops.search_nograd(cost_maps, start_maps, goal_maps, passable_maps, self.g_ratio, max_iters, want_log, flags, order, order_out,
-                                         check_order, sptr_now, None, True, cptr_now, None, exact_now, neighbor_mask=nmask)
+                                         check_order, sptr_now, None, True, cptr_now, None, exact_now, neighbor_mask=nmask, heuristic=h0)
             cost, start, goal, passable = cost_maps[:, 0], start_maps[:, 0], goal_maps[:, 0], obstacles_maps[:, 0]
             mask_arg = ops.NEIGHBORS_MOORE8 if nmask is None else nmask
-            if needs_grad and in_lds and nmask is None and (order is not None or order_out is not None or B >= ops.PLACEMENT_MIN_BATCH):
+            if h0 is not None:
+                if order is None and order_out is None:
+                    o = torch.ops.nastar.astar_forward(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, sptr_now, exact_now,
+                                                       mask_arg, h0[:, 0])
+                else:
+                    o = torch.ops.nastar.astar_forward_ordered(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, order,
+                                                               order_out, check_order, sptr_now, exact_now, mask_arg, h0[:, 0])
+            elif needs_grad and in_lds and nmask is None and (order is not None or order_out is not None or B >= ops.PLACEMENT_MIN_BATCH):
                 # large batches under autograd: the replay backward starts longest-first, by the order THIS forward's searches finish in
                 o = ops.astar_forward_placed(cost, start, goal, passable, self.g_ratio, max_iters, 0, order, order_out, check_order, sptr_now, exact_now)
             elif order is None and order_out is None:
@@ -600,6 +625,22 @@ class DifferentiableAstar(nn.Module):
         if store_intermediate_results:
             intermediate_results = _intermediate_results(hist[:, 0], paths[:, 0], goal_maps[:, 0], iters, sel_log)
         return AstarOutput(hist, paths, intermediate_results)
+
+
+def _checked_heuristic(h: torch.Tensor, cost_maps: torch.Tensor) -> torch.Tensor:
+    """``heuristic_maps`` of forward(): a [B,1,H,W] float32 tensor on the device of ``cost_maps`` (nothing is launched before this passes)"""
+    if not torch.is_tensor(h):
+        raise TypeError(f"heuristic_maps must be a tensor of shape [B, 1, H, W] (a callable is not taken: evaluate it first), got {type(h).__name__}")
+    if h.dtype != torch.float32:
+        raise TypeError(f"heuristic_maps must be float32, got {h.dtype}")
+    B, _, H, W = cost_maps.shape
+    if h.ndim != 4 or tuple(h.shape) != (B, 1, H, W):
+        raise ValueError(f"heuristic_maps must have shape {(B, 1, H, W)} (one value per cell of every map), got {tuple(h.shape)}")
+    if h.device != cost_maps.device:
+        raise ValueError(f"heuristic_maps lives on {h.device}, cost_maps on {cost_maps.device}: they must share a device")
+    if not cost_maps.is_cuda:
+        ops._require_device(cost_maps)  # (the package's "no CPU" error)
+    return h if h.is_contiguous() else h.contiguous()
 
 
 def _filter_mask(f) -> int:
