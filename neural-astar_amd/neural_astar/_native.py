@@ -23,6 +23,7 @@ NASTAR_ERR_UNSOLVABLE = 3
 NASTAR_ERR_HIP = 4
 NASTAR_ERR_NULL = 5
 NASTAR_ERR_WORKSPACE = 6
+NASTAR_ERR_NOT_UNIT_COST = 7  # per-map status only
 NASTAR_ERR_BAD_HEURISTIC = 8  # per-map status only
 
 _ERR_NAMES = {
@@ -32,85 +33,105 @@ _ERR_NAMES = {
     NASTAR_ERR_HIP: "HIP runtime error",
     NASTAR_ERR_NULL: "NULL pointer argument",
     NASTAR_ERR_WORKSPACE: "workspace too small",
+    NASTAR_ERR_NOT_UNIT_COST: "NASTAR_FLAG_UNIT_COST was passed for a map that holds a value other than 0.0 / 1.0",
+    NASTAR_ERR_BAD_HEURISTIC: "a NaN or an infinite value in a map's heuristic",
+}
+
+# ---- the signatures of include/nastar.h, each written ONCE: "<return type> <argument types>", one letter per C type (tests/test_capi_library.py
+# compares every entry with the header's prototype).  load() / load_dev() turn them into ctypes restype / argtypes.
+_CTYPES = {"p": ctypes.c_void_p,                  # any pointer (device or host); NULL = None
+           "P": ctypes.POINTER(ctypes.c_void_p),  # pointer to pointer: a HOST array of device pointers
+           "i": ctypes.c_int, "u": ctypes.c_uint, "f": ctypes.c_float, "d": ctypes.c_double, "z": ctypes.c_size_t, "q": ctypes.c_longlong,
+           "s": ctypes.c_char_p}                  # (return type only: const char*)
+_MAPS = "pppp"            # cost, start, goal, passable
+_BUDGET = "iiidi"         # B, H, W, g_ratio, max_iters
+_OUTPUTS = "ppppp"        # histories_out, paths_out, sel_log_out, iters_out, status_out
+_WORKSPACE = "pz"         # workspace, workspace_bytes
+_FORWARD = _MAPS + _BUDGET + _OUTPUTS
+_REPLAY = _MAPS + "p" + _BUDGET + "ppp" + _WORKSPACE  # ..., sel_log, ..., iters, t_batch_dev, grad_cost_out, ...
+
+
+def _family(name: str, args: str) -> dict:
+    """an entry point whose last argument is the stream, and its twins `_masked` (`unsigned neighbor_mask` in front of the stream) and
+    `_heuristic` (`unsigned neighbor_mask, const float* h0`)"""
+    return {name: "i " + args + "p", name + "_masked": "i " + args + "up", name + "_heuristic": "i " + args + "upp"}
+
+
+SIGNATURES = {
+    "nastar_version": "i ",
+    "nastar_last_error": "s ",
+    "nastar_workspace_bytes": "z iiii",
+    "nastar_forward": "i " + _FORWARD + _WORKSPACE + "ip",
+    "nastar_forward_packed": "i " + _FORWARD + "p" + _WORKSPACE + "ip",
+    "nastar_forward_ordered": "i " + _FORWARD + "p" + _WORKSPACE + "ippp",
+    # ... packed_out, workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter
+    **_family("nastar_forward_ex", _FORWARD + "p" + _WORKSPACE + "ipppp"),
+    "nastar_batchloop_workspace_bytes": "z iiii",
+    **_family("nastar_forward_batchloop_finish", _FORWARD + _WORKSPACE),
+    "nastar_completion_supported": "i ii",
+    "nastar_host_wait_nonzero": "i pi",
+    "nastar_placement_from_levels": "i pipp",
+    "nastar_placement_predict": "i pppiiippzp",
+    "nastar_backward_workspace_bytes": "z iiii",
+    "nastar_backward_replay": "i p" + _REPLAY + "ip",
+    # grad_histories, histories, opt_trajs, grad_loss_dev, ..., flags, order
+    **_family("nastar_backward_replay_ordered", "pppp" + _REPLAY + "ip"),
+    "nastar_backward_l1_replay": "i ppp" + _REPLAY + "p",
+    "nastar_l1_loss": "i ppqppzp",
+    "nastar_policy_rollout": "i pppiiiiippp",
+    "nastar_heuristic": "i piiipp",
+    "nastar_debug_occupancy": "i iip",
+    "nastar_pack_outputs": "i ppiiipp",
+    "nastar_unpack_outputs": "i piiippp",
+    "nastar_encoder_workspace_bytes": "z iii",
+    "nastar_encoder_cnn_forward": "i pppiiiiPPPfppzp",
+    "nastar_encoder_workspace_bytes_f16x3": "z iii",
+    "nastar_encoder_cnn_forward_f16x3": "i pppiiiipPPPfppzp",
+    "nastar_encoder_workspace_bytes_f16": "z iii",
+    "nastar_encoder_cnn_forward_f16": "i pppiiiipPPPfppzp",
+    "nastar_conv3x3_bf16": "i pppppiiiiiip",
+    "nastar_encoder_downsize_workspace_bytes": "z iiiii",
+    "nastar_encoder_cnn_downsize_forward": "i pppiiiiiiiiPPPfppzp",
+    "nastar_conv3x3_f16": "i pppppppiiiiiiifp",
+    "nastar_conv3x3_img32_f16": "i pppppiiiip",
+    "nastar_maxpool2x2_f16": "i ppiiiiip",
+    "nastar_encoder_prep_f16": "i pppiqiipp",
+    "nastar_conv3x3_wgrad_workspace_bytes": "z iiiii",
+    "nastar_conv3x3_wgrad_f16": "i pppiiiiiiiifppzp",
+    "nastar_chan_stats_f16": "i ppppppqiip",
+    "nastar_chan_stats_workspace_bytes": "z qi",
+    "nastar_absmax_multi_f32": "i pipp",
+    "nastar_pack_conv_weights_multi_f16": "i piiipppp",
+    "nastar_rmsprop_multi_f32": "i pifffp",
+    "nastar_bn1_parts": "i q",
+    "nastar_bn1_fwd_partial": "i pqpp",
+    "nastar_bn1_sigmoid_fwd": "i pqpidppdpdppppp",
+    "nastar_bn1_sigmoid_bwd_partial": "i ppqpppppp",
+    "nastar_bn1_sigmoid_bwd": "i ppqpppppidppppp",
+    "nastar_chan_stats_f16_ws": "i ppppppqiipzp",
+    "nastar_chan_affine_f16": "i ppppppppqiiip",
+    "nastar_pack_conv_weight_f16": "i piiiipppppip",
+    "nastar_bn_coef_fwd": "i pppdqdppppppip",
+    "nastar_bn_coef_bwd": "i pppppqppppppip",
+    "nastar_bn_coef_bwd_io": "i pppppqpppppppip",
+    "nastar_bn_stats_coef_fwd_f16": "i pqiippddppppppppzp",
+    "nastar_bn_stats_coef_bwd_f16": "i ppppqiippppppppppppzp",
+    "nastar_grad_seed_f16": "i pqipppp",
+    "nastar_conv3x3_co1_workspace_bytes": "z iiii",
+    "nastar_conv3x3_co1_f16": "i pppiiiiippppzp",
+    "nastar_conv3x3_co1_wgrad_f16": "i ppiiiiippppzp",
+    "nastar_grad_scale_f32": "i pqppp",
+    "nastar_bn_stats_coef_bwd_u1_f16": "i ppiiipppiippppppppppppzp",
+    "nastar_chan_affine_u1_f16": "i pppiiipppppppiip",
+    "nastar_chan_stats_u1_f16_ws": "i pppiiipppppiipzp",
+    "nastar_maxpool2x2_bwd_f16": "i pppiiiiip",
+    "nastar_upcat_f16": "i pppiiiiiip",
+    "nastar_upcat_bwd_f16": "i pppiiiiiip",
+    "nastar_grad_add_f16": "i ppppppqiip",
 }
 
 # every symbol include/nastar.h declares -- tests check the library exports all of them
-EXPORTED_SYMBOLS = (
-    "nastar_version",
-    "nastar_last_error",
-    "nastar_workspace_bytes",
-    "nastar_forward",
-    "nastar_forward_packed",
-    "nastar_forward_ordered",
-    "nastar_forward_ex",
-    "nastar_forward_ex_masked",
-    "nastar_forward_ex_heuristic",
-    "nastar_batchloop_workspace_bytes",
-    "nastar_forward_batchloop_finish",
-    "nastar_forward_batchloop_finish_masked",
-    "nastar_forward_batchloop_finish_heuristic",
-    "nastar_completion_supported",
-    "nastar_host_wait_nonzero",
-    "nastar_placement_from_levels",
-    "nastar_placement_predict",
-    "nastar_backward_workspace_bytes",
-    "nastar_backward_replay",
-    "nastar_backward_replay_ordered",
-    "nastar_backward_replay_ordered_masked",
-    "nastar_backward_replay_ordered_heuristic",
-    "nastar_backward_l1_replay",
-    "nastar_l1_loss",
-    "nastar_policy_rollout",
-    "nastar_heuristic",
-    "nastar_debug_occupancy",
-    "nastar_pack_outputs",
-    "nastar_unpack_outputs",
-    "nastar_encoder_workspace_bytes",
-    "nastar_encoder_cnn_forward",
-    "nastar_encoder_workspace_bytes_f16x3",
-    "nastar_encoder_cnn_forward_f16x3",
-    "nastar_encoder_workspace_bytes_f16",
-    "nastar_encoder_cnn_forward_f16",
-    "nastar_conv3x3_bf16",
-    "nastar_encoder_downsize_workspace_bytes",
-    "nastar_encoder_cnn_downsize_forward",
-    "nastar_conv3x3_f16",
-    "nastar_conv3x3_img32_f16",
-    "nastar_maxpool2x2_f16",
-    "nastar_encoder_prep_f16",
-    "nastar_conv3x3_wgrad_workspace_bytes",
-    "nastar_conv3x3_wgrad_f16",
-    "nastar_chan_stats_f16",
-    "nastar_chan_stats_workspace_bytes",
-    "nastar_absmax_multi_f32",
-    "nastar_pack_conv_weights_multi_f16",
-    "nastar_rmsprop_multi_f32",
-    "nastar_bn1_parts",
-    "nastar_bn1_fwd_partial",
-    "nastar_bn1_sigmoid_fwd",
-    "nastar_bn1_sigmoid_bwd_partial",
-    "nastar_bn1_sigmoid_bwd",
-    "nastar_chan_stats_f16_ws",
-    "nastar_chan_affine_f16",
-    "nastar_pack_conv_weight_f16",
-    "nastar_bn_coef_fwd",
-    "nastar_bn_coef_bwd",
-    "nastar_bn_coef_bwd_io",
-    "nastar_bn_stats_coef_fwd_f16",
-    "nastar_bn_stats_coef_bwd_f16",
-    "nastar_grad_seed_f16",
-    "nastar_conv3x3_co1_workspace_bytes",
-    "nastar_conv3x3_co1_f16",
-    "nastar_conv3x3_co1_wgrad_f16",
-    "nastar_grad_scale_f32",
-    "nastar_bn_stats_coef_bwd_u1_f16",
-    "nastar_chan_affine_u1_f16",
-    "nastar_chan_stats_u1_f16_ws",
-    "nastar_maxpool2x2_bwd_f16",
-    "nastar_upcat_f16",
-    "nastar_upcat_bwd_f16",
-    "nastar_grad_add_f16",
-)
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -131,21 +152,18 @@ DEV_LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libnastar_hip_dev.so")
 _dev_lib: Optional[ctypes.CDLL] = None
 
 
+def _bind(lib: ctypes.CDLL, names) -> None:
+    for name in names:
+        ret, args = SIGNATURES[name].split(" ")
+        fn = getattr(lib, name)
+        fn.restype = _CTYPES[ret]
+        fn.argtypes = [_CTYPES[k] for k in args]
+
+
 def _bind_search(lib: ctypes.CDLL) -> None:
-    """argument types of the search entry points (shared by the product library and the development build)"""
-    vp, ci, cd, cz = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
-    lib.nastar_workspace_bytes.restype = cz
-    lib.nastar_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.nastar_forward_ex.restype = ci
-    lib.nastar_forward_ex.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, cz, ci, vp, vp, vp, vp, vp]
-    lib.nastar_batchloop_workspace_bytes.restype = cz
-    lib.nastar_batchloop_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.nastar_forward_batchloop_finish.restype = ci
-    lib.nastar_forward_batchloop_finish.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, cz, vp]
-    lib.nastar_backward_workspace_bytes.restype = cz
-    lib.nastar_backward_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.nastar_backward_replay.restype = ci
-    lib.nastar_backward_replay.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, ci, vp]
+    """the search entry points the development build is called through (the product library binds every symbol)"""
+    _bind(lib, ("nastar_workspace_bytes", "nastar_forward_ex", "nastar_batchloop_workspace_bytes", "nastar_forward_batchloop_finish",
+                "nastar_backward_workspace_bytes", "nastar_backward_replay"))
 
 
 def load_dev() -> ctypes.CDLL:
@@ -196,159 +214,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} not found: the MI355X HIP extension is the only compute path of this package "
             f"(no CPU fallback). Build it with `make -C {CSRC_DIR}` or `python __graft_entry__.py build`.")
     lib = ctypes.CDLL(LIB_PATH)
-    vp, ci, cd, cz = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
-    _bind_search(lib)
-    lib.nastar_version.restype = ci
-    lib.nastar_version.argtypes = []
-    lib.nastar_last_error.restype = ctypes.c_char_p
-    lib.nastar_last_error.argtypes = []
-    lib.nastar_workspace_bytes.restype = cz
-    lib.nastar_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.nastar_forward.restype = ci
-    lib.nastar_forward.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, cz, ci, vp]
-    lib.nastar_forward_ordered.restype = ci
-    lib.nastar_forward_ordered.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, cz, ci, vp, vp, vp]
-    lib.nastar_forward_ex.restype = ci
-    lib.nastar_forward_ex.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, cz, ci, vp, vp, vp, vp, vp]
-    lib.nastar_completion_supported.restype = ci
-    lib.nastar_completion_supported.argtypes = [ci, ci]
-    lib.nastar_host_wait_nonzero.restype = ci
-    lib.nastar_host_wait_nonzero.argtypes = [vp, ci]
-    lib.nastar_placement_from_levels.restype = ci
-    lib.nastar_placement_from_levels.argtypes = [vp, ci, vp, vp]
-    lib.nastar_placement_predict.restype = ci
-    lib.nastar_placement_predict.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, cz, vp]
-    lib.nastar_forward_packed.restype = ci
-    lib.nastar_forward_packed.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, cz, ci, vp]
-    lib.nastar_backward_workspace_bytes.restype = cz
-    lib.nastar_backward_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.nastar_backward_replay.restype = ci
-    lib.nastar_backward_replay.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, ci, vp]
-    lib.nastar_backward_replay_ordered.restype = ci
-    lib.nastar_backward_replay_ordered.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, ci, vp, vp]
-    # the masked entry points (DifferentiableAstar.neighbor_filter): one `unsigned neighbor_mask` in front of the stream
-    cu = ctypes.c_uint
-    lib.nastar_forward_ex_masked.restype = ci
-    lib.nastar_forward_ex_masked.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, vp, cz, ci, vp, vp, vp, vp, cu, vp]
-    lib.nastar_forward_batchloop_finish_masked.restype = ci
-    lib.nastar_forward_batchloop_finish_masked.argtypes = [vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, cz, cu, vp]
-    lib.nastar_backward_replay_ordered_masked.restype = ci
-    lib.nastar_backward_replay_ordered_masked.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, ci, vp, cu, vp]
-    # the entry points with a caller-supplied heuristic: `unsigned neighbor_mask, const float* h0` in front of the stream
-    lib.nastar_forward_ex_heuristic.restype = ci
-    lib.nastar_forward_ex_heuristic.argtypes = lib.nastar_forward_ex_masked.argtypes[:-1] + [vp, vp]
-    lib.nastar_forward_batchloop_finish_heuristic.restype = ci
-    lib.nastar_forward_batchloop_finish_heuristic.argtypes = lib.nastar_forward_batchloop_finish_masked.argtypes[:-1] + [vp, vp]
-    lib.nastar_backward_replay_ordered_heuristic.restype = ci
-    lib.nastar_backward_replay_ordered_heuristic.argtypes = lib.nastar_backward_replay_ordered_masked.argtypes[:-1] + [vp, vp]
-    lib.nastar_backward_l1_replay.restype = ci
-    lib.nastar_backward_l1_replay.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, cd, ci, vp, vp, vp, vp, cz, vp]
-    lib.nastar_l1_loss.restype = ci
-    lib.nastar_l1_loss.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, cz, vp]
-    lib.nastar_policy_rollout.restype = ci
-    lib.nastar_policy_rollout.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]
-    lib.nastar_heuristic.restype = ci
-    lib.nastar_heuristic.argtypes = [vp, ci, ci, ci, vp, vp]
-    lib.nastar_pack_outputs.restype = ci
-    lib.nastar_pack_outputs.argtypes = [vp, vp, ci, ci, ci, vp, vp]
-    lib.nastar_unpack_outputs.restype = ci
-    lib.nastar_unpack_outputs.argtypes = [vp, ci, ci, ci, vp, vp, vp]
-    lib.nastar_encoder_workspace_bytes.restype = cz
-    lib.nastar_encoder_workspace_bytes.argtypes = [ci, ci, ci]
-    lib.nastar_encoder_cnn_forward.restype = ci
-    lib.nastar_encoder_cnn_forward.argtypes = [vp, vp, vp, ci, ci, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                               ctypes.POINTER(vp), ctypes.c_float, vp, vp, cz, vp]
-    lib.nastar_encoder_workspace_bytes_f16x3.restype = cz
-    lib.nastar_encoder_workspace_bytes_f16x3.argtypes = [ci, ci, ci]
-    lib.nastar_encoder_cnn_forward_f16x3.restype = ci
-    lib.nastar_encoder_cnn_forward_f16x3.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                                     ctypes.POINTER(vp), ctypes.c_float, vp, vp, cz, vp]
-    lib.nastar_encoder_workspace_bytes_f16.restype = cz
-    lib.nastar_encoder_workspace_bytes_f16.argtypes = [ci, ci, ci]
-    lib.nastar_encoder_cnn_forward_f16.restype = ci
-    lib.nastar_encoder_cnn_forward_f16.argtypes = lib.nastar_encoder_cnn_forward_f16x3.argtypes
-    lib.nastar_encoder_downsize_workspace_bytes.restype = cz
-    lib.nastar_encoder_downsize_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
-    lib.nastar_encoder_cnn_downsize_forward.restype = ci
-    lib.nastar_encoder_cnn_downsize_forward.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp),
-                                                        ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_float, vp, vp, cz, vp]
-    lib.nastar_conv3x3_bf16.restype = ci
-    lib.nastar_conv3x3_bf16.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    lib.nastar_conv3x3_f16.restype = ci
-    lib.nastar_conv3x3_f16.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
-    lib.nastar_conv3x3_img32_f16.restype = ci
-    lib.nastar_conv3x3_img32_f16.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    lib.nastar_maxpool2x2_f16.restype = ci
-    lib.nastar_maxpool2x2_f16.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
-    lib.nastar_encoder_prep_f16.restype = ci
-    lib.nastar_encoder_prep_f16.argtypes = [vp, vp, vp, ci, ctypes.c_longlong, ci, ci, vp, vp]
-    lib.nastar_conv3x3_wgrad_f16.restype = ci
-    lib.nastar_conv3x3_wgrad_f16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp, vp, cz, vp]
-    lib.nastar_conv3x3_wgrad_workspace_bytes.restype = cz
-    lib.nastar_conv3x3_wgrad_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
-    lib.nastar_chan_stats_f16.restype = ci
-    lib.nastar_chan_stats_f16.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_longlong, ci, ci, vp]
-    cll = ctypes.c_longlong
-    lib.nastar_bn1_parts.restype = ci
-    lib.nastar_bn1_parts.argtypes = [cll]
-    lib.nastar_bn1_fwd_partial.restype = ci
-    lib.nastar_bn1_fwd_partial.argtypes = [vp, cll, vp, vp]
-    lib.nastar_bn1_sigmoid_fwd.restype = ci
-    lib.nastar_bn1_sigmoid_fwd.argtypes = [vp, cll, vp, ci, cd, vp, vp, cd, vp, cd, vp, vp, vp, vp, vp]
-    lib.nastar_bn1_sigmoid_bwd_partial.restype = ci
-    lib.nastar_bn1_sigmoid_bwd_partial.argtypes = [vp, vp, cll, vp, vp, vp, vp, vp, vp]
-    lib.nastar_bn1_sigmoid_bwd.restype = ci
-    lib.nastar_bn1_sigmoid_bwd.argtypes = [vp, vp, cll, vp, vp, vp, vp, vp, ci, cd, vp, vp, vp, vp, vp]
-    lib.nastar_absmax_multi_f32.restype = ci
-    lib.nastar_absmax_multi_f32.argtypes = [vp, ci, vp, vp]
-    lib.nastar_pack_conv_weights_multi_f16.restype = ci
-    lib.nastar_pack_conv_weights_multi_f16.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp]
-    lib.nastar_rmsprop_multi_f32.restype = ci
-    lib.nastar_rmsprop_multi_f32.argtypes = [vp, ci, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
-    lib.nastar_chan_stats_workspace_bytes.restype = cz
-    lib.nastar_chan_stats_workspace_bytes.argtypes = [ctypes.c_longlong, ci]
-    lib.nastar_chan_stats_f16_ws.restype = ci
-    lib.nastar_chan_stats_f16_ws.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_longlong, ci, ci, vp, cz, vp]
-    lib.nastar_conv3x3_co1_workspace_bytes.restype = cz
-    lib.nastar_conv3x3_co1_workspace_bytes.argtypes = [ci, ci, ci, ci]
-    lib.nastar_conv3x3_co1_f16.restype = ci
-    lib.nastar_conv3x3_co1_f16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, cz, vp]
-    lib.nastar_conv3x3_co1_wgrad_f16.restype = ci
-    lib.nastar_conv3x3_co1_wgrad_f16.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, cz, vp]
-    lib.nastar_grad_scale_f32.restype = ci
-    lib.nastar_grad_scale_f32.argtypes = [vp, ctypes.c_longlong, vp, vp, vp]
-    lib.nastar_bn_stats_coef_bwd_u1_f16.restype = ci
-    lib.nastar_bn_stats_coef_bwd_u1_f16.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cz, vp]
-    lib.nastar_chan_stats_u1_f16_ws.restype = ci
-    lib.nastar_chan_stats_u1_f16_ws.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, cz, vp]
-    lib.nastar_chan_affine_u1_f16.restype = ci
-    lib.nastar_chan_affine_u1_f16.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
-    lib.nastar_chan_affine_f16.restype = ci
-    lib.nastar_chan_affine_f16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_longlong, ci, ci, ci, vp]
-    lib.nastar_pack_conv_weight_f16.restype = ci
-    lib.nastar_pack_conv_weight_f16.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp]
-    lib.nastar_bn_stats_coef_fwd_f16.restype = ci
-    lib.nastar_bn_stats_coef_fwd_f16.argtypes = [vp, ctypes.c_longlong, ci, ci, vp, vp, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp, cz, vp]
-    lib.nastar_bn_stats_coef_bwd_f16.restype = ci
-    lib.nastar_bn_stats_coef_bwd_f16.argtypes = [vp, vp, vp, vp, ctypes.c_longlong, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cz, vp]
-    lib.nastar_bn_coef_bwd_io.restype = ci
-    lib.nastar_bn_coef_bwd_io.argtypes = [vp, vp, vp, vp, vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, vp, ci, vp]
-    lib.nastar_bn_coef_fwd.restype = ci
-    lib.nastar_bn_coef_fwd.argtypes = [vp, vp, vp, cd, ctypes.c_longlong, cd, vp, vp, vp, vp, vp, vp, ci, vp]
-    lib.nastar_bn_coef_bwd.restype = ci
-    lib.nastar_bn_coef_bwd.argtypes = [vp, vp, vp, vp, vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, ci, vp]
-    lib.nastar_upcat_f16.restype = ci
-    lib.nastar_upcat_f16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    lib.nastar_upcat_bwd_f16.restype = ci
-    lib.nastar_upcat_bwd_f16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]
-    lib.nastar_grad_add_f16.restype = ci
-    lib.nastar_grad_add_f16.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_longlong, ci, ci, vp]
-    lib.nastar_maxpool2x2_bwd_f16.restype = ci
-    lib.nastar_maxpool2x2_bwd_f16.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp]
-    lib.nastar_grad_seed_f16.restype = ci
-    lib.nastar_grad_seed_f16.argtypes = [vp, ctypes.c_longlong, ci, vp, vp, vp, vp]
-    lib.nastar_debug_occupancy.restype = ci
-    lib.nastar_debug_occupancy.argtypes = [ci, ci, ctypes.POINTER(ci)]
+    _bind(lib, SIGNATURES)
     _lib = lib
     return lib
 

@@ -190,8 +190,52 @@ def in_lds(H: int, W: int) -> bool:
     return v
 
 
-def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, order, order_out, check_order, summary_ptr, dev,
-                   one_meta=False, stream_ptr=None, out_4d=False, counter_ptr=0, keep=None, exact=False, neighbor_mask=None, heuristic=None):
+def _entry_family(neighbor_mask: Optional[int], heuristic):
+    """THE choice among the three twins of every search / finish / ordered-replay entry point (include/nastar.h): -> (suffix of the symbol,
+    the arguments it takes between the base entry's and the stream).  Plain: no mask (None -- Moore-8 on the fastest kernels) and no
+    heuristic; `_masked`: a mask, NEIGHBORS_MOORE8 included; `_heuristic`: a heuristic, with the given mask or Moore-8."""
+    if heuristic is not None:
+        return "_heuristic", (NEIGHBORS_MOORE8 if neighbor_mask is None else int(neighbor_mask), heuristic)
+    if neighbor_mask is not None:
+        return "_masked", (int(neighbor_mask),)
+    return "", ()
+
+
+def forward_calls(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                  workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, stream, exact=False,
+                  neighbor_mask=None, h0=None):
+    """The C calls of ONE search as plain values (addresses as ints, None / 0 = absent; no tensor, no device): -> ((symbol, arguments) of the
+    launch, (symbol, arguments) of the batch-loop finish behind it -- None unless ``exact``).  The parameters up to ``stream`` ARE those of
+    nastar_forward_ex in include/nastar.h, names and order (less packed_out; tests/test_capi_library.py pins it): ``_launch_search`` passes
+    them by position -- keywords cost the Python lane 1.5 us per launch.  ``completion_counter`` goes out only with a ``status_summary``."""
+    suffix, tail = _entry_family(neighbor_mask, h0)
+    problem = (cost, start, goal, passable, B, H, W, float(g_ratio), int(max_iters), histories_out, paths_out, sel_log_out or None, iters_out,
+               status_out)
+    launch = ("nastar_forward_ex" + suffix,
+              (*problem, None, workspace or None, workspace_bytes, flags, order or None, order_out or None, status_summary or None,
+               (completion_counter or None) if status_summary else None, *tail, stream))
+    finish = ("nastar_forward_batchloop_finish" + suffix, (*problem, workspace, workspace_bytes, *tail, stream)) if exact else None
+    return launch, finish
+
+
+def replay_call(*, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_iters, iters, t_batch, grad_cost, workspace, ws_bytes, stream,
+                grad_hist=None, histories=None, opt_trajs=None, grad_loss=None, flags=0, order=None, neighbor_mask=None, heuristic=None):
+    """The C call of ONE replay backward as plain values: -> (symbol, arguments).  ``grad_hist`` given: dL/dhistories comes from autograd;
+    None: the fused L1 form (``histories``, ``opt_trajs``, ``grad_loss``).  nastar_backward_replay / nastar_backward_l1_replay where they
+    suffice (no order, mask or heuristic; the L1 one takes no flags either), the `_ordered` family otherwise."""
+    suffix, tail = _entry_family(neighbor_mask, heuristic)
+    replay = (cost, start, goal, passable, sel_log, B, H, W, float(g_ratio), int(max_iters), iters, t_batch, grad_cost, workspace, ws_bytes)
+    if not suffix and order is None:
+        if grad_hist is not None:
+            return "nastar_backward_replay", (grad_hist,) + replay + (int(flags), stream)
+        if not flags:
+            return "nastar_backward_l1_replay", (histories, opt_trajs, grad_loss) + replay + (stream,)
+    return "nastar_backward_replay_ordered" + suffix, (grad_hist, histories, opt_trajs, grad_loss) + replay + (int(flags), order) + tail + (stream,)
+
+
+def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, dev, order=None, order_out=None,
+                   check_order=False, summary_ptr=0, one_meta=False, stream_ptr=None, out_4d=False, counter_ptr=0, keep=None, exact=False,
+                   neighbor_mask=None, heuristic=None):
     """allocate the five outputs and issue ONE nastar_forward_ex launch on torch's current stream (shared by the custom ops and the
     no-autograd fast path).  cost / start / goal / passable: contiguous fp32 tensors of B*H*W elements (any leading shape).
     ``keep``: a list that receives the launch's temporaries (its workspace) when the launch goes to ANOTHER stream than the one the
@@ -203,7 +247,7 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
     ``neighbor_mask``: None = the reference's default neighbourhood (Moore-8) on the fastest kernels; an int = the search neighbourhood of a
     ``neighbor_filter`` (NEIGHBORS_*), searched by the masked entry points (nastar_forward_ex_masked: the compiled step loops, for every mask).
     ``heuristic``: None = the reference's get_heuristic, computed by the kernels; a contiguous fp32 [B, H, W] tensor = the caller's heuristic
-    maps (nastar_forward_ex_heuristic; with ``neighbor_mask`` or Moore-8)."""
+    maps (nastar_forward_ex_heuristic; with ``neighbor_mask`` or Moore-8).  Which symbols are called with which arguments: ``forward_calls``."""
     shape = (B, 1, H, W) if out_4d else (B, H, W)
     hist = torch.empty(shape, dtype=torch.float32, device=dev)
     paths = torch.empty(shape, dtype=torch.int64, device=dev)
@@ -216,15 +260,13 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
     # entries at positions >= iters[b] are never read (the backward replays iters[b] steps, _intermediate_results masks by iters)
     sel_log = torch.empty((B, max_iters), dtype=torch.int32, device=dev) if want_log else (None if out_4d else torch.empty((0,), dtype=torch.int32, device=dev))
     flags = int(flags) | FORWARD_FLAGS
-    op = oo = 0
+    order_ptr = None
     if order is not None:
-        op = _order_ptr(order, B, dev)
+        order_ptr = _order_ptr(order, B, dev)
         if check_order:
             flags |= FLAG_CHECK_ORDER
-    if order_out is not None:
-        if order_out.dtype != torch.int32 or order_out.numel() != B + 1 or order_out.device != dev or not order_out.is_contiguous():
-            raise ValueError(f"order_out must be a contiguous int32 tensor of exactly {B + 1} elements on {dev} (ops.new_placement_buffer)")
-        oo = order_out.data_ptr()
+    if order_out is not None and (order_out.dtype != torch.int32 or order_out.numel() != B + 1 or order_out.device != dev or not order_out.is_contiguous()):
+        raise ValueError(f"order_out must be a contiguous int32 tensor of exactly {B + 1} elements on {dev} (ops.new_placement_buffer)")
     # workspace: > 0 for maps too large for LDS, for a checked order and for the marks / probe bitmaps of an exact launch
     if exact and B > 1 and not (flags & FLAG_LOCKSTEP):
         flags |= FLAG_MARK_COUPLED
@@ -238,36 +280,21 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
             raise ValueError("a launch on a foreign stream that needs a workspace must be given a `keep` list (the allocator would hand the "
                              "workspace to the next launch on the current stream while this one still runs)")
         keep.append(workspace)
-    sp = stream_ptr if stream_ptr is not None else torch.cuda.current_stream(dev).cuda_stream
-    args = (cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, float(g_ratio), int(max_iters), hist.data_ptr(),
-            paths.data_ptr(), sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(), None,
-            workspace.data_ptr() if workspace is not None else None, ws_bytes, flags, op or None, oo or None, summary_ptr or None,
-            (counter_ptr or None) if summary_ptr else None, sp)
-    fin = None
-    if exact:
-        fin = args[:9] + (hist.data_ptr(), paths.data_ptr(), sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(),
-                          workspace.data_ptr(), ws_bytes, sp)
-    fwd, finish = lib.nastar_forward_ex, lib.nastar_forward_batchloop_finish
-    if neighbor_mask is not None:  # the masked entry points: one `neighbor_mask` in front of the stream
-        fwd, finish = lib.nastar_forward_ex_masked, lib.nastar_forward_batchloop_finish_masked
-        args = args[:-1] + (int(neighbor_mask), sp)
-        if fin is not None:
-            fin = fin[:-1] + (int(neighbor_mask), sp)
-    if heuristic is not None:  # ... and with a heuristic: `neighbor_mask, h0` in front of the stream
-        fwd, finish = lib.nastar_forward_ex_heuristic, lib.nastar_forward_batchloop_finish_heuristic
-        tail = (int(neighbor_mask) if neighbor_mask is not None else NEIGHBORS_MOORE8, heuristic.data_ptr(), sp)
-        args = args[:22] + tail
-        if fin is not None:
-            fin = fin[:16] + tail
+    (fwd, args), fin = forward_calls(
+        cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, g_ratio, max_iters, hist.data_ptr(), paths.data_ptr(),
+        sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(), workspace.data_ptr() if workspace is not None else None,
+        ws_bytes, flags, order_ptr, order_out.data_ptr() if order_out is not None else None, summary_ptr, counter_ptr,
+        stream_ptr if stream_ptr is not None else torch.cuda.current_stream(dev).cuda_stream, exact, neighbor_mask,
+        heuristic.data_ptr() if heuristic is not None else None)
     if dev.index is None or torch.cuda.current_device() == dev.index:
-        rc = fwd(*args)
+        rc = getattr(lib, fwd)(*args)
         if not rc and fin is not None:
-            rc = finish(*fin)
+            rc = getattr(lib, fin[0])(*fin[1])
     else:
         with torch.cuda.device(dev):
-            rc = fwd(*args)
+            rc = getattr(lib, fwd)(*args)
             if not rc and fin is not None:
-                rc = finish(*fin)
+                rc = getattr(lib, fin[0])(*fin[1])
     if rc:
         _native.check(rc, "nastar_forward_ex")
     return hist, paths, iters, status, sel_log
@@ -283,16 +310,28 @@ def astar_forward(cost: torch.Tensor, start: torch.Tensor, goal: torch.Tensor, p
     ``summary_ptr``: address of a ``StatusBoard`` row (0 = none) that receives the launch's status summary; ``exact``: see ``_launch_search``;
     ``neighbor_mask``: the search neighbourhood (NEIGHBORS_*, DifferentiableAstar.neighbor_filter); the backward replays with the same one.
     ``heuristic``: [B,H,W] fp32 heuristic maps in place of the reference's get_heuristic (None = that one); its gradient is the cost's."""
+    return _op_search(cost, start, goal, passable, g_ratio, max_iters, want_log, flags, neighbor_mask, heuristic, summary_ptr=summary_ptr, exact=exact)
+
+
+def _op_search(cost, start, goal, passable, g_ratio, max_iters, want_log, flags, neighbor_mask, heuristic, **options):
+    """body of the two forward ops: [B,H,W] tensors as they come -> ``_launch_search``"""
     _require_device(cost, start, goal, passable)
     lib = _native.load()
     cost, start, goal, passable = (x.contiguous() for x in (cost, start, goal, passable))
     B, H, W = cost.shape
-    return _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, None, None, False, summary_ptr, cost.device,
-                          exact=exact, neighbor_mask=_mask_arg(neighbor_mask), heuristic=_heuristic_arg(heuristic, cost))
+    return _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, cost.device,
+                          neighbor_mask=_mask_arg(neighbor_mask), heuristic=_heuristic_arg(heuristic, cost), **options)
+
+
+def _op_search_fake(cost, max_iters, want_log):
+    B, H, W = cost.shape
+    return (cost.new_empty((B, H, W)), cost.new_empty((B, H, W), dtype=torch.int64),
+            cost.new_empty((B,), dtype=torch.int32), cost.new_empty((B,), dtype=torch.int32),
+            cost.new_empty((B, max_iters) if want_log else (0,), dtype=torch.int32))
 
 
 def _mask_arg(neighbor_mask: int) -> Optional[int]:
-    """the custom ops' `neighbor_mask` -> ``_launch_search``'s: Moore-8 keeps the entry points (and kernels) without a mask"""
+    """the custom ops' `neighbor_mask` -> ``_entry_family``'s: Moore-8 keeps the entry points (and kernels) without a mask"""
     return None if int(neighbor_mask) == NEIGHBORS_MOORE8 else int(neighbor_mask)
 
 
@@ -308,10 +347,7 @@ def _heuristic_arg(heuristic: Optional[torch.Tensor], cost: torch.Tensor) -> Opt
 
 @astar_forward.register_fake
 def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags=0, summary_ptr=0, exact=False, neighbor_mask=NEIGHBORS_MOORE8, heuristic=None):
-    B, H, W = cost.shape
-    return (cost.new_empty((B, H, W)), cost.new_empty((B, H, W), dtype=torch.int64),
-            cost.new_empty((B,), dtype=torch.int32), cost.new_empty((B,), dtype=torch.int32),
-            cost.new_empty((B, max_iters) if want_log else (0,), dtype=torch.int32))
+    return _op_search_fake(cost, max_iters, want_log)
 
 
 @torch.library.custom_op("nastar::astar_forward_ordered", mutates_args=("order_out",))
@@ -327,25 +363,18 @@ def astar_forward_ordered(cost: torch.Tensor, start: torch.Tensor, goal: torch.T
     launch verifies ``order`` on the device (one small launch) and searches in the natural order when it is not a permutation -- every
     map is searched whatever the caller passed; False only for orders that are permutations by construction (an earlier launch's
     ``order_out``, ``order_from_levels``, ``placement_predict``, an argsort).  No autograd."""
-    _require_device(cost, start, goal, passable)
-    lib = _native.load()
-    cost, start, goal, passable = (x.contiguous() for x in (cost, start, goal, passable))
-    B, H, W = cost.shape
-    return _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, order, order_out, check_order,
-                          summary_ptr, cost.device, exact=exact, neighbor_mask=_mask_arg(neighbor_mask), heuristic=_heuristic_arg(heuristic, cost))
+    return _op_search(cost, start, goal, passable, g_ratio, max_iters, want_log, flags, neighbor_mask, heuristic, order=order, order_out=order_out,
+                      check_order=check_order, summary_ptr=summary_ptr, exact=exact)
 
 
 @astar_forward_ordered.register_fake
 def _(cost, start, goal, passable, g_ratio, max_iters, want_log, flags, order, order_out, check_order=True, summary_ptr=0, exact=False,
       neighbor_mask=NEIGHBORS_MOORE8, heuristic=None):
-    B, H, W = cost.shape
-    return (cost.new_empty((B, H, W)), cost.new_empty((B, H, W), dtype=torch.int64),
-            cost.new_empty((B,), dtype=torch.int32), cost.new_empty((B,), dtype=torch.int32),
-            cost.new_empty((B, max_iters) if want_log else (0,), dtype=torch.int32))
+    return _op_search_fake(cost, max_iters, want_log)
 
 
 def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, g_ratio: float,
-                  max_iters: int, want_log: bool = False, flags: int = 0, order: Optional[torch.Tensor] = None,
+                  max_iters: int, want_log: bool = False, flags: int = 0, *, order: Optional[torch.Tensor] = None,
                   order_out: Optional[torch.Tensor] = None, check_order: bool = True, summary_ptr: int = 0, stream_ptr: Optional[int] = None,
                   out_4d: bool = False, counter_ptr: int = 0, keep: Optional[list] = None, exact: bool = False, lib=None,
                   neighbor_mask: Optional[int] = None, heuristic: Optional[torch.Tensor] = None):
@@ -391,9 +420,11 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
             raise ValueError("heuristic maps must have the shape and device of the cost maps")
         if not heuristic.is_contiguous():
             heuristic = heuristic.contiguous()
+    # (the options by position, in ``_launch_search``'s order, here alone: twelve keywords cost this lane 1 us per launch -- the ops pass keywords;
+    # the True is one_meta)
     return _launch_search(lib if lib is not None else _native.load(), cost_maps, start_maps, goal_maps, obstacles_maps, B, H, W, g_ratio, max_iters,
-                          want_log, flags, order, order_out, check_order, summary_ptr, cost_maps.device, True, stream_ptr, out_4d, counter_ptr, keep, exact,
-                          neighbor_mask, heuristic)
+                          want_log, flags, cost_maps.device, order, order_out, check_order, summary_ptr, True, stream_ptr, out_4d, counter_ptr,
+                          keep, exact, neighbor_mask, heuristic)
 
 
 def order_from_levels(levels: torch.Tensor) -> torch.Tensor:
@@ -498,43 +529,36 @@ def astar_backward_replay(grad_hist: torch.Tensor, cost: torch.Tensor, start: to
     ``FLAG_LOCKSTEP`` for the log of an ``exact`` forward (goal selections before the last entry: the general replay loop).
     ``neighbor_mask``: the neighbourhood the forward searched (NEIGHBORS_*; anything but Moore-8: nastar_backward_replay_ordered_masked).
     ``heuristic``: the heuristic maps the forward searched with (nastar_backward_replay_ordered_heuristic); the result is then dL/dheuristic too."""
-    _require_device(grad_hist, cost, start, goal, passable)
+    _require_device(grad_hist)
+    return _replay(cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_batch, order, flags, "nastar_backward_replay", grad_hist=grad_hist,
+                   neighbor_mask=_mask_arg(neighbor_mask), heuristic=heuristic)
+
+
+def _replay(cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_batch, order, flags, what, *, neighbor_mask=None, heuristic=None,
+            **upstream):
+    """body of the two replay ops: allocate dL/dcost and the workspace, issue the call ``replay_call`` assembles.  ``upstream``: the tensors
+    of ``replay_call``'s first arguments (grad_hist, or histories / opt_trajs / grad_loss), None where absent"""
+    _require_device(cost, start, goal, passable)
     lib = _native.load()
-    grad_hist, cost, start, goal, passable, sel_log = (x.contiguous() for x in (grad_hist, cost, start, goal, passable, sel_log))
+    cost, start, goal, passable, sel_log = (x.contiguous() for x in (cost, start, goal, passable, sel_log))
+    upstream = {k: t.contiguous() for k, t in upstream.items() if t is not None}
     B, H, W = cost.shape
     dev = cost.device
     grad_cost = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     ws_bytes = int(lib.nastar_backward_workspace_bytes(B, H, W, int(max_iters)))
-    if ws_bytes == 0:
+    if ws_bytes == 0 and "grad_hist" in upstream:
         raise RuntimeError(f"nastar_backward_replay: unsupported map size {H}x{W}")
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
     heuristic = _heuristic_arg(heuristic, cost)
     with torch.cuda.device(dev):
-        if heuristic is not None:
-            rc = lib.nastar_backward_replay_ordered_heuristic(grad_hist.data_ptr(), None, None, None, cost.data_ptr(), start.data_ptr(), goal.data_ptr(),
-                                                              passable.data_ptr(), sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters),
-                                                              iters.data_ptr(), t_batch.data_ptr() if t_batch is not None else None, grad_cost.data_ptr(),
-                                                              ws.data_ptr(), ws_bytes, int(flags),
-                                                              _order_ptr(order, B, dev, True) if order is not None else None, int(neighbor_mask),
-                                                              heuristic.data_ptr(), _stream_ptr(dev))
-        elif int(neighbor_mask) != NEIGHBORS_MOORE8:
-            rc = lib.nastar_backward_replay_ordered_masked(grad_hist.data_ptr(), None, None, None, cost.data_ptr(), start.data_ptr(), goal.data_ptr(),
-                                                           passable.data_ptr(), sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters),
-                                                           iters.data_ptr(), t_batch.data_ptr() if t_batch is not None else None, grad_cost.data_ptr(),
-                                                           ws.data_ptr(), ws_bytes, int(flags),
-                                                           _order_ptr(order, B, dev, True) if order is not None else None, int(neighbor_mask),
-                                                           _stream_ptr(dev))
-        elif order is None:
-            rc = lib.nastar_backward_replay(grad_hist.data_ptr(), cost.data_ptr(), start.data_ptr(), goal.data_ptr(),
-                                            passable.data_ptr(), sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters),
-                                            iters.data_ptr(), t_batch.data_ptr() if t_batch is not None else None,
-                                            grad_cost.data_ptr(), ws.data_ptr(), ws_bytes, int(flags), _stream_ptr(dev))
-        else:
-            rc = lib.nastar_backward_replay_ordered(grad_hist.data_ptr(), None, None, None, cost.data_ptr(), start.data_ptr(), goal.data_ptr(),
-                                                    passable.data_ptr(), sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters),
-                                                    iters.data_ptr(), t_batch.data_ptr() if t_batch is not None else None,
-                                                    grad_cost.data_ptr(), ws.data_ptr(), ws_bytes, int(flags), _order_ptr(order, B, dev, True), _stream_ptr(dev))
-    _native.check(rc, "nastar_backward_replay")
+        name, args = replay_call(
+            cost=cost.data_ptr(), start=start.data_ptr(), goal=goal.data_ptr(), passable=passable.data_ptr(), sel_log=sel_log.data_ptr(), B=B, H=H,
+            W=W, g_ratio=g_ratio, max_iters=max_iters, iters=iters.data_ptr(), t_batch=t_batch.data_ptr() if t_batch is not None else None,
+            grad_cost=grad_cost.data_ptr(), workspace=ws.data_ptr(), ws_bytes=ws_bytes, stream=_stream_ptr(dev), flags=flags,
+            order=_order_ptr(order, B, dev, True) if order is not None else None, neighbor_mask=neighbor_mask,
+            heuristic=heuristic.data_ptr() if heuristic is not None else None, **{k: t.data_ptr() for k, t in upstream.items()})
+        rc = getattr(lib, name)(*args)
+    _native.check(rc, what)
     return grad_cost
 
 
@@ -543,19 +567,22 @@ def _(grad_hist, cost, start, goal, passable, sel_log, g_ratio, max_iters, iters
     return torch.empty_like(cost)
 
 
+_FORWARD_ARGS = tuple(a.name for a in torch.ops.nastar.astar_forward.default._schema.arguments)  # the op's inputs, by name
+
+
 def _setup_context(ctx, inputs, output):
-    cost, start, goal, passable, g_ratio, max_iters = inputs[:6]
+    a = dict(zip(_FORWARD_ARGS, inputs))
     _, _, iters, _, sel_log = output
-    heuristic = inputs[11] if len(inputs) > 11 else None  # the heuristic maps the forward searched with: the replay rebuilds its keys from them
+    heuristic = a.get("heuristic")  # the heuristic maps the forward searched with: the replay rebuilds its keys from them
     ctx.has_heuristic = heuristic is not None
+    saved = [a["cost"], a["start"], a["goal"], a["passable"], iters, sel_log]
     if heuristic is not None:
-        ctx.save_for_backward(cost, start, goal, passable, iters, sel_log, heuristic)
-    else:
-        ctx.save_for_backward(cost, start, goal, passable, iters, sel_log)
-    ctx.g_ratio = g_ratio
-    ctx.max_iters = max_iters
-    ctx.lockstep = bool(inputs[9]) if len(inputs) > 9 else False  # `exact`: the log may hold goal selections before its last entry
-    ctx.neighbor_mask = int(inputs[10]) if len(inputs) > 10 else NEIGHBORS_MOORE8  # the replay rebuilds the open sets of THIS neighbourhood
+        saved.append(heuristic)
+    ctx.save_for_backward(*saved)
+    ctx.g_ratio = a["g_ratio"]
+    ctx.max_iters = a["max_iters"]
+    ctx.lockstep = bool(a.get("exact", False))  # the log may hold goal selections before its last entry
+    ctx.neighbor_mask = int(a.get("neighbor_mask", NEIGHBORS_MOORE8))  # the replay rebuilds the open sets of THIS neighbourhood
     ctx.n_inputs = len(inputs)
     ctx.set_materialize_grads(False)  # no zero-filled gradient tensors for paths / iters / status / sel_log (4 fill launches per step)
 
@@ -563,8 +590,9 @@ def _setup_context(ctx, inputs, output):
 def _backward(ctx, g_hist, g_paths, g_iters, g_status, g_log):
     cost, start, goal, passable, iters, sel_log = ctx.saved_tensors[:6]
     heuristic = ctx.saved_tensors[6] if ctx.has_heuristic else None
+    grads = [None] * ctx.n_inputs
     if g_hist is None:
-        return (None,) * ctx.n_inputs
+        return tuple(grads)
     # t_batch: the reference's batch-wide loop index (differentiable_astar.py:251-255).  BatchCoupling lets the
     # sharded planner substitute the maximum over ALL ranks so gradients match a single-device run.
     t_batch = BatchCoupling.t_batch(iters)
@@ -574,10 +602,11 @@ def _backward(ctx, g_hist, g_paths, g_iters, g_status, g_log):
     grad_cost = torch.ops.nastar.astar_backward_replay(g_hist.contiguous(), cost, start, goal, passable, sel_log,
                                                        ctx.g_ratio, ctx.max_iters, iters, t_batch, None, FLAG_LOCKSTEP if ctx.lockstep else 0,
                                                        ctx.neighbor_mask, heuristic)
+    grads[_FORWARD_ARGS.index("cost")] = grad_cost
     if heuristic is not None:
         # dL/dh0 == dL/dcost: g is detached every step (differentiable_astar.py:239), so the loss sees both only through h = h0 + cost
-        return (grad_cost,) + (None,) * 10 + (grad_cost,) + (None,) * (ctx.n_inputs - 12)
-    return (grad_cost,) + (None,) * (ctx.n_inputs - 1)
+        grads[_FORWARD_ARGS.index("heuristic")] = grad_cost
+    return tuple(grads)
 
 
 astar_forward.register_autograd(_backward, setup_context=_setup_context)
@@ -633,32 +662,9 @@ def astar_backward_l1_replay(histories: torch.Tensor, opt_trajs: torch.Tensor, g
                              t_batch: Optional[torch.Tensor], order: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
     """dL/dcost for L = grad_loss * mean|histories - opt_trajs| by replay of the selection log: the sign gradient is formed while the
     upstream values are loaded (no gradient tensor is materialised).  ``flags``: ``FLAG_LOCKSTEP`` for the log of an ``exact`` forward."""
-    _require_device(histories, opt_trajs, cost, start, goal, passable)
-    lib = _native.load()
-    histories, opt_trajs, cost, start, goal, passable, sel_log = (
-        x.contiguous() for x in (histories, opt_trajs, cost, start, goal, passable, sel_log))
-    B, H, W = cost.shape
-    dev = cost.device
-    gl = grad_loss.reshape(1).to(torch.float32).contiguous() if grad_loss is not None else None
-    grad_cost = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    ws_bytes = int(lib.nastar_backward_workspace_bytes(B, H, W, int(max_iters)))
-    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        if order is None and not flags:
-            rc = lib.nastar_backward_l1_replay(histories.data_ptr(), opt_trajs.data_ptr(), gl.data_ptr() if gl is not None else None,
-                                               cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(),
-                                               sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters), iters.data_ptr(),
-                                               t_batch.data_ptr() if t_batch is not None else None, grad_cost.data_ptr(),
-                                               ws.data_ptr(), ws_bytes, _stream_ptr(dev))
-        else:
-            rc = lib.nastar_backward_replay_ordered(None, histories.data_ptr(), opt_trajs.data_ptr(), gl.data_ptr() if gl is not None else None,
-                                                    cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(),
-                                                    sel_log.data_ptr(), B, H, W, float(g_ratio), int(max_iters), iters.data_ptr(),
-                                                    t_batch.data_ptr() if t_batch is not None else None, grad_cost.data_ptr(),
-                                                    ws.data_ptr(), ws_bytes, int(flags), _order_ptr(order, B, dev, True) if order is not None else None,
-                                                    _stream_ptr(dev))
-    _native.check(rc, "nastar_backward_l1_replay")
-    return grad_cost
+    _require_device(histories, opt_trajs)
+    return _replay(cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_batch, order, flags, "nastar_backward_l1_replay",
+                   histories=histories, opt_trajs=opt_trajs, grad_loss=grad_loss.reshape(1).to(torch.float32) if grad_loss is not None else None)
 
 
 @astar_backward_l1_replay.register_fake

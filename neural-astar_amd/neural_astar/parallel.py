@@ -484,8 +484,9 @@ class InFlightPlanner:
             row = board.acquire() if (self.check_solvable or (unit and self.unit_cost == "auto")) else -1
             keep: list = []  # the launch's workspace (maps larger than LDS, a checked order): allocated for the current stream, used on stream k
             try:
-                out = ops.search_nograd(cost, start_maps, goal_maps, passable, astar.g_ratio, max_iters, False, flags, order, None, bool(check),
-                                        board.ptr(row) if row >= 0 else 0, self._ptrs[k], True, 0, keep, exact)
+                out = ops.search_nograd(cost, start_maps, goal_maps, passable, astar.g_ratio, max_iters, False, flags, order=order,
+                                        check_order=bool(check), summary_ptr=board.ptr(row) if row >= 0 else 0, stream_ptr=self._ptrs[k], out_4d=True,
+                                        keep=keep, exact=exact)
             except BaseException:
                 if row >= 0:
                     board.release(row)
@@ -526,8 +527,8 @@ class InFlightPlanner:
                 try:
                     exact = start_maps.shape[0] > 1 and ops.coupling_possible(astar.g_ratio)
                     hist, paths, iters, status, _ = ops.search_nograd(cost, start_maps, goal_maps, passable, astar.g_ratio,
-                                                                      ops.max_iters_for(start_maps.shape[-1], 1.0, False), False, 0, order, None,
-                                                                      bool(check), board.ptr(r2), None, True, 0, None, exact)
+                                                                      ops.max_iters_for(start_maps.shape[-1], 1.0, False), order=order,
+                                                                      check_order=bool(check), summary_ptr=board.ptr(r2), out_4d=True, exact=exact)
                     torch.cuda.current_stream(dev).synchronize()
                     r = board.read(r2)
                     summ = None if r is None else r.copy()

@@ -385,8 +385,8 @@ class DifferentiableAstar(nn.Module):
         (include/nastar.h), any map size, no host round trip.  -> (histories, paths, iters, status, sel_log).  ``neighbor_mask``: -1 = this
         module's (``neighbor_mask()``)"""
         nmask = self.neighbor_mask() if neighbor_mask == -1 else neighbor_mask
-        return ops.search_nograd(cost_maps, start_maps, goal_maps, passable, self.g_ratio, max_iters, want_log, 0, None, None, False, 0, None, out_4d,
-                                 0, None, True, neighbor_mask=nmask)
+        return ops.search_nograd(cost_maps, start_maps, goal_maps, passable, self.g_ratio, max_iters, want_log, out_4d=out_4d, exact=True,
+                                 neighbor_mask=nmask)
 
     def _repair_in_place(self, inputs, outputs, max_iters, want_log, neighbor_mask=None):
         """for a DEFERRED verdict: the launch it belongs to reported the note after its outputs had been handed out -- run the exact search now
@@ -577,26 +577,23 @@ class DifferentiableAstar(nn.Module):
         def launch(exact_now: bool, sptr_now: int, cptr_now: int):
             if not traced:
                 # no gradient can flow and nothing is tracing: straight to the C ABI (no torch.library dispatch)
-                return ops.search_nograd(cost_maps, start_maps, goal_maps, passable_maps, self.g_ratio, max_iters, want_log, flags, order, order_out,
-                                         check_order, sptr_now, None, True, cptr_now, None, exact_now, neighbor_mask=nmask, heuristic=h0)
+                return ops.search_nograd(cost_maps, start_maps, goal_maps, passable_maps, self.g_ratio, max_iters, want_log, flags, order=order,
+                                         order_out=order_out, check_order=check_order, summary_ptr=sptr_now, out_4d=True, counter_ptr=cptr_now,
+                                         exact=exact_now, neighbor_mask=nmask, heuristic=h0)
             cost, start, goal, passable = cost_maps[:, 0], start_maps[:, 0], goal_maps[:, 0], obstacles_maps[:, 0]
             mask_arg = ops.NEIGHBORS_MOORE8 if nmask is None else nmask
-            if h0 is not None:
-                if order is None and order_out is None:
-                    o = torch.ops.nastar.astar_forward(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, sptr_now, exact_now,
-                                                       mask_arg, h0[:, 0])
-                else:
-                    o = torch.ops.nastar.astar_forward_ordered(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, order,
-                                                               order_out, check_order, sptr_now, exact_now, mask_arg, h0[:, 0])
-            elif needs_grad and in_lds and nmask is None and (order is not None or order_out is not None or B >= ops.PLACEMENT_MIN_BATCH):
+            heuristic = h0[:, 0] if h0 is not None else None
+            placed = order is not None or order_out is not None
+            if needs_grad and in_lds and nmask is None and h0 is None and (placed or B >= ops.PLACEMENT_MIN_BATCH):
                 # large batches under autograd: the replay backward starts longest-first, by the order THIS forward's searches finish in
-                o = ops.astar_forward_placed(cost, start, goal, passable, self.g_ratio, max_iters, 0, order, order_out, check_order, sptr_now, exact_now)
-            elif order is None and order_out is None:
+                o = ops.astar_forward_placed(cost, start, goal, passable, self.g_ratio, max_iters, flags=0, order_in=order, order_out=order_out,
+                                             check_order=check_order, summary_ptr=sptr_now, exact=exact_now)
+            elif not placed:
                 o = torch.ops.nastar.astar_forward(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, sptr_now, exact_now,
-                                                   mask_arg)
+                                                   mask_arg, heuristic)
             else:
                 o = torch.ops.nastar.astar_forward_ordered(cost, start, goal, passable, float(self.g_ratio), max_iters, want_log, flags, order, order_out,
-                                                           check_order, sptr_now, exact_now, mask_arg)
+                                                           check_order, sptr_now, exact_now, mask_arg, heuristic)
             return o[0].unsqueeze(1), o[1].unsqueeze(1), o[2], o[3], o[4]
 
         try:

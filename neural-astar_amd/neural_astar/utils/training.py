@@ -212,7 +212,7 @@ def fused_l1_step(planner: VanillaAstar, map_designs: torch.Tensor, start_maps: 
     exact = cost_maps.shape[0] > 1 and ops.coupling_possible(astar.g_ratio)
     args = (cost_maps[:, 0], start_maps[:, 0], goal_maps[:, 0], obstacles[:, 0], opt_trajs[:, 0], astar.g_ratio, max_iters)
     try:
-        loss, hist, paths, iters, status = ops.astar_l1_loss(*args, order, check, astar.summary_ptr(row, cost_maps), exact)
+        loss, hist, paths, iters, status = ops.astar_l1_loss(*args, order_in=order, check_order=check, summary_ptr=astar.summary_ptr(row, cost_maps), exact=exact)
     except BaseException:
         if row >= 0:
             ops.StatusBoard.of(cost_maps.device).release(row)
@@ -220,6 +220,6 @@ def fused_l1_step(planner: VanillaAstar, map_designs: torch.Tensor, start_maps: 
     repair = _refuse_late_repair if (astar.check_solvable == "deferred" and not exact and cost_maps.shape[0] > 1) else None
     # same contract as DifferentiableAstar.forward (default: raises in THIS call, before any backward)
     if astar.note_status(status, iters, row=row, repair=repair) and not exact:
-        loss, hist, paths, iters, status = ops.astar_l1_loss(*args, None, False, 0, True)
+        loss, hist, paths, iters, status = ops.astar_l1_loss(*args, check_order=False, exact=True)
         astar.last_status, astar.last_iters = status, iters
     return loss, AstarOutput(hist.unsqueeze(1), paths.unsqueeze(1), [])

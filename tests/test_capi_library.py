@@ -19,6 +19,167 @@ def test_header_and_binding_agree():
     assert _declared_symbols() == sorted(_native.EXPORTED_SYMBOLS)
 
 
+_SCALARS = {"int": "i", "unsigned": "u", "float": "f", "double": "d", "size_t": "z", "long long": "q"}
+_RETURNS = {"int": "i", "size_t": "z", "const char*": "s"}
+
+
+def _prototypes():
+    """include/nastar.h -> {symbol: (return kind, [(argument kind, argument name), ...])} in the letters of _native.SIGNATURES: p pointer,
+    P pointer to pointer, i int, u unsigned, f float, d double, z size_t, q long long; returns i / z / s (const char*).  A type this does
+    not know raises."""
+    txt = open(os.path.join(ROOT, "include", "nastar.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \*]*?)\s*\b(nastar_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
+        args = []
+        for prm in (x.strip() for x in params.split(",")):
+            if prm == "void":
+                continue
+            typ, arg = re.fullmatch(r"(.*?)(\w+)", prm).groups()
+            stars = typ.count("*")
+            base = " ".join(w for w in typ.replace("*", " ").split() if w not in ("const", "volatile"))
+            if stars:
+                assert stars <= 2 and re.fullmatch(r"void|float|double|long long|u?int\d+_t|int", base), (name, prm)
+                args.append(("pP"[stars - 1], arg))
+            else:
+                assert base in _SCALARS, (name, prm)
+                args.append((_SCALARS[base], arg))
+        ret = " ".join(ret.replace("*", " * ").split()).replace(" *", "*")
+        assert ret in _RETURNS, (name, ret)
+        out[name] = (_RETURNS[ret], args)
+    return out
+
+
+def _defines():
+    txt = open(os.path.join(ROOT, "include", "nastar.h")).read()
+    return {k: int(v, 0) for k, v in re.findall(r"^#define (NASTAR_[A-Z0-9_]+) (0x[0-9A-Fa-f]+|\d+)\b", txt, flags=re.M)}
+
+
+def test_signature_table_and_constants_match_the_header():
+    """every prototype of include/nastar.h against _native.SIGNATURES (the ONE place the ctypes signatures come from): return type,
+    parameter count, kind per position -- and the Python mirrors of the header's #defines against their values"""
+    from neural_astar import _native, ops
+    protos = _prototypes()
+    assert sorted(protos) == sorted(_native.SIGNATURES) == _declared_symbols() and len(protos) == 74
+    for name, (ret, args) in protos.items():
+        assert _native.SIGNATURES[name] == ret + " " + "".join(k for k, _ in args), name
+    assert set("".join(_native.SIGNATURES.values())) - {" "} <= set(_native._CTYPES)
+    d = _defines()
+    mirrors = {k: v for k, v in vars(ops).items() if k.startswith(("FLAG_", "STATUS_", "SUMMARY_", "NEIGHBORS_")) and isinstance(v, int)}
+    assert {"FLAG_UNIT_COST", "FLAG_LOCKSTEP", "FLAG_CHECK_ORDER", "FLAG_MARK_COUPLED", "STATUS_UNSOLVABLE", "STATUS_NOT_UNIT_COST",
+            "STATUS_BAD_HEURISTIC", "SUMMARY_WORDS", "SUMMARY_BAD_ORDER", "SUMMARY_COUPLED", "NEIGHBORS_MOORE8", "NEIGHBORS_VON_NEUMANN"} <= set(mirrors)
+    for k, v in mirrors.items():
+        assert v == d["NASTAR_" + k.replace("STATUS_", "ERR_")], k
+    codes = {k: v for k, v in d.items() if k == "NASTAR_OK" or k.startswith("NASTAR_ERR_")}
+    assert codes == {k: v for k, v in vars(_native).items() if k in codes} and len(codes) == 9
+    assert sorted(_native._ERR_NAMES) == sorted(v for v in codes.values() if v)
+    assert ops.SUMMARY_ERRORS == slice(1, ops.SUMMARY_COUPLED)
+
+
+class _Sentinels:
+    """distinct integers, one per name asked for"""
+
+    def __init__(self):
+        self.v = {}
+
+    def __call__(self, name):
+        return self.v.setdefault(name, 0x1000 + 0x10 * len(self.v))
+
+
+def _check_call(call, expect, protos):
+    """``call`` = (symbol, arguments) from an assembler; ``expect`` = header parameter name -> value: every parameter of the symbol's prototype is
+    named in ``expect`` and holds that value; the stream is last"""
+    name, args = call
+    params = [n for _, n in protos[name][1]]
+    assert len(args) == len(params), (name, len(args), len(params))
+    assert params[-1] == "stream" and sorted(params) == sorted(expect), (name, sorted(set(params) ^ set(expect)))
+    for prm, val in zip(params, args):
+        assert val == expect[prm] and type(val) is type(expect[prm]), (name, prm, val, expect[prm])
+
+
+@pytest.mark.parametrize("exact", [False, True])
+@pytest.mark.parametrize("family", ["", "_masked", "_heuristic", "_heuristic_moore8"])
+def test_assembled_forward_calls_put_every_value_under_its_header_name(family, exact):
+    """ops.forward_calls (what ops._launch_search issues) against the parameter NAMES of include/nastar.h, for the three entry families x
+    exact on / off x every subset of the optional pointers"""
+    import inspect
+    import itertools
+    from neural_astar import ops
+    protos = _prototypes()
+    header = [n for _, n in protos["nastar_forward_ex"][1]]
+    # the assembler's own parameters ARE the header's, names and order (ops._launch_search passes them by position)
+    assert list(inspect.signature(ops.forward_calls).parameters) == [n for n in header if n != "packed_out"] + ["exact", "neighbor_mask", "h0"]
+    for opts in itertools.product([False, True], repeat=5):
+        with_order, with_order_out, with_summary, with_counter, with_log = opts
+        s = _Sentinels()
+        mask = {"": None, "_masked": ops.NEIGHBORS_MOORE8, "_heuristic": ops.NEIGHBORS_VON_NEUMANN, "_heuristic_moore8": None}[family]
+        h0 = s("h0") if family.startswith("_heuristic") else None
+        suffix = family.replace("_moore8", "")
+        given = {"cost": s("cost"), "start": s("start"), "goal": s("goal"), "passable": s("passable"), "B": 7, "H": 32, "W": 48, "g_ratio": 0.25,
+                 "max_iters": 99, "histories_out": s("histories_out"), "paths_out": s("paths_out"), "sel_log_out": s("sel_log_out") if with_log else None,
+                 "iters_out": s("iters_out"), "status_out": s("status_out"), "workspace": s("workspace") if exact else None,
+                 "workspace_bytes": 4096 if exact else 0, "flags": ops.FLAG_MARK_COUPLED if exact else 0, "order": s("order") if with_order else None,
+                 "order_out": s("order_out") if with_order_out else None, "status_summary": s("status_summary") if with_summary else 0,
+                 "completion_counter": s("completion_counter") if with_counter else 0, "stream": s("stream")}
+        launch, finish = ops.forward_calls(**given, exact=exact, neighbor_mask=mask, h0=h0)
+        assert ops.forward_calls(*given.values(), exact, mask, h0) == (launch, finish)
+        tail = {}
+        if suffix:
+            tail["neighbor_mask"] = ops.NEIGHBORS_MOORE8 if mask is None else mask
+        if h0 is not None:
+            tail["h0"] = h0
+        assert launch[0] == "nastar_forward_ex" + suffix
+        _check_call(launch, dict(given, packed_out=None, status_summary=given["status_summary"] or None,
+                                 completion_counter=(given["completion_counter"] or None) if with_summary else None, **tail), protos)
+        if exact:
+            assert finish[0] == "nastar_forward_batchloop_finish" + suffix
+            _check_call(finish, dict({k: given[k] for k in header[:14] + ["workspace", "workspace_bytes", "stream"]}, **tail), protos)
+        else:
+            assert finish is None
+
+
+@pytest.mark.parametrize("case,symbol", [("plain", "nastar_backward_replay"), ("plain_flags", "nastar_backward_replay"),
+                                         ("ordered", "nastar_backward_replay_ordered"), ("masked", "nastar_backward_replay_ordered_masked"),
+                                         ("heuristic", "nastar_backward_replay_ordered_heuristic"),
+                                         ("heuristic_masked_ordered", "nastar_backward_replay_ordered_heuristic"),
+                                         ("l1", "nastar_backward_l1_replay"), ("l1_ordered", "nastar_backward_replay_ordered"),
+                                         ("l1_flags", "nastar_backward_replay_ordered")])
+def test_assembled_replay_calls_put_every_value_under_its_header_name(case, symbol):
+    """ops.replay_call (what the two replay ops issue) against the parameter names of include/nastar.h, and WHICH symbol serves which call"""
+    from neural_astar import ops
+    protos = _prototypes()
+    s = _Sentinels()
+    l1 = case.startswith("l1")
+    flags = ops.FLAG_LOCKSTEP if "flags" in case else 0
+    order = s("order") if "ordered" in case else None
+    mask = ops.NEIGHBORS_VON_NEUMANN if "masked" in case else None
+    h0 = s("h0") if "heuristic" in case else None
+    t_batch = None if case == "plain" else s("t_batch_dev")
+    up = ({"histories": s("histories"), "opt_trajs": s("opt_trajs"), "grad_loss": s("grad_loss_dev") if case != "l1" else None} if l1
+          else {"grad_hist": s("grad_histories")})
+    call = ops.replay_call(cost=s("cost"), start=s("start"), goal=s("goal"), passable=s("passable"), sel_log=s("sel_log"), B=5, H=16, W=24, g_ratio=0.75,
+                           max_iters=77, iters=s("iters"), t_batch=t_batch, grad_cost=s("grad_cost_out"), workspace=s("workspace"), ws_bytes=8192,
+                           stream=s("stream"), flags=flags, order=order, neighbor_mask=mask, heuristic=h0, **up)
+    assert call[0] == symbol
+    expect = {"cost": s("cost"), "start": s("start"), "goal": s("goal"), "passable": s("passable"), "sel_log": s("sel_log"), "B": 5, "H": 16, "W": 24,
+              "g_ratio": 0.75, "max_iters": 77, "iters": s("iters"), "t_batch_dev": t_batch, "grad_cost_out": s("grad_cost_out"),
+              "workspace": s("workspace"), "workspace_bytes": 8192, "stream": s("stream")}
+    if symbol != "nastar_backward_l1_replay":
+        expect["flags"] = flags
+    if symbol != "nastar_backward_replay":
+        expect.update(histories=up.get("histories"), opt_trajs=up.get("opt_trajs"), grad_loss_dev=up.get("grad_loss"))
+    if symbol != "nastar_backward_l1_replay":
+        expect["grad_histories"] = up.get("grad_hist")
+    if "_ordered" in symbol:
+        expect["order"] = order
+    if symbol.endswith(("_masked", "_heuristic")):
+        expect["neighbor_mask"] = ops.NEIGHBORS_MOORE8 if mask is None else mask
+    if symbol.endswith("_heuristic"):
+        expect["h0"] = h0
+    _check_call(call, expect, protos)
+
+
 def test_library_builds_loads_and_exports_everything():
     from neural_astar import _native
     if not os.path.exists(_native.LIB_PATH):
