@@ -5,6 +5,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <stddef.h>
 #include <time.h>
 
 #include "nastar_host.hip.h"
@@ -20,6 +21,8 @@
 #include "nastar_placement.hip.h"
 #include "nastar_backward_replay.hip.h"
 #include "nastar_backward_replay_asm.hip.h"
+#include "nastar_routes.hip.h"
+#include "../../include/nastar_routes.h"
 
 namespace nastar {
 
@@ -50,6 +53,7 @@ struct FwdCArgs {
     int B;
     int flags;
     CompactDims d;
+    RouteOut route;        // optional (include/nastar_routes.h): the ordered route of every map, its length and cost; null for every entry point of nastar.h
 };
 
 // which map this workgroup searches: `order[blockIdx.x]`, unless the launch was asked to check `order` (NASTAR_FLAG_CHECK_ORDER) and the
@@ -200,6 +204,14 @@ __global__ __launch_bounds__(64) void nastar_forward_unit_kernel(const FwdCArgs 
         compact_backtrack<LOGW>(d, cl, lane, start_idx, goal_idx, solved ? HW : iters - 1);
     }
     unit_store_paths<LOGW>(l, lane, a.paths + off, a.packed ? a.packed + (size_t)b * (size_t)(HW >> 2) : nullptr, bad);
+    const RouteOut ro = kernel_route_args<offsetof(FwdCArgs, route)>();  // (a.route, read here: nastar_routes.hip.h)
+    if (ro.routes != nullptr) {  // no cost word in LDS: every cell the search opened is passable and costs 1, the start's cost is read
+        const float start_cost = start_idx >= 0 ? a.cost[off + start_idx] : 0.f;
+        const int n = route_walk(l.pdir, lane, start_idx, goal_idx, solved ? HW : iters - 1, goal_idx >= 0 && !bad,
+                                 [&](int c, uint32_t code) { return compact_parent_of(d, c, code); },
+                                 [&](int c) { return c == start_idx ? start_cost : 1.0f; }, ro, b);
+        route_fill_tail(ro, b, n, lane);
+    }
 }
 
 
@@ -581,6 +593,7 @@ struct FwdLaunch {
     int32_t *order_out = nullptr, *summary = nullptr, *done_counter = nullptr;
     LockArgs lock = {};
     Neighbourhood nb = {};
+    RouteOut route = {};  // routes_out, route_cap, route_len_out, route_cost_out of include/nastar_routes.h
 };
 
 // large map: cells in the caller's HBM workspace, open list in LDS (nastar_search_hybrid.hip.h)
@@ -597,6 +610,7 @@ static int forward_hybrid(const FwdLaunch& f, int* marks_out)
     ha.workspace = static_cast<unsigned char*>(f.workspace); ha.slab_bytes = slab; ha.max_iters = f.max_iters;
     ha.marks_out = marks_out;
     ha.marks = f.lock.marks; ha.t_end = f.lock.t_end; ha.bitmap = f.lock.bitmap; ha.bitmap_words = f.lock.bitmap_words;
+    ha.route = f.route;
     HybridDims& hd = ha.d;
     hd.H = f.H; hd.W = f.W; hd.HW = f.H * f.W;
     hd.nchunks = (hd.HW + 63) / 64; hd.nsuper = (hd.nchunks + 63) / 64; hd.spl = (hd.nsuper + 63) / 64;
@@ -661,6 +675,7 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     c.order_bad = nullptr;
     c.marks_out = marks_out;
     c.marks = f.lock.marks; c.t_end = f.lock.t_end; c.bitmap = f.lock.bitmap; c.bitmap_words = f.lock.bitmap_words;
+    c.route = f.route;
     if (f.order && (f.flags & NASTAR_FLAG_CHECK_ORDER)) {
         rc = check_order(f.order, f.B, f.workspace, f.workspace_bytes, ws_layout(f.B, f.H, f.W, f.flags).chk_off + kOrderCheckBytes, f.summary, s,
                          &c.order_bad);
@@ -855,6 +870,54 @@ int nastar_forward_batchloop_finish_heuristic(const float* cost, const float* st
                 workspace, workspace_bytes, 0, stream};
     f.nb = Neighbourhood{true, neighbor_mask, h0};
     return batchloop_finish(f);
+}
+
+// ---- include/nastar_routes.h: the search launch that also returns every map's ordered route, its length and its cost ----------------------
+int nastar_routes_abi(void) { return NASTAR_ROUTES_ABI; }
+
+// the route group of both entry points, checked before any HIP call; the neighbourhood: Moore-8 without a heuristic is the launch of
+// nastar_forward_ex (its kernels: hand-scheduled streams, unit-cost layout), any other mask the masked twins, a heuristic the third ones
+static int routes_launch(FwdLaunch& f, unsigned neighbor_mask, const float* h0, int32_t* routes_out, int route_cap, int32_t* route_len_out,
+                         float* route_cost_out)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    if (!routes_out || !route_len_out) return NASTAR_ERR_NULL;
+    if (route_cap < 1) return NASTAR_ERR_BAD_SHAPE;
+    if (h0) f.nb = Neighbourhood{true, neighbor_mask, h0};
+    else if (neighbor_mask != NASTAR_NEIGHBORS_MOORE8) f.nb = Neighbourhood{true, neighbor_mask};
+    f.route = RouteOut{routes_out, route_cap, route_len_out, route_cost_out};
+    return NASTAR_OK;
+}
+
+int nastar_forward_routes(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
+                          int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
+                          uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
+                          int32_t* status_summary, int32_t* completion_counter, unsigned neighbor_mask, const float* h0, int32_t* routes_out,
+                          int route_cap, int32_t* route_len_out, float* route_cost_out, void* stream)
+{
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, flags, stream};
+    const int rc = routes_launch(f, neighbor_mask, h0, routes_out, route_cap, route_len_out, route_cost_out);
+    if (rc) return rc;
+    f.packed_out = packed_out;
+    f.order = order;
+    f.order_out = order_out;
+    f.summary = status_summary;
+    f.done_counter = completion_counter;
+    return forward(f);
+}
+
+int nastar_forward_routes_batchloop_finish(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
+                                           double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
+                                           int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes,
+                                           unsigned neighbor_mask, const float* h0, int32_t* routes_out, int route_cap, int32_t* route_len_out,
+                                           float* route_cost_out, void* stream)
+{
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, 0, stream};
+    const int rc = routes_launch(f, neighbor_mask, h0, routes_out, route_cap, route_len_out, route_cost_out);
+    if (rc) return rc;
+    return batchloop_finish(f);  // (its FINAL launch rewrites the rows of the maps it re-runs: routes, lengths and costs with them)
 }
 
 int nastar_completion_supported(int H, int W)

@@ -188,3 +188,9 @@
     if (goal_idx >= 0 && !(kHeur && bad_h0)) compact_backtrack<(LOGW == LOGH ? LOGW : 0)>(d, l, lane, start_idx, goal_idx, solved ? d.HW : iters - 1);
     compact_store_outputs<kVec4, false>(d, l, lane, a.hist + off, a.paths + off,
                                         a.packed ? a.packed + (size_t)b * (size_t)(d.HW >> 2) : nullptr);
+    const RouteOut ro = kernel_route_args<offsetof(FwdCArgs, route)>();  // (a.route, read here: nastar_routes.hip.h)
+    if (ro.routes != nullptr) {  // wave-uniform; null unless the launch came through include/nastar_routes.h
+        const int n = route_walk(l.pdir, lane, start_idx, goal_idx, solved ? d.HW : iters - 1, goal_idx >= 0 && !(kHeur && bad_h0),
+                                 [&](int c, uint32_t code) { return compact_parent_of(d, c, code); }, [&](int c) { return l.gc[c].y; }, ro, b);
+        route_fill_tail(ro, b, n, lane);
+    }

@@ -231,3 +231,13 @@
         }
     }
     global_step_fence();
+    const RouteOut ro = kernel_route_args<offsetof(FwdHybridArgs, route)>();  // (a.route, read here: nastar_routes.hip.h)
+    if (ro.routes != nullptr) {  // wave-uniform; parents from the slab, costs from the caller's tensor; the -1 tail: store launch
+        route_walk(pdir, lane, sidx, gidx, solved ? d.HW : iters - 1, gidx >= 0 && !(kHeur && status == NASTAR_ERR_BAD_HEURISTIC),
+                   [&](int c, uint32_t code) {
+                       int pdr, pdc;
+                       neighbour_delta((int)code, pdr, pdc);
+                       return c - (pdr * d.W + pdc);
+                   },
+                   [&](int c) { return cost[c]; }, ro, b);
+    }

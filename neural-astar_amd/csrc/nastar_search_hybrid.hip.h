@@ -29,6 +29,7 @@
 // Keys are never stored: q = fl(f / fl32(sqrt(W))) is re-derived from (g, cost, coordinates), with the IEEE division (no reciprocal).
 #pragma once
 #include "nastar_search.hip.h"
+#include "nastar_routes.hip.h"
 
 namespace nastar {
 
@@ -77,6 +78,7 @@ struct FwdHybridArgs {
     uint32_t* bitmap;      // lock-step PROBE launch: [B][bitmap_words], bit t = the goal was selected at step t
     int bitmap_words;
     HybridDims d;
+    RouteOut route;        // optional (include/nastar_routes.h): ordered routes, lengths, costs; null for every entry point of nastar.h
 };
 
 // row of flat index i (< 2^21): (i + 0.5) / W in fp32 lands within one row of the true quotient (the product's error is ~2^-23 of a row
@@ -178,6 +180,11 @@ __global__ __launch_bounds__(256) void nastar_hybrid_store_kernel(const FwdHybri
         const uint32_t m = pdir[i];
         a.hist[off + i] = ((m & P_PASS) && g[i] == NASTAR_NEG_INF) ? 1.0f : 0.0f;  // closed list (:222-223)
         a.paths[off + i] = (m & P_PATH) ? 1 : 0;
+    }
+    if (a.route.routes != nullptr) {  // the -1 tail of the map's route row (the search launch wrote the cells and the length)
+        const int len = a.route.len[b];
+        int* const row = a.route.routes + (size_t)b * (size_t)a.route.cap;
+        for (int i = (len < a.route.cap ? len : a.route.cap) + blockIdx.x * 256 + threadIdx.x; i < a.route.cap; i += gridDim.x * 256) row[i] = -1;
     }
 }
 

@@ -133,6 +133,16 @@ SIGNATURES = {
 # every symbol include/nastar.h declares -- tests check the library exports all of them
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
+# the signatures of include/nastar_routes.h (the second header: ordered routes, lengths and costs from the search launch), same letter code;
+# a table of its own -- SIGNATURES is include/nastar.h and nothing else (tests/test_routes.py compares this one with ITS header)
+_ROUTES = "pipp"          # routes_out, route_cap, route_len_out, route_cost_out
+ROUTE_SIGNATURES = {
+    "nastar_routes_abi": "i ",
+    # ... nastar_forward_ex_heuristic's arguments (h0 may be NULL), the route outputs, the stream
+    "nastar_forward_routes": "i " + _FORWARD + "p" + _WORKSPACE + "ipppp" + "up" + _ROUTES + "p",
+    "nastar_forward_routes_batchloop_finish": "i " + _FORWARD + _WORKSPACE + "up" + _ROUTES + "p",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -152,9 +162,10 @@ DEV_LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libnastar_hip_dev.so")
 _dev_lib: Optional[ctypes.CDLL] = None
 
 
-def _bind(lib: ctypes.CDLL, names) -> None:
+def _bind(lib: ctypes.CDLL, names, table=None) -> None:
+    table = SIGNATURES if table is None else table
     for name in names:
-        ret, args = SIGNATURES[name].split(" ")
+        ret, args = table[name].split(" ")
         fn = getattr(lib, name)
         fn.restype = _CTYPES[ret]
         fn.argtypes = [_CTYPES[k] for k in args]
@@ -215,6 +226,7 @@ def load() -> ctypes.CDLL:
             f"(no CPU fallback). Build it with `make -C {CSRC_DIR}` or `python __graft_entry__.py build`.")
     lib = ctypes.CDLL(LIB_PATH)
     _bind(lib, SIGNATURES)
+    _bind(lib, ROUTE_SIGNATURES, ROUTE_SIGNATURES)
     _lib = lib
     return lib
 

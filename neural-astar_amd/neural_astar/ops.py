@@ -14,7 +14,7 @@ import torch
 from . import _native
 
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
-           "StatusBoard"]
+           "StatusBoard", "route_forward_calls", "search_routes"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -218,6 +218,24 @@ def forward_calls(cost, start, goal, passable, B, H, W, g_ratio, max_iters, hist
     return launch, finish
 
 
+def route_forward_calls(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                        workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, neighbor_mask, h0, routes_out,
+                        route_cap, route_len_out, route_cost_out, stream, exact=False):
+    """``forward_calls`` for the launch that also returns ordered routes (include/nastar_routes.h): -> ((nastar_forward_routes, arguments),
+    (nastar_forward_routes_batchloop_finish, arguments) -- None unless ``exact``).  The parameters up to ``stream`` ARE those of
+    nastar_forward_routes, names and order (less packed_out; tests/test_routes.py pins it).  ONE entry point serves every neighbourhood:
+    ``neighbor_mask`` None = Moore-8, ``h0`` None = the reference's heuristic -- both None is the launch of nastar_forward_ex."""
+    problem = (cost, start, goal, passable, B, H, W, float(g_ratio), int(max_iters), histories_out, paths_out, sel_log_out or None, iters_out,
+               status_out)
+    tail = (NEIGHBORS_MOORE8 if neighbor_mask is None else int(neighbor_mask), h0 or None, routes_out, int(route_cap), route_len_out,
+            route_cost_out or None, stream)
+    launch = ("nastar_forward_routes",
+              (*problem, None, workspace or None, workspace_bytes, flags, order or None, order_out or None, status_summary or None,
+               (completion_counter or None) if status_summary else None, *tail))
+    finish = ("nastar_forward_routes_batchloop_finish", (*problem, workspace, workspace_bytes, *tail)) if exact else None
+    return launch, finish
+
+
 def replay_call(*, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_iters, iters, t_batch, grad_cost, workspace, ws_bytes, stream,
                 grad_hist=None, histories=None, opt_trajs=None, grad_loss=None, flags=0, order=None, neighbor_mask=None, heuristic=None):
     """The C call of ONE replay backward as plain values: -> (symbol, arguments).  ``grad_hist`` given: dL/dhistories comes from autograd;
@@ -235,7 +253,7 @@ def replay_call(*, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_i
 
 def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, dev, order=None, order_out=None,
                    check_order=False, summary_ptr=0, one_meta=False, stream_ptr=None, out_4d=False, counter_ptr=0, keep=None, exact=False,
-                   neighbor_mask=None, heuristic=None):
+                   neighbor_mask=None, heuristic=None, route_cap=None):
     """allocate the five outputs and issue ONE nastar_forward_ex launch on torch's current stream (shared by the custom ops and the
     no-autograd fast path).  cost / start / goal / passable: contiguous fp32 tensors of B*H*W elements (any leading shape).
     ``keep``: a list that receives the launch's temporaries (its workspace) when the launch goes to ANOTHER stream than the one the
@@ -247,7 +265,9 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
     ``neighbor_mask``: None = the reference's default neighbourhood (Moore-8) on the fastest kernels; an int = the search neighbourhood of a
     ``neighbor_filter`` (NEIGHBORS_*), searched by the masked entry points (nastar_forward_ex_masked: the compiled step loops, for every mask).
     ``heuristic``: None = the reference's get_heuristic, computed by the kernels; a contiguous fp32 [B, H, W] tensor = the caller's heuristic
-    maps (nastar_forward_ex_heuristic; with ``neighbor_mask`` or Moore-8).  Which symbols are called with which arguments: ``forward_calls``."""
+    maps (nastar_forward_ex_heuristic; with ``neighbor_mask`` or Moore-8).  Which symbols are called with which arguments: ``forward_calls``.
+    ``route_cap``: None = the five outputs; an int >= 1 = the launch of include/nastar_routes.h (``route_forward_calls``: same kernels, same
+    five outputs) that also writes routes [B, route_cap] int32, route lengths [B] int32 and route costs [B] float32 -- three more results."""
     shape = (B, 1, H, W) if out_4d else (B, H, W)
     hist = torch.empty(shape, dtype=torch.float32, device=dev)
     paths = torch.empty(shape, dtype=torch.int64, device=dev)
@@ -280,12 +300,23 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
             raise ValueError("a launch on a foreign stream that needs a workspace must be given a `keep` list (the allocator would hand the "
                              "workspace to the next launch on the current stream while this one still runs)")
         keep.append(workspace)
-    (fwd, args), fin = forward_calls(
-        cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, g_ratio, max_iters, hist.data_ptr(), paths.data_ptr(),
-        sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(), workspace.data_ptr() if workspace is not None else None,
-        ws_bytes, flags, order_ptr, order_out.data_ptr() if order_out is not None else None, summary_ptr, counter_ptr,
-        stream_ptr if stream_ptr is not None else torch.cuda.current_stream(dev).cuda_stream, exact, neighbor_mask,
-        heuristic.data_ptr() if heuristic is not None else None)
+    if route_cap is None:
+        (fwd, args), fin = forward_calls(
+            cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, g_ratio, max_iters, hist.data_ptr(), paths.data_ptr(),
+            sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(), workspace.data_ptr() if workspace is not None else None,
+            ws_bytes, flags, order_ptr, order_out.data_ptr() if order_out is not None else None, summary_ptr, counter_ptr,
+            stream_ptr if stream_ptr is not None else torch.cuda.current_stream(dev).cuda_stream, exact, neighbor_mask,
+            heuristic.data_ptr() if heuristic is not None else None)
+    else:
+        routes = torch.empty((B, route_cap), dtype=torch.int32, device=dev)
+        route_len = torch.empty((B,), dtype=torch.int32, device=dev)
+        route_cost = torch.empty((B,), dtype=torch.float32, device=dev)
+        (fwd, args), fin = route_forward_calls(
+            cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, g_ratio, max_iters, hist.data_ptr(), paths.data_ptr(),
+            sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(), workspace.data_ptr() if workspace is not None else None,
+            ws_bytes, flags, order_ptr, order_out.data_ptr() if order_out is not None else None, summary_ptr, counter_ptr, neighbor_mask,
+            heuristic.data_ptr() if heuristic is not None else None, routes.data_ptr(), route_cap, route_len.data_ptr(), route_cost.data_ptr(),
+            stream_ptr if stream_ptr is not None else torch.cuda.current_stream(dev).cuda_stream, exact)
     if dev.index is None or torch.cuda.current_device() == dev.index:
         rc = getattr(lib, fwd)(*args)
         if not rc and fin is not None:
@@ -296,7 +327,9 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
             if not rc and fin is not None:
                 rc = getattr(lib, fin[0])(*fin[1])
     if rc:
-        _native.check(rc, "nastar_forward_ex")
+        _native.check(rc, fwd)
+    if route_cap is not None:
+        return hist, paths, iters, status, sel_log, routes, route_len, route_cost
     return hist, paths, iters, status, sel_log
 
 
@@ -377,7 +410,7 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
                   max_iters: int, want_log: bool = False, flags: int = 0, *, order: Optional[torch.Tensor] = None,
                   order_out: Optional[torch.Tensor] = None, check_order: bool = True, summary_ptr: int = 0, stream_ptr: Optional[int] = None,
                   out_4d: bool = False, counter_ptr: int = 0, keep: Optional[list] = None, exact: bool = False, lib=None,
-                  neighbor_mask: Optional[int] = None, heuristic: Optional[torch.Tensor] = None):
+                  neighbor_mask: Optional[int] = None, heuristic: Optional[torch.Tensor] = None, route_cap: Optional[int] = None):
     """The search launch WITHOUT the torch.library dispatch: what ``DifferentiableAstar.forward`` calls when no gradient can flow
     (``torch.no_grad()`` / inputs that do not require one) and nothing is being traced -- the custom-op machinery costs more host time
     than the launch itself at 4096 maps.  Takes the reference's [B,1,H,W] tensors (or [B,H,W]) as they are; same five outputs
@@ -388,7 +421,7 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
     a copy made here would be made on the current stream, after the caller ordered the streams -- and holds ``keep``, the list that
     receives the launch's workspace, until that stream is done).  ``exact``: the reference's batch loop to the letter (``_launch_search``).
     ``lib``: another build of the C ABI (``_native.load_dev()``: stream-equality tests).  ``neighbor_mask``, ``heuristic`` ([B,1,H,W] or
-    [B,H,W] fp32 on the maps' device; made contiguous here): see ``_launch_search``."""
+    [B,H,W] fp32 on the maps' device; made contiguous here): see ``_launch_search``.  ``route_cap``: what ``search_routes`` passes."""
     if stream_ptr is not None and not (cost_maps.is_contiguous() and start_maps.is_contiguous() and goal_maps.is_contiguous()
                                        and obstacles_maps.is_contiguous()):
         raise ValueError("search_nograd(stream_ptr=...): the maps must be contiguous (make the copies before ordering the streams)")
@@ -424,7 +457,23 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
     # the True is one_meta)
     return _launch_search(lib if lib is not None else _native.load(), cost_maps, start_maps, goal_maps, obstacles_maps, B, H, W, g_ratio, max_iters,
                           want_log, flags, cost_maps.device, order, order_out, check_order, summary_ptr, True, stream_ptr, out_4d, counter_ptr,
-                          keep, exact, neighbor_mask, heuristic)
+                          keep, exact, neighbor_mask, heuristic, route_cap)
+
+
+def search_routes(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, g_ratio: float,
+                  max_iters: int, flags: int = 0, *, route_cap: Optional[int] = None, **options):
+    """The search launch that also returns every map's ORDERED route (include/nastar_routes.h): a no-grad call to the C ABI, same kernels and
+    same first five outputs as ``search_nograd`` (whose ``options`` it takes: order, order_out, check_order, summary_ptr, counter_ptr, out_4d,
+    exact, neighbor_mask, heuristic) -> (histories, paths, iters, status, sel_log, routes [B, route_cap] int32, route_lengths [B] int32,
+    route_costs [B] float32).  Row b of ``routes``: the last min(len, route_cap) cells of the route as flat indices r*W + c, the goal last
+    among them, then -1; ``route_lengths`` is the true length whatever the capacity; ``route_costs`` the fp64 sum of the costs of the route
+    cells but the goal, rounded once.  ``route_cap``: None = min(H*W, max_iters + 1), which always suffices."""
+    H, W = int(cost_maps.shape[-2]), int(cost_maps.shape[-1])
+    if route_cap is None:
+        route_cap = min(H * W, int(max_iters) + 1)
+    if isinstance(route_cap, bool) or not isinstance(route_cap, int) or route_cap < 1:
+        raise ValueError(f"route_cap must be an int >= 1, got {route_cap!r}")
+    return search_nograd(cost_maps, start_maps, goal_maps, obstacles_maps, g_ratio, max_iters, False, flags, route_cap=route_cap, **options)
 
 
 def order_from_levels(levels: torch.Tensor) -> torch.Tensor:

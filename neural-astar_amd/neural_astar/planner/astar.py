@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import encoder
-from .differentiable_astar import AstarOutput, DifferentiableAstar
+from .differentiable_astar import AstarOutput, DifferentiableAstar, RoutedAstarOutput, _checked_heuristic, _checked_route_len
 from .pq_astar import pq_astar  # noqa: F401  (the reference's astar.py imports it here: a stub that fails loudly when called)
 
 
@@ -64,6 +64,16 @@ class VanillaAstar(nn.Module):
     def forward(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 store_intermediate_results: bool = False, heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:
         return self.perform_astar(map_designs, start_maps, goal_maps, map_designs, store_intermediate_results, heuristic_maps)
+
+
+    def plan_routes(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
+                    heuristic_maps: Optional[torch.Tensor] = None, max_route_len: Optional[int] = None) -> RoutedAstarOutput:
+        """``forward()``'s search with every map's ORDERED route, its length and its cost beside the two masks
+        (``DifferentiableAstar.plan_routes``): an evaluation call -- no autograd graph, detached tensors."""
+        if not self.use_differentiable_astar:
+            raise NotImplementedError("use_differentiable_astar=False selects the reference's CPU-only pq_astar, which is out of scope for "
+                                      "the MI355X-native hot path; plan_routes() runs the HIP DifferentiableAstar kernel only")
+        return self.astar.plan_routes(map_designs, start_maps, goal_maps, map_designs, heuristic_maps, max_route_len)
 
 
 class NeuralAstar(VanillaAstar):
@@ -219,3 +229,17 @@ class NeuralAstar(VanillaAstar):
         cost_maps = self.encode(map_designs, start_maps, goal_maps)
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.perform_astar(cost_maps, start_maps, goal_maps, obstacles_maps, store_intermediate_results, heuristic_maps)
+
+    def plan_routes(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
+                    heuristic_maps: Optional[torch.Tensor] = None, max_route_len: Optional[int] = None) -> RoutedAstarOutput:
+        """``forward()``'s encode + search with every map's ORDERED route, its length and its cost beside the two masks
+        (``DifferentiableAstar.plan_routes``): an evaluation call -- the predicted cost maps are detached, no autograd graph is kept."""
+        _checked_route_len(max_route_len)  # (both refusals before the encoder launches anything)
+        if heuristic_maps is not None:
+            _checked_heuristic(heuristic_maps, start_maps)
+        if not self.use_differentiable_astar:
+            raise NotImplementedError("use_differentiable_astar=False selects the reference's CPU-only pq_astar, which is out of scope for "
+                                      "the MI355X-native hot path; plan_routes() runs the HIP DifferentiableAstar kernel only")
+        cost_maps = self.encode(map_designs, start_maps, goal_maps).detach()
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.plan_routes(cost_maps, start_maps, goal_maps, obstacles_maps, heuristic_maps, max_route_len)

@@ -26,6 +26,37 @@ class AstarOutput(NamedTuple):
     intermediate_results: Optional[List[dict]] = None
 
 
+class RoutedAstarOutput(NamedTuple):
+    """What ``plan_routes()`` returns: the two masks of ``AstarOutput`` and, per map, the ORDERED route they cannot give (with 8-connected
+    moves a path cell may have more than two path neighbours).  ``routes`` [B, L] int32: flat cell indices r*W + c in travel order, the goal
+    last, then -1 (``route_coords`` turns them into (row, col)); ``route_lengths`` [B] int32: the number of route cells (== paths.sum per
+    map), the true length also when L is smaller -- the row then holds the LAST L cells; ``route_costs`` [B] float32: the cost of the cells
+    the route leaves (every cell but the goal), summed in float64 and rounded once.  DESIGN.md section 2, item 6c."""
+
+    histories: torch.Tensor
+    paths: torch.Tensor
+    routes: torch.Tensor
+    route_lengths: torch.Tensor
+    route_costs: torch.Tensor
+
+
+def route_coords(routes: torch.Tensor, W: int) -> torch.Tensor:
+    """``routes`` [B, L] (flat indices r*W + c, -1 = no cell) -> [B, L, 2] (row, col), -1 where the route is -1"""
+    none = routes < 0
+    idx = routes.clamp(min=0)
+    rc = torch.stack((torch.div(idx, W, rounding_mode="floor"), idx % W), dim=-1)
+    return rc.masked_fill(none.unsqueeze(-1), -1)
+
+
+def _checked_route_len(max_route_len) -> Optional[int]:
+    """``max_route_len`` of plan_routes(): None (the capacity that always suffices) or an int >= 1"""
+    if max_route_len is None:
+        return None
+    if isinstance(max_route_len, bool) or not isinstance(max_route_len, int) or max_route_len < 1:
+        raise ValueError(f"max_route_len must be an int >= 1 (or None: min(H*W, max_iters + 1), which always suffices), got {max_route_len!r}")
+    return max_route_len
+
+
 # ---- the reference module's public helpers, kept importable under their names (differentiable_astar.py:26-52, :77-93, :96-125) -------------
 # The search kernel fuses all three (a-2, a-4, a-7 of SURVEY.md 8a): nothing in this package calls them.  They exist for code that imports them
 # from the reference's module -- same arguments, same results -- and work on device tensors (no CPU path in this package).
@@ -502,6 +533,70 @@ class DifferentiableAstar(nn.Module):
             self.last_packed = None  # (the slot holds the masks of the first launch)
         return AstarOutput(hist, paths, [])
 
+    def _refuse_replaced_heuristic(self) -> None:
+        if self.get_heuristic is not get_heuristic:
+            raise NotImplementedError("DifferentiableAstar.get_heuristic was replaced: the MI355X search kernels hard-wire the reference's heuristic "
+                                      "(Chebyshev + 0.001 x Euclidean, differentiable_astar.py:26-52) and would silently ignore another one; "
+                                      "pass the heuristic as a tensor instead: forward(..., heuristic_maps=h0) with h0 of shape [B, 1, H, W]")
+
+    def plan_routes(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                    heuristic_maps: Optional[torch.Tensor] = None, max_route_len: Optional[int] = None) -> RoutedAstarOutput:
+        """The search of ``forward()`` -- same kernels, ``histories`` and ``paths`` bit-identical to its -- that also returns every map's ORDERED
+        route, its length and its cost (``RoutedAstarOutput``; the launch of include/nastar_routes.h writes them from the parent chain it
+        backtracks along).  An EVALUATION call: it runs without an autograd graph and returns detached tensors, whatever requires a gradient.
+        Honours ``neighbor_filter``, ``g_ratio``, ``Tmax`` / ``self.training``, ``unit_cost``, ``heuristic_maps`` and the exact batch-loop rule
+        of ``forward()`` (a launch that reports NASTAR_SUMMARY_COUPLED is repeated exactly).  ``check_solvable`` False: nothing is checked;
+        any other value: the status is read before returning (one host synchronisation) and ``UnsolvableMapError`` raised as ``forward()``
+        does.  ``max_route_len``: the row length L of ``routes``; None = min(H*W, max_iters + 1), which always suffices; a shorter row keeps
+        the last L cells of a longer route.  Takes no placement and no native host lane."""
+        assert cost_maps.ndim == 4
+        assert start_maps.ndim == 4
+        assert goal_maps.ndim == 4
+        assert obstacles_maps.ndim == 4
+        route_cap = _checked_route_len(max_route_len)
+        self._refuse_replaced_heuristic()
+        h0 = _checked_heuristic(heuristic_maps, cost_maps).detach() if heuristic_maps is not None else None
+        ops._require_device(cost_maps, start_maps, goal_maps, obstacles_maps)
+        nmask = self.neighbor_mask()
+        B, _, H, W = cost_maps.shape
+        max_iters = ops.max_iters_for(W, self.Tmax, self.training)
+        same = obstacles_maps is cost_maps or (cost_maps.data_ptr() == obstacles_maps.data_ptr() and cost_maps.shape == obstacles_maps.shape
+                                               and cost_maps.stride() == obstacles_maps.stride())
+        unit = same and self.unit_cost is True and nmask is None and h0 is None
+        exact = B > 1 and (ops.coupling_possible(self.g_ratio) or h0 is not None) and not unit  # forward()'s rule, to the letter
+        dev = cost_maps.device
+        cost = cost_maps.detach()
+        passable = cost if same else obstacles_maps.detach()
+        start, goal = start_maps.detach(), goal_maps.detach()
+        board = ops.StatusBoard.of(dev) if (self.check_solvable and not _capturing(cost_maps)) else None
+        row = board.acquire() if board is not None else -1
+        cptr = board.counter_ptr(row) if (board is not None and ops.in_lds(H, W)) else 0
+
+        def launch(exact_now: bool, sptr: int, cptr_now: int):
+            return ops.search_routes(cost, start, goal, passable, self.g_ratio, max_iters, ops.FLAG_UNIT_COST if unit else 0, route_cap=route_cap,
+                                     summary_ptr=sptr, counter_ptr=cptr_now, out_4d=True, exact=exact_now, neighbor_mask=nmask, heuristic=h0)
+
+        try:
+            hist, paths, iters, status, _, routes, lengths, costs = launch(exact, board.ptr(row) if board is not None else 0, cptr)
+        except BaseException:
+            if row >= 0:
+                board.release(row)
+            raise
+        self.last_status, self.last_iters = status, iters
+        self._calls += 1
+        if row >= 0:
+            summ = self._collect_sync(row, dev, bool(cptr))
+            if summ is not None:
+                if summ[ops.SUMMARY_BAD_ORDER]:
+                    _warn_bad_order()
+                if summ[ops.SUMMARY_ERRORS].any():
+                    _raise_unsolvable(status, self._calls)
+                if summ[ops.SUMMARY_COUPLED] and B > 1 and not exact:
+                    # a finished map of this batch is not at a fixed point of the reference's batch loop (negative costs): the batch again, exactly
+                    hist, paths, iters, status, _, routes, lengths, costs = launch(True, 0, 0)
+                    self.last_status, self.last_iters = status, iters
+        return RoutedAstarOutput(hist, paths, routes, lengths, costs)
+
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
                 heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:
@@ -516,10 +611,7 @@ class DifferentiableAstar(nn.Module):
         assert start_maps.ndim == 4
         assert goal_maps.ndim == 4
         assert obstacles_maps.ndim == 4
-        if self.get_heuristic is not get_heuristic:
-            raise NotImplementedError("DifferentiableAstar.get_heuristic was replaced: the MI355X search kernels hard-wire the reference's heuristic "
-                                      "(Chebyshev + 0.001 x Euclidean, differentiable_astar.py:26-52) and would silently ignore another one; "
-                                      "pass the heuristic as a tensor instead: forward(..., heuristic_maps=h0) with h0 of shape [B, 1, H, W]")
+        self._refuse_replaced_heuristic()
         h0 = None
         if heuristic_maps is not None:
             h0 = _checked_heuristic(heuristic_maps, cost_maps)
