@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void nastar_bwdr_sweep_heuristic_kernel(const 
 template <bool kGlobal, bool kHistLds, bool kFastDiv, bool kWide = false>
 __global__ __launch_bounds__(64) void nastar_backward_replay_kernel(const BwdRArgs a, const float rcp_sqrtW)
 {
-    constexpr bool kMasked = false, kHeur = false;
+    constexpr bool kMasked = false, kHeur = false, kMulti = false;
     constexpr uint32_t nmask = 0x1EFu;  // (NASTAR_NEIGHBORS_MOORE8; never read)
     constexpr const float* h0p = nullptr;
 #include "nastar_backward_replay_body.inc"
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void nastar_backward_replay_kernel(const BwdRAr
 template <bool kGlobal, bool kHistLds, bool kFastDiv, bool kWide = false>
 __global__ __launch_bounds__(64) void nastar_backward_replay_masked_kernel(const BwdRArgs a, const float rcp_sqrtW, const uint32_t nmask)
 {
-    constexpr bool kMasked = true, kHeur = false;
+    constexpr bool kMasked = true, kHeur = false, kMulti = false;
     constexpr const float* h0p = nullptr;
 #include "nastar_backward_replay_body.inc"
 }
@@ -217,7 +217,17 @@ template <bool kGlobal, bool kHistLds, bool kFastDiv, bool kWide = false>
 __global__ __launch_bounds__(64) void nastar_backward_replay_heuristic_kernel(const BwdRArgs a, const float rcp_sqrtW, const uint32_t nmask,
                                                                               const float* __restrict__ h0p)
 {
-    constexpr bool kMasked = true, kHeur = true;
+    constexpr bool kMasked = true, kHeur = true, kMulti = false;
+#include "nastar_backward_replay_body.inc"
+}
+
+// the replay of a MULTI-SOURCE search (include/nastar_sources.h: nastar_backward_replay_sources): every non-zero cell of the start map is open
+// from history index 0.  kHeur = false: the masked kernel's replay (h0p is not read); kHeur = true: the heuristic kernel's.
+template <bool kGlobal, bool kHistLds, bool kFastDiv, bool kHeur, bool kWide = false>
+__global__ __launch_bounds__(64) void nastar_backward_replay_sources_kernel(const BwdRArgs a, const float rcp_sqrtW, const uint32_t nmask,
+                                                                            const float* __restrict__ h0p)
+{
+    constexpr bool kMasked = true, kMulti = true;
 #include "nastar_backward_replay_body.inc"
 }
 

@@ -1,6 +1,8 @@
 // nastar_backward_replay_body.inc -- the body of nastar_backward_replay_kernel and nastar_backward_replay_masked_kernel
 // (nastar_backward_replay.hip.h), included INSIDE each kernel so that the kernel without a mask keeps its instruction stream (see
-// nastar_forward_compact_body.inc).  In scope: kGlobal, kHistLds, kFastDiv, kWide, `a`, `rcp_sqrtW`, and `constexpr bool kMasked` / `nmask`, `constexpr bool kHeur` / `h0p`.
+// nastar_forward_compact_body.inc).  In scope: kGlobal, kHistLds, kFastDiv, kWide, `a`, `rcp_sqrtW`, and `constexpr bool kMasked` / `nmask`, `constexpr bool kHeur` / `h0p`,
+// and `constexpr bool kMulti` (nastar_backward_replay_sources_kernel, include/nastar_sources.h): every non-zero cell of the start map is open from
+// history index 0, so the initial softmax sums run over all of them.
     static_assert(!kWide || kGlobal, "wide stamps exist for the HBM state only");
     using stamp_t = typename std::conditional<kWide, uint32_t, unsigned short>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -77,6 +79,59 @@
     // ... and from the step after its last re-selection on (budget-truncated runs only) the goal's gradient counts again
     const int t_restore = (goal_zeroed && extra <= 0 && t_last_goal < n_steps - 1) ? t_last_goal : -1;
     const float goal_up = bwdr_upstream(a, off + (size_t)gidx);
+    if constexpr (kMulti) {
+        if (lane == 0 && goal_zeroed) st_st<kGlobal>(&G[gidx], 0.f);
+        // open list = every start cell (:187 open_maps = start_maps), each with g = 0 and open from history index 0: S = sum v, D = sum G v.
+        // (fp64 sums of fp32 terms, as every later change of S and D; the goal's zeroed upstream value must be in place first)
+        if constexpr (kGlobal) global_step_fence();
+        wave_sync();
+        double dS = 0.0, dD = 0.0;
+        auto open = [&](int i) {
+            const int r = i / d.W, c = i - r * d.W;
+            const float hh = d.omg * (h0(i, r, c, goal_r, goal_c) + st_ld<kGlobal>(&cst[i]));
+            const float v = bwdr_v<kFastDiv>(d, 0.0f, hh, rcp_sqrtW);
+            st_st<kGlobal>(&g[i], 0.0f);
+            dS += (double)v;
+            dD += (double)(st_ld<kGlobal>(&G[i]) * v);
+        };
+        const float* const sm = a.start + off;
+        int done = 0;
+        if constexpr (kGlobal) {
+            // a large map: ONE wavefront reads the whole start map -- 16 cells per lane and trip, four 16-byte loads in flight (as the
+            // forward's seeding pass, hybrid_open_sources), where the map's row is 16-byte aligned
+            if ((d.HW & 3) == 0 && (reinterpret_cast<uintptr_t>(sm) & 15u) == 0) {
+                const float4* s4 = reinterpret_cast<const float4*>(sm);
+                const int n4 = d.HW >> 2;
+                int q = lane;
+                for (; q + 192 < n4; q += 256) {
+                    float4 sv[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) sv[k] = s4[q + 64 * k];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = (q + 64 * k) << 2;
+                        if (sv[k].x != 0.f) open(i);
+                        if (sv[k].y != 0.f) open(i + 1);
+                        if (sv[k].z != 0.f) open(i + 2);
+                        if (sv[k].w != 0.f) open(i + 3);
+                    }
+                }
+                for (; q < n4; q += 64) {
+                    const float4 sv = s4[q];
+                    const int i = q << 2;
+                    if (sv.x != 0.f) open(i);
+                    if (sv.y != 0.f) open(i + 1);
+                    if (sv.z != 0.f) open(i + 2);
+                    if (sv.w != 0.f) open(i + 3);
+                }
+                done = d.HW;
+            }
+        }
+        for (int i = done + lane; i < d.HW; i += 64)
+            if (sm[i] != 0.f) open(i);
+        const uint32_t sda0 = (uint32_t)(uintptr_t)sd;
+        asm volatile("ds_add_f64 %0, %1\n\tds_add_f64 %0, %2 offset:8" ::"v"(sda0), "v"(dS), "v"(dD) : "memory");
+    } else
     if (lane == 0) {
         if (goal_zeroed) st_st<kGlobal>(&G[gidx], 0.f);
         // open list = {start} (:187), g[start] = 0 (:193): the start is open from history index 0

@@ -23,6 +23,7 @@
 #include "nastar_backward_replay_asm.hip.h"
 #include "nastar_routes.hip.h"
 #include "../../include/nastar_routes.h"
+#include "../../include/nastar_sources.h"
 
 namespace nastar {
 
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(1024) void nastar_order_check_kernel(const int* __r
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, bool kAsm = false>
 __global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCArgs a, const float rcp_sqrtW)
 {
-    constexpr bool kMasked = false, kHeur = false;
+    constexpr bool kMasked = false, kHeur = false, kMulti = false;
     constexpr uint32_t nmask = NASTAR_NEIGHBORS_MOORE8;
     constexpr const float* h0 = nullptr;
 #include "nastar_forward_compact_body.inc"
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCAr
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 __global__ __launch_bounds__(64) void nastar_forward_compact_masked_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask)
 {
-    constexpr bool kAsm = false, kMasked = true, kHeur = false;
+    constexpr bool kAsm = false, kMasked = true, kHeur = false, kMulti = false;
     constexpr const float* h0 = nullptr;
 #include "nastar_forward_compact_body.inc"
 }
@@ -141,7 +142,18 @@ template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 __global__ __launch_bounds__(64) void nastar_forward_compact_heuristic_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask,
                                                                               const float* __restrict__ h0)
 {
-    constexpr bool kAsm = false, kMasked = true, kHeur = true;
+    constexpr bool kAsm = false, kMasked = true, kHeur = true, kMulti = false;
+#include "nastar_forward_compact_body.inc"
+}
+
+// the compiled step loop of a MULTI-SOURCE search (include/nastar_sources.h: nastar_forward_sources): every non-zero cell of the start map is
+// open with g = 0 when the search begins (compact_open_sources), and a parent walk ends at an unset parent.  Two families: kHeur = false, the
+// masked kernel's step with the built-in heuristic (h0 is not read); kHeur = true, the heuristic kernel's.  Both take the neighbourhood mask.
+template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, bool kHeur>
+__global__ __launch_bounds__(64) void nastar_forward_compact_sources_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask,
+                                                                            const float* __restrict__ h0)
+{
+    constexpr bool kAsm = false, kMasked = true, kMulti = true;
 #include "nastar_forward_compact_body.inc"
 }
 
@@ -482,6 +494,7 @@ struct Neighbourhood {
     bool masked = false;
     uint32_t mask = NASTAR_NEIGHBORS_MOORE8;
     const float* h0 = nullptr;
+    bool multi = false;  // include/nastar_sources.h: every non-zero cell of the start map is a source (the fourth and fifth twin of each kernel)
 };
 
 // map widths for which the FMA-based division by fl32(sqrt(W)) was verified bit-exact against IEEE division for
@@ -495,11 +508,12 @@ static bool fastdiv_verified(int W)
     return false;
 }
 
-// kKind: 0 = Moore-8, 1 = masked, 2 = masked with a caller-supplied heuristic
+// kKind: 0 = Moore-8, 1 = masked, 2 = masked with a caller-supplied heuristic, 3 / 4 = the multi-source forms of 1 / 2
 template <int kKind, bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 static auto compiled_compact_kernel()
 {
-    if constexpr (kKind == 2) return &nastar_forward_compact_heuristic_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
+    if constexpr (kKind >= 3) return &nastar_forward_compact_sources_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog, kKind == 4>;
+    else if constexpr (kKind == 2) return &nastar_forward_compact_heuristic_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
     else if constexpr (kKind == 1) return &nastar_forward_compact_masked_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
     else return &nastar_forward_compact_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
 }
@@ -631,7 +645,10 @@ static int forward_hybrid(const FwdLaunch& f, int* marks_out)
     }
     const size_t hl = hybrid_lds_bytes(hd.HW);
     if (hl > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
-    const int rc = with_bools([&](auto fd, auto lk, auto masked, auto heur) {
+    const int rc = f.nb.multi ? with_bools([&](auto fd, auto lk, auto heur) {
+        return launch(nastar_forward_hybrid_sources_kernel<fd, lk, heur>, f.B, hl, s, ha, f.nb.mask, f.nb.h0);
+    }, fastdiv_verified(f.W), (f.flags & NASTAR_FLAG_LOCKSTEP) != 0, f.nb.h0 != nullptr)
+    : with_bools([&](auto fd, auto lk, auto masked, auto heur) {
         if constexpr (heur) return launch(nastar_forward_hybrid_heuristic_kernel<fd, lk>, f.B, hl, s, ha, f.nb.mask, f.nb.h0);
         else if constexpr (masked) return launch(nastar_forward_hybrid_masked_kernel<fd, lk>, f.B, hl, s, ha, f.nb.mask);
         else return launch(nastar_forward_hybrid_kernel<fd, lk>, f.B, hl, s, ha);
@@ -704,6 +721,9 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     const bool rank_after = f.order_out && (long long)f.B > resident_capacity(kernel_lds);
     if (rank_after) c.order_out = nullptr;
     if (unit) rc = forward_unit(c, marks_out, kernel_lds, rcp, s);
+    else if (f.nb.multi) rc = with_bools([&](auto heur, auto lg) {  // (always masked: Moore-8 is a mask like any other here)
+        return launch(compact_kernel<(heur ? 4 : 3), lg>(c.d, vec4, fast, false), f.B, lds, s, c, rcp, f.nb.mask, f.nb.h0);
+    }, f.nb.h0 != nullptr, f.sel_log_out != nullptr);
     else rc = with_bools([&](auto masked, auto heur, auto lg) {
         const auto kern = compact_kernel<(heur ? 2 : masked ? 1 : 0), lg>(c.d, vec4, fast, use_asm);
         if constexpr (heur) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask, f.nb.h0);
@@ -920,6 +940,55 @@ int nastar_forward_routes_batchloop_finish(const float* cost, const float* start
     return batchloop_finish(f);  // (its FINAL launch rewrites the rows of the maps it re-runs: routes, lengths and costs with them)
 }
 
+// ---- include/nastar_sources.h: the search from EVERY non-zero cell of the start map, and its replay -----------------------------------------
+int nastar_sources_abi(void) { return NASTAR_SOURCES_ABI; }
+
+// the mask, the heuristic and the optional route group of both search entry points, checked before any HIP call.  A multi-source launch
+// always runs the masked twins (Moore-8 is a mask like any other): the hand-scheduled streams and the unit-cost layout take no start set.
+static int sources_launch(FwdLaunch& f, unsigned neighbor_mask, const float* h0, int32_t* routes_out, int route_cap, int32_t* route_len_out,
+                          float* route_cost_out)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    if (routes_out) {
+        if (!route_len_out) return NASTAR_ERR_NULL;
+        if (route_cap < 1) return NASTAR_ERR_BAD_SHAPE;
+        f.route = RouteOut{routes_out, route_cap, route_len_out, route_cost_out};
+    }
+    f.nb = Neighbourhood{true, neighbor_mask, h0, true};
+    return NASTAR_OK;
+}
+
+int nastar_forward_sources(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
+                           int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
+                           uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order, int32_t* order_out,
+                           int32_t* status_summary, int32_t* completion_counter, unsigned neighbor_mask, const float* h0, int32_t* routes_out,
+                           int route_cap, int32_t* route_len_out, float* route_cost_out, void* stream)
+{
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, flags, stream};
+    const int rc = sources_launch(f, neighbor_mask, h0, routes_out, route_cap, route_len_out, route_cost_out);
+    if (rc) return rc;
+    f.packed_out = packed_out;
+    f.order = order;
+    f.order_out = order_out;
+    f.summary = status_summary;
+    f.done_counter = completion_counter;
+    return forward(f);
+}
+
+int nastar_forward_sources_batchloop_finish(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W,
+                                            double g_ratio, int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out,
+                                            int32_t* iters_out, int32_t* status_out, void* workspace, size_t workspace_bytes,
+                                            unsigned neighbor_mask, const float* h0, int32_t* routes_out, int route_cap, int32_t* route_len_out,
+                                            float* route_cost_out, void* stream)
+{
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, 0, stream};
+    const int rc = sources_launch(f, neighbor_mask, h0, routes_out, route_cap, route_len_out, route_cost_out);
+    if (rc) return rc;
+    return batchloop_finish(f);  // (the PROBE and FINAL launches seed every start too: FwdLaunch::nb travels with them)
+}
+
 int nastar_completion_supported(int H, int W)
 {
     return (H > 0 && W > 0 && (long long)H * W <= kMaxGlobalCells && !needs_global_state(H, W)) ? 1 : 0;
@@ -1056,6 +1125,9 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
         // history in LDS as long as at least 2 maps (or what the state alone allows) stay resident per CU
         const size_t st = bwdr_state_bytes(a.d.HWp), with_hist = st + (size_t)hlen * 16;
         const bool hist_lds = with_hist <= kMaxLdsBytes && (kMaxLdsBytes / with_hist >= 2 || kMaxLdsBytes / st < 2);
+        if (nb.multi) return with_bools([&](auto hl, auto fd, auto heur) {
+            return launch(nastar_backward_replay_sources_kernel<false, hl, fd, heur>, B, hl ? with_hist : st, s, a, rcp, nb.mask, nb.h0);
+        }, hist_lds, fast, nb.h0 != nullptr);
         return with_bools([&](auto hl, auto fd, auto masked, auto heur) {
             const size_t lds = hl ? with_hist : st;
             if constexpr (heur) return launch(nastar_backward_replay_heuristic_kernel<false, hl, fd>, B, lds, s, a, rcp, nb.mask, nb.h0);
@@ -1073,7 +1145,10 @@ static int backward_replay_impl(BwdRArgs& a, const float* cost, const float* sta
     const unsigned per_map = (unsigned)((a.d.HW + 255) / 256);
     const dim3 grid2(per_map < 64u ? per_map : 64u, (unsigned)B);
     with_bools([&](auto w) { hipLaunchKernelGGL(nastar_bwdr_fill_kernel<w>, grid2, dim3(256), 0, s, a); }, wide);
-    const int rc = with_bools([&](auto fd, auto w, auto masked, auto heur) {
+    const int rc = nb.multi ? with_bools([&](auto fd, auto w, auto heur) {
+        return launch(nastar_backward_replay_sources_kernel<true, false, fd, heur, w>, B, 64, s, a, rcp, nb.mask, nb.h0);
+    }, fast, wide, nb.h0 != nullptr)
+    : with_bools([&](auto fd, auto w, auto masked, auto heur) {
         if constexpr (heur) return launch(nastar_backward_replay_heuristic_kernel<true, false, fd, w>, B, 64, s, a, rcp, nb.mask, nb.h0);
         else if constexpr (masked) return launch(nastar_backward_replay_masked_kernel<true, false, fd, w>, B, 64, s, a, rcp, nb.mask);
         else return launch(nastar_backward_replay_kernel<true, false, fd, w>, B, 64, s, a, rcp);
@@ -1177,6 +1252,18 @@ int nastar_backward_replay_ordered_heuristic(const float* grad_histories, const 
     return backward_replay_ordered_impl(grad_histories, histories, opt_trajs, grad_loss_dev, cost, start, goal, passable, sel_log, B, H, W, g_ratio,
                                         max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order,
                                         Neighbourhood{true, neighbor_mask, h0}, stream);
+}
+
+int nastar_backward_replay_sources(const float* grad_histories, const float* histories, const float* opt_trajs, const float* grad_loss_dev,
+                                   const float* cost, const float* start, const float* goal, const float* passable, const int32_t* sel_log,
+                                   int B, int H, int W, double g_ratio, int max_iters, const int32_t* iters, const int32_t* t_batch_dev,
+                                   float* grad_cost_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* order,
+                                   unsigned neighbor_mask, const float* h0, void* stream)
+{
+    if (!neighbor_mask_valid(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
+    return backward_replay_ordered_impl(grad_histories, histories, opt_trajs, grad_loss_dev, cost, start, goal, passable, sel_log, B, H, W, g_ratio,
+                                        max_iters, iters, t_batch_dev, grad_cost_out, workspace, workspace_bytes, flags, order,
+                                        Neighbourhood{true, neighbor_mask, h0, true}, stream);
 }
 
 int nastar_pack_outputs(const float* histories, const int64_t* paths, int B, int H, int W, uint8_t* packed_out, void* stream)

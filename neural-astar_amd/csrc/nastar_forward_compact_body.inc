@@ -3,7 +3,8 @@
 // instruction stream is unchanged (a shared __device__ function changes how the optimiser sees the body and with it the register allocation).
 // In scope: the kernel's template parameters, `a`, `rcp_sqrtW`, and `constexpr bool kMasked` / `nmask` (the neighbor_filter mask, an SGPR).
 // nastar_forward_compact_heuristic_kernel shares it too: `constexpr bool kHeur` / `h0` (the caller's heuristic maps, [B, H, W]); every
-// kHeur branch below is discarded in the other two kernels.
+// kHeur branch below is discarded in the other two kernels.  nastar_forward_compact_sources_kernel (include/nastar_sources.h) is the fourth:
+// `constexpr bool kMulti` -- every non-zero cell of the start map is a source, and a parent walk ends at an unset parent only.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = placed_map(a.order, a.order_bad, a.B);
     if ((unsigned)b >= (unsigned)a.B) return;  // not a permutation (and not checked: NASTAR_FLAG_CHECK_ORDER): never read or write outside the batch
@@ -70,6 +71,8 @@
         const bool asm4 = raw;
 #endif
         const bool half = asm4 && d.gr == 0.5f && d.omg == 0.5f;
+        if constexpr (kMulti) compact_open_sources<kVec4, kFastDiv, kHeur>(d, l, hhv, a.start + off, lane, goal_r, goal_c, rcp_sqrtW);
+        else
         if constexpr (kHeur) {  // open list = {start} (:187), g[start] = 0 (:193), keyed by the stored hh
             if (lane == 0) {
                 l.gc[start_idx].x = 0.0f;
@@ -185,12 +188,12 @@
         // (the COUPLED note above is a summary cell like any other: it must be visible before this search counts itself -- ADVICE r5)
         if (a.done_counter) note_done(a.done_counter, a.summary, a.B, status != NASTAR_OK || coupled);
     }
-    if (goal_idx >= 0 && !(kHeur && bad_h0)) compact_backtrack<(LOGW == LOGH ? LOGW : 0)>(d, l, lane, start_idx, goal_idx, solved ? d.HW : iters - 1);
+    if (goal_idx >= 0 && !(kHeur && bad_h0)) compact_backtrack<(LOGW == LOGH ? LOGW : 0)>(d, l, lane, kMulti ? -1 : start_idx, goal_idx, solved ? d.HW : iters - 1);
     compact_store_outputs<kVec4, false>(d, l, lane, a.hist + off, a.paths + off,
                                         a.packed ? a.packed + (size_t)b * (size_t)(d.HW >> 2) : nullptr);
     const RouteOut ro = kernel_route_args<offsetof(FwdCArgs, route)>();  // (a.route, read here: nastar_routes.hip.h)
     if (ro.routes != nullptr) {  // wave-uniform; null unless the launch came through include/nastar_routes.h
-        const int n = route_walk(l.pdir, lane, start_idx, goal_idx, solved ? d.HW : iters - 1, goal_idx >= 0 && !(kHeur && bad_h0),
+        const int n = route_walk(l.pdir, lane, kMulti ? -1 : start_idx, goal_idx, solved ? d.HW : iters - 1, goal_idx >= 0 && !(kHeur && bad_h0),
                                  [&](int c, uint32_t code) { return compact_parent_of(d, c, code); }, [&](int c) { return l.gc[c].y; }, ro, b);
         route_fill_tail(ro, b, n, lane);
     }

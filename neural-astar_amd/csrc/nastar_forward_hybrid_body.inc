@@ -3,6 +3,8 @@
 // In scope: kFastDiv, kLock, `a`, and `constexpr bool kMasked` / `nmask` (the neighbor_filter mask, an SGPR).
 // nastar_forward_hybrid_heuristic_kernel shares it too: `constexpr bool kHeur` / `h0` (the caller's heuristic maps, [B, H, W], read cell by
 // cell next to the cost in the step's one HBM round trip); every kHeur branch is discarded in the other two kernels.
+// nastar_forward_hybrid_sources_kernel (include/nastar_sources.h) is the fourth: `constexpr bool kMulti` -- the searching wavefront opens
+// every non-zero cell of the start map in a pass before its first step, and a parent walk ends at an unset parent only.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x;
     if constexpr (kLock) {
@@ -39,6 +41,10 @@
         else
         h_start = heuristic0(sr, sc, goal_r, goal_c) + cost[sidx];
     }
+    unsigned long long first_sel = ~0ull;  // kMulti: (key << 32 | cell) of the first selection
+    if constexpr (kMulti) {
+        if (sidx >= 0 && gidx >= 0) first_sel = hybrid_open_sources<kFastDiv, kHeur>(d, g, pdir, cmin, smin, cost, h0m, a.start + off, lane, goal_r, goal_c);
+    } else
     if (lane == 0 && sidx >= 0) {  // open list = {start} (:187), g[start] = 0 (:193); the start is expanded even on an obstacle
         const uint32_t k0 = hybrid_key<kFastDiv>(d, 0.0f, h_start);
         const unsigned long long e = ((unsigned long long)k0 << 32) | (uint32_t)sidx;
@@ -65,6 +71,10 @@
         // (key << 32 | cell) of the next selection, wave-uniform in scalar registers; ~0 = open list empty
         uint32_t sel_key = hybrid_key<kFastDiv>(d, 0.0f, __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(h_start))));
         uint32_t sel_cell = (uint32_t)sidx;
+        if constexpr (kMulti) {
+            sel_key = (uint32_t)(first_sel >> 32);
+            sel_cell = (uint32_t)first_sel;
+        }
         while (iters < budget) {  // :203
             // ---- select: the entry the previous step left behind names s* (no LDS read, no reduction on this path) -------------
             const int s = (int)sel_cell;
@@ -222,7 +232,7 @@
             for (int k2 = 0; k2 < cap; ++k2) {
                 const uint32_t ml = pdir[loc];
                 pdir[loc] = (uint8_t)(ml | P_PATH);
-                if (loc == sidx) break;
+                if (!kMulti && loc == sidx) break;
                 const uint32_t cd = ml & P_DIRMASK;
                 if (cd == PARENT_UNSET) break;
                 neighbour_delta((int)cd, pdr, pdc);
@@ -233,7 +243,7 @@
     global_step_fence();
     const RouteOut ro = kernel_route_args<offsetof(FwdHybridArgs, route)>();  // (a.route, read here: nastar_routes.hip.h)
     if (ro.routes != nullptr) {  // wave-uniform; parents from the slab, costs from the caller's tensor; the -1 tail: store launch
-        route_walk(pdir, lane, sidx, gidx, solved ? d.HW : iters - 1, gidx >= 0 && !(kHeur && status == NASTAR_ERR_BAD_HEURISTIC),
+        route_walk(pdir, lane, kMulti ? -1 : sidx, gidx, solved ? d.HW : iters - 1, gidx >= 0 && !(kHeur && status == NASTAR_ERR_BAD_HEURISTIC),
                    [&](int c, uint32_t code) {
                        int pdr, pdc;
                        neighbour_delta((int)code, pdr, pdc);

@@ -239,6 +239,45 @@ __device__ __forceinline__ void compact_open_start(const CompactDims& d, const C
     wave_sync();
 }
 
+// open list = EVERY non-zero cell of `start` (the multi-source kernels, include/nastar_sources.h; the reference's open_maps = start_maps, :187):
+// each is open with g = 0 and an unset parent, on an obstacle too.  All lanes look at the start map once more (their own cells of the load
+// pass); a start enters its chunk's minimum by ds_min_u64 on (key << 32 | cell) -- several starts may share one 16-cell chunk, and among
+// equal keys the lower cell wins, as in every later step.  kHeur: the key comes from the stored hh (compact_load_heuristic).
+template <bool kVec4, bool kFastDiv, bool kHeur>
+__device__ __forceinline__ void compact_open_sources(const CompactDims& d, const CompactLds& l, const float* hhv, const float* __restrict__ start,
+                                                     int lane, int goal_r, int goal_c, float rcp_sqrtW)
+{
+    auto open = [&](int i) {
+        float hh;
+        if constexpr (kHeur) {
+            hh = hhv[i];
+        } else {
+            const int r = (int)div_magic((uint32_t)i, d.magicW);
+            const int c = i - r * d.W;
+            hh = d.omg * (heuristic0_fast(r, c, goal_r, goal_c) + l.gc[i].y);  // :191-192 h = h0 + cost ; :206
+        }
+        const uint32_t k0 = compact_key<kFastDiv>(d, 0.0f, hh, rcp_sqrtW);
+        l.gc[i].x = 0.0f;
+        l.pdir[i] = (uint8_t)(PARENT_UNSET | P_PASS);
+        atomicMin(&l.cmin[i >> CCL], cmin_entry(k0, (uint32_t)i));
+    };
+    if constexpr (kVec4) {
+        const float4* s4 = reinterpret_cast<const float4*>(start);
+        const int n4 = d.HW >> 2;
+        for (int q = lane; q < n4; q += 64) {
+            const float4 sv = s4[q];
+            if (sv.x != 0.f) open(q << 2);
+            if (sv.y != 0.f) open((q << 2) + 1);
+            if (sv.z != 0.f) open((q << 2) + 2);
+            if (sv.w != 0.f) open((q << 2) + 3);
+        }
+    } else {
+        for (int i = lane; i < d.HW; i += 64)
+            if (start[i] != 0.f) open(i);
+    }
+    wave_sync();
+}
+
 // ---- selection: first flat index of the minimal key; returns -1 when the open list is empty --------------------------
 // CPL_T > 0: chunk minima per lane known at compile time (1: <= 1024 cells, 4: <= 4096 cells); 0: runtime d.CPL.
 // Lane l owns the CONTIGUOUS entries [l*CPL, (l+1)*CPL): first lane == first chunk == first cell.

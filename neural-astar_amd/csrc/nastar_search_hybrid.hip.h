@@ -308,13 +308,82 @@ __global__ __launch_bounds__(256) void nastar_hybrid_header_heuristic_kernel(uns
     }
 }
 
+// The seeding pass of the multi-source kernels (nastar_forward_hybrid_sources_kernel), run by the searching wavefront before its first step:
+// every non-zero cell of `start` is opened with g = 0 and an unset parent (on an obstacle too) and enters cmin / smin by ds_min_u64 on
+// (key << 32 | cell), so that several starts in one chunk or super-chunk leave the first minimal one behind.  The start map is read 16 cells
+// per lane and trip (four 16-byte loads in flight) where its row is 16-byte aligned.  Returns the first selection, the minimum over smin
+// (wave-uniform; ~0 = no source).  The fill launch cannot do this: the open list lives in the LDS of the searching wavefront, and the
+// built-in heuristic needs the goal cell, which the fill launch is still looking for.
+template <bool kFastDiv, bool kHeur>
+__device__ __forceinline__ unsigned long long hybrid_open_sources(const HybridDims& d, float* g, uint8_t* pdir, unsigned long long* cmin,
+                                                                  unsigned long long* smin, const float* cost, const float* h0m,
+                                                                  const float* __restrict__ start, int lane, int goal_r, int goal_c)
+{
+    auto open = [&](int i) {
+        float h;
+        if constexpr (kHeur) {
+            h = h0m[i] + cost[i];
+        } else {
+            int c;
+            const int r = hybrid_row_nb(i, d, c);
+            h = heuristic0(r, c, goal_r, goal_c) + cost[i];  // :191-192 h = h0 + cost
+        }
+        const unsigned long long e = ((unsigned long long)hybrid_key<kFastDiv>(d, 0.0f, h) << 32) | (uint32_t)i;
+        g[i] = 0.0f;
+        pdir[i] = (uint8_t)(PARENT_UNSET | P_PASS);
+        atomicMin(&cmin[i >> 6], e);
+        atomicMin(&smin[i >> 12], e);
+    };
+    int done = 0;
+    if ((d.HW & 3) == 0 && (reinterpret_cast<uintptr_t>(start) & 15u) == 0) {
+        const float4* s4 = reinterpret_cast<const float4*>(start);
+        const int n4 = d.HW >> 2;
+        int q = lane;
+        for (; q + 192 < n4; q += 256) {
+            float4 sv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sv[k] = s4[q + 64 * k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = (q + 64 * k) << 2;
+                if (sv[k].x != 0.f) open(i);
+                if (sv[k].y != 0.f) open(i + 1);
+                if (sv[k].z != 0.f) open(i + 2);
+                if (sv[k].w != 0.f) open(i + 3);
+            }
+        }
+        for (; q < n4; q += 64) {
+            const float4 sv = s4[q];
+            const int i = q << 2;
+            if (sv.x != 0.f) open(i);
+            if (sv.y != 0.f) open(i + 1);
+            if (sv.z != 0.f) open(i + 2);
+            if (sv.w != 0.f) open(i + 3);
+        }
+        done = d.HW;
+    }
+    for (int i = done + lane; i < d.HW; i += 64)
+        if (start[i] != 0.f) open(i);
+    global_step_fence();
+    __syncthreads();
+    // the first selection: the u64 minimum over the super-chunk entries (lane l owns [l spl, (l + 1) spl), ascending cells)
+    unsigned long long e0 = smin[lane * d.spl];
+    for (int j = 1; j < d.spl; ++j) {
+        const unsigned long long ej = smin[lane * d.spl + j];
+        e0 = ej < e0 ? ej : e0;
+    }
+    const unsigned long long m = first_min_entry((uint32_t)(e0 >> 32), (uint32_t)e0);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 // kMasked: the neighbourhood of DifferentiableAstar.neighbor_filter (nmask, see neighbour_enabled) instead of the Moore-8 stencil.
 // kHeur (nastar_forward_hybrid_heuristic_kernel): h0 is the caller's tensor instead of the built-in heuristic; it always takes the mask.
 // All three kernels share one body, nastar_forward_hybrid_body.inc.
 template <bool kFastDiv, bool kLock = false>
 __global__ __launch_bounds__(64) void nastar_forward_hybrid_kernel(const FwdHybridArgs a)
 {
-    constexpr bool kMasked = false, kHeur = false;
+    constexpr bool kMasked = false, kHeur = false, kMulti = false;
     constexpr uint32_t nmask = 0x1EFu;  // (NASTAR_NEIGHBORS_MOORE8; never read)
     constexpr const float* h0 = nullptr;
 #include "nastar_forward_hybrid_body.inc"
@@ -323,7 +392,7 @@ __global__ __launch_bounds__(64) void nastar_forward_hybrid_kernel(const FwdHybr
 template <bool kFastDiv, bool kLock>
 __global__ __launch_bounds__(64) void nastar_forward_hybrid_masked_kernel(const FwdHybridArgs a, const uint32_t nmask)
 {
-    constexpr bool kMasked = true, kHeur = false;
+    constexpr bool kMasked = true, kHeur = false, kMulti = false;
     constexpr const float* h0 = nullptr;
 #include "nastar_forward_hybrid_body.inc"
 }
@@ -331,7 +400,16 @@ __global__ __launch_bounds__(64) void nastar_forward_hybrid_masked_kernel(const 
 template <bool kFastDiv, bool kLock>
 __global__ __launch_bounds__(64) void nastar_forward_hybrid_heuristic_kernel(const FwdHybridArgs a, const uint32_t nmask, const float* __restrict__ h0)
 {
-    constexpr bool kMasked = true, kHeur = true;
+    constexpr bool kMasked = true, kHeur = true, kMulti = false;
+#include "nastar_forward_hybrid_body.inc"
+}
+
+// the MULTI-SOURCE search (include/nastar_sources.h): kHeur = false, the masked kernel's step with the built-in heuristic (h0 is not read);
+// kHeur = true, the heuristic kernel's.  Both take the neighbourhood mask.
+template <bool kFastDiv, bool kLock, bool kHeur>
+__global__ __launch_bounds__(64) void nastar_forward_hybrid_sources_kernel(const FwdHybridArgs a, const uint32_t nmask, const float* __restrict__ h0)
+{
+    constexpr bool kMasked = true, kMulti = true;
 #include "nastar_forward_hybrid_body.inc"
 }
 

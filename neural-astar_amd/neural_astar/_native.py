@@ -143,6 +143,17 @@ ROUTE_SIGNATURES = {
     "nastar_forward_routes_batchloop_finish": "i " + _FORWARD + _WORKSPACE + "up" + _ROUTES + "p",
 }
 
+# the signatures of include/nastar_sources.h (the third header: the search from every non-zero cell of the start map, and its replay), same
+# letter code; again a table of its own (tests/test_multisource.py compares it with ITS header)
+SOURCE_SIGNATURES = {
+    "nastar_sources_abi": "i ",
+    # ... the arguments of nastar_forward_routes (h0 and the route outputs may be NULL)
+    "nastar_forward_sources": "i " + _FORWARD + "p" + _WORKSPACE + "ipppp" + "up" + _ROUTES + "p",
+    "nastar_forward_sources_batchloop_finish": "i " + _FORWARD + _WORKSPACE + "up" + _ROUTES + "p",
+    # ... the arguments of nastar_backward_replay_ordered_heuristic (h0 may be NULL)
+    "nastar_backward_replay_sources": "i pppp" + _REPLAY + "ip" + "upp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -227,6 +238,7 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     _bind(lib, SIGNATURES)
     _bind(lib, ROUTE_SIGNATURES, ROUTE_SIGNATURES)
+    _bind(lib, SOURCE_SIGNATURES, SOURCE_SIGNATURES)
     _lib = lib
     return lib
 

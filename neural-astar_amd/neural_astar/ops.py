@@ -14,7 +14,7 @@ import torch
 from . import _native
 
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
-           "StatusBoard", "route_forward_calls", "search_routes"]
+           "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -190,10 +190,14 @@ def in_lds(H: int, W: int) -> bool:
     return v
 
 
-def _entry_family(neighbor_mask: Optional[int], heuristic):
+def _entry_family(neighbor_mask: Optional[int], heuristic, multi_source: bool = False):
     """THE choice among the three twins of every search / finish / ordered-replay entry point (include/nastar.h): -> (suffix of the symbol,
     the arguments it takes between the base entry's and the stream).  Plain: no mask (None -- Moore-8 on the fastest kernels) and no
-    heuristic; `_masked`: a mask, NEIGHBORS_MOORE8 included; `_heuristic`: a heuristic, with the given mask or Moore-8."""
+    heuristic; `_masked`: a mask, NEIGHBORS_MOORE8 included; `_heuristic`: a heuristic, with the given mask or Moore-8.
+    ``multi_source``: the family of include/nastar_sources.h instead (`_sources`: nastar_forward_sources, nastar_forward_sources_batchloop_finish,
+    nastar_backward_replay_sources) -- always a mask (Moore-8 by default) and a heuristic slot that may stay empty."""
+    if multi_source:
+        return "_sources", (NEIGHBORS_MOORE8 if neighbor_mask is None else int(neighbor_mask), heuristic or None)
     if heuristic is not None:
         return "_heuristic", (NEIGHBORS_MOORE8 if neighbor_mask is None else int(neighbor_mask), heuristic)
     if neighbor_mask is not None:
@@ -218,6 +222,28 @@ def forward_calls(cost, start, goal, passable, B, H, W, g_ratio, max_iters, hist
     return launch, finish
 
 
+def _routed_calls(multi_source, cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                  workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, neighbor_mask, h0, routes_out, route_cap,
+                  route_len_out, route_cost_out, stream, exact):
+    """the one assembler behind ``route_forward_calls`` and ``source_forward_calls``: both headers give their launch the parameters of
+    nastar_forward_routes and their finish those of nastar_forward_routes_batchloop_finish; the family (``_entry_family``) names the symbols"""
+    problem = (cost, start, goal, passable, B, H, W, float(g_ratio), int(max_iters), histories_out, paths_out, sel_log_out or None, iters_out,
+               status_out)
+    if multi_source:
+        suffix, family = _entry_family(neighbor_mask, h0, True)
+        names = ("nastar_forward" + suffix, "nastar_forward" + suffix + "_batchloop_finish")
+        routes = (routes_out, int(route_cap), route_len_out, route_cost_out or None) if routes_out else (None, 0, None, None)  # optional here
+    else:
+        family = (NEIGHBORS_MOORE8 if neighbor_mask is None else int(neighbor_mask), h0 or None)
+        names = ("nastar_forward_routes", "nastar_forward_routes_batchloop_finish")
+        routes = (routes_out, int(route_cap), route_len_out, route_cost_out or None)
+    tail = (*family, *routes, stream)
+    launch = (names[0], (*problem, None, workspace or None, workspace_bytes, flags, order or None, order_out or None, status_summary or None,
+                         (completion_counter or None) if status_summary else None, *tail))
+    finish = (names[1], (*problem, workspace, workspace_bytes, *tail)) if exact else None
+    return launch, finish
+
+
 def route_forward_calls(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
                         workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, neighbor_mask, h0, routes_out,
                         route_cap, route_len_out, route_cost_out, stream, exact=False):
@@ -225,24 +251,34 @@ def route_forward_calls(cost, start, goal, passable, B, H, W, g_ratio, max_iters
     (nastar_forward_routes_batchloop_finish, arguments) -- None unless ``exact``).  The parameters up to ``stream`` ARE those of
     nastar_forward_routes, names and order (less packed_out; tests/test_routes.py pins it).  ONE entry point serves every neighbourhood:
     ``neighbor_mask`` None = Moore-8, ``h0`` None = the reference's heuristic -- both None is the launch of nastar_forward_ex."""
-    problem = (cost, start, goal, passable, B, H, W, float(g_ratio), int(max_iters), histories_out, paths_out, sel_log_out or None, iters_out,
-               status_out)
-    tail = (NEIGHBORS_MOORE8 if neighbor_mask is None else int(neighbor_mask), h0 or None, routes_out, int(route_cap), route_len_out,
-            route_cost_out or None, stream)
-    launch = ("nastar_forward_routes",
-              (*problem, None, workspace or None, workspace_bytes, flags, order or None, order_out or None, status_summary or None,
-               (completion_counter or None) if status_summary else None, *tail))
-    finish = ("nastar_forward_routes_batchloop_finish", (*problem, workspace, workspace_bytes, *tail)) if exact else None
-    return launch, finish
+    return _routed_calls(False, cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                         workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, neighbor_mask, h0, routes_out,
+                         route_cap, route_len_out, route_cost_out, stream, exact)
+
+
+def source_forward_calls(cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                         workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, neighbor_mask, h0, routes_out,
+                         route_cap, route_len_out, route_cost_out, stream, exact=False):
+    """``route_forward_calls`` for the MULTI-SOURCE launch (include/nastar_sources.h: every non-zero cell of the start maps is a source): ->
+    ((nastar_forward_sources, arguments), (nastar_forward_sources_batchloop_finish, arguments) -- None unless ``exact``).  The parameters up
+    to ``stream`` ARE those of nastar_forward_sources, names and order (less packed_out; tests/test_multisource.py pins it).  The route outputs
+    are optional here: ``routes_out`` None = no routes (the other three then go out as NULL / 0 too)."""
+    return _routed_calls(True, cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                         workspace, workspace_bytes, flags, order, order_out, status_summary, completion_counter, neighbor_mask, h0, routes_out,
+                         route_cap, route_len_out, route_cost_out, stream, exact)
 
 
 def replay_call(*, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_iters, iters, t_batch, grad_cost, workspace, ws_bytes, stream,
-                grad_hist=None, histories=None, opt_trajs=None, grad_loss=None, flags=0, order=None, neighbor_mask=None, heuristic=None):
+                grad_hist=None, histories=None, opt_trajs=None, grad_loss=None, flags=0, order=None, neighbor_mask=None, heuristic=None,
+                multi_source=False):
     """The C call of ONE replay backward as plain values: -> (symbol, arguments).  ``grad_hist`` given: dL/dhistories comes from autograd;
     None: the fused L1 form (``histories``, ``opt_trajs``, ``grad_loss``).  nastar_backward_replay / nastar_backward_l1_replay where they
-    suffice (no order, mask or heuristic; the L1 one takes no flags either), the `_ordered` family otherwise."""
-    suffix, tail = _entry_family(neighbor_mask, heuristic)
+    suffice (no order, mask or heuristic; the L1 one takes no flags either), the `_ordered` family otherwise.  ``multi_source``: the log of a
+    multi-source search -- nastar_backward_replay_sources (include/nastar_sources.h), one entry point for every mask, heuristic and order."""
+    suffix, tail = _entry_family(neighbor_mask, heuristic, multi_source)
     replay = (cost, start, goal, passable, sel_log, B, H, W, float(g_ratio), int(max_iters), iters, t_batch, grad_cost, workspace, ws_bytes)
+    if multi_source:
+        return "nastar_backward_replay" + suffix, (grad_hist, histories, opt_trajs, grad_loss) + replay + (int(flags), order) + tail + (stream,)
     if not suffix and order is None:
         if grad_hist is not None:
             return "nastar_backward_replay", (grad_hist,) + replay + (int(flags), stream)
@@ -253,7 +289,7 @@ def replay_call(*, cost, start, goal, passable, sel_log, B, H, W, g_ratio, max_i
 
 def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters, want_log, flags, dev, order=None, order_out=None,
                    check_order=False, summary_ptr=0, one_meta=False, stream_ptr=None, out_4d=False, counter_ptr=0, keep=None, exact=False,
-                   neighbor_mask=None, heuristic=None, route_cap=None):
+                   neighbor_mask=None, heuristic=None, route_cap=None, multi_source=False):
     """allocate the five outputs and issue ONE nastar_forward_ex launch on torch's current stream (shared by the custom ops and the
     no-autograd fast path).  cost / start / goal / passable: contiguous fp32 tensors of B*H*W elements (any leading shape).
     ``keep``: a list that receives the launch's temporaries (its workspace) when the launch goes to ANOTHER stream than the one the
@@ -267,7 +303,9 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
     ``heuristic``: None = the reference's get_heuristic, computed by the kernels; a contiguous fp32 [B, H, W] tensor = the caller's heuristic
     maps (nastar_forward_ex_heuristic; with ``neighbor_mask`` or Moore-8).  Which symbols are called with which arguments: ``forward_calls``.
     ``route_cap``: None = the five outputs; an int >= 1 = the launch of include/nastar_routes.h (``route_forward_calls``: same kernels, same
-    five outputs) that also writes routes [B, route_cap] int32, route lengths [B] int32 and route costs [B] float32 -- three more results."""
+    five outputs) that also writes routes [B, route_cap] int32, route lengths [B] int32 and route costs [B] float32 -- three more results.
+    ``multi_source``: the launch of include/nastar_sources.h (``source_forward_calls``) -- every non-zero cell of ``start`` is a source; with or
+    without ``route_cap``."""
     shape = (B, 1, H, W) if out_4d else (B, H, W)
     hist = torch.empty(shape, dtype=torch.float32, device=dev)
     paths = torch.empty(shape, dtype=torch.int64, device=dev)
@@ -300,23 +338,22 @@ def _launch_search(lib, cost, start, goal, passable, B, H, W, g_ratio, max_iters
             raise ValueError("a launch on a foreign stream that needs a workspace must be given a `keep` list (the allocator would hand the "
                              "workspace to the next launch on the current stream while this one still runs)")
         keep.append(workspace)
-    if route_cap is None:
-        (fwd, args), fin = forward_calls(
-            cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, g_ratio, max_iters, hist.data_ptr(), paths.data_ptr(),
-            sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(), workspace.data_ptr() if workspace is not None else None,
-            ws_bytes, flags, order_ptr, order_out.data_ptr() if order_out is not None else None, summary_ptr, counter_ptr,
-            stream_ptr if stream_ptr is not None else torch.cuda.current_stream(dev).cuda_stream, exact, neighbor_mask,
-            heuristic.data_ptr() if heuristic is not None else None)
-    else:
-        routes = torch.empty((B, route_cap), dtype=torch.int32, device=dev)
-        route_len = torch.empty((B,), dtype=torch.int32, device=dev)
-        route_cost = torch.empty((B,), dtype=torch.float32, device=dev)
-        (fwd, args), fin = route_forward_calls(
-            cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, g_ratio, max_iters, hist.data_ptr(), paths.data_ptr(),
-            sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(), workspace.data_ptr() if workspace is not None else None,
-            ws_bytes, flags, order_ptr, order_out.data_ptr() if order_out is not None else None, summary_ptr, counter_ptr, neighbor_mask,
-            heuristic.data_ptr() if heuristic is not None else None, routes.data_ptr(), route_cap, route_len.data_ptr(), route_cost.data_ptr(),
-            stream_ptr if stream_ptr is not None else torch.cuda.current_stream(dev).cuda_stream, exact)
+    stream = stream_ptr if stream_ptr is not None else torch.cuda.current_stream(dev).cuda_stream
+    fixed = (cost.data_ptr(), start.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, g_ratio, max_iters, hist.data_ptr(), paths.data_ptr(),
+             sel_log.data_ptr() if want_log else None, iters.data_ptr(), status.data_ptr(), workspace.data_ptr() if workspace is not None else None,
+             ws_bytes, flags, order_ptr, order_out.data_ptr() if order_out is not None else None, summary_ptr, counter_ptr)
+    h0_ptr = heuristic.data_ptr() if heuristic is not None else None
+    if route_cap is None and not multi_source:
+        (fwd, args), fin = forward_calls(*fixed, stream, exact, neighbor_mask, h0_ptr)
+    else:  # the routed families: include/nastar_routes.h, include/nastar_sources.h (its routes are optional)
+        routes = route_len = route_cost = None
+        if route_cap is not None:
+            routes = torch.empty((B, route_cap), dtype=torch.int32, device=dev)
+            route_len = torch.empty((B,), dtype=torch.int32, device=dev)
+            route_cost = torch.empty((B,), dtype=torch.float32, device=dev)
+        (fwd, args), fin = _routed_calls(bool(multi_source), *fixed, neighbor_mask, h0_ptr, routes.data_ptr() if routes is not None else None,
+                                         route_cap or 0, route_len.data_ptr() if routes is not None else None,
+                                         route_cost.data_ptr() if routes is not None else None, stream, exact)
     if dev.index is None or torch.cuda.current_device() == dev.index:
         rc = getattr(lib, fwd)(*args)
         if not rc and fin is not None:
@@ -410,7 +447,8 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
                   max_iters: int, want_log: bool = False, flags: int = 0, *, order: Optional[torch.Tensor] = None,
                   order_out: Optional[torch.Tensor] = None, check_order: bool = True, summary_ptr: int = 0, stream_ptr: Optional[int] = None,
                   out_4d: bool = False, counter_ptr: int = 0, keep: Optional[list] = None, exact: bool = False, lib=None,
-                  neighbor_mask: Optional[int] = None, heuristic: Optional[torch.Tensor] = None, route_cap: Optional[int] = None):
+                  neighbor_mask: Optional[int] = None, heuristic: Optional[torch.Tensor] = None, route_cap: Optional[int] = None,
+                  multi_source: bool = False):
     """The search launch WITHOUT the torch.library dispatch: what ``DifferentiableAstar.forward`` calls when no gradient can flow
     (``torch.no_grad()`` / inputs that do not require one) and nothing is being traced -- the custom-op machinery costs more host time
     than the launch itself at 4096 maps.  Takes the reference's [B,1,H,W] tensors (or [B,H,W]) as they are; same five outputs
@@ -421,7 +459,8 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
     a copy made here would be made on the current stream, after the caller ordered the streams -- and holds ``keep``, the list that
     receives the launch's workspace, until that stream is done).  ``exact``: the reference's batch loop to the letter (``_launch_search``).
     ``lib``: another build of the C ABI (``_native.load_dev()``: stream-equality tests).  ``neighbor_mask``, ``heuristic`` ([B,1,H,W] or
-    [B,H,W] fp32 on the maps' device; made contiguous here): see ``_launch_search``.  ``route_cap``: what ``search_routes`` passes."""
+    [B,H,W] fp32 on the maps' device; made contiguous here): see ``_launch_search``.  ``route_cap``: what ``search_routes`` passes.
+    ``multi_source``: every non-zero cell of ``start_maps`` is a source (include/nastar_sources.h); False = the highest-index one only."""
     if stream_ptr is not None and not (cost_maps.is_contiguous() and start_maps.is_contiguous() and goal_maps.is_contiguous()
                                        and obstacles_maps.is_contiguous()):
         raise ValueError("search_nograd(stream_ptr=...): the maps must be contiguous (make the copies before ordering the streams)")
@@ -457,7 +496,7 @@ def search_nograd(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: 
     # the True is one_meta)
     return _launch_search(lib if lib is not None else _native.load(), cost_maps, start_maps, goal_maps, obstacles_maps, B, H, W, g_ratio, max_iters,
                           want_log, flags, cost_maps.device, order, order_out, check_order, summary_ptr, True, stream_ptr, out_4d, counter_ptr,
-                          keep, exact, neighbor_mask, heuristic, route_cap)
+                          keep, exact, neighbor_mask, heuristic, route_cap, multi_source)
 
 
 def search_routes(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, g_ratio: float,
@@ -584,7 +623,7 @@ def astar_backward_replay(grad_hist: torch.Tensor, cost: torch.Tensor, start: to
 
 
 def _replay(cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_batch, order, flags, what, *, neighbor_mask=None, heuristic=None,
-            **upstream):
+            multi_source=False, **upstream):
     """body of the two replay ops: allocate dL/dcost and the workspace, issue the call ``replay_call`` assembles.  ``upstream``: the tensors
     of ``replay_call``'s first arguments (grad_hist, or histories / opt_trajs / grad_loss), None where absent"""
     _require_device(cost, start, goal, passable)
@@ -605,7 +644,8 @@ def _replay(cost, start, goal, passable, sel_log, g_ratio, max_iters, iters, t_b
             W=W, g_ratio=g_ratio, max_iters=max_iters, iters=iters.data_ptr(), t_batch=t_batch.data_ptr() if t_batch is not None else None,
             grad_cost=grad_cost.data_ptr(), workspace=ws.data_ptr(), ws_bytes=ws_bytes, stream=_stream_ptr(dev), flags=flags,
             order=_order_ptr(order, B, dev, True) if order is not None else None, neighbor_mask=neighbor_mask,
-            heuristic=heuristic.data_ptr() if heuristic is not None else None, **{k: t.data_ptr() for k, t in upstream.items()})
+            heuristic=heuristic.data_ptr() if heuristic is not None else None, multi_source=multi_source,
+            **{k: t.data_ptr() for k, t in upstream.items()})
         rc = getattr(lib, name)(*args)
     _native.check(rc, what)
     return grad_cost
@@ -786,6 +826,49 @@ class _AstarForwardPlaced(torch.autograd.Function):
         grad_cost = torch.ops.nastar.astar_backward_replay(g_hist.contiguous(), cost, start, goal, passable, sel_log, ctx.g_ratio, ctx.max_iters,
                                                            iters, BatchCoupling.t_batch(iters), ctx.order, FLAG_LOCKSTEP if ctx.lockstep else 0)
         return (grad_cost,) + (None,) * 11
+
+
+class _AstarForwardSources(torch.autograd.Function):
+    """the MULTI-SOURCE search under autograd (include/nastar_sources.h): forward = nastar_forward_sources (+ its batch-loop finish when
+    ``exact``) with the selection log kept, backward = nastar_backward_replay_sources.  The existing custom ops keep their schemas: this
+    node alone carries the flag.  ``heuristic``: [B,H,W] or None; its gradient is the cost's (the loss sees both only through h = h0 + cost)."""
+
+    @staticmethod
+    def forward(ctx, cost, start, goal, passable, heuristic, g_ratio, max_iters, summary_ptr, exact, neighbor_mask):
+        _require_device(cost, start, goal, passable)
+        cost, start, goal, passable = (x.contiguous() for x in (cost, start, goal, passable))
+        heuristic = _heuristic_arg(heuristic, cost)
+        B, H, W = cost.shape
+        with torch.no_grad():
+            hist, paths, iters, status, sel_log = _launch_search(_native.load(), cost, start, goal, passable, B, H, W, g_ratio, max_iters, True, 0,
+                                                                 cost.device, summary_ptr=summary_ptr, exact=exact, neighbor_mask=neighbor_mask,
+                                                                 heuristic=heuristic, multi_source=True)
+        ctx.has_heuristic = heuristic is not None
+        ctx.save_for_backward(cost, start, goal, passable, iters, sel_log, *((heuristic,) if heuristic is not None else ()))
+        ctx.g_ratio, ctx.max_iters, ctx.neighbor_mask = g_ratio, max_iters, neighbor_mask
+        ctx.lockstep = bool(exact) and B > 1
+        ctx.mark_non_differentiable(paths, iters, status, sel_log)
+        ctx.set_materialize_grads(False)
+        return hist, paths, iters, status, sel_log
+
+    @staticmethod
+    def backward(ctx, g_hist, g_paths, g_iters, g_status, g_log):
+        if g_hist is None:
+            return (None,) * 10
+        cost, start, goal, passable, iters, sel_log = ctx.saved_tensors[:6]
+        heuristic = ctx.saved_tensors[6] if ctx.has_heuristic else None
+        grad = _replay(cost, start, goal, passable, sel_log, ctx.g_ratio, ctx.max_iters, iters, BatchCoupling.t_batch(iters), None,
+                       FLAG_LOCKSTEP if ctx.lockstep else 0, "nastar_backward_replay_sources", neighbor_mask=ctx.neighbor_mask, heuristic=heuristic,
+                       multi_source=True, grad_hist=g_hist.contiguous())
+        return (grad if ctx.needs_input_grad[0] else None, None, None, None, grad if (ctx.has_heuristic and ctx.needs_input_grad[4]) else None,
+                None, None, None, None, None)
+
+
+def astar_forward_sources(cost, start, goal, passable, g_ratio: float, max_iters: int, heuristic=None, summary_ptr: int = 0, exact: bool = False,
+                          neighbor_mask: Optional[int] = None):
+    """differentiable multi-source search on [B,H,W] tensors -> (histories, paths, iters, status, sel_log); see ``_AstarForwardSources``"""
+    return _AstarForwardSources.apply(cost, start, goal, passable, heuristic, float(g_ratio), int(max_iters), int(summary_ptr), bool(exact),
+                                      None if neighbor_mask is None else int(neighbor_mask))
 
 
 def astar_forward_placed(cost, start, goal, passable, g_ratio: float, max_iters: int, flags: int = 0, order_in=None, order_out=None,

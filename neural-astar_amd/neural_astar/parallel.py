@@ -423,6 +423,7 @@ class InFlightPlanner:
         """Queue one batch (the reference's [B,1,H,W] tensors); returns its ticket (0, 1, 2, ... since the last collection).
         ``inputs_ready=True``: the caller guarantees the three tensors are complete (e.g. resident data-set tensors) -- the launch stream
         then does not wait for the current stream."""
+        self._refuse_multi_source()  # (before the encoder launches anything)
         if not map_designs.is_cuda:
             raise RuntimeError("InFlightPlanner needs tensors on a HIP device (no CPU path)")
         planner = self.planner
@@ -437,11 +438,18 @@ class InFlightPlanner:
                 return self.submit_search(cost, start_maps, goal_maps, passable, False)
             return self.submit_search(map_designs, start_maps, goal_maps, map_designs, inputs_ready)
 
+    def _refuse_multi_source(self) -> None:
+        """this lane searches from ONE start cell per map; a planner that was told to search from all of them must not get another answer here"""
+        if self.planner.astar.multi_source:
+            raise NotImplementedError("InFlightPlanner searches from ONE start cell per map (the highest-index non-zero cell of start_maps), but "
+                                      "planner.astar.multi_source is True: call the planner itself, which honours it")
+
     def submit_search(self, cost: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, passable: torch.Tensor,
                       inputs_ready: bool = False) -> int:
         """Queue ONE search launch on the next stream: ``planner.astar``'s g_ratio, eval-mode budget, no gradients (the validation pair of
         ``utils.training.PlannerModule.validate`` stacks the planner's and the VanillaAstar problem into one such launch).  ``passable is
         cost`` (one binary tensor) is what the unit-cost kernel needs."""
+        self._refuse_multi_source()
         dev = cost.device
         self._setup(dev)
         astar = self.planner.astar

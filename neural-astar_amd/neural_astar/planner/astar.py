@@ -47,6 +47,16 @@ class VanillaAstar(nn.Module):
         self.g_ratio = g_ratio
         self.use_differentiable_astar = use_differentiable_astar
 
+    @property
+    def multi_source(self) -> bool:
+        """``self.astar.multi_source``: True = every non-zero cell of ``start_maps`` is a source of the search (``forward()`` and
+        ``plan_routes()``); False (default) = the highest-index one only, as before."""
+        return self.astar.multi_source
+
+    @multi_source.setter
+    def multi_source(self, value: bool) -> None:
+        self.astar.multi_source = bool(value)
+
     def perform_astar(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                       obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
                       heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:

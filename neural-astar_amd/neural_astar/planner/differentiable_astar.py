@@ -261,6 +261,12 @@ class DifferentiableAstar(nn.Module):
         self.Tmax = Tmax
         self.check_solvable = check_solvable
         self.unit_cost = unit_cost
+        # MULTI-SOURCE search (extension; the reference does it with any multi-hot ``start_maps``: its open list begins as open_maps = start_maps):
+        # False (default) = forward() / plan_routes() as they were in every respect -- of several non-zero cells in a start map the kernels
+        # take the one with the HIGHEST flat index and say nothing; True = every non-zero cell is a source, open with g = 0 when the search
+        # begins, and the path ends at whichever source reached the goal.  An attribute, not a keyword of
+        # forward(): the reference's positional calls and the trailing ``heuristic_maps`` keep their places.
+        self.multi_source = False
         # collation of sharded steps (parallel.BucketedCollator): a contiguous uint8 tensor [B, 2 * ceil(HW / 8)] the NEXT call's search launch
         # writes its bit-packed masks into (2 bits per cell; fused into the launch for 32x32 / 64x64 maps).  `last_packed` is that tensor when
         # the call did fill it (the checked no-grad call through the native host lane), None otherwise (the collator then packs the outputs itself)
@@ -327,6 +333,7 @@ class DifferentiableAstar(nn.Module):
         self.__dict__.setdefault("_calls", 0)
         self.__dict__.setdefault("placement", None)
         self.__dict__.setdefault("_nf_mask", None)
+        self.__dict__.setdefault("multi_source", False)
         self._nf_key = None  # (a new process / a copied tensor: read the filter again on first use)
 
     def raise_if_unsolvable(self, wait: bool = True) -> None:
@@ -409,7 +416,7 @@ class DifferentiableAstar(nn.Module):
             self._pending.pop(0).raise_if_unsolvable()
         return False
 
-    def exact_search(self, cost_maps, start_maps, goal_maps, passable, max_iters, want_log=False, out_4d=True, neighbor_mask=-1):
+    def exact_search(self, cost_maps, start_maps, goal_maps, passable, max_iters, want_log=False, out_4d=True, neighbor_mask=-1, multi_source=False):
         """The reference's batch loop to the letter for a batch in which a finished map is NOT at a fixed point (NASTAR_SUMMARY_COUPLED;
         DESIGN.md section 2.3): every map of the class is stepped, goal selections included, until the first step at which ALL maps of the
         batch select their goal (reference :219-225, :251) or the budget ends -- the search launch with marks + nastar_forward_batchloop_finish
@@ -417,9 +424,9 @@ class DifferentiableAstar(nn.Module):
         module's (``neighbor_mask()``)"""
         nmask = self.neighbor_mask() if neighbor_mask == -1 else neighbor_mask
         return ops.search_nograd(cost_maps, start_maps, goal_maps, passable, self.g_ratio, max_iters, want_log, out_4d=out_4d, exact=True,
-                                 neighbor_mask=nmask)
+                                 neighbor_mask=nmask, multi_source=multi_source)
 
-    def _repair_in_place(self, inputs, outputs, max_iters, want_log, neighbor_mask=None):
+    def _repair_in_place(self, inputs, outputs, max_iters, want_log, neighbor_mask=None, multi_source=False):
         """for a DEFERRED verdict: the launch it belongs to reported the note after its outputs had been handed out -- run the exact search now
         and overwrite those tensors (histories, paths, iters, status, sel_log) before the caller, who asked for the verdict first, reads them"""
         import weakref
@@ -437,7 +444,7 @@ class DifferentiableAstar(nn.Module):
                 raise RuntimeError("a batch searched with check_solvable='deferred' holds a map that is not at a fixed point of the reference's batch loop "
                                    "(negative costs), and its inputs were released before the verdict was collected: the outputs still alive are those of "
                                    "each map searched alone.  Keep the inputs until raise_if_unsolvable(), or use check_solvable=True (DESIGN.md section 2.3)")
-            new = self.exact_search(*src, max_iters, want_log, out_4d=False, neighbor_mask=neighbor_mask)
+            new = self.exact_search(*src, max_iters, want_log, out_4d=False, neighbor_mask=neighbor_mask, multi_source=multi_source)
             for old, fresh in zip(live, new):
                 if old is not None and fresh is not None and old.numel() == fresh.numel():
                     old.data.copy_(fresh.reshape(old.shape))
@@ -548,7 +555,9 @@ class DifferentiableAstar(nn.Module):
         of ``forward()`` (a launch that reports NASTAR_SUMMARY_COUPLED is repeated exactly).  ``check_solvable`` False: nothing is checked;
         any other value: the status is read before returning (one host synchronisation) and ``UnsolvableMapError`` raised as ``forward()``
         does.  ``max_route_len``: the row length L of ``routes``; None = min(H*W, max_iters + 1), which always suffices; a shorter row keeps
-        the last L cells of a longer route.  Takes no placement and no native host lane."""
+        the last L cells of a longer route.  Takes no placement and no native host lane.  With ``self.multi_source`` every non-zero cell of
+        ``start_maps`` is a source: the route begins at the source that reached the goal (``routes[b, 0]`` when it fits the row) and may pass
+        through another start cell; False takes the highest-index start cell only."""
         assert cost_maps.ndim == 4
         assert start_maps.ndim == 4
         assert goal_maps.ndim == 4
@@ -562,7 +571,8 @@ class DifferentiableAstar(nn.Module):
         max_iters = ops.max_iters_for(W, self.Tmax, self.training)
         same = obstacles_maps is cost_maps or (cost_maps.data_ptr() == obstacles_maps.data_ptr() and cost_maps.shape == obstacles_maps.shape
                                                and cost_maps.stride() == obstacles_maps.stride())
-        unit = same and self.unit_cost is True and nmask is None and h0 is None
+        multi = bool(self.multi_source)
+        unit = same and self.unit_cost is True and nmask is None and h0 is None and not multi
         exact = B > 1 and (ops.coupling_possible(self.g_ratio) or h0 is not None) and not unit  # forward()'s rule, to the letter
         dev = cost_maps.device
         cost = cost_maps.detach()
@@ -574,7 +584,8 @@ class DifferentiableAstar(nn.Module):
 
         def launch(exact_now: bool, sptr: int, cptr_now: int):
             return ops.search_routes(cost, start, goal, passable, self.g_ratio, max_iters, ops.FLAG_UNIT_COST if unit else 0, route_cap=route_cap,
-                                     summary_ptr=sptr, counter_ptr=cptr_now, out_4d=True, exact=exact_now, neighbor_mask=nmask, heuristic=h0)
+                                     summary_ptr=sptr, counter_ptr=cptr_now, out_4d=True, exact=exact_now, neighbor_mask=nmask, heuristic=h0,
+                                     **({"multi_source": True} if multi else {}))
 
         try:
             hist, paths, iters, status, _, routes, lengths, costs = launch(exact, board.ptr(row) if board is not None else 0, cptr)
@@ -606,7 +617,13 @@ class DifferentiableAstar(nn.Module):
         a callable: a learned heuristic depends on the map, not on the goal alone.  Its gradient is the gradient of ``cost_maps`` (the
         loss sees both only through h = h0 + cost) and flows when either of the two requires one.  With a free heuristic a finished map is
         often not at a fixed point of the reference's batch loop, so a batch of more than one map always runs the exact pipeline (DESIGN.md
-        section 2, item 6b).  Composes with ``neighbor_filter``; takes no native host lane, unit-cost layout or hand-scheduled stream."""
+        section 2, item 6b).  Composes with ``neighbor_filter``; takes no native host lane, unit-cost layout or hand-scheduled stream.
+
+        ``start_maps`` with SEVERAL non-zero cells in a map: with ``self.multi_source = False`` (the default) the search starts from the one
+        with the highest flat index only, silently -- NOT what the reference computes; set ``self.multi_source = True`` for the reference's
+        behaviour (every non-zero cell is open with g = 0).  True composes with ``neighbor_filter``,
+        ``heuristic_maps``, ``store_intermediate_results``, every ``check_solvable`` mode, autograd and training budgets; it takes no placement,
+        native host lane, unit-cost layout, hand-scheduled stream or torch.compile trace, and a one-hot batch gives bit-identical outputs."""
         assert cost_maps.ndim == 4
         assert start_maps.ndim == 4
         assert goal_maps.ndim == 4
@@ -617,7 +634,11 @@ class DifferentiableAstar(nn.Module):
             h0 = _checked_heuristic(heuristic_maps, cost_maps)
         self.last_packed = None
         nmask = self.neighbor_mask()  # None: the default (Moore-8) filter -- its kernels, its native host lane, its unit-cost layout
-        if (nmask is None and h0 is None and self.check_solvable is True and not store_intermediate_results and not self._pending and type(cost_maps) is torch.Tensor
+        multi = bool(self.multi_source)
+        if multi and torch.compiler.is_compiling():
+            raise NotImplementedError("DifferentiableAstar.multi_source = True takes no torch.compile trace (its search is an autograd node of its own, "
+                                      "not one of the traceable custom ops): call it outside the compiled region")
+        if (not multi and nmask is None and h0 is None and self.check_solvable is True and not store_intermediate_results and not self._pending and type(cost_maps) is torch.Tensor
                 and not (cost_maps.requires_grad and torch.is_grad_enabled())):
             out = self._forward_fast(cost_maps, start_maps, goal_maps, obstacles_maps)
             if out is not None:
@@ -639,11 +660,11 @@ class DifferentiableAstar(nn.Module):
         # the unit-cost layout pays with SEVERAL launches in flight (more maps resident per CU); one launch at a time is a serial chain whose
         # length does not depend on the layout (probe_boundary: 117 us unit vs 114 us general per placed 4096-map launch), so forward()
         # takes it only on request -- parallel.InFlightPlanner is where "auto" means "unit-cost first"
-        unit = same and not want_log and self.unit_cost is True and nmask is None and h0 is None
+        unit = same and not want_log and self.unit_cost is True and nmask is None and h0 is None and not multi
         in_lds = ops.in_lds(H, W)
         # a recurring batch starts its longest searches first (Placement), a fresh one by its loader's hint; maps whose state lives in HBM take no placement
-        if self.placement is None and not hasattr(start_maps, "placement_order"):
-            order = order_out = pl = None
+        if multi or (self.placement is None and not hasattr(start_maps, "placement_order")):
+            order = order_out = pl = None  # (a multi-source call runs in natural order; a pending ``placement`` stays for the next call)
             check_order = False
         else:
             order, order_out, check_order, pl = self.resolve_placement(B, start_maps, in_lds)
@@ -671,8 +692,12 @@ class DifferentiableAstar(nn.Module):
                 # no gradient can flow and nothing is tracing: straight to the C ABI (no torch.library dispatch)
                 return ops.search_nograd(cost_maps, start_maps, goal_maps, passable_maps, self.g_ratio, max_iters, want_log, flags, order=order,
                                          order_out=order_out, check_order=check_order, summary_ptr=sptr_now, out_4d=True, counter_ptr=cptr_now,
-                                         exact=exact_now, neighbor_mask=nmask, heuristic=h0)
+                                         exact=exact_now, neighbor_mask=nmask, heuristic=h0, **({"multi_source": True} if multi else {}))
             cost, start, goal, passable = cost_maps[:, 0], start_maps[:, 0], goal_maps[:, 0], obstacles_maps[:, 0]
+            if multi:  # the autograd node of include/nastar_sources.h (the custom ops keep their schemas)
+                o = ops.astar_forward_sources(cost, start, goal, passable, self.g_ratio, max_iters, h0[:, 0] if h0 is not None else None, sptr_now,
+                                              exact_now, nmask)
+                return o[0].unsqueeze(1), o[1].unsqueeze(1), o[2], o[3], o[4]
             mask_arg = ops.NEIGHBORS_MOORE8 if nmask is None else nmask
             heuristic = h0[:, 0] if h0 is not None else None
             placed = order is not None or order_out is not None
@@ -702,7 +727,7 @@ class DifferentiableAstar(nn.Module):
                 repair = _refuse_late_repair
             else:  # (no graph holds these tensors: a late verdict that reports the note completes them in place)
                 repair = self._repair_in_place((cost_maps, start_maps, goal_maps, passable_maps), (hist, paths, iters, status, sel_log), max_iters, want_log,
-                                               nmask)
+                                               nmask, multi)
         coupled = self.note_status(status, iters, None, row, flagged=bool(cptr) and not traced, repair=repair)
         if coupled and not exact:
             # the same-call verdict says a finished map of this batch is not at a fixed point (negative costs): the batch again, exactly

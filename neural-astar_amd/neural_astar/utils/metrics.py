@@ -45,6 +45,7 @@ def plan_with_vanilla(planner: NeuralAstar, map_designs: torch.Tensor, start_map
         passable = map_designs if not planner.learn_obstacles else torch.ones_like(start_maps)
         if float(planner.g_ratio) != float(g_ratio_vanilla) or planner.training or planner.astar.neighbor_mask() is not None:
             va = VanillaAstar(g_ratio=g_ratio_vanilla).to(map_designs.device).eval()
+            va.multi_source = planner.astar.multi_source  # (both planners answer the same question; the one-launch path below goes through planner.astar)
             return planner.perform_astar(cost, start_maps, goal_maps, passable), va(map_designs, start_maps, goal_maps)
         B = map_designs.shape[0]
         both = planner.astar(torch.cat((cost, map_designs[:, :1]), 0), torch.cat((start_maps, start_maps), 0),

@@ -128,7 +128,8 @@ def validate_in_flight(module: "PlannerModule", loader, streams: int = 4, window
     planners the pair launch does not cover."""
     from ..parallel import InFlightPlanner
     planner = module.planner
-    pair_ok = (hasattr(planner, "encode") and not planner.training and float(planner.g_ratio) == 0.5)
+    # (a multi-source planner takes validation_step per batch: the in-flight lane searches from one start cell per map and refuses it)
+    pair_ok = (hasattr(planner, "encode") and not planner.training and float(planner.g_ratio) == 0.5 and not planner.astar.multi_source)
     sums: dict = {}
     n = 0
     if not pair_ok:
@@ -186,9 +187,10 @@ def fused_l1_step(planner: VanillaAstar, map_designs: torch.Tensor, start_maps: 
     # The fused node computes mean|histories - opt_trajs| for ONE trajectory per map.  The reference's L1Loss broadcasts
     # histories [B,1,H,W] against opt_trajs [B,S,H,W] when num_starts S > 1 (training.py:58), and use_differentiable_astar=False
     # selects another planner altogether: both go through the planner's own forward + nn.L1Loss, exactly like the reference.
-    # A neighbor_filter other than the default takes the same route (the fused node replays the Moore-8 neighbourhood).
+    # A neighbor_filter other than the default takes the same route (the fused node replays the Moore-8 neighbourhood), and so does a
+    # planner with multi_source set (the fused node searches and replays from ONE start cell per map).
     if (opt_trajs.shape[1] != 1 or opt_trajs.shape[-2:] != start_maps.shape[-2:] or not getattr(planner, "use_differentiable_astar", True)
-            or planner.astar.neighbor_mask() is not None):
+            or planner.astar.neighbor_mask() is not None or planner.astar.multi_source):
         outputs = planner(map_designs, start_maps, goal_maps)
         return nn.L1Loss()(outputs.histories, opt_trajs), outputs
     if hasattr(planner, "encode"):
