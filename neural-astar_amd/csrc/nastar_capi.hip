@@ -24,6 +24,7 @@
 #include "nastar_routes.hip.h"
 #include "../../include/nastar_routes.h"
 #include "../../include/nastar_sources.h"
+#include "../../include/nastar_levels.h"
 
 namespace nastar {
 
@@ -120,7 +121,21 @@ __global__ __launch_bounds__(1024) void nastar_order_check_kernel(const int* __r
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, bool kAsm = false>
 __global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCArgs a, const float rcp_sqrtW)
 {
-    constexpr bool kMasked = false, kHeur = false, kMulti = false;
+    constexpr bool kMasked = false, kHeur = false, kMulti = false, kRanked = false;
+    constexpr uint32_t nmask = NASTAR_NEIGHBORS_MOORE8;
+    constexpr const float* h0 = nullptr;
+    constexpr const int* levels = nullptr;
+#include "nastar_forward_compact_body.inc"
+}
+
+// the first kernel with its placement computed IN the launch (include/nastar_levels.h: nastar_forward_levels): workgroup i searches
+// ranked_map(levels, B) (nastar_placement.hip.h) -- no sort launch in front, no order array.  Instantiated for the hand-scheduled streams only.
+// `levels` is a kernel argument of its own, behind rcp_sqrtW: a member appended to FwdCArgs would move rcp_sqrtW (and nmask, h0) in the
+// argument segment of EVERY kernel that takes the struct, and with it their scalar-load offsets.
+template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, bool kAsm>
+__global__ __launch_bounds__(64) void nastar_forward_compact_ranked_kernel(const FwdCArgs a, const float rcp_sqrtW, const int* __restrict__ levels)
+{
+    constexpr bool kMasked = false, kHeur = false, kMulti = false, kRanked = true;
     constexpr uint32_t nmask = NASTAR_NEIGHBORS_MOORE8;
     constexpr const float* h0 = nullptr;
 #include "nastar_forward_compact_body.inc"
@@ -130,8 +145,9 @@ __global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCAr
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 __global__ __launch_bounds__(64) void nastar_forward_compact_masked_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask)
 {
-    constexpr bool kAsm = false, kMasked = true, kHeur = false, kMulti = false;
+    constexpr bool kAsm = false, kMasked = true, kHeur = false, kMulti = false, kRanked = false;
     constexpr const float* h0 = nullptr;
+    constexpr const int* levels = nullptr;
 #include "nastar_forward_compact_body.inc"
 }
 
@@ -142,7 +158,8 @@ template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 __global__ __launch_bounds__(64) void nastar_forward_compact_heuristic_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask,
                                                                               const float* __restrict__ h0)
 {
-    constexpr bool kAsm = false, kMasked = true, kHeur = true, kMulti = false;
+    constexpr bool kAsm = false, kMasked = true, kHeur = true, kMulti = false, kRanked = false;
+    constexpr const int* levels = nullptr;
 #include "nastar_forward_compact_body.inc"
 }
 
@@ -153,7 +170,8 @@ template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, b
 __global__ __launch_bounds__(64) void nastar_forward_compact_sources_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask,
                                                                             const float* __restrict__ h0)
 {
-    constexpr bool kAsm = false, kMasked = true, kMulti = true;
+    constexpr bool kAsm = false, kMasked = true, kMulti = true, kRanked = false;
+    constexpr const int* levels = nullptr;
 #include "nastar_forward_compact_body.inc"
 }
 
@@ -608,7 +626,17 @@ struct FwdLaunch {
     LockArgs lock = {};
     Neighbourhood nb = {};
     RouteOut route = {};  // routes_out, route_cap, route_len_out, route_cost_out of include/nastar_routes.h
+    const int32_t* levels = nullptr;  // include/nastar_levels.h: the placement is ranked from these inside the launch (no order, no order_out)
 };
+
+// does a launch of this shape have a kernel that ranks levels itself (nastar_forward_compact_ranked_kernel)?  Host only.  The hand-scheduled
+// streams without a selection log: not the unit-cost layout, not lock-step mode, no compiled loop, no map outside LDS
+static bool levels_in_launch(int H, int W, int flags, bool want_log)
+{
+    if (want_log || H != W || (W != 16 && W != 32 && W != 64)) return false;
+    if (flags & ~kKnownFlags) return false;
+    return (flags & (NASTAR_FLAG_UNIT_COST | NASTAR_FLAG_LOCKSTEP | NASTAR_FLAG_NO_ASM)) == 0;
+}
 
 // large map: cells in the caller's HBM workspace, open list in LDS (nastar_search_hybrid.hip.h)
 static int forward_hybrid(const FwdLaunch& f, int* marks_out)
@@ -720,6 +748,13 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     // (longest first; the trailing counter cell is not used and stays 0)
     const bool rank_after = f.order_out && (long long)f.B > resident_capacity(kernel_lds);
     if (rank_after) c.order_out = nullptr;
+    if (f.levels) {  // (nastar_forward_levels checked the shape, the flags and the log: what is left is the alignment of the caller's pointers)
+        if (!vec4 || !fast || !use_asm || unit) return NASTAR_ERR_UNSUPPORTED;
+        const int* lv = f.levels;
+        rc = f.W == 32   ? launch(&nastar_forward_compact_ranked_kernel<true, 5, 5, 1, true, false, true>, f.B, lds, s, c, rcp, lv)
+             : f.W == 16 ? launch(&nastar_forward_compact_ranked_kernel<true, 4, 4, 1, true, false, true>, f.B, lds, s, c, rcp, lv)
+                         : launch(&nastar_forward_compact_ranked_kernel<true, 6, 6, 4, true, false, true>, f.B, lds, s, c, rcp, lv);
+    } else
     if (unit) rc = forward_unit(c, marks_out, kernel_lds, rcp, s);
     else if (f.nb.multi) rc = with_bools([&](auto heur, auto lg) {  // (always masked: Moore-8 is a mask like any other here)
         return launch(compact_kernel<(heur ? 4 : 3), lg>(c.d, vec4, fast, false), f.B, lds, s, c, rcp, f.nb.mask, f.nb.h0);
@@ -987,6 +1022,37 @@ int nastar_forward_sources_batchloop_finish(const float* cost, const float* star
     const int rc = sources_launch(f, neighbor_mask, h0, routes_out, route_cap, route_len_out, route_cost_out);
     if (rc) return rc;
     return batchloop_finish(f);  // (the PROBE and FINAL launches seed every start too: FwdLaunch::nb travels with them)
+}
+
+// ---- include/nastar_levels.h: the search launch that places its maps by their levels itself ------------------------------------------------
+int nastar_levels_abi(void) { return NASTAR_LEVELS_ABI; }
+
+int nastar_levels_in_launch(int H, int W, int flags, int want_log) { return levels_in_launch(H, W, flags, want_log != 0) ? 1 : 0; }
+
+int nastar_forward_levels(const float* cost, const float* start, const float* goal, const float* passable, int B, int H, int W, double g_ratio,
+                          int max_iters, float* histories_out, int64_t* paths_out, int32_t* sel_log_out, int32_t* iters_out, int32_t* status_out,
+                          uint8_t* packed_out, void* workspace, size_t workspace_bytes, int flags, const int32_t* levels,
+                          int32_t* status_summary, int32_t* completion_counter, void* stream)
+{
+    if (!levels) return NASTAR_ERR_NULL;
+    if (!levels_in_launch(H, W, flags, sel_log_out != nullptr)) return NASTAR_ERR_UNSUPPORTED;
+    FwdLaunch f{cost, start, goal, passable, B, H, W, g_ratio, max_iters, histories_out, paths_out, sel_log_out, iters_out, status_out,
+                workspace, workspace_bytes, flags, stream};
+    f.packed_out = packed_out;
+    f.summary = status_summary;
+    f.done_counter = completion_counter;
+    f.levels = levels;
+    return forward(f);
+}
+
+int nastar_placement_slots(const int32_t* levels, int B, int32_t* order_out, void* stream)
+{
+    if (!levels || !order_out) return NASTAR_ERR_NULL;
+    if (B <= 0) return NASTAR_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL(nastar_placement_slots_kernel, dim3((unsigned)B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), levels, B, order_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+    return NASTAR_OK;
 }
 
 int nastar_completion_supported(int H, int W)

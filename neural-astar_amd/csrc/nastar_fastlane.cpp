@@ -6,8 +6,10 @@
 // data_ptr(), one 23-argument ctypes call, the status-board bookkeeping).  This file is that host work in C++, behind the SAME C ABI:
 //
 //   search(fn, cost, start, goal, passable | None, g_ratio, max_iters, want_log, flags, order | None, order_out | None, ws_bytes,
-//          summary_host, counter_dev, stream, spin_us, levels | None, sort_fn, packed | None)
-//     0. (a batch that carries its loader's levels instead of an order: launches nastar_placement_from_levels in front of the search)
+//          summary_host, counter_dev, stream, spin_us, levels | None, sort_fn, packed | None, levels_fn)
+//     0. (a batch that carries its loader's levels instead of an order: `levels_fn` != 0 -- the address of nastar_forward_levels,
+//        include/nastar_levels.h, given when nastar_levels_in_launch says so -- replaces `fn` and the search launch ranks the levels itself;
+//        otherwise nastar_placement_from_levels is launched in front of the search)
 //     1. allocates the AstarOutput tensors in their final layout ([B,1,H,W] fp32 / int64, iters + status as one [2,B] int32 block) through ATen
 //        (the caching allocator; no torch types cross the C ABI below),
 //        (`packed`: the caller's uint8 slot for the bit-packed masks, 2 bits per cell, which the search launch then emits itself),
@@ -31,13 +33,18 @@ namespace {
 using sort_t = int (*)(const int32_t*, int, int32_t*, void*);  // nastar_placement_from_levels
 using fwd_ex_t = int (*)(const float*, const float*, const float*, const float*, int, int, int, double, int, float*, int64_t*, int32_t*, int32_t*,
                          int32_t*, uint8_t*, void*, size_t, int, const int32_t*, int32_t*, int32_t*, int32_t*, void*);
+using fwd_levels_t = int (*)(const float*, const float*, const float*, const float*, int, int, int, double, int, float*, int64_t*, int32_t*, int32_t*,
+                             int32_t*, uint8_t*, void*, size_t, int, const int32_t*, int32_t*, int32_t*, void*);  // nastar_forward_levels
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline bool plain_f32(const at::Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous(); }
 
 py::tuple search(uintptr_t fn, const at::Tensor& cost, const at::Tensor& start, const at::Tensor& goal, const c10::optional<at::Tensor>& passable,
                  double g_ratio, int64_t max_iters, bool want_log, int64_t flags, const c10::optional<at::Tensor>& order,
                  const c10::optional<at::Tensor>& order_out, int64_t ws_bytes, uintptr_t summary_host, uintptr_t counter_dev, uintptr_t stream,
-                 int64_t spin_us, const c10::optional<at::Tensor>& levels, uintptr_t sort_fn, const c10::optional<at::Tensor>& packed)
+                 int64_t spin_us, const c10::optional<at::Tensor>& levels, uintptr_t sort_fn, const c10::optional<at::Tensor>& packed,
+                 uintptr_t levels_fn)
 {
     const at::Tensor& pas = passable.has_value() ? *passable : cost;
     // anything the fast lane does not take goes back to the Python path, which raises the proper errors: rc = -1
@@ -60,11 +67,20 @@ py::tuple search(uintptr_t fn, const at::Tensor& cost, const at::Tensor& start, 
         op = order->data_ptr<int32_t>();
     }
     at::Tensor sorted;
-    if (!order.has_value() && levels.has_value() && sort_fn != 0) {
-        // the batch carries its loader's LEVELS (the start cells' optimal distances), not an order yet: the counting sort that turns them into a
-        // placement is launched here, in front of the search, on the same stream (a permutation by construction: nothing to check)
+    const int32_t* in_launch = nullptr;  // the levels, when the search launch ranks them itself
+    if (!order.has_value() && levels.has_value() && (sort_fn != 0 || levels_fn != 0)) {
         if (levels->scalar_type() != at::kInt || levels->numel() != B || !levels->is_contiguous() || levels->device() != cost.device())
             return py::make_tuple(py::none(), py::none(), py::none(), py::none(), py::none(), -1, -1);
+        // the batch carries its loader's LEVELS (the start cells' optimal distances), not an order.  A launch that has a ranking kernel
+        // (levels_fn, what nastar_levels_in_launch told the caller) places its maps itself: no sort, no order array.  That kernel wants
+        // 16-byte aligned maps and has no selection log or order_out; anything else takes the sort below
+        if (levels_fn != 0 && !want_log && !order_out.has_value() && aligned16(cost.data_ptr()) && aligned16(start.data_ptr()) &&
+            aligned16(goal.data_ptr()) && aligned16(pas.data_ptr()))
+            in_launch = levels->data_ptr<int32_t>();
+    }
+    if (in_launch == nullptr && !order.has_value() && levels.has_value() && sort_fn != 0) {
+        // the counting sort that turns the levels into a placement is launched here, in front of the search, on the same stream (a
+        // permutation by construction: nothing to check)
         sorted = at::empty({B}, fopt.dtype(at::kInt));
         const int src = reinterpret_cast<sort_t>(sort_fn)(levels->data_ptr<int32_t>(), (int)B, sorted.data_ptr<int32_t>(), reinterpret_cast<void*>(stream));
         if (src != 0) return py::make_tuple(py::none(), py::none(), py::none(), py::none(), py::none(), src, -1);
@@ -85,7 +101,13 @@ py::tuple search(uintptr_t fn, const at::Tensor& cost, const at::Tensor& start, 
     int32_t* iters = meta.data_ptr<int32_t>();
     int32_t* status = iters + B;
     volatile int32_t* summ = reinterpret_cast<volatile int32_t*>(summary_host);
-    const int rc = reinterpret_cast<fwd_ex_t>(fn)(cost.data_ptr<float>(), start.data_ptr<float>(), goal.data_ptr<float>(), pas.data_ptr<float>(), (int)B, (int)H,
+    const int rc = in_launch != nullptr
+        ? reinterpret_cast<fwd_levels_t>(levels_fn)(cost.data_ptr<float>(), start.data_ptr<float>(), goal.data_ptr<float>(), pas.data_ptr<float>(), (int)B, (int)H,
+                                                    (int)W, g_ratio, (int)max_iters, hist.data_ptr<float>(), paths.data_ptr<int64_t>(), nullptr, iters, status, pk,
+                                                    ws_bytes > 0 ? ws.data_ptr() : nullptr, (size_t)ws_bytes, (int)flags, in_launch,
+                                                    reinterpret_cast<int32_t*>(summary_host), summary_host ? reinterpret_cast<int32_t*>(counter_dev) : nullptr,
+                                                    reinterpret_cast<void*>(stream))
+        : reinterpret_cast<fwd_ex_t>(fn)(cost.data_ptr<float>(), start.data_ptr<float>(), goal.data_ptr<float>(), pas.data_ptr<float>(), (int)B, (int)H,
                                                   (int)W, g_ratio, (int)max_iters, hist.data_ptr<float>(), paths.data_ptr<int64_t>(),
                                                   want_log ? log.data_ptr<int32_t>() : nullptr, iters, status, pk,
                                                   ws_bytes > 0 ? ws.data_ptr() : nullptr, (size_t)ws_bytes, (int)flags, op, oo,
@@ -127,5 +149,5 @@ PYBIND11_MODULE(_nastar_fastlane, m)
     m.def("search", &search, py::arg("fn"), py::arg("cost"), py::arg("start"), py::arg("goal"), py::arg("passable"), py::arg("g_ratio"),
           py::arg("max_iters"), py::arg("want_log"), py::arg("flags"), py::arg("order"), py::arg("order_out"), py::arg("ws_bytes"),
           py::arg("summary_host"), py::arg("counter_dev"), py::arg("stream"), py::arg("spin_us"), py::arg("levels") = py::none(), py::arg("sort_fn") = 0,
-          py::arg("packed") = py::none());
+          py::arg("packed") = py::none(), py::arg("levels_fn") = 0);
 }

@@ -5,8 +5,10 @@
 // nastar_forward_compact_heuristic_kernel shares it too: `constexpr bool kHeur` / `h0` (the caller's heuristic maps, [B, H, W]); every
 // kHeur branch below is discarded in the other two kernels.  nastar_forward_compact_sources_kernel (include/nastar_sources.h) is the fourth:
 // `constexpr bool kMulti` -- every non-zero cell of the start map is a source, and a parent walk ends at an unset parent only.
+// nastar_forward_compact_ranked_kernel (include/nastar_levels.h) is the fifth: `constexpr bool kRanked` / `levels` -- the workgroup finds its
+// map from the batch's levels (ranked_map, nastar_placement.hip.h) instead of an order array; everything behind that line is the first kernel's.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int b = placed_map(a.order, a.order_bad, a.B);
+    const int b = kRanked ? ranked_map(levels, a.B) : placed_map(a.order, a.order_bad, a.B);
     if ((unsigned)b >= (unsigned)a.B) return;  // not a permutation (and not checked: NASTAR_FLAG_CHECK_ORDER): never read or write outside the batch
     const bool lockstep = !kAsm && (a.flags & NASTAR_FLAG_LOCKSTEP);  // (forward_impl picks a compiled instantiation for it)
     if (lockstep && a.marks != nullptr && a.marks[b] == 0) return;    // not in the batch-coupled class: the early-exit launch's outputs stand

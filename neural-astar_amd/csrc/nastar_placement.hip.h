@@ -169,4 +169,40 @@ __global__ __launch_bounds__(PLC_RANK_THREADS) void nastar_rank_levels_kernel(co
     }
 }
 
+// ---- placement by levels INSIDE the search launch (include/nastar_levels.h): no sort launch, no order array ---------------------------------
+// An exact rank needs all B levels -- a grid-wide dependency.  A workgroup can rank 64 of them alone, and that is enough (see the header of
+// this file: early and spread, not the exact rank).  nblk = ceil(B / 64) strided blocks: block j holds the maps j, j + nblk, j + 2 nblk, ...
+// below B, at most 64, lane k holds map j + k nblk.  Workgroup i takes block j = i % nblk and rank r = i / nblk: the member of block j with
+// exactly r members ahead of it, larger clamp(level, 0, PLC_MAX_LEVEL) first, the lower lane first among equals.
+//   permutation    map j + r nblk exists exactly when i = r nblk + j < B: block j has more than r members exactly when workgroup i exists
+//   in bounds      the result is a member, hence < B, whatever `levels` holds
+//   longest first  workgroups [0, nblk) are the longest map of every block, [nblk, 2 nblk) the second longest, ...; strided blocks keep
+//                  that true for a batch that arrives sorted by level
+// One gather of 64 levels, a key per lane ((level + 1) << 6 | 63 - lane; 0 = no map: members' keys are distinct and positive), and a
+// 19-step descent over the key bits for the (r + 1)-th largest key: one compare + one ballot per step, everything else scalar.  Wave-uniform.
+__device__ __forceinline__ int ranked_map(const int* __restrict__ levels, int B)
+{
+    const unsigned i = blockIdx.x, nblk = ((unsigned)B + 63u) >> 6;
+    const unsigned r = i / nblk, j = i - r * nblk;
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned m = j + lane * nblk;  // <= B + 62: no wrap
+    unsigned key = 0u;
+    if (m < (unsigned)B) key = ((unsigned)(min(max(levels[m], 0), PLC_MAX_LEVEL) + 1) << 6) | (63u - lane);
+    unsigned T = 0u;  // the largest T with more than r keys >= T: the (r + 1)-th largest key
+#pragma unroll
+    for (int bit = 18; bit >= 0; --bit) {  // keys < 2^19
+        const unsigned cand = T | (1u << bit);
+        if ((unsigned)__popcll(__ballot(key >= cand)) > r) T = cand;
+    }
+    T = (unsigned)__builtin_amdgcn_readfirstlane((int)T);
+    return (int)(j + (63u - (T & 63u)) * nblk);
+}
+
+// order_out[i] = the map workgroup i of a ranked search launch takes (nastar_placement_slots): the same function, observed
+__global__ __launch_bounds__(64) void nastar_placement_slots_kernel(const int* __restrict__ levels, int B, int* __restrict__ order_out)
+{
+    const int b = ranked_map(levels, B);
+    if (threadIdx.x == 0) order_out[blockIdx.x] = b;
+}
+
 }  // namespace nastar

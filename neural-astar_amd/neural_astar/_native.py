@@ -154,6 +154,16 @@ SOURCE_SIGNATURES = {
     "nastar_backward_replay_sources": "i pppp" + _REPLAY + "ip" + "upp",
 }
 
+# the signatures of include/nastar_levels.h (the fourth header: the search launch that places its maps by their levels itself), same letter
+# code; a table of its own (tests/test_levels_in_launch.py compares it with ITS header)
+LEVEL_SIGNATURES = {
+    "nastar_levels_abi": "i ",
+    # ... nastar_forward_ex's arguments with `levels` in place of order, order_out
+    "nastar_forward_levels": "i " + _FORWARD + "p" + _WORKSPACE + "ippp" + "p",
+    "nastar_levels_in_launch": "i iiii",
+    "nastar_placement_slots": "i pipp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -227,6 +237,24 @@ def load_fastlane():
     return _fastlane
 
 
+_levels_entry: dict = {}
+
+
+def forward_levels_address(H: int, W: int, flags: int) -> int:
+    """the address of nastar_forward_levels (include/nastar_levels.h) when a search of H x W maps under ``flags``, without a selection log,
+    ranks its levels inside the launch (nastar_levels_in_launch), else 0 -- also 0 when the library lacks the symbol.  Cached per launch
+    shape: what the native host lane takes as its trailing ``levels_fn`` argument."""
+    key = (H, W, flags)
+    v = _levels_entry.get(key)
+    if v is None:
+        lib = load()
+        v = 0
+        if hasattr(lib, "nastar_forward_levels") and lib.nastar_levels_in_launch(H, W, flags, 0) == 1:
+            v = int(ctypes.cast(lib.nastar_forward_levels, ctypes.c_void_p).value)
+        _levels_entry[key] = v
+    return v
+
+
 def load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
@@ -239,6 +267,8 @@ def load() -> ctypes.CDLL:
     _bind(lib, SIGNATURES)
     _bind(lib, ROUTE_SIGNATURES, ROUTE_SIGNATURES)
     _bind(lib, SOURCE_SIGNATURES, SOURCE_SIGNATURES)
+    if hasattr(lib, "nastar_levels_abi"):  # (another build of the C ABI, NASTAR_LIB, may be older than the fourth header)
+        _bind(lib, LEVEL_SIGNATURES, LEVEL_SIGNATURES)
     _lib = lib
     return lib
 

@@ -556,8 +556,13 @@ def attach_order(start_maps: torch.Tensor, levels: torch.Tensor) -> torch.Tensor
 
 def attach_levels(start_maps: torch.Tensor, levels: torch.Tensor) -> torch.Tensor:
     """tag ``start_maps`` with the LEVELS its loader has (``levels[b]`` = |opt_dists[start]| of map b, int32 [B] on the device; see
-    ``order_from_levels``) and leave the sort to the ``forward()`` call that searches the batch: its counting-sort launch then goes out right in
-    front of the search launch, from the same native call (csrc/nastar_fastlane.cpp).  Returns ``start_maps``."""
+    ``order_from_levels``) and leave the placement to the ``forward()`` call that searches the batch.  For 16x16, 32x32 and 64x64 maps on the
+    hand-scheduled streams the search launch places the maps itself (include/nastar_levels.h): with ``nblk = ceil(B / 64)``, workgroup ``i``
+    looks at the at most 64 maps ``j, j + nblk, j + 2 nblk, ...`` (``j = i % nblk``) and searches the one with exactly ``i // nblk`` of them
+    ahead of it, larger level first, lower index first among equals -- a permutation whatever the levels hold, the longest map of every
+    block in the first ``nblk`` workgroups, and no sort launch.  Every other launch (unit-cost layout, compiled loops) sorts: its counting-sort
+    launch goes out right in front of the search launch, from the same native call (csrc/nastar_fastlane.cpp).  The Python lane sorts on
+    first use and keeps the order on the hint.  Returns ``start_maps``."""
     lv = levels.reshape(-1)
     if lv.dtype != torch.int32:
         lv = lv.abs().to(torch.int32)

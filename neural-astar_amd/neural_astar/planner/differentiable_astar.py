@@ -493,7 +493,9 @@ class DifferentiableAstar(nn.Module):
         hint = getattr(start_maps, "placement_order", None)
         if (self.placement is None and type(hint) is ops.OrderHint and hint.order is None and hint.levels is not None and hint.levels.numel() == B
                 and hint.levels.device == dev):
-            levels = hint.levels  # the loader's levels: the native call sorts them into a placement right in front of the search launch
+            # the loader's levels: the search launch ranks them itself where it has a kernel for that (16x16, 32x32, 64x64 on the hand-scheduled
+            # streams: include/nastar_levels.h), else the native call sorts them into a placement right in front of the search launch
+            levels = hint.levels
         elif self.placement is not None or hint is not None:
             order, order_out, check_order, pl = self.resolve_placement(B, start_maps, True)
             if order is not None and check_order:
@@ -506,7 +508,8 @@ class DifferentiableAstar(nn.Module):
             hist, paths, iters, status, _, rc, verdict = fl[0].search(
                 fl[1], cost_maps, start_maps, goal_maps, None if same else obstacles_maps, float(self.g_ratio),
                 ops.max_iters_for(W, self.Tmax, self.training), False, flags, order, order_out, ws_bytes, board.ptr(row), board.counter_ptr(row),
-                torch._C._cuda_getCurrentRawStream(dev.index), 2000, levels, fl[2], sink)
+                torch._C._cuda_getCurrentRawStream(dev.index), 2000, levels, fl[2], sink,
+                0 if levels is None else _native.forward_levels_address(H, W, flags))
         except BaseException:
             board.release(row)
             raise
