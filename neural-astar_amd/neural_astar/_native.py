@@ -25,6 +25,8 @@ NASTAR_ERR_NULL = 5
 NASTAR_ERR_WORKSPACE = 6
 NASTAR_ERR_NOT_UNIT_COST = 7  # per-map status only
 NASTAR_ERR_BAD_HEURISTIC = 8  # per-map status only
+NASTAR_ERR_BAD_COST = 9  # per-map status of include/nastar_fields.h only
+NASTAR_ERR_NO_CONVERGENCE = 10  # per-map status of include/nastar_fields.h only
 
 _ERR_NAMES = {
     NASTAR_ERR_BAD_SHAPE: "bad shape (B, H, W and max_iters must be positive)",
@@ -164,6 +166,16 @@ LEVEL_SIGNATURES = {
     "nastar_placement_slots": "i pipp",
 }
 
+# the signatures of include/nastar_fields.h (the fifth header: the cost-to-go field of whole maps and its optimal policy), same letter code;
+# a table of its own (tests/test_fields.py compares it with ITS header)
+FIELD_SIGNATURES = {
+    "nastar_fields_abi": "i ",
+    "nastar_fields_max_cells": "i ",
+    # cost, goal, passable, B, H, W, neighbor_mask, dist_out, policy_out, status_out, (sweeps_out,) stream
+    "nastar_cost_to_go": "i pppiiiupppp",
+    "nastar_cost_to_go_sweeps": "i pppiiiuppppp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -269,6 +281,8 @@ def load() -> ctypes.CDLL:
     _bind(lib, SOURCE_SIGNATURES, SOURCE_SIGNATURES)
     if hasattr(lib, "nastar_levels_abi"):  # (another build of the C ABI, NASTAR_LIB, may be older than the fourth header)
         _bind(lib, LEVEL_SIGNATURES, LEVEL_SIGNATURES)
+    if hasattr(lib, "nastar_fields_abi"):  # (likewise the fifth)
+        _bind(lib, FIELD_SIGNATURES, FIELD_SIGNATURES)
     _lib = lib
     return lib
 

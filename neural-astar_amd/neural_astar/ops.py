@@ -7,14 +7,14 @@ the hand-written HIP kernel.  There is no CPU path: CPU tensors raise.
 from __future__ import annotations
 
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _native
 
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
-           "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources"]
+           "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -905,3 +905,83 @@ def heuristic(goal_maps: torch.Tensor) -> torch.Tensor:
         rc = lib.nastar_heuristic(g.data_ptr(), B, H, W, out.data_ptr(), _stream_ptr(g.device))
     _native.check(rc, "nastar_heuristic")
     return out.reshape(shape)
+
+
+# ---- include/nastar_fields.h: the cost-to-go field of whole maps and its optimal policy ----------------------
+FIELD_BAD_COST = 9  # NASTAR_ERR_BAD_COST (per-map status of nastar_cost_to_go): a NaN or a negative cost on a passable cell
+FIELD_NO_CONVERGENCE = 10  # NASTAR_ERR_NO_CONVERGENCE: the sweep bound was hit (impossible for accepted inputs)
+FIELDS_MAX_CELLS = 16384  # nastar_fields_max_cells(): field + cost of one map in the LDS of one workgroup
+
+
+class FieldOutput(NamedTuple):
+    """What ``cost_to_go()`` returns.  ``dists`` [B,1,H,W] fp32: the exact cost to the nearest goal cell from every cell under the search's
+    cost semantics (a move costs the cell being LEFT), 0 on goals, +inf on obstacles and where no goal can be reached; ``policies``
+    [B,8,H,W] one-hot fp32 (action k = ``utils.synthetic.ACTION_MOVES[k]``: the first move to a neighbour with the smallest distance, if
+    that is strictly closer; all-zero on goals, obstacles, unreachable cells and zero-cost plateaus) or None; ``status`` [B] int32: 0, or
+    ``STATUS_UNSOLVABLE`` for a map without a goal cell (its field is all +inf)."""
+
+    dists: torch.Tensor
+    policies: Optional[torch.Tensor]
+    status: torch.Tensor
+
+
+def _checked_neighbor_mask(neighbor_mask) -> int:
+    mask = NEIGHBORS_MOORE8 if neighbor_mask is None else neighbor_mask
+    if isinstance(mask, bool) or not isinstance(mask, int) or mask & ~0x1FF or mask & 0x10:
+        raise ValueError(f"neighbor_mask must be a 9-bit int with a zero centre bit (include/nastar.h NASTAR_NEIGHBORS_*), got {neighbor_mask!r}")
+    return mask
+
+
+def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
+               policies: bool = True, sweeps_out: Optional[torch.Tensor] = None) -> FieldOutput:
+    """The cost-to-go field of every map of the batch, and the optimal policy that follows it, in one launch (include/nastar_fields.h).
+
+    ``cost_maps``, ``goal_maps``, ``obstacles_maps``: [B,1,H,W] (or [B,H,W]) float32 on one HIP device; EVERY non-zero cell of a goal map
+    is a goal (nearest of K); ``neighbor_mask``: the move set as the search takes it (None = Moore-8).  An evaluation call: no autograd
+    graph, detached outputs, on the current stream of the inputs' device.  The per-map status is read before returning (one host
+    synchronisation; not inside a hipGraph capture): a NaN or a negative cost on a passable cell raises ValueError naming the rows; a map
+    without a goal is reported in ``status``, not raised.  Maps of more than ``FIELDS_MAX_CELLS`` cells raise NotImplementedError.
+    ``sweeps_out``: a [B] int32 tensor that receives the sweeps every map's relaxation took (probes)."""
+    maps = (cost_maps, goal_maps, obstacles_maps)
+    for name, t in zip(("cost_maps", "goal_maps", "obstacles_maps"), maps):
+        if not torch.is_tensor(t) or t.ndim not in (3, 4) or (t.ndim == 4 and t.shape[1] < 1):
+            raise ValueError(f"{name} must be a [B,1,H,W] or [B,H,W] tensor, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"expected float32 maps, got {t.dtype} for {name}")
+    shapes = [(t.shape[0],) + tuple(t.shape[-2:]) for t in maps]
+    if shapes[1] != shapes[0] or shapes[2] != shapes[0] or min(shapes[0]) < 1:
+        raise ValueError(f"cost_maps, goal_maps and obstacles_maps must share one non-empty [B,H,W]: got {shapes[0]}, {shapes[1]}, {shapes[2]}")
+    mask = _checked_neighbor_mask(neighbor_mask)
+    B, H, W = shapes[0]
+    if H * W > FIELDS_MAX_CELLS:
+        raise NotImplementedError(f"cost_to_go: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_MAX_CELLS} cells (one workgroup "
+                                  "relaxes one map in LDS; larger maps need a tiled kernel)")
+    _require_device(*maps)
+    dev = cost_maps.device
+    if goal_maps.device != dev or obstacles_maps.device != dev:
+        raise ValueError(f"cost_maps lives on {dev}, goal_maps on {goal_maps.device}, obstacles_maps on {obstacles_maps.device}: they must share a device")
+    lib = _native.load()
+    if not hasattr(lib, "nastar_cost_to_go"):
+        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields.h: rebuild it with `make -C {_native.CSRC_DIR}`")
+    if sweeps_out is not None and (sweeps_out.dtype != torch.int32 or sweeps_out.numel() != B or sweeps_out.device != dev or not sweeps_out.is_contiguous()):
+        raise ValueError(f"sweeps_out must be a contiguous int32 tensor of {B} elements on {dev}")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(t.detach()) for t in maps)
+        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_cost_to_go_sweeps(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, dists.data_ptr(),
+                                              pol.data_ptr() if pol is not None else None, status.data_ptr(),
+                                              sweeps_out.data_ptr() if sweeps_out is not None else None, _stream_ptr(dev))
+        _native.check(rc, "nastar_cost_to_go")
+        if not torch.cuda.is_current_stream_capturing():
+            st = status.cpu()
+            bad = torch.nonzero(st == FIELD_BAD_COST).flatten().tolist()
+            if bad:
+                raise ValueError(f"cost_to_go: a NaN or a negative cost on a passable cell of map(s) {bad[:16]}{' ...' if len(bad) > 16 else ''} "
+                                 f"({len(bad)} of {B}); the other maps were computed")
+            stuck = torch.nonzero(st == FIELD_NO_CONVERGENCE).flatten().tolist()
+            if stuck:
+                raise RuntimeError(f"cost_to_go: map(s) {stuck[:16]} did not converge within H*W sweeps (NASTAR_ERR_NO_CONVERGENCE)")
+    return FieldOutput(dists, pol, status)

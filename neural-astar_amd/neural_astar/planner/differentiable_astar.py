@@ -40,6 +40,9 @@ class RoutedAstarOutput(NamedTuple):
     route_costs: torch.Tensor
 
 
+FieldOutput = ops.FieldOutput  # what ``cost_to_go()`` returns (dists, policies, status): DESIGN.md section 2, item 6e
+
+
 def route_coords(routes: torch.Tensor, W: int) -> torch.Tensor:
     """``routes`` [B, L] (flat indices r*W + c, -1 = no cell) -> [B, L, 2] (row, col), -1 where the route is -1"""
     none = routes < 0
@@ -610,6 +613,13 @@ class DifferentiableAstar(nn.Module):
                     hist, paths, iters, status, _, routes, lengths, costs = launch(True, 0, 0)
                     self.last_status, self.last_iters = status, iters
         return RoutedAstarOutput(hist, paths, routes, lengths, costs)
+
+    def cost_to_go(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, policies: bool = True) -> FieldOutput:
+        """The exact cost to the goal from EVERY cell of every map, and the optimal policy that follows it (``ops.cost_to_go``, the kernel of
+        include/nastar_fields.h), under this module's own move set: ``neighbor_filter`` through the cached mask.  A move costs the cell being
+        left, as the search's g does; ``g_ratio``, ``Tmax`` and the heuristic play no part.  An evaluation call: no autograd graph, detached
+        tensors, one host synchronisation for the status."""
+        return ops.cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies)
 
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,

@@ -79,6 +79,16 @@ def start_thresholds(opt_dists: np.ndarray, pcts: np.ndarray) -> np.ndarray:
     return th
 
 
+def fields_to_dataset(dists: torch.Tensor, policies: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``ops.cost_to_go`` outputs -> the file convention (``synthetic.write_maze_npz``): ``dists`` [N,1,H,W] (+inf = obstacle / unreachable)
+    becomes ``opt_dists`` [N,1,H,W] of NEGATIVE distances with the map's -(largest finite distance + 1) on the +inf cells; ``policies``
+    [N,8,H,W] becomes ``opt_policies`` [N,8,1,H,W].  On the tensors' device, no host copy."""
+    N = dists.shape[0]
+    finite = torch.isfinite(dists)
+    worst = torch.where(finite, dists, torch.zeros_like(dists)).reshape(N, -1).max(1).values.reshape(N, 1, 1, 1)
+    return torch.where(finite, -dists, -(worst + 1.0)), policies.unsqueeze(2)
+
+
 class MazeDataset(data.Dataset):
     """Shortest-path problems from a planning-datasets ``.npz`` (same constructor, attributes and item layout as the reference:
     ``map_design [1,W,W]``, ``start_map [num_starts,W,W]``, ``goal_map [1,W,W]``, ``opt_traj [num_starts,W,W]`` float32)."""
@@ -168,17 +178,53 @@ class DeviceMazeBatches:
             raise RuntimeError("DeviceMazeBatches needs a HIP device (the trajectory roll-out is a HIP kernel)")
         if ds.num_orient != 1:
             raise NotImplementedError("oriented policies (num_orient > 1)")
-        self.device, self.num_starts, self.batch_size, self.shuffle, self.generator = dev, ds.num_starts, batch_size, shuffle, generator
-        N, W = len(ds), ds.map_designs.shape[-1]
-        self.N, self.H, self.W, self.A = N, ds.map_designs.shape[-2], W, ds.num_actions
-        self.map_designs = torch.from_numpy(ds.map_designs).to(dev).unsqueeze(1).contiguous()
-        self.goal_maps = torch.from_numpy(ds.goal_maps).to(dev).contiguous()
-        self.goal_idx = self.goal_maps.reshape(N, -1).argmax(1).to(torch.int32)
-        self.opt_policies = torch.from_numpy(ds.opt_policies[:, :, 0]).to(dev).contiguous()          # [N,A,H,W]
-        self.opt_dists = torch.from_numpy(ds.opt_dists).to(dev).reshape(N, -1).contiguous()           # [N,HW]
-        self.thresholds = torch.from_numpy(ds.thresholds).to(dev)   # [N,4] float64: compared in double, exactly as numpy does
+        N = len(ds)
+        self._adopt(dev, ds.num_starts, batch_size, shuffle, generator,
+                    map_designs=torch.from_numpy(ds.map_designs).to(dev).unsqueeze(1).contiguous(),
+                    goal_maps=torch.from_numpy(ds.goal_maps).to(dev).contiguous(),
+                    opt_policies=torch.from_numpy(ds.opt_policies[:, :, 0]).to(dev).contiguous(),          # [N,A,H,W]
+                    opt_dists=torch.from_numpy(ds.opt_dists).to(dev).reshape(N, -1).contiguous(),           # [N,HW]
+                    thresholds=torch.from_numpy(ds.thresholds).to(dev))   # [N,4] float64: compared in double, exactly as numpy does
+
+    def _adopt(self, dev, num_starts, batch_size, shuffle, generator, *, map_designs, goal_maps, opt_policies, opt_dists, thresholds) -> None:
+        """the split's state from device tensors: what ``__init__`` reads from a file and ``from_maps`` computes"""
+        self.device, self.num_starts, self.batch_size, self.shuffle, self.generator = dev, num_starts, batch_size, shuffle, generator
+        N, _, self.H, self.W = map_designs.shape
+        self.N, self.A = N, opt_policies.shape[1]
+        self.map_designs, self.goal_maps = map_designs, goal_maps
+        self.goal_idx = goal_maps.reshape(N, -1).argmax(1).to(torch.int32)
+        self.opt_policies, self.opt_dists, self.thresholds = opt_policies, opt_dists, thresholds
         self.last_status: Optional[torch.Tensor] = None
         self.emit_placement = True  # tag every batch's start_maps with a longest-first placement (see sample())
+
+    @classmethod
+    def from_maps(cls, map_designs, goal_maps, device, batch_size: int = 100, shuffle: bool = False,
+                  generator: Optional[torch.Generator] = None, num_starts: int = 1, pcts=(0.55, 0.70, 0.85)) -> "DeviceMazeBatches":
+        """The split built from RAW maps: ``map_designs`` [N,H,W] (or [N,1,H,W]; 1 = passable) and one-hot ``goal_maps`` [N,1,H,W], numpy or
+        tensors.  ``opt_dists`` and ``opt_policies`` come from the cost-to-go kernel (``ops.cost_to_go`` with cost = passable = the map,
+        Moore-8: what the planning-datasets files hold), the percentile thresholds from ``start_thresholds`` on ONE copy of the distances
+        to the host.  The result equals ``MazeDataset(npz).to_device()`` on the same maps, attribute for attribute.  A map without a goal
+        raises ValueError."""
+        from .. import ops
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("DeviceMazeBatches needs a HIP device (the cost-to-go field and the trajectory roll-out are HIP kernels)")
+        maps, goals = (torch.as_tensor(a, dtype=torch.float32).to(dev) for a in (map_designs, goal_maps))
+        if maps.ndim == 3:
+            maps = maps.unsqueeze(1)
+        N, _, H, W = maps.shape
+        goals = goals.reshape(N, 1, H, W).contiguous()
+        maps = maps.contiguous()
+        out = ops.cost_to_go(maps, goals, maps)
+        missing = torch.nonzero(out.status).flatten().tolist()
+        if missing:
+            raise ValueError(f"DeviceMazeBatches.from_maps: map(s) {missing[:16]} have no goal cell")
+        opt_dists, opt_policies = fields_to_dataset(out.dists, out.policies)
+        self = cls.__new__(cls)
+        self._adopt(dev, num_starts, batch_size, shuffle, generator, map_designs=maps, goal_maps=goals,
+                    opt_policies=opt_policies[:, :, 0].contiguous(), opt_dists=opt_dists.reshape(N, -1).contiguous(),
+                    thresholds=torch.from_numpy(start_thresholds(opt_dists.cpu().numpy(), np.array(list(pcts) + [1.0]))).to(dev))
+        return self
 
     def __len__(self) -> int:
         return (self.N + self.batch_size - 1) // self.batch_size
