@@ -176,6 +176,19 @@ FIELD_SIGNATURES = {
     "nastar_cost_to_go_sweeps": "i pppiiiuppppp",
 }
 
+# the signatures of include/nastar_fields_tiled.h (the sixth header: the same field for maps of up to 1179648 cells, by a tiled relaxation),
+# same letter code; a table of its own (tests/test_fields_tiled.py compares it with ITS header)
+TILED_FIELD_SIGNATURES = {
+    "nastar_fields_tiled_abi": "i ",
+    "nastar_fields_tiled_max_cells": "i ",
+    "nastar_fields_tile": "i pp",
+    "nastar_cost_to_go_tiled_workspace_bytes": "z iii",
+    # cost, goal, passable, B, H, W, neighbor_mask, dist_out, policy_out, status_out, visits_out, workspace, workspace_bytes, max_rounds,
+    # (launches_per_batch,) rounds_out, stream
+    "nastar_cost_to_go_tiled": "i pppiiiupppppzqpp",
+    "nastar_cost_to_go_tiled_batched": "i pppiiiupppppzqipp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -283,6 +296,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, LEVEL_SIGNATURES, LEVEL_SIGNATURES)
     if hasattr(lib, "nastar_fields_abi"):  # (likewise the fifth)
         _bind(lib, FIELD_SIGNATURES, FIELD_SIGNATURES)
+    if hasattr(lib, "nastar_fields_tiled_abi"):  # (and the sixth)
+        _bind(lib, TILED_FIELD_SIGNATURES, TILED_FIELD_SIGNATURES)
     _lib = lib
     return lib
 

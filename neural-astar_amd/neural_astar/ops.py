@@ -14,7 +14,7 @@ import torch
 from . import _native
 
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
-           "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput"]
+           "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput", "cost_to_go_tiled"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -932,16 +932,8 @@ def _checked_neighbor_mask(neighbor_mask) -> int:
     return mask
 
 
-def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
-               policies: bool = True, sweeps_out: Optional[torch.Tensor] = None) -> FieldOutput:
-    """The cost-to-go field of every map of the batch, and the optimal policy that follows it, in one launch (include/nastar_fields.h).
-
-    ``cost_maps``, ``goal_maps``, ``obstacles_maps``: [B,1,H,W] (or [B,H,W]) float32 on one HIP device; EVERY non-zero cell of a goal map
-    is a goal (nearest of K); ``neighbor_mask``: the move set as the search takes it (None = Moore-8).  An evaluation call: no autograd
-    graph, detached outputs, on the current stream of the inputs' device.  The per-map status is read before returning (one host
-    synchronisation; not inside a hipGraph capture): a NaN or a negative cost on a passable cell raises ValueError naming the rows; a map
-    without a goal is reported in ``status``, not raised.  Maps of more than ``FIELDS_MAX_CELLS`` cells raise NotImplementedError.
-    ``sweeps_out``: a [B] int32 tensor that receives the sweeps every map's relaxation took (probes)."""
+def _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask):
+    """the argument checks ``cost_to_go`` and ``cost_to_go_tiled`` share, in one order: -> (the three maps, the mask, (B, H, W))"""
     maps = (cost_maps, goal_maps, obstacles_maps)
     for name, t in zip(("cost_maps", "goal_maps", "obstacles_maps"), maps):
         if not torch.is_tensor(t) or t.ndim not in (3, 4) or (t.ndim == 4 and t.shape[1] < 1):
@@ -951,15 +943,45 @@ def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps:
     shapes = [(t.shape[0],) + tuple(t.shape[-2:]) for t in maps]
     if shapes[1] != shapes[0] or shapes[2] != shapes[0] or min(shapes[0]) < 1:
         raise ValueError(f"cost_maps, goal_maps and obstacles_maps must share one non-empty [B,H,W]: got {shapes[0]}, {shapes[1]}, {shapes[2]}")
-    mask = _checked_neighbor_mask(neighbor_mask)
-    B, H, W = shapes[0]
+    return maps, _checked_neighbor_mask(neighbor_mask), shapes[0]
+
+
+def _field_device(maps) -> torch.device:
+    _require_device(*maps)
+    dev = maps[0].device
+    if maps[1].device != dev or maps[2].device != dev:
+        raise ValueError(f"cost_maps lives on {dev}, goal_maps on {maps[1].device}, obstacles_maps on {maps[2].device}: they must share a device")
+    return dev
+
+
+def _raise_bad_cost(st: torch.Tensor, B: int, what: str) -> None:
+    bad = torch.nonzero(st == FIELD_BAD_COST).flatten().tolist()
+    if bad:
+        raise ValueError(f"{what}: a NaN or a negative cost on a passable cell of map(s) {bad[:16]}{' ...' if len(bad) > 16 else ''} "
+                         f"({len(bad)} of {B}); the other maps were computed")
+
+
+def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
+               policies: bool = True, sweeps_out: Optional[torch.Tensor] = None, tiled: bool = False) -> FieldOutput:
+    """The cost-to-go field of every map of the batch, and the optimal policy that follows it (include/nastar_fields.h).  What follows
+    describes the default, ``tiled=False``: one launch, maps of at most ``FIELDS_MAX_CELLS`` cells; see the last sentence for ``tiled=True``.
+
+    ``cost_maps``, ``goal_maps``, ``obstacles_maps``: [B,1,H,W] (or [B,H,W]) float32 on one HIP device; EVERY non-zero cell of a goal map
+    is a goal (nearest of K); ``neighbor_mask``: the move set as the search takes it (None = Moore-8).  An evaluation call: no autograd
+    graph, detached outputs, on the current stream of the inputs' device.  The per-map status is read before returning (one host
+    synchronisation; not inside a hipGraph capture): a NaN or a negative cost on a passable cell raises ValueError naming the rows; a map
+    without a goal is reported in ``status``, not raised.  Maps of more than ``FIELDS_MAX_CELLS`` cells raise NotImplementedError.
+    ``sweeps_out``: a [B] int32 tensor that receives the sweeps every map's relaxation took (probes).  ``tiled=True`` computes the same
+    tensors with ``cost_to_go_tiled`` -- at any map size up to ``FIELDS_TILED_MAX_CELLS``; that call blocks and cannot be captured."""
+    if tiled:
+        if sweeps_out is not None:
+            raise ValueError("cost_to_go: sweeps_out belongs to the one-workgroup kernel; cost_to_go_tiled() reports rounds and tile visits")
+        return cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, neighbor_mask=neighbor_mask, policies=policies)[0]
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     if H * W > FIELDS_MAX_CELLS:
         raise NotImplementedError(f"cost_to_go: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_MAX_CELLS} cells (one workgroup "
-                                  "relaxes one map in LDS; larger maps need a tiled kernel)")
-    _require_device(*maps)
-    dev = cost_maps.device
-    if goal_maps.device != dev or obstacles_maps.device != dev:
-        raise ValueError(f"cost_maps lives on {dev}, goal_maps on {goal_maps.device}, obstacles_maps on {obstacles_maps.device}: they must share a device")
+                                  "relaxes one map in LDS; larger maps need a tiled kernel: pass tiled=True)")
+    dev = _field_device(maps)
     lib = _native.load()
     if not hasattr(lib, "nastar_cost_to_go"):
         raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields.h: rebuild it with `make -C {_native.CSRC_DIR}`")
@@ -977,11 +999,82 @@ def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps:
         _native.check(rc, "nastar_cost_to_go")
         if not torch.cuda.is_current_stream_capturing():
             st = status.cpu()
-            bad = torch.nonzero(st == FIELD_BAD_COST).flatten().tolist()
-            if bad:
-                raise ValueError(f"cost_to_go: a NaN or a negative cost on a passable cell of map(s) {bad[:16]}{' ...' if len(bad) > 16 else ''} "
-                                 f"({len(bad)} of {B}); the other maps were computed")
+            _raise_bad_cost(st, B, "cost_to_go")
             stuck = torch.nonzero(st == FIELD_NO_CONVERGENCE).flatten().tolist()
             if stuck:
                 raise RuntimeError(f"cost_to_go: map(s) {stuck[:16]} did not converge within H*W sweeps (NASTAR_ERR_NO_CONVERGENCE)")
     return FieldOutput(dists, pol, status)
+
+
+# ---- include/nastar_fields_tiled.h: the same field for maps of up to 1179648 cells, by a tiled relaxation ------
+FIELDS_TILED_MAX_CELLS = 1179648  # nastar_fields_tiled_max_cells(): the limit of the search entry points
+
+
+def fields_tile() -> Tuple[int, int]:
+    """(rows, columns) of the interior of one tile of ``cost_to_go_tiled`` (nastar_fields_tile)"""
+    import ctypes
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    _native.check(_tiled_lib().nastar_fields_tile(ctypes.byref(th), ctypes.byref(tw)), "nastar_fields_tile")
+    return th.value, tw.value
+
+
+def _tiled_lib():
+    lib = _native.load()
+    if not hasattr(lib, "nastar_cost_to_go_tiled"):
+        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields_tiled.h: rebuild it with `make -C {_native.CSRC_DIR}`")
+    return lib
+
+
+def cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
+                     policies: bool = True, max_rounds: Optional[int] = None, visits_out: Optional[torch.Tensor] = None,
+                     launches_per_batch: Optional[int] = None) -> Tuple[FieldOutput, int]:
+    """``cost_to_go`` for maps of up to ``FIELDS_TILED_MAX_CELLS`` cells: the same definition and the same BITS, reached by a tiled
+    relaxation (include/nastar_fields_tiled.h) -> ``(FieldOutput, rounds)``.
+
+    The working field lives in ``dists``; a round is one launch in which every active tile relaxes to its local fixed point and marks the
+    neighbours that have to look again; rounds are enqueued in batches and the host reads one word per map after each batch.  The call
+    therefore BLOCKS on the current stream and is refused while that stream is capturing a graph.  ``rounds``: the rounds in which some
+    tile was active.  ``max_rounds=None``: the bound H*W + 1, which no accepted input reaches; status 10 then raises RuntimeError as in
+    ``cost_to_go``.  With an explicit ``max_rounds`` a map that still has an active tile is reported in ``status`` (``FIELD_NO_CONVERGENCE``),
+    not raised; its ``dists`` are upper bounds of its field, finite only where the field is.  ``visits_out``: a [B] int32 tensor that
+    receives every map's (tile, round) visits; ``launches_per_batch``: probes only, not a stable part of the interface (None = the library's choice)."""
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    if H * W > FIELDS_TILED_MAX_CELLS:
+        raise NotImplementedError(f"cost_to_go_tiled: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_TILED_MAX_CELLS} cells")
+    if max_rounds is not None and (isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or max_rounds < 1):
+        raise ValueError(f"max_rounds must be a positive int or None, got {max_rounds!r}")
+    if launches_per_batch is not None and (isinstance(launches_per_batch, bool) or not isinstance(launches_per_batch, int) or launches_per_batch < 1):
+        raise ValueError(f"launches_per_batch must be a positive int or None, got {launches_per_batch!r}")
+    dev = _field_device(maps)
+    lib = _tiled_lib()
+    if visits_out is not None and (visits_out.dtype != torch.int32 or visits_out.numel() != B or visits_out.device != dev or not visits_out.is_contiguous()):
+        raise ValueError(f"visits_out must be a contiguous int32 tensor of {B} elements on {dev}")
+    with torch.cuda.device(dev):
+        capturing = torch.cuda.is_current_stream_capturing()
+    if capturing:
+        raise RuntimeError("cost_to_go_tiled: the call synchronises its stream between batches of rounds and cannot be captured into a graph")
+    import ctypes
+    nbytes = lib.nastar_cost_to_go_tiled_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        raise NotImplementedError(f"cost_to_go_tiled: a batch of {B} maps of {H}x{W} has more than 2^24 tiles")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(t.detach()) for t in maps)
+        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        rounds = ctypes.c_int(0)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_cost_to_go_tiled_batched(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, dists.data_ptr(),
+                                                     pol.data_ptr() if pol is not None else None, status.data_ptr(),
+                                                     visits_out.data_ptr() if visits_out is not None else None, workspace.data_ptr(), nbytes,
+                                                     0 if max_rounds is None else max_rounds, launches_per_batch or 0,
+                                                     ctypes.cast(ctypes.pointer(rounds), ctypes.c_void_p), _stream_ptr(dev))
+        _native.check(rc, "nastar_cost_to_go_tiled")
+        st = status.cpu()
+        _raise_bad_cost(st, B, "cost_to_go_tiled")
+        if max_rounds is None:
+            stuck = torch.nonzero(st == FIELD_NO_CONVERGENCE).flatten().tolist()
+            if stuck:
+                raise RuntimeError(f"cost_to_go_tiled: map(s) {stuck[:16]} did not converge within H*W + 1 rounds (NASTAR_ERR_NO_CONVERGENCE)")
+    return FieldOutput(dists, pol, status), rounds.value

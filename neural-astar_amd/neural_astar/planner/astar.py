@@ -85,10 +85,10 @@ class VanillaAstar(nn.Module):
                                       "the MI355X-native hot path; plan_routes() runs the HIP DifferentiableAstar kernel only")
         return self.astar.plan_routes(map_designs, start_maps, goal_maps, map_designs, heuristic_maps, max_route_len)
 
-    def cost_to_go(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True) -> FieldOutput:
+    def cost_to_go(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True, tiled: bool = False) -> FieldOutput:
         """The exact cost to the goal from every cell and the optimal policy (``DifferentiableAstar.cost_to_go``) with cost = passable =
         ``map_designs``: on a binary map the number of moves to the goal."""
-        return self.astar.cost_to_go(map_designs, goal_maps, map_designs, policies)
+        return self.astar.cost_to_go(map_designs, goal_maps, map_designs, policies, tiled)
 
 
 class NeuralAstar(VanillaAstar):
@@ -259,9 +259,10 @@ class NeuralAstar(VanillaAstar):
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.astar.plan_routes(cost_maps, start_maps, goal_maps, obstacles_maps, heuristic_maps, max_route_len)
 
-    def cost_to_go(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True) -> FieldOutput:
+    def cost_to_go(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True,
+                   tiled: bool = False) -> FieldOutput:
         """The cost-to-go field and optimal policy of the PREDICTED cost maps: encodes as ``plan_routes()`` does (detached), then
         ``DifferentiableAstar.cost_to_go``; ``learn_obstacles`` makes every cell passable, as it does for the search."""
         cost_maps = self.encode(map_designs, start_maps, goal_maps).detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
-        return self.astar.cost_to_go(cost_maps, goal_maps, obstacles_maps, policies)
+        return self.astar.cost_to_go(cost_maps, goal_maps, obstacles_maps, policies, tiled)

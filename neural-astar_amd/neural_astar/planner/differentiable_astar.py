@@ -614,12 +614,13 @@ class DifferentiableAstar(nn.Module):
                     self.last_status, self.last_iters = status, iters
         return RoutedAstarOutput(hist, paths, routes, lengths, costs)
 
-    def cost_to_go(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, policies: bool = True) -> FieldOutput:
+    def cost_to_go(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, policies: bool = True,
+                   tiled: bool = False) -> FieldOutput:
         """The exact cost to the goal from EVERY cell of every map, and the optimal policy that follows it (``ops.cost_to_go``, the kernel of
         include/nastar_fields.h), under this module's own move set: ``neighbor_filter`` through the cached mask.  A move costs the cell being
         left, as the search's g does; ``g_ratio``, ``Tmax`` and the heuristic play no part.  An evaluation call: no autograd graph, detached
         tensors, one host synchronisation for the status."""
-        return ops.cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies)
+        return ops.cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies, tiled=tiled)
 
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,

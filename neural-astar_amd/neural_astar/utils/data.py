@@ -215,7 +215,7 @@ class DeviceMazeBatches:
         N, _, H, W = maps.shape
         goals = goals.reshape(N, 1, H, W).contiguous()
         maps = maps.contiguous()
-        out = ops.cost_to_go(maps, goals, maps)
+        out = ops.cost_to_go(maps, goals, maps, tiled=H * W > ops.FIELDS_MAX_CELLS)   # (above the one-workgroup kernel's limit: the tiled call)
         missing = torch.nonzero(out.status).flatten().tolist()
         if missing:
             raise ValueError(f"DeviceMazeBatches.from_maps: map(s) {missing[:16]} have no goal cell")
