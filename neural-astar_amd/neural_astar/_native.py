@@ -189,6 +189,16 @@ TILED_FIELD_SIGNATURES = {
     "nastar_cost_to_go_tiled_batched": "i pppiiiupppppzqipp",
 }
 
+# the signatures of include/nastar_verdict.h (the seventh header: the proof, launched beside a search, that every map of the batch is
+# solvable), same letter code; a table of its own (tests/test_verdict_proof.py compares it with ITS header)
+VERDICT_SIGNATURES = {
+    "nastar_verdict_abi": "i ",
+    "nastar_solvable_proof_supported": "i ii",
+    # cost, start, goal, passable, B, H, W, proved_out, word, counter, stream
+    "nastar_solvable_proof": "i " + _MAPS + "iii" + "pppp",
+    "nastar_solvable_proof_sync": "i ",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -280,6 +290,26 @@ def forward_levels_address(H: int, W: int, flags: int) -> int:
     return v
 
 
+# NASTAR_EARLY_VERDICT=0 (read once): a checked forward() never returns on the proof of include/nastar_verdict.h -- A/B runs and tests
+EARLY_VERDICT = os.environ.get("NASTAR_EARLY_VERDICT", "1") != "0"
+_proof_entry: dict = {}
+
+
+def solvable_proof_address(H: int, W: int) -> int:
+    """the address of nastar_solvable_proof (include/nastar_verdict.h) when there is a proof kernel for H x W maps and the early verdict is
+    not switched off, else 0 -- also 0 when the library lacks the symbol.  Cached per size: what the native host lane takes as ``proof_fn``."""
+    if not EARLY_VERDICT:
+        return 0
+    v = _proof_entry.get((H, W))
+    if v is None:
+        lib = load()
+        v = 0
+        if hasattr(lib, "nastar_solvable_proof") and lib.nastar_solvable_proof_supported(H, W) == 1:
+            v = int(ctypes.cast(lib.nastar_solvable_proof, ctypes.c_void_p).value)
+        _proof_entry[(H, W)] = v
+    return v
+
+
 def load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
@@ -298,6 +328,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, FIELD_SIGNATURES, FIELD_SIGNATURES)
     if hasattr(lib, "nastar_fields_tiled_abi"):  # (and the sixth)
         _bind(lib, TILED_FIELD_SIGNATURES, TILED_FIELD_SIGNATURES)
+    if hasattr(lib, "nastar_verdict_abi"):  # (and the seventh)
+        _bind(lib, VERDICT_SIGNATURES, VERDICT_SIGNATURES)
     _lib = lib
     return lib
 

@@ -61,6 +61,16 @@ def coupling_possible(g_ratio: float) -> bool:
     return not (0.5 <= float(g_ratio) < 1.0)
 
 
+# the largest g_ratio at which forward() relies on the solvability proof (include/nastar_verdict.h): the proof's bound on the costs keeps the
+# fixed-point inequality strict in fp32 only while 1 - g_ratio >= 0.25 (csrc/nastar_verdict.hip.h: kProofMaxRouteCost)
+PROOF_MAX_G_RATIO = 0.75
+
+
+def proof_covers(g_ratio: float) -> bool:
+    """is "every map ends with status 0 and no summary cell" implied by the solvability proof at this g_ratio?"""
+    return 0.5 <= float(g_ratio) <= PROOF_MAX_G_RATIO
+
+
 def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -104,6 +114,7 @@ class StatusBoard:
         self.device = device
         self.free = list(range(rows - 1, -1, -1))
         self.zombies: list = []  # rows whose owner went away before its launch was known to be over (retire()): reaped by acquire()
+        self.proved: dict = {}  # zombie rows of launches whose caller returned on the PROOF that every map is solvable -> who that was (retire(proved=...))
         self.lib = _native.load()
 
     @classmethod
@@ -123,25 +134,42 @@ class StatusBoard:
             raise RuntimeError("more than 256 search launches with an unread status: call raise_if_unsolvable() / collect() on the planners that issued them")
         return self.free.pop()
 
-    def retire(self, row: int, event: Optional["torch.cuda.Event"]) -> None:
+    def retire(self, row: int, event: Optional["torch.cuda.Event"], proved: Optional[str] = None) -> None:
         """give a row back although nobody read it (its planner was dropped with verdicts pending): it is reused only once its launch is over
-        -- the completion flag is up, or ``event`` (recorded behind the launch) has passed"""
+        -- the completion flag is up, or ``event`` (recorded behind the launch) has passed.  ``proved``: the caller returned early on the proof
+        that every map of the launch is solvable (include/nastar_verdict.h) -- a description of the call, for the error message; the launch
+        still owns the row until its flag is up, and must then have reported nothing"""
         self.zombies.append((row, event))
+        if proved:
+            self.proved[row] = proved
 
     def _reap(self, wait: bool) -> None:
         keep = []
+        broken = []  # (row, cells) of launches that reported a status although their batch had been PROVED solvable
         for row, ev in self.zombies:
             if self.np[row, 0] or (ev is not None and ev.query()):
-                self.release(row)
+                pass
             elif wait:
                 if ev is not None:
                     ev.synchronize()
                 else:
                     torch.cuda.synchronize(self.device)
-                self.release(row)
             else:
                 keep.append((row, ev))
+                continue
+            who = self.proved.pop(row, None)
+            if who is not None:
+                cells = [c for c in range(1, SUMMARY_WORDS) if self.np[row, c]]
+                if cells:
+                    broken.append((who, row, cells))
+            self.release(row)
         self.zombies = keep
+        if broken:
+            # (raised from whichever call reaps the row: the call it is about returned long ago -- so every one of them is named)
+            raise RuntimeError("search launch(es) that the solvability proof (include/nastar_verdict.h) had declared solvable reported a status, and "
+                               "the forward() calls that issued them returned WITHOUT raising -- their outputs are suspect: "
+                               + "; ".join(f"{who} (status row {row}): summary cell(s) {cells}" for who, row, cells in broken)
+                               + ".  Set NASTAR_EARLY_VERDICT=0 and report this")
 
     def ptr(self, row: int) -> int:
         return self.base + 4 * SUMMARY_WORDS * row
@@ -153,12 +181,12 @@ class StatusBoard:
         """has the launch that was handed ``ptr(row)`` AND ``counter_ptr(row)`` finished every search?  (one host read)"""
         return bool(self.np[row, 0])
 
-    def wait(self, row: int, stream: Optional["torch.cuda.Stream"] = None, spin_us: int = 2000) -> None:
-        """return once the verdict of the launch that owns ``row`` is complete: poll the completion flag for at most ``spin_us``, then fall
+    def wait(self, row: int, stream: Optional["torch.cuda.Stream"] = None, spin_us: int = 2000) -> bool:
+        """return once the verdict of the launch that owns ``row`` is complete (True: its completion flag was seen; False: a stream was waited for): poll the completion flag for at most ``spin_us``, then fall
         back to waiting for ``stream`` (default: the device) -- a launch that carried no completion counter (maps larger than LDS) or one
         that takes longer than the spin budget ends up there"""
         if self.np[row, 0] or (spin_us > 0 and self.lib.nastar_host_wait_nonzero(self.ptr(row), spin_us)):
-            return
+            return True
         if stream is not None:
             stream.synchronize()
         else:
@@ -168,6 +196,7 @@ class StatusBoard:
             # launch left the cell out of phase.  (Launches WITHOUT a counter -- custom-op path, maps larger than LDS -- end up here on every
             # call and must not pay a device write for it: ADVICE r5.)
             self.counters[row] = 0
+        return False
 
     def read(self, row: int):
         """the row as a numpy view if any STATUS cell (1..15) is set, else None (the launch that was handed the row must be over: wait())"""

@@ -277,6 +277,10 @@ class DifferentiableAstar(nn.Module):
         self.last_packed = None
         self.last_status: Optional[torch.Tensor] = None
         self.last_iters: Optional[torch.Tensor] = None
+        # how the same-call verdict of the latest checked call reached the host: "proof" (the batch was proved solvable beside its search,
+        # include/nastar_verdict.h: forward() returned while the searches were still running), "flag" (the launch's completion flag was seen
+        # in pinned memory) or "sync" (a stream was waited for); None before the first such call
+        self.last_verdict_source: Optional[str] = None
         self._pending: List[_PendingStatus] = []
         self._calls = 0  # searches launched through this module (names the call in UnsolvableMapError)
         # placement memory of the batch the NEXT forward() searches (see Placement); consumed by that call
@@ -337,6 +341,7 @@ class DifferentiableAstar(nn.Module):
         self.__dict__.setdefault("placement", None)
         self.__dict__.setdefault("_nf_mask", None)
         self.__dict__.setdefault("multi_source", False)
+        self.__dict__.setdefault("last_verdict_source", None)
         self._nf_key = None  # (a new process / a copied tensor: read the filter again on first use)
 
     def raise_if_unsolvable(self, wait: bool = True) -> None:
@@ -369,7 +374,7 @@ class DifferentiableAstar(nn.Module):
         board = ops.StatusBoard.of(device)
         # the ONE device->host wait of a checked call: a poll of the launch's completion flag in pinned memory (no stream wait, no driver
         # wake-up; the outputs themselves stay stream-ordered), falling back to the stream for launches without a completion counter
-        board.wait(row, torch.cuda.current_stream(device), 2000 if flagged else 0)
+        self.last_verdict_source = "flag" if board.wait(row, torch.cuda.current_stream(device), 2000 if flagged else 0) else "sync"
         r = board.np[row]
         r = r.copy() if r[1:].any() else None
         board.release(row)
@@ -405,6 +410,7 @@ class DifferentiableAstar(nn.Module):
                 coupled = summ is not None and bool(summ[ops.SUMMARY_COUPLED]) and status.numel() > 1
             else:
                 coupled = False
+                self.last_verdict_source = "sync"  # (the caller read it on the host, or the status tensor is read below: a blocking copy)
             if row >= 0:
                 ops.StatusBoard.of(status.device).release(row)
             if (not clean) if clean is not None else bool((status != 0).any()):
@@ -504,18 +510,40 @@ class DifferentiableAstar(nn.Module):
             if order is not None and check_order:
                 flags |= ops.FLAG_CHECK_ORDER
                 ws_bytes = 16
+        max_iters = ops.max_iters_for(W, self.Tmax, self.training)
+        # EARLY VERDICT (include/nastar_verdict.h): for this launch "every map ends with status 0 and no summary cell" is a property of the inputs
+        # alone -- Moore-8, the built-in heuristic, one source (this lane), the general kernel with no flag at all (no order to check, none of
+        # the development switches of NASTAR_FORWARD_FLAGS: nothing was proved about those streams), a g_ratio at which a finished map is
+        # at a fixed point of the batch loop IN FP32 for every cost the proof accepts (ops.proof_covers: [0.5, 0.75]), a budget no search can
+        # exhaust -- and there is a proof kernel for the size
+        proof_fn = 0
+        if flags == 0 and ops.proof_covers(self.g_ratio) and max_iters >= H * W:
+            proof_fn = _native.solvable_proof_address(H, W)
         sink = self.packed_sink  # (a collation slot: the search launch emits the 2-bit-per-cell masks itself, include/nastar.h: packed_out)
         board = ops.StatusBoard.of(dev)
         row = board.acquire()
+        prow = -1
         try:
-            hist, paths, iters, status, _, rc, verdict = fl[0].search(
+            prow = board.acquire() if proof_fn else -1  # the proof's own row: word + completion counter
+            hist, paths, iters, status, _, rc, verdict, proof = fl[0].search(
                 fl[1], cost_maps, start_maps, goal_maps, None if same else obstacles_maps, float(self.g_ratio),
-                ops.max_iters_for(W, self.Tmax, self.training), False, flags, order, order_out, ws_bytes, board.ptr(row), board.counter_ptr(row),
+                max_iters, False, flags, order, order_out, ws_bytes, board.ptr(row), board.counter_ptr(row),
                 torch._C._cuda_getCurrentRawStream(dev.index), 2000, levels, fl[2], sink,
-                0 if levels is None else _native.forward_levels_address(H, W, flags))
+                0 if levels is None else _native.forward_levels_address(H, W, flags),
+                proof_fn, board.ptr(prow) if proof_fn else 0, board.counter_ptr(prow) if proof_fn else 0)
         except BaseException:
             board.release(row)
+            if prow >= 0:
+                board.release(prow)
             raise
+        if prow >= 0:
+            if proof == 3:
+                # the proof's word did not come up within the spin budget: its launch may still read the inputs and owns its row -- wait for it
+                _native.check(_native.load().nastar_solvable_proof_sync(), "nastar_solvable_proof_sync")
+                board.counters[prow] = 0  # (a launch that ended without its word left the cell out of phase)
+                board.release(prow)
+            else:
+                board.free.append(prow)  # (not launched, or its word was read and zeroed: the row came back clean)
         if rc:
             board.release(row)
             if rc == -1:
@@ -526,6 +554,13 @@ class DifferentiableAstar(nn.Module):
         self.last_status, self.last_iters = status, iters
         self._calls += 1
         self.last_packed = sink
+        if proof == 1:
+            # every map is PROVED solvable: the verdict is 0 whenever the searches end.  They are still running and their launch owns the row
+            # until its completion flag is up: the board reaps it then (and checks that the launch indeed reported nothing)
+            board.retire(row, None, proved=f"search call #{self._calls} of a {type(self).__name__} at {id(self):#x} ({B} maps of {H}x{W})")
+            self.last_verdict_source = "proof"
+            return AstarOutput(hist, paths, [])
+        self.last_verdict_source = "flag"
         if verdict == 0:  # every map ended with status 0 (the row came back zeroed)
             board.free.append(row)
             return AstarOutput(hist, paths, [])
@@ -541,7 +576,7 @@ class DifferentiableAstar(nn.Module):
         if verdict & (1 << ops.SUMMARY_COUPLED) and B > 1:
             # a finished map of this batch is not at a fixed point of the reference's batch loop (negative costs): the batch again, exactly
             hist, paths, iters, status, _ = self.exact_search(cost_maps, start_maps, goal_maps, cost_maps if same else obstacles_maps,
-                                                              ops.max_iters_for(W, self.Tmax, self.training), neighbor_mask=None)
+                                                              max_iters, neighbor_mask=None)
             self.last_status, self.last_iters = status, iters
             self.last_packed = None  # (the slot holds the masks of the first launch)
         return AstarOutput(hist, paths, [])
