@@ -12,6 +12,8 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _native
+from .status import (CLEAN, PROOF_MAX_G_RATIO, STATUS_BAD_HEURISTIC, STATUS_NOT_UNIT_COST, STATUS_UNSOLVABLE, SUMMARY_BAD_ORDER, SUMMARY_COUPLED, SUMMARY_ERRORS,  # noqa: F401
+                     SUMMARY_WORDS, StatusBoard, Summary, coupling_possible, needs_exact, proof_covers)  # (a launch's status lives in status.py; the names stay importable from here)
 
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
            "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput", "cost_to_go_tiled"]
@@ -37,13 +39,6 @@ FLAG_UNIT_COST = 64  # include/nastar.h NASTAR_FLAG_UNIT_COST
 FLAG_LOCKSTEP = 1024  # NASTAR_FLAG_LOCKSTEP: the reference's batch loop to the letter (no exit at the goal; exactly max_iters steps)
 FLAG_CHECK_ORDER = 256  # NASTAR_FLAG_CHECK_ORDER: the launch verifies `order` on the device and ignores it when it is not a permutation
 FLAG_MARK_COUPLED = 32768  # NASTAR_FLAG_MARK_COUPLED: the launch marks the maps of the batch-coupled class for nastar_forward_batchloop_finish
-STATUS_UNSOLVABLE = 3  # NASTAR_ERR_UNSOLVABLE (per-map status)
-STATUS_NOT_UNIT_COST = 7  # NASTAR_ERR_NOT_UNIT_COST (per-map status)
-STATUS_BAD_HEURISTIC = 8  # NASTAR_ERR_BAD_HEURISTIC (per-map status): a NaN / infinite value in this map's heuristic_maps
-SUMMARY_WORDS = 16  # NASTAR_SUMMARY_WORDS
-SUMMARY_BAD_ORDER = 15  # NASTAR_SUMMARY_BAD_ORDER
-SUMMARY_COUPLED = 14  # NASTAR_SUMMARY_COUPLED: a NOTE (a finished map is not at a fixed point of the reference's batch loop), cells 1..13 are errors
-SUMMARY_ERRORS = slice(1, 14)
 # DifferentiableAstar.neighbor_filter as a 9-bit mask (include/nastar.h NASTAR_NEIGHBORS_*): bit r*3+c <=> filter cell (r, c) is 1
 NEIGHBORS_MOORE8 = 0x1EF
 NEIGHBORS_VON_NEUMANN = 0x0AA
@@ -52,23 +47,6 @@ NEIGHBORS_VON_NEUMANN = 0x0AA
 FORWARD_FLAGS = int(os.environ.get("NASTAR_FORWARD_FLAGS", "0"))
 if FORWARD_FLAGS & ~(8 | 16 | 32 | 64 | 128):
     raise ValueError(f"NASTAR_FORWARD_FLAGS={FORWARD_FLAGS}: unknown flag bits (include/nastar.h NASTAR_FLAG_*, csrc/nastar_dev_flags.h)")
-
-
-def coupling_possible(g_ratio: float) -> bool:
-    """Can a map that reached its goal fail to be at a fixed point of the reference's batch loop with costs >= 0?
-    f(n) - f(goal) = (2 g_ratio - 1) c_goal + (1 - g_ratio)(h0(n) + c_n) is positive for every g_ratio in [0.5, 1): never there.  (With
-    NEGATIVE costs any g_ratio can: the launch's status summary reports it, NASTAR_SUMMARY_COUPLED.)"""
-    return not (0.5 <= float(g_ratio) < 1.0)
-
-
-# the largest g_ratio at which forward() relies on the solvability proof (include/nastar_verdict.h): the proof's bound on the costs keeps the
-# fixed-point inequality strict in fp32 only while 1 - g_ratio >= 0.25 (csrc/nastar_verdict.hip.h: kProofMaxRouteCost)
-PROOF_MAX_G_RATIO = 0.75
-
-
-def proof_covers(g_ratio: float) -> bool:
-    """is "every map ends with status 0 and no summary cell" implied by the solvability proof at this g_ratio?"""
-    return 0.5 <= float(g_ratio) <= PROOF_MAX_G_RATIO
 
 
 def _stream_ptr(device: torch.device) -> int:
@@ -93,119 +71,6 @@ def _maps3(t: torch.Tensor) -> torch.Tensor:
     if t.ndim == 4:
         t = t[:, 0]
     return t.contiguous()
-
-
-class StatusBoard:
-    """Pinned host memory the search launches write their STATUS SUMMARY into (include/nastar.h: status_summary of nastar_forward_ex): one
-    row of NASTAR_SUMMARY_WORDS int32 per launch in flight; cell c (1..15) becomes 1 when some map of that launch ended with per-map status
-    c, cell 0 when every search of the launch is over (completion_counter: one device cell per row).  "Did any map of this batch fail?" is
-    then a poll of one host word and a 64-byte read -- no reduction launch, no device-to-host copy, no stream wait, nothing on a side
-    stream.  One board per device; rows are handed out and returned by the callers."""
-
-    _boards: dict = {}
-
-    def __init__(self, device: torch.device, rows: int = 256):
-        with torch.cuda.device(device):
-            self.t = torch.zeros((rows, SUMMARY_WORDS), dtype=torch.int32).pin_memory()
-            self.counters = torch.zeros((rows,), dtype=torch.int32, device=device)
-        self.np = self.t.numpy()
-        self.base = self.t.data_ptr()
-        self.cbase = self.counters.data_ptr()
-        self.device = device
-        self.free = list(range(rows - 1, -1, -1))
-        self.zombies: list = []  # rows whose owner went away before its launch was known to be over (retire()): reaped by acquire()
-        self.proved: dict = {}  # zombie rows of launches whose caller returned on the PROOF that every map is solvable -> who that was (retire(proved=...))
-        self.lib = _native.load()
-
-    @classmethod
-    def of(cls, device: torch.device) -> "StatusBoard":
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        b = cls._boards.get(key)
-        if b is None:
-            b = cls._boards[key] = cls(torch.device("cuda", key))
-        return b
-
-    def acquire(self) -> int:
-        if self.zombies:
-            self._reap(False)
-        if not self.free and self.zombies:
-            self._reap(True)
-        if not self.free:
-            raise RuntimeError("more than 256 search launches with an unread status: call raise_if_unsolvable() / collect() on the planners that issued them")
-        return self.free.pop()
-
-    def retire(self, row: int, event: Optional["torch.cuda.Event"], proved: Optional[str] = None) -> None:
-        """give a row back although nobody read it (its planner was dropped with verdicts pending): it is reused only once its launch is over
-        -- the completion flag is up, or ``event`` (recorded behind the launch) has passed.  ``proved``: the caller returned early on the proof
-        that every map of the launch is solvable (include/nastar_verdict.h) -- a description of the call, for the error message; the launch
-        still owns the row until its flag is up, and must then have reported nothing"""
-        self.zombies.append((row, event))
-        if proved:
-            self.proved[row] = proved
-
-    def _reap(self, wait: bool) -> None:
-        keep = []
-        broken = []  # (row, cells) of launches that reported a status although their batch had been PROVED solvable
-        for row, ev in self.zombies:
-            if self.np[row, 0] or (ev is not None and ev.query()):
-                pass
-            elif wait:
-                if ev is not None:
-                    ev.synchronize()
-                else:
-                    torch.cuda.synchronize(self.device)
-            else:
-                keep.append((row, ev))
-                continue
-            who = self.proved.pop(row, None)
-            if who is not None:
-                cells = [c for c in range(1, SUMMARY_WORDS) if self.np[row, c]]
-                if cells:
-                    broken.append((who, row, cells))
-            self.release(row)
-        self.zombies = keep
-        if broken:
-            # (raised from whichever call reaps the row: the call it is about returned long ago -- so every one of them is named)
-            raise RuntimeError("search launch(es) that the solvability proof (include/nastar_verdict.h) had declared solvable reported a status, and "
-                               "the forward() calls that issued them returned WITHOUT raising -- their outputs are suspect: "
-                               + "; ".join(f"{who} (status row {row}): summary cell(s) {cells}" for who, row, cells in broken)
-                               + ".  Set NASTAR_EARLY_VERDICT=0 and report this")
-
-    def ptr(self, row: int) -> int:
-        return self.base + 4 * SUMMARY_WORDS * row
-
-    def counter_ptr(self, row: int) -> int:
-        return self.cbase + 4 * row
-
-    def done(self, row: int) -> bool:
-        """has the launch that was handed ``ptr(row)`` AND ``counter_ptr(row)`` finished every search?  (one host read)"""
-        return bool(self.np[row, 0])
-
-    def wait(self, row: int, stream: Optional["torch.cuda.Stream"] = None, spin_us: int = 2000) -> bool:
-        """return once the verdict of the launch that owns ``row`` is complete (True: its completion flag was seen; False: a stream was waited for): poll the completion flag for at most ``spin_us``, then fall
-        back to waiting for ``stream`` (default: the device) -- a launch that carried no completion counter (maps larger than LDS) or one
-        that takes longer than the spin budget ends up there"""
-        if self.np[row, 0] or (spin_us > 0 and self.lib.nastar_host_wait_nonzero(self.ptr(row), spin_us)):
-            return True
-        if stream is not None:
-            stream.synchronize()
-        else:
-            torch.cuda.synchronize(self.device)
-        if spin_us > 0 and not self.np[row, 0]:
-            # the launch was given the row's completion counter (callers spin only then) and is over without having raised the flag: an aborted
-            # launch left the cell out of phase.  (Launches WITHOUT a counter -- custom-op path, maps larger than LDS -- end up here on every
-            # call and must not pay a device write for it: ADVICE r5.)
-            self.counters[row] = 0
-        return False
-
-    def read(self, row: int):
-        """the row as a numpy view if any STATUS cell (1..15) is set, else None (the launch that was handed the row must be over: wait())"""
-        r = self.np[row]
-        return r if r[1:].any() else None  # (incl. the notes in cells 14 / 15: the caller tells errors -- SUMMARY_ERRORS -- from notes)
-
-    def release(self, row: int) -> None:
-        self.np[row] = 0
-        self.free.append(row)
 
 
 _IN_LDS: dict = {}

@@ -19,6 +19,7 @@ import torch.distributed as dist
 
 from . import ops
 from .planner.differentiable_astar import AstarOutput, UnsolvableMapError, _raise_unsolvable
+from .status import CLEAN, Summary, needs_exact
 
 _BIT_WEIGHTS = None
 _SEARCH_STREAMS: dict = {}
@@ -479,9 +480,7 @@ class InFlightPlanner:
             max_iters = ops.max_iters_for(start_maps.shape[-1], 1.0, False)
             unit = same and self.unit_cost in (True, "auto")
             flags = ops.FLAG_UNIT_COST if unit else 0
-            # batch semantics: outside g_ratio in [0.5, 1) a finished map may not be at a fixed point of the reference's
-            # batch loop -- the exact pipeline (marks + lock-step re-run of the marked maps) goes to the stream with the search; unit costs never are
-            exact = (not unit) and start_maps.shape[0] > 1 and ops.coupling_possible(astar.g_ratio)
+            exact = needs_exact(start_maps.shape[0], astar.g_ratio, unit=unit)  # (the exact pipeline then goes to the stream with the search)
             order = check = None
             hint = getattr(start_maps, "placement_order", None) if self.use_placement else None
             if hint is not None and ops.in_lds(start_maps.shape[-2], start_maps.shape[-1]):
@@ -521,35 +520,32 @@ class InFlightPlanner:
         summaries = []
         for item in inflight:
             row = item[2]
-            r = board.read(row) if row >= 0 else None
-            summaries.append(None if r is None else r.copy())
+            summaries.append(Summary.of_row(board.read(row)) if row >= 0 else CLEAN)
             if row >= 0:
                 board.release(row)
         for (ticket, k, row, ins, out, flags, order, check, _keep, exact), summ in zip(inflight, summaries):
             hist, paths, iters, status, _ = out
-            if summ is not None and summ[ops.STATUS_NOT_UNIT_COST] and self.unit_cost == "auto":
+            if summ.not_unit and self.unit_cost == "auto":
                 # a non-binary map in a batch that went to the unit-cost kernel optimistically: the batch again on the general kernel
                 self.reruns += 1
                 cost, start_maps, goal_maps, passable = ins
                 r2 = board.acquire()
                 try:
-                    exact = start_maps.shape[0] > 1 and ops.coupling_possible(astar.g_ratio)
+                    exact = needs_exact(start_maps.shape[0], astar.g_ratio)
                     hist, paths, iters, status, _ = ops.search_nograd(cost, start_maps, goal_maps, passable, astar.g_ratio,
                                                                       ops.max_iters_for(start_maps.shape[-1], 1.0, False), order=order,
                                                                       check_order=bool(check), summary_ptr=board.ptr(r2), out_4d=True, exact=exact)
                     torch.cuda.current_stream(dev).synchronize()
-                    r = board.read(r2)
-                    summ = None if r is None else r.copy()
+                    summ = Summary.of_row(board.read(r2))
                 finally:
                     board.release(r2)
-            coupled = summ is not None and summ[ops.SUMMARY_COUPLED] and not summ[ops.SUMMARY_ERRORS].any() and status.numel() > 1
-            if coupled and not exact:
+            if summ.coupled and not summ.errors and status.numel() > 1 and not exact:
                 # a finished map of this batch is not at a fixed point of the reference's batch loop although g_ratio is in [0.5, 1) (negative
                 # costs): the batch again through the exact pipeline, exactly as planner.forward() does
                 self.reruns += 1
                 cost, start_maps, goal_maps, passable = ins
                 hist, paths, iters, status, _ = astar.exact_search(cost, start_maps, goal_maps, passable, ops.max_iters_for(start_maps.shape[-1], 1.0, False))
-            if summ is not None and summ[ops.SUMMARY_ERRORS].any() and self.check_solvable and failed is None:
+            if summ.errors and self.check_solvable and failed is None:
                 failed = (ticket, status)
             outs.append(AstarOutput(hist, paths, []))
             astar.last_status, astar.last_iters = status, iters

@@ -14,8 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import _native, ops
-
-_ERROR_BITS = sum(1 << c for c in range(1, 14))  # summary cells 1..13 are per-map error codes (ops.SUMMARY_ERRORS); 14 / 15 are notes
+from ..status import Summary, needs_exact
 
 
 class AstarOutput(NamedTuple):
@@ -140,17 +139,11 @@ class _PendingStatus:
             self.board.wait(self.row, self.stream)  # (flagged launch: spins on the completion flag first)
         else:
             self.event.synchronize()
-        r = self.board.read(self.row)
-        bad = r is not None and bool(r[ops.SUMMARY_ERRORS].any())
-        coupled = r is not None and bool(r[ops.SUMMARY_COUPLED]) and self.status.numel() > 1
-        if r is not None and r[ops.SUMMARY_BAD_ORDER]:
-            _warn_bad_order()
+        summ = Summary.of_row(self.board.read(self.row))
         self.board.release(self.row)
         self.released = True
         repair, self.repair = self.repair, None
-        if bad:
-            _raise_unsolvable(self.status, self.seq, deferred=True)
-        if coupled and repair is not None:
+        if deliver(summ, self.status, self.seq, deferred=True) and repair is not None:
             repair()
 
     def __del__(self):  # a planner dropped with verdicts pending: the row goes back once its launch is over (never while it may still be written)
@@ -181,6 +174,21 @@ def _raise_unsolvable(status: torch.Tensor, seq: int = 0, deferred: bool = False
     raise UnsolvableMapError(
         f"{len(bad)} map(s) have no start->goal route or a non-one-hot start/goal map "
         f"(batch rows {bad[:16]}{'...' if len(bad) > 16 else ''} of {where})")
+
+
+def deliver(summary: Summary, status: torch.Tensor, seq: int, deferred: bool = False) -> bool:
+    """What the ``Summary`` of search call #``seq`` means to its caller, in this order: warn (once) about an ignored placement order; raise for an error
+    cell; True = the launch reported NASTAR_SUMMARY_COUPLED for a batch of more than one map (the caller runs the batch again, exactly)."""
+    if summary.bad_order:
+        _warn_bad_order()
+    if summary.errors:
+        _raise_unsolvable(status, seq, deferred)
+    return summary.coupled and status.numel() > 1
+
+
+def _same_tensor(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """are the cost map and the obstacle map ONE tensor?  (VanillaAstar hands one over as both, reference astar.py:93-94: the kernel then loads it once)"""
+    return a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride())
 
 
 class Placement:
@@ -363,59 +371,38 @@ class DifferentiableAstar(nn.Module):
     def summary_ptr(row: int, like: torch.Tensor) -> int:
         return ops.StatusBoard.of(like.device).ptr(row) if row >= 0 else 0
 
-    @staticmethod
-    def counter_ptr(row: int, like: torch.Tensor) -> int:
-        """the completion counter of the row (device cell), for launches of LDS-resident sizes; 0 otherwise"""
-        return ops.StatusBoard.of(like.device).counter_ptr(row) if (row >= 0 and ops.in_lds(like.shape[-2], like.shape[-1])) else 0
-
-    def _collect_sync(self, row: int, device: torch.device, flagged: bool = False):
-        """wait for the launch that owns ``row`` and return a COPY of its summary row (None = every map ended with status 0);
+    def _collect_sync(self, row: int, device: torch.device, flagged: bool = False) -> Summary:
+        """wait for the launch that owns ``row``, hand the row back and return what it said (``CLEAN`` = every map ended with status 0);
         ``flagged``: the launch was given the row's completion counter"""
         board = ops.StatusBoard.of(device)
         # the ONE device->host wait of a checked call: a poll of the launch's completion flag in pinned memory (no stream wait, no driver
         # wake-up; the outputs themselves stay stream-ordered), falling back to the stream for launches without a completion counter
         self.last_verdict_source = "flag" if board.wait(row, torch.cuda.current_stream(device), 2000 if flagged else 0) else "sync"
-        r = board.np[row]
-        r = r.copy() if r[1:].any() else None
+        summ = Summary.of_row(board.read(row))
         board.release(row)
-        return r
+        return summ
 
-    def note_status(self, status: torch.Tensor, iters: torch.Tensor, clean: Optional[bool] = None, row: int = -1, flagged: bool = False,
-                    repair=None) -> bool:
-        """record a launch's per-map status / step counts and apply the ``check_solvable`` policy (also used by the fused training
-        step and the validation pair, which launch the search themselves).  ``row``: the ``begin_launch()`` row whose address the
-        launch was given as ``summary_ptr`` (``flagged``: and its ``counter_ptr``) -- the verdict is then a poll of the row's completion flag
-        (unflagged: a stream wait / an event) and one 64-byte host read; without a row the status tensor is reduced on the device (one
-        more launch + a blocking copy).  ``clean``: the
-        caller has already read the verdict on the host (True = all zero) -- the "sync" policy then does not wait a second time.
-        Returns True when the launch reported NASTAR_SUMMARY_COUPLED and the verdict was read in THIS call: the caller then runs the batch
-        again with ``exact=True`` (the reference's batch loop to the letter, ``ops._launch_search``).  ``repair``: what a DEFERRED verdict
-        that reports the note calls to do the same in place (``_repair_in_place``)."""
+    def note_status(self, status: torch.Tensor, iters: torch.Tensor, row: int = -1, flagged: bool = False, repair=None) -> bool:
+        """record a launch's per-map status / step counts and apply the ``check_solvable`` policy (also used by the fused training step, which
+        launches the search itself).  ``row``: the ``begin_launch()`` row whose address the launch was given as ``summary_ptr`` (``flagged``: and the
+        row's completion counter) -- the verdict is then a poll of the row's completion flag (unflagged: a stream wait / an event) and one 64-byte
+        host read; without a row the status tensor is reduced on the device (one more launch + a blocking copy).  Returns ``deliver()``'s answer when
+        the verdict was read in THIS call: True = the caller runs the batch again with ``exact=True`` (the reference's batch loop to the letter,
+        ``ops._launch_search``).  ``repair``: what a DEFERRED verdict that reports the note calls to do the same in place (``_repair_in_place``)."""
         self.last_status, self.last_iters = status, iters
         self._calls += 1
         mode = self.check_solvable
-        if clean is True and row < 0 and mode is not False and mode != "deferred":
-            return False  # the caller has read a clean verdict for THIS call already
         if not mode or _capturing(status) or torch.compiler.is_compiling():  # nothing may synchronise inside a hipGraph capture / a trace
             if row >= 0:
                 ops.StatusBoard.of(status.device).release(row)
             return False
         if mode != "deferred":  # True / "sync": the verdict belongs to THIS call
-            if clean is None and row >= 0:
-                summ = self._collect_sync(row, status.device, flagged)
-                row = -1
-                clean = summ is None or not (summ[ops.SUMMARY_ERRORS].any())
-                if summ is not None and summ[ops.SUMMARY_BAD_ORDER]:
-                    _warn_bad_order()
-                coupled = summ is not None and bool(summ[ops.SUMMARY_COUPLED]) and status.numel() > 1
-            else:
-                coupled = False
-                self.last_verdict_source = "sync"  # (the caller read it on the host, or the status tensor is read below: a blocking copy)
             if row >= 0:
-                ops.StatusBoard.of(status.device).release(row)
-            if (not clean) if clean is not None else bool((status != 0).any()):
+                return deliver(self._collect_sync(row, status.device, flagged), status, self._calls)
+            self.last_verdict_source = "sync"  # (no row: the status tensor itself is read, a blocking copy)
+            if bool((status != 0).any()):
                 _raise_unsolvable(status, self._calls)
-            return coupled
+            return False
         if row < 0:  # a launch that carried no summary: reduce on the device into a fresh row's worth of pinned memory
             row = ops.StatusBoard.of(status.device).acquire()
             ops.StatusBoard.of(status.device).t[row, ops.STATUS_UNSOLVABLE:ops.STATUS_UNSOLVABLE + 1].copy_((status != 0).any().reshape(1), non_blocking=True)
@@ -491,7 +478,7 @@ class DifferentiableAstar(nn.Module):
             return None
         B, _, H, W = cost_maps.shape
         dev = cost_maps.device
-        if (not cost_maps.is_cuda or not ops.in_lds(H, W) or (B > 1 and ops.coupling_possible(self.g_ratio)) or torch.compiler.is_compiling()
+        if (not cost_maps.is_cuda or not ops.in_lds(H, W) or needs_exact(B, self.g_ratio) or torch.compiler.is_compiling()
                 or torch.cuda.is_current_stream_capturing() or dev.index != torch.cuda.current_device()):
             return None
         same = obstacles_maps is cost_maps
@@ -566,14 +553,10 @@ class DifferentiableAstar(nn.Module):
             return AstarOutput(hist, paths, [])
         if verdict < 0:  # the flag did not come up within the spin budget (a very long launch): wait for the stream, read the row
             summ = self._collect_sync(row, dev, True)
-            verdict = 0 if summ is None else int(sum((1 << c) for c in range(1, ops.SUMMARY_WORDS) if summ[c]))
         else:
             board.free.append(row)
-        if verdict & (1 << ops.SUMMARY_BAD_ORDER):
-            _warn_bad_order()
-        if verdict & _ERROR_BITS:
-            _raise_unsolvable(status, self._calls)
-        if verdict & (1 << ops.SUMMARY_COUPLED) and B > 1:
+            summ = Summary.of_bits(verdict)
+        if deliver(summ, status, self._calls):
             # a finished map of this batch is not at a fixed point of the reference's batch loop (negative costs): the batch again, exactly
             hist, paths, iters, status, _ = self.exact_search(cost_maps, start_maps, goal_maps, cost_maps if same else obstacles_maps,
                                                               max_iters, neighbor_mask=None)
@@ -599,10 +582,7 @@ class DifferentiableAstar(nn.Module):
         the last L cells of a longer route.  Takes no placement and no native host lane.  With ``self.multi_source`` every non-zero cell of
         ``start_maps`` is a source: the route begins at the source that reached the goal (``routes[b, 0]`` when it fits the row) and may pass
         through another start cell; False takes the highest-index start cell only."""
-        assert cost_maps.ndim == 4
-        assert start_maps.ndim == 4
-        assert goal_maps.ndim == 4
-        assert obstacles_maps.ndim == 4
+        assert cost_maps.ndim == start_maps.ndim == goal_maps.ndim == obstacles_maps.ndim == 4
         route_cap = _checked_route_len(max_route_len)
         self._refuse_replaced_heuristic()
         h0 = _checked_heuristic(heuristic_maps, cost_maps).detach() if heuristic_maps is not None else None
@@ -610,11 +590,10 @@ class DifferentiableAstar(nn.Module):
         nmask = self.neighbor_mask()
         B, _, H, W = cost_maps.shape
         max_iters = ops.max_iters_for(W, self.Tmax, self.training)
-        same = obstacles_maps is cost_maps or (cost_maps.data_ptr() == obstacles_maps.data_ptr() and cost_maps.shape == obstacles_maps.shape
-                                               and cost_maps.stride() == obstacles_maps.stride())
+        same = _same_tensor(cost_maps, obstacles_maps)
         multi = bool(self.multi_source)
         unit = same and self.unit_cost is True and nmask is None and h0 is None and not multi
-        exact = B > 1 and (ops.coupling_possible(self.g_ratio) or h0 is not None) and not unit  # forward()'s rule, to the letter
+        exact = needs_exact(B, self.g_ratio, h0 is not None, unit)
         dev = cost_maps.device
         cost = cost_maps.detach()
         passable = cost if same else obstacles_maps.detach()
@@ -636,17 +615,10 @@ class DifferentiableAstar(nn.Module):
             raise
         self.last_status, self.last_iters = status, iters
         self._calls += 1
-        if row >= 0:
-            summ = self._collect_sync(row, dev, bool(cptr))
-            if summ is not None:
-                if summ[ops.SUMMARY_BAD_ORDER]:
-                    _warn_bad_order()
-                if summ[ops.SUMMARY_ERRORS].any():
-                    _raise_unsolvable(status, self._calls)
-                if summ[ops.SUMMARY_COUPLED] and B > 1 and not exact:
-                    # a finished map of this batch is not at a fixed point of the reference's batch loop (negative costs): the batch again, exactly
-                    hist, paths, iters, status, _, routes, lengths, costs = launch(True, 0, 0)
-                    self.last_status, self.last_iters = status, iters
+        if row >= 0 and deliver(self._collect_sync(row, dev, bool(cptr)), status, self._calls) and not exact:
+            # a finished map of this batch is not at a fixed point of the reference's batch loop (negative costs): the batch again, exactly
+            hist, paths, iters, status, _, routes, lengths, costs = launch(True, 0, 0)
+            self.last_status, self.last_iters = status, iters
         return RoutedAstarOutput(hist, paths, routes, lengths, costs)
 
     def cost_to_go(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, policies: bool = True,
@@ -673,14 +645,9 @@ class DifferentiableAstar(nn.Module):
         behaviour (every non-zero cell is open with g = 0).  True composes with ``neighbor_filter``,
         ``heuristic_maps``, ``store_intermediate_results``, every ``check_solvable`` mode, autograd and training budgets; it takes no placement,
         native host lane, unit-cost layout, hand-scheduled stream or torch.compile trace, and a one-hot batch gives bit-identical outputs."""
-        assert cost_maps.ndim == 4
-        assert start_maps.ndim == 4
-        assert goal_maps.ndim == 4
-        assert obstacles_maps.ndim == 4
+        assert cost_maps.ndim == start_maps.ndim == goal_maps.ndim == obstacles_maps.ndim == 4
         self._refuse_replaced_heuristic()
-        h0 = None
-        if heuristic_maps is not None:
-            h0 = _checked_heuristic(heuristic_maps, cost_maps)
+        h0 = _checked_heuristic(heuristic_maps, cost_maps) if heuristic_maps is not None else None
         self.last_packed = None
         nmask = self.neighbor_mask()  # None: the default (Moore-8) filter -- its kernels, its native host lane, its unit-cost layout
         multi = bool(self.multi_source)
@@ -702,9 +669,7 @@ class DifferentiableAstar(nn.Module):
         capturing = cost_maps.is_cuda and torch.cuda.is_current_stream_capturing()
         if self._pending and not capturing:
             self.raise_if_unsolvable(wait=False)  # deferred verdicts of earlier calls that have reached the host
-        # VanillaAstar hands ONE tensor over as cost and obstacle map (reference astar.py:93-94): the kernel then loads it once
-        same = obstacles_maps is cost_maps or (cost_maps.data_ptr() == obstacles_maps.data_ptr() and cost_maps.shape == obstacles_maps.shape
-                                               and cost_maps.stride() == obstacles_maps.stride())
+        same = _same_tensor(cost_maps, obstacles_maps)
         mode = self.check_solvable
         # the unit-cost layout pays with SEVERAL launches in flight (more maps resident per CU); one launch at a time is a serial chain whose
         # length does not depend on the layout (probe_boundary: 117 us unit vs 114 us general per placed 4096-map launch), so forward()
@@ -729,12 +694,7 @@ class DifferentiableAstar(nn.Module):
         flags = ops.FLAG_UNIT_COST if unit else 0
         traced = needs_grad or type(cost_maps) is not torch.Tensor or compiling
         passable_maps = cost_maps if same else obstacles_maps
-        # Batch semantics.  For g_ratio in [0.5, 1) with costs >= 0 a finished map is at a fixed point of the reference's
-        # batch loop and ONE launch is the whole story; the launch reports the rare exception (negative costs) in its status summary.  Outside
-        # that range the class is reachable with ordinary costs: the exact pipeline runs straight away (marks + three launches that do nothing
-        # when no map is marked) -- under autograd, with deferred or no checking, inside a hipGraph capture or a trace alike.
-        # With a caller's heuristic the class is reachable at every g_ratio (the fixed-point proof needs h0(n) >= 1.001 and h0(goal) = 0).
-        exact = B > 1 and (ops.coupling_possible(self.g_ratio) or h0 is not None) and not unit
+        exact = needs_exact(B, self.g_ratio, h0 is not None, unit)  # batch semantics: the exact pipeline up front?
 
         def launch(exact_now: bool, sptr_now: int, cptr_now: int):
             if not traced:
@@ -777,8 +737,7 @@ class DifferentiableAstar(nn.Module):
             else:  # (no graph holds these tensors: a late verdict that reports the note completes them in place)
                 repair = self._repair_in_place((cost_maps, start_maps, goal_maps, passable_maps), (hist, paths, iters, status, sel_log), max_iters, want_log,
                                                nmask, multi)
-        coupled = self.note_status(status, iters, None, row, flagged=bool(cptr) and not traced, repair=repair)
-        if coupled and not exact:
+        if self.note_status(status, iters, row, flagged=bool(cptr) and not traced, repair=repair) and not exact:
             # the same-call verdict says a finished map of this batch is not at a fixed point (negative costs): the batch again, exactly
             order = order_out = None
             hist, paths, iters, status, sel_log = launch(True, 0, 0)
@@ -837,7 +796,7 @@ def _warn_bad_order() -> None:
         _BAD_ORDER_WARNED = True
         import warnings
         warnings.warn("a placement order handed to the search was not a permutation of 0..B-1: it was ignored (natural order, identical "
-                      "outputs); build orders with ops.order_from_levels / Placement", RuntimeWarning, stacklevel=3)
+                      "outputs); build orders with ops.order_from_levels / Placement", RuntimeWarning, stacklevel=4)  # (past deliver() and the method that read the row)
 
 
 def _intermediate_results(hist, paths, goal, iters, sel_log) -> List[dict]:

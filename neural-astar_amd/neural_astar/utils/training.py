@@ -209,9 +209,9 @@ def fused_l1_step(planner: VanillaAstar, map_designs: torch.Tensor, start_maps: 
     order, _, check, _ = astar.resolve_placement(cost_maps.shape[0], start_maps, ops.workspace_bytes(cost_maps.shape) == 0)
     astar.placement = pl_keep
     row = astar.begin_launch(cost_maps)
-    # batch semantics as in DifferentiableAstar.forward: outside g_ratio in [0.5, 1) the exact pipeline runs with the launch; inside, the same-call
-    # verdict re-runs a batch that reports the batch-coupled note (negative costs), a deferred one refuses (the graph is built by then)
-    exact = cost_maps.shape[0] > 1 and ops.coupling_possible(astar.g_ratio)
+    # batch semantics as in DifferentiableAstar.forward: the exact pipeline with the launch where ``needs_exact``; elsewhere the same-call verdict
+    # re-runs a batch that reports the batch-coupled note (negative costs), a deferred one refuses (the graph is built by then)
+    exact = ops.needs_exact(cost_maps.shape[0], astar.g_ratio)
     args = (cost_maps[:, 0], start_maps[:, 0], goal_maps[:, 0], obstacles[:, 0], opt_trajs[:, 0], astar.g_ratio, max_iters)
     try:
         loss, hist, paths, iters, status = ops.astar_l1_loss(*args, order_in=order, check_order=check, summary_ptr=astar.summary_ptr(row, cost_maps), exact=exact)

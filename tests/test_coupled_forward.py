@@ -353,3 +353,86 @@ def test_replay_of_an_arbitrary_lockstep_log_equals_the_dense_reverse_mode():
                                                       None, ops.FLAG_LOCKSTEP)
         err = float(np.abs(grad[0].cpu().numpy() - want).max())
         assert err <= 1e-5 * max(1.0, float(np.abs(want).max())), (case, err)
+
+
+@pytest.mark.gpu
+def test_errors_come_before_the_coupled_note_on_every_lane(monkeypatch):
+    """One launch that reports BOTH an error cell (3: a walled-in goal) and the batch-coupled note (14: negative costs at g_ratio 0.5): every
+    lane raises for the error and none of them answers the note -- no exact re-run, no repair, no second launch."""
+    import re
+    import torch
+    import neural_astar.planner.differentiable_astar as DA
+    from neural_astar import _native, ops
+    from neural_astar.parallel import InFlightPlanner
+    g = G.load("coupled_signed_g050")
+    walled = g.B - 1  # (the slowest map of the golden's batch: the maps that wander on past their goals stay as they are)
+    passable = g.passable.copy()
+    r0, c0 = (int(v) for v in np.argwhere(g.goal_maps[walled, 0])[0])
+    for dr in (-1, 0, 1):
+        for dc in (-1, 0, 1):
+            if (dr or dc) and 0 <= r0 + dr < g.H and 0 <= c0 + dc < g.W:
+                passable[walled, 0, r0 + dr, c0 + dc] = 0
+    c, s, go, _ = _gpu_inputs(g)
+    p = torch.from_numpy(passable).to(c.device)
+    board = ops.StatusBoard.of(c.device)
+    row = board.acquire()
+    status = ops.search_nograd(c, s, go, p, g.g_ratio, g.max_iters, summary_ptr=board.ptr(row))[3]
+    torch.cuda.synchronize()
+    r = board.np[row].copy()
+    board.release(row)
+    assert r[ops.STATUS_UNSOLVABLE] and r[ops.SUMMARY_COUPLED], r  # the launch says both
+    assert status.cpu().tolist() == [0] * walled + [ops.STATUS_UNSOLVABLE]
+
+    def planner(mode=True):
+        da = DA.DifferentiableAstar(g.g_ratio, g.Tmax, check_solvable=mode).to(c.device).eval()
+        calls = {"exact": 0, "noted": 0}
+        exact_search, note_status = da.exact_search, da.note_status
+        monkeypatch.setattr(da, "exact_search", lambda *a, **k: (calls.__setitem__("exact", calls["exact"] + 1), exact_search(*a, **k))[1])
+        monkeypatch.setattr(da, "note_status", lambda *a, **k: (calls.__setitem__("noted", calls["noted"] + 1), note_status(*a, **k))[1])
+        return da, calls
+
+    launches = {"search_nograd": 0, "search_routes": 0}
+    for fn in launches:
+        monkeypatch.setattr(DA.ops, fn, lambda *a, _fn=fn, _f=getattr(ops, fn), **k: (launches.__setitem__(_fn, launches[_fn] + 1), _f(*a, **k))[1])
+    with torch.no_grad():
+        # (a) the native host lane of a checked forward()
+        assert _native.load_fastlane() is not None
+        da, calls = planner()
+        with pytest.raises(DA.UnsolvableMapError) as native:
+            da(c, s, go, p)
+        assert calls == {"exact": 0, "noted": 0} and launches["search_nograd"] == 0  # (the native lane: nothing of the general path ran)
+        assert da.last_status.cpu().tolist() == status.cpu().tolist()
+        # (b) the same call through the general Python lane
+        da, calls = planner()
+        with pytest.raises(DA.UnsolvableMapError) as general:
+            da(c, s, go, p, store_intermediate_results=True)
+        assert calls == {"exact": 0, "noted": 1} and launches["search_nograd"] == 1
+        number = re.compile(r"#\d+")
+        assert number.sub("#N", str(general.value)) == number.sub("#N", str(native.value))
+        assert f"batch rows [{walled}]" in str(native.value)
+        # (c) a deferred verdict: forward() returns, the verdict raises late and repairs nothing
+        da, calls = planner("deferred")
+        out = da(c, s, go, p)
+        assert out.histories.shape == (g.B, 1, g.H, g.W)
+        with pytest.raises(DA.UnsolvableMapError, match="an EARLIER call: check_solvable='deferred' delivers verdicts late"):
+            da.raise_if_unsolvable()
+        assert calls["exact"] == 0 and launches["search_nograd"] == 2 and not da._pending
+        # (d) batches in flight
+        da, calls = planner()
+
+        class _P:  # the planner surface InFlightPlanner.submit needs (cost map and obstacle map are two tensors)
+            astar = da
+            learn_obstacles = False
+
+            @staticmethod
+            def encode(m, st, gl):
+                return c
+        fly = InFlightPlanner(_P(), streams=2, unit_cost=False)
+        with pytest.raises(DA.UnsolvableMapError, match="InFlightPlanner, batch #0 since the last collection"):
+            fly.plan_many([(p, s, go)])
+        assert fly.reruns == 0 and calls["exact"] == 0
+        # (e) plan_routes()
+        da, calls = planner()
+        with pytest.raises(DA.UnsolvableMapError):
+            da.plan_routes(c, s, go, p)
+        assert launches["search_routes"] == 1 and calls["exact"] == 0
