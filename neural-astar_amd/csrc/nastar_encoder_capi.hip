@@ -22,13 +22,8 @@ static int launch_conv(const ConvArgs& ca, hipStream_t stream)
     constexpr int KS = (CIN < ENC_KS) ? CIN : ENC_KS;
     constexpr size_t lds = (size_t)(ENC_TH + 2) * (ENC_TW + 2) * ENC_PIX_B + (size_t)9 * (KS / 16) * 2 * NT * 16 + (size_t)NT * 8;
     auto kern = &nastar_conv3x3_kernel<CIN, COUT, NT, kRelu, kFinal>;
-    int rc = ensure_lds(kern, lds);
-    if (rc) return rc;
     const unsigned grid = (unsigned)((size_t)ca.B * (ca.H / ENC_TH) * (ca.W / ENC_TW) * (COUT / NT));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(ENC_THREADS), lds, stream, ca);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3(grid), dim3(ENC_THREADS), lds, stream, ca);
 }
 
 // 32x32 images, CIN >= 32 and COUT >= 64: whole-image workgroups (nastar_conv3x3_img32_kernel), otherwise the tiled kernel
@@ -54,31 +49,21 @@ static int launch_conv_auto(const ConvArgs& ca, hipStream_t stream)
     const bool whole = ca.H == 32 && ca.W == 32;
     void (*kern)(const ConvArgs) = &nastar_conv3x3_img32_kernel<CIN, COUT, kRelu>;
     if (!whole) kern = &nastar_conv3x3_img32_kernel<CIN, COUT, kRelu, false, 0, true>;
-    int rc = ensure_lds(kern, I32_LDS_BYTES);
-    if (rc) return rc;
     int n_cu = 0;
-    if ((rc = conv_cu_count(&n_cu))) return rc;
+    if (int rc = conv_cu_count(&n_cu)) return rc;
     const long long items = (long long)ca.B * (ca.H / 32) * (ca.W / 32) * (COUT / I32_NT);
     const unsigned grid = (unsigned)(items < n_cu ? items : n_cu);  // persistent: one workgroup per CU
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), I32_LDS_BYTES, stream, ca);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3(grid), dim3(512), I32_LDS_BYTES, stream, ca);
 }
 
 // input assembly + 2 -> 32 + 32 -> 64 channels for 32x32 maps in one persistent kernel
 static int launch_conv_stem32(const StemArgs& sa, hipStream_t stream, bool f16 = false)
 {
     void (*kern)(const StemArgs) = f16 ? &nastar_conv_stem32_kernel<true> : &nastar_conv_stem32_kernel<false>;
-    int rc = ensure_lds(kern, STEM_LDS_BYTES);
-    if (rc) return rc;
     int n_cu = 0;
-    if ((rc = conv_cu_count(&n_cu))) return rc;
+    if (int rc = conv_cu_count(&n_cu)) return rc;
     const unsigned grid = (unsigned)(sa.B < n_cu ? sa.B : n_cu);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), STEM_LDS_BYTES, stream, sa);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3(grid), dim3(512), STEM_LDS_BYTES, stream, sa);
 }
 
 // 128 -> 256 channels + the fused 256 -> 1 layer + sigmoid * const: writes the cost map, the 256-channel tensor never exists
@@ -89,15 +74,10 @@ static int launch_conv_fused_final(const ConvArgs& ca, hipStream_t stream, bool 
     if (split) kern = &nastar_conv3x3_img32_kernel<128, 256, true, true, 0, false, true, true>;  // f16x3: the last layer's three split products chained in the epilogue
     if (enc_flags() & 512) kern = &nastar_conv3x3_img32_kernel<128, 256, true, true, 2>;  // dev: every workgroup reads image 0 (L2 hits)
     if (enc_flags() & 256) kern = &nastar_conv3x3_img32_kernel<128, 256, true, true, 1>;  // dev: cycle totals into the (unused) output slab
-    int rc = ensure_lds(kern, I32_LDS_BYTES);
-    if (rc) return rc;
     int n_cu = 0;
-    if ((rc = conv_cu_count(&n_cu))) return rc;
+    if (int rc = conv_cu_count(&n_cu)) return rc;
     const unsigned grid = (unsigned)(ca.B < n_cu ? ca.B : n_cu);  // a workgroup owns whole images
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), I32_LDS_BYTES, stream, ca);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3(grid), dim3(512), I32_LDS_BYTES, stream, ca);
 }
 
 // f16x3 split precision: persistent 32x32-tile kernel over 3 CIN virtual channels; H, W multiples of 32
@@ -107,40 +87,25 @@ static int launch_conv_split(const ConvArgs& ca, hipStream_t stream)
     const bool whole = ca.H == 32 && ca.W == 32;
     void (*kern)(const ConvArgs) = &nastar_conv3x3_img32_kernel<CIN, COUT, true, false, 0, false, true, kSplit>;
     if (!whole) kern = &nastar_conv3x3_img32_kernel<CIN, COUT, true, false, 0, true, true, kSplit>;
-    int rc = ensure_lds(kern, I32_LDS_BYTES);
-    if (rc) return rc;
     int n_cu = 0;
-    if ((rc = conv_cu_count(&n_cu))) return rc;
+    if (int rc = conv_cu_count(&n_cu)) return rc;
     const long long items = (long long)ca.B * (ca.H / 32) * (ca.W / 32) * (COUT / I32_NT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(items < n_cu ? items : n_cu)), dim3(512), I32_LDS_BYTES, stream, ca);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3((unsigned)(items < n_cu ? items : n_cu)), dim3(512), I32_LDS_BYTES, stream, ca);
 }
 
 static int launch_conv_final_split_pass(const ConvArgs& ca, hipStream_t stream)
 {
     constexpr size_t lds = (size_t)(ENC_TH + 2) * (ENC_TW + 2) * ENC_PIX_B + (size_t)(((ENC_TH + 2) * (ENC_TW + 2) + 31) / 32) * 32 * 9 * 4;
     auto kern = &nastar_conv3x3_final_kernel<256, true>;
-    int rc = ensure_lds(kern, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)ca.B * (ca.H / ENC_TH) * (ca.W / ENC_TW))), dim3(ENC_THREADS), lds, stream, ca);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3((unsigned)((size_t)ca.B * (ca.H / ENC_TH) * (ca.W / ENC_TW))), dim3(ENC_THREADS), lds, stream, ca);
 }
 
 static int launch_conv_final(const ConvArgs& ca, hipStream_t stream)
 {
     constexpr size_t lds = (size_t)(ENC_TH + 2) * (ENC_TW + 2) * ENC_PIX_B + (size_t)(((ENC_TH + 2) * (ENC_TW + 2) + 31) / 32) * 32 * 9 * 4;
     auto kern = &nastar_conv3x3_final_kernel<256>;
-    int rc = ensure_lds(kern, lds);
-    if (rc) return rc;
     const unsigned grid = (unsigned)((size_t)ca.B * (ca.H / ENC_TH) * (ca.W / ENC_TW));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(ENC_THREADS), lds, stream, ca);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3(grid), dim3(ENC_THREADS), lds, stream, ca);
 }
 // ---- fp16 forms of the same encoder ------------------------------------------------------------------------------------------------------
 // f16x3 ("fp32-grade"): every conv is hi*hi + lo*hi + hi*lo on the fp16 MFMA, activations [hi | lo];  f16: plain fp16 operands.
@@ -203,16 +168,14 @@ static int encoder_fp16_impl(const float* map, const float* start, const float* 
                 continue;
             }
         }
-        if (plus)
-            hipLaunchKernelGGL((nastar_conv_first_f32_kernel<2, kSplit>), dim3(pg), dim3(256), 0, s, map + off, start + off, goal + off,
-                               w1_f32, scale[0], shift[0], a1, nb, H, W);
-        else
-            hipLaunchKernelGGL((nastar_conv_first_f32_kernel<1, kSplit>), dim3(pg), dim3(256), 0, s, map + off, map, map, w1_f32, scale[0],
-                               shift[0], a1, nb, H, W);
+        int rc = plus ? launch_grid(nastar_conv_first_f32_kernel<2, kSplit>, dim3(pg), dim3(256), 0, s, map + off, start + off, goal + off, w1_f32,
+                                    scale[0], shift[0], a1, nb, H, W)
+                      : launch_grid(nastar_conv_first_f32_kernel<1, kSplit>, dim3(pg), dim3(256), 0, s, map + off, map, map, w1_f32, scale[0],
+                                    shift[0], a1, nb, H, W);
+        if (rc) return rc;
         ConvArgs ca;
         ca.B = nb; ca.H = H; ca.W = W; ca.out_f32 = nullptr; ca.final_mul = final_mul;
         ca.wfin = nullptr; ca.wfin_lo = nullptr; ca.fscale = nullptr; ca.fshift = nullptr; ca.in_stride = 0; ca.pass_flags = 0; ca.zacc = nullptr;
-        int rc;
         ca.in = a1; ca.out = a2; ca.wpack = w2; ca.scale = scale[1]; ca.shift = shift[1];
         if ((rc = launch_conv_split<32, 64, kSplit>(ca, s))) return rc;
         ca.in = a2; ca.out = a3; ca.wpack = w3; ca.scale = scale[2]; ca.shift = shift[2];
@@ -242,8 +205,6 @@ static int encoder_fp16_impl(const float* map, const float* start, const float* 
             if ((rc = launch_conv_final_split_pass(ca, s))) return rc;
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return NASTAR_OK;
 }
 
@@ -307,8 +268,9 @@ int nastar_encoder_cnn_forward(const float* map, const float* start, const float
             sa.out = pong;
             if ((rc = launch_conv_stem32(sa, s))) return rc;
         } else {
-            hipLaunchKernelGGL(nastar_encoder_prep_kernel, dim3(pg), dim3(256), 0, s, map + off, plus ? start + off : map,
-                               plus ? goal + off : map, x0, npix, plus);
+            if ((rc = launch_grid(nastar_encoder_prep_kernel, dim3(pg), dim3(256), 0, s, map + off, plus ? start + off : map,
+                                  plus ? goal + off : map, x0, npix, plus)))
+                return rc;
             ca.in = x0; ca.out = ping; ca.wpack = wpack[0]; ca.scale = scale[0]; ca.shift = shift[0];
             if ((rc = launch_conv<16, 32, 32, true, false>(ca, s))) return rc;
             ca.in = ping; ca.out = pong; ca.wpack = wpack[1]; ca.scale = scale[1]; ca.shift = shift[1];
@@ -326,8 +288,6 @@ int nastar_encoder_cnn_forward(const float* map, const float* start, const float
         ca.in = pong; ca.out = nullptr; ca.out_f32 = cost_out + off; ca.wpack = wpack[4]; ca.scale = scale[4]; ca.shift = shift[4];
         if ((rc = launch_conv_final(ca, s))) return rc;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return NASTAR_OK;
 }
 
@@ -380,13 +340,8 @@ static int launch_ds_conv(const DsConvArgs& a, hipStream_t s)
 {
     auto kern = &nastar_conv3x3_f32mfma_kernel<CIN, COUTP, kPool, kFinal>;
     const size_t lds = (size_t)(DS_TR + 2) * (DS_TC + 2) * CIN * sizeof(float);
-    int rc = ensure_lds(kern, lds);
-    if (rc) return rc;
     const unsigned grid = (unsigned)((size_t)a.B * ((a.H + DS_TR - 1) / DS_TR) * ((a.W + DS_TC - 1) / DS_TC));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * (COUTP / 32)), lds, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3(grid), dim3(64 * (COUTP / 32)), lds, s, a);
 }
 static int ds_cin_pad(int c) { return c <= 2 ? 2 : 4; }
 }  // namespace nastar
@@ -422,13 +377,13 @@ int nastar_encoder_cnn_downsize_forward(const float* image, const float* start, 
     float* x = static_cast<float*>(workspace);
     const long long npix = (long long)B * H * W;
     const unsigned pg = (unsigned)((npix + 255) / 256 < 16384 ? (npix + 255) / 256 : 16384);
-    hipLaunchKernelGGL(nastar_downsize_prep_kernel, dim3(pg), dim3(256), 0, s, image, plus ? start : image, plus ? goal : image, x, B, C,
-                       H, W, plus ? h : 1, plus ? w : 1, plus, cp);
+    int rc = launch_grid(nastar_downsize_prep_kernel, dim3(pg), dim3(256), 0, s, image, plus ? start : image, plus ? goal : image, x, B, C, H, W,
+                         plus ? h : 1, plus ? w : 1, plus, cp);
+    if (rc) return rc;
     DsConvArgs a;
     a.B = B; a.H = H; a.W = W; a.final_mul = final_mul;
     a.in = x;
     float* nxt = x + (size_t)npix * cp;
-    int rc = NASTAR_OK;
     for (int l = 0; l < depth; ++l) {  // hidden blocks: conv + BN + ReLU + 2x2 max-pool (encoder.py:91-95)
         a.w = wts[l]; a.scale = scale[l]; a.shift = shift[l]; a.out = nxt;
         if (l == 0) rc = cp == 2 ? launch_ds_conv<2, 32, true, false>(a, s) : launch_ds_conv<4, 32, true, false>(a, s);
@@ -441,11 +396,10 @@ int nastar_encoder_cnn_downsize_forward(const float* image, const float* start, 
         nxt += (size_t)B * a.H * a.W * (32 << l);
     }
     a.w = wts[depth]; a.scale = scale[depth]; a.shift = shift[depth]; a.out = cost_out;  // last block + sigmoid * const
-    if (depth == 1) rc = launch_ds_conv<32, 32, false, true>(a, s);
-    else if (depth == 2) rc = launch_ds_conv<64, 32, false, true>(a, s);
-    else if (depth == 3) rc = launch_ds_conv<128, 32, false, true>(a, s);
-    else rc = launch_ds_conv<256, 32, false, true>(a, s);
-    return rc;
+    if (depth == 1) return launch_ds_conv<32, 32, false, true>(a, s);
+    if (depth == 2) return launch_ds_conv<64, 32, false, true>(a, s);
+    if (depth == 3) return launch_ds_conv<128, 32, false, true>(a, s);
+    return launch_ds_conv<256, 32, false, true>(a, s);
 }
 
 }  // extern "C"
@@ -457,22 +411,16 @@ template <int CIN, int COUT, bool kRelu, bool kSplit>
 static int launch_img32_layer(const ConvArgs& ca, hipStream_t stream)
 {
     void (*kern)(const ConvArgs) = &nastar_conv3x3_img32_kernel<CIN, COUT, kRelu, false, 0, false, true, kSplit>;
-    int rc = ensure_lds(kern, I32_LDS_BYTES);
-    if (rc) return rc;
     int n_cu = 0;
-    if ((rc = conv_cu_count(&n_cu))) return rc;
+    if (int rc = conv_cu_count(&n_cu)) return rc;
     const long long items = (long long)ca.B * (COUT / I32_NT);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(items < n_cu ? items : n_cu)), dim3(512), I32_LDS_BYTES, stream, ca);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3((unsigned)(items < n_cu ? items : n_cu)), dim3(512), I32_LDS_BYTES, stream, ca);
 }
 
 template <int CIN, int COUT>
 static int launch_img32_pick(const ConvArgs& ca, bool relu, bool split, hipStream_t s)
 {
-    if (split) return relu ? launch_img32_layer<CIN, COUT, true, true>(ca, s) : launch_img32_layer<CIN, COUT, false, true>(ca, s);
-    return relu ? launch_img32_layer<CIN, COUT, true, false>(ca, s) : launch_img32_layer<CIN, COUT, false, false>(ca, s);
+    return with_bools([&](auto rl, auto sp) { return launch_img32_layer<CIN, COUT, rl, sp>(ca, s); }, relu, split);
 }
 
 }  // namespace nastar
@@ -505,19 +453,13 @@ int nastar_conv3x3_img32_f16(const uint16_t* in, const uint16_t* wpack, const fl
 // ---- generic fp16 / f16x3 building blocks (nastar_conv_flat.hip.h): any image size, any channel count -------------------------------
 namespace nastar {
 
-
 template <int NT, bool kFinal, bool kSplit>
 static int launch_flat(const FlatConvArgs& fa, hipStream_t s)
 {
     auto kern = &nastar_conv3x3_flat_kernel<NT, kFinal, kSplit>;
     const size_t lds = (size_t)FC_PIXB + (size_t)(fa.wide ? FC_WSLOTS : FC_TP + 2 * (fa.W + 1)) * FC_PIXB + (size_t)9 * 4 * NT * 16 + (size_t)NT * 8;
-    int rc = ensure_lds(kern, lds);
-    if (rc) return rc;
     const unsigned grid = (unsigned)(((fa.ntiles + 7) / 8) * 8 * (fa.COUT / NT));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(FC_THREADS), lds, s, fa);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return launch_grid(kern, dim3(grid), dim3(FC_THREADS), lds, s, fa);
 }
 
 }  // namespace nastar
@@ -544,9 +486,11 @@ int nastar_conv3x3_f16(const uint16_t* in, const uint16_t* in2, const uint16_t* 
     fa.wide = W > FC_MAXW ? 1 : 0;  // images wider than the flat tiles' halo allows: 2-D tiles (64 x 4 pixels of one image, framed)
     if (fa.wide) fa.ntiles = B * ((H + FC_WTH - 1) / FC_WTH) * ((W + FC_WTW - 1) / FC_WTW);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (fin) return split ? launch_flat<32, true, true>(fa, s) : launch_flat<32, true, false>(fa, s);
-    if (cout % 64 == 0) return split ? launch_flat<64, false, true>(fa, s) : launch_flat<64, false, false>(fa, s);
-    return split ? launch_flat<32, false, true>(fa, s) : launch_flat<32, false, false>(fa, s);
+    return with_bools([&](auto sp) {
+        if (fin) return launch_flat<32, true, sp>(fa, s);
+        if (cout % 64 == 0) return launch_flat<64, false, sp>(fa, s);
+        return launch_flat<32, false, sp>(fa, s);
+    }, split);
 }
 
 int nastar_maxpool2x2_f16(const uint16_t* in, uint16_t* out, int B, int H, int W, int C, int split, void* stream)
@@ -557,11 +501,7 @@ int nastar_maxpool2x2_f16(const uint16_t* in, uint16_t* out, int B, int H, int W
     const long long total = (long long)B * (H / 2) * (W / 2) * (C / 8);
     const unsigned grid = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (split) hipLaunchKernelGGL(nastar_maxpool2x2_f16_kernel<true>, dim3(grid), dim3(256), 0, s, in, out, B, H, W, C);
-    else hipLaunchKernelGGL(nastar_maxpool2x2_f16_kernel<false>, dim3(grid), dim3(256), 0, s, in, out, B, H, W, C);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    return with_bools([&](auto sp) { return launch_grid(nastar_maxpool2x2_f16_kernel<sp>, dim3(grid), dim3(256), 0, s, in, out, B, H, W, C); }, split != 0);
 }
 
 int nastar_encoder_prep_f16(const float* map, const float* start, const float* goal, int plus, long long npix, int cp, int split,
@@ -570,11 +510,8 @@ int nastar_encoder_prep_f16(const float* map, const float* start, const float* g
     if (!map || !out || (plus && (!start || !goal))) return NASTAR_ERR_NULL;
     if (npix <= 0 || cp < 2 || cp % 8) return NASTAR_ERR_BAD_SHAPE;
     const unsigned grid = (unsigned)((npix + 255) / 256 < 65536 ? (npix + 255) / 256 : 65536);
-    hipLaunchKernelGGL(nastar_encoder_prep_f16_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), map, start, goal,
+    return launch_grid(nastar_encoder_prep_f16_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), map, start, goal,
                        out, npix, plus, cp, split);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
 }
 
 }  // extern "C"

@@ -68,8 +68,8 @@ template <bool kSplit, bool kU1 = false>
 __global__ __launch_bounds__(256) void nastar_chan_stats_kernel(const uint16_t* __restrict__ u, const uint16_t* __restrict__ v,
                                                                 const float* __restrict__ ms, const float* __restrict__ mt,
                                                                 double* __restrict__ sums, unsigned int* __restrict__ amax_bits,
-                                                                long long npix, int C, double* __restrict__ part = nullptr,
-                                                                float* __restrict__ amax_part = nullptr, const U1Src u1 = U1Src())
+                                                                long long npix, int C, double* __restrict__ part,
+                                                                float* __restrict__ amax_part, const U1Src u1)
 {
     __shared__ double red[256][16];
     const int stride = kSplit ? 2 * C : C;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void nastar_chan_affine_kernel(const uint16_t*
                                                                  const float* __restrict__ k1, const float* __restrict__ k2,
                                                                  const float* __restrict__ k3, const float* __restrict__ ms,
                                                                  const float* __restrict__ mt, uint16_t* __restrict__ out, long long npix,
-                                                                 int C, int relu, const U1Src u1 = U1Src())
+                                                                 int C, int relu, const U1Src u1)
 {
     const int stride = kSplit ? 2 * C : C;
     const int CG = C >> 3;
@@ -624,7 +624,7 @@ __global__ __launch_bounds__(256) void nastar_bn_coef_bwd_kernel(const double* _
                                                                  const float* __restrict__ gamma, double npix, float* __restrict__ gscale,
                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                  float* __restrict__ c1, float* __restrict__ c2, float* __restrict__ c3, int C,
-                                                                 const float* __restrict__ gscale_in = nullptr)
+                                                                 const float* __restrict__ gscale_in)
 {
     __shared__ float red[4];
     const double S = (double)(gscale_in ? gscale_in[0] : gscale[0]);  // gscale_in: read the scale there, leave it alone, write the new one to gscale
@@ -826,8 +826,8 @@ __global__ __launch_bounds__(256) void nastar_bn1_sigmoid_bwd_kernel(const float
 // consecutive lanes (C/8 a power of two <= 64) and are summed by xor shuffles; lane `tap` of the group stores P[p][tap]
 template <bool kSplit>
 __global__ __launch_bounds__(256) void nastar_co1_proj_kernel(const uint16_t* __restrict__ a, const float* __restrict__ w, float* __restrict__ P,
-                                                              long long npix, int C, const float* __restrict__ k2 = nullptr,
-                                                              const float* __restrict__ k3 = nullptr)
+                                                              long long npix, int C, const float* __restrict__ k2,
+                                                              const float* __restrict__ k3)
 {
     const int stride = kSplit ? 2 * C : C;
     const int CG = C >> 3;
@@ -918,8 +918,8 @@ __global__ __launch_bounds__(256) void nastar_co1_shift_kernel(const float* __re
 // order by nastar_co1_wgrad_finish_kernel (double accumulation) -> dw [C][9] = torch's [1][C][3][3]
 template <bool kSplit>
 __global__ __launch_bounds__(256) void nastar_co1_wgrad_kernel(const float* __restrict__ d, const uint16_t* __restrict__ a, float* __restrict__ part,
-                                                               long long npix, int C, int H, int W, const float* __restrict__ k2 = nullptr,
-                                                               const float* __restrict__ k3 = nullptr)
+                                                               long long npix, int C, int H, int W, const float* __restrict__ k2,
+                                                               const float* __restrict__ k3)
 {
     __shared__ float co1_red[2048];  // [NPL][C]: NPL * C = 2048 whatever C
     const int stride = kSplit ? 2 * C : C;

@@ -7,20 +7,6 @@
 
 using namespace nastar;
 
-// one wavefront relaxes a map of up to 1024 cells (16 cells per lane, the barrier of a sweep costs nothing); 4 wavefronts up to 4096 cells,
-// 16 above -- 16 cells per lane at every limit
-template <int T>
-static int fields_launch(const FieldArgs& a, int B, hipStream_t stream)
-{
-    const size_t lds = fields_lds_bytes(a.H * a.W);
-    int rc = ensure_lds(nastar_cost_to_go_kernel<T>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(nastar_cost_to_go_kernel<T>, dim3((unsigned)B), dim3(T), lds, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
-}
-
 extern "C" {
 
 int nastar_fields_abi(void) { return NASTAR_FIELDS_ABI; }
@@ -38,9 +24,12 @@ int nastar_cost_to_go_sweeps(const float* cost, const float* goal, const float* 
     const FieldArgs a{cost, goal, passable, dist_out, policy_out, status_out, sweeps_out, H, W, neighbor_mask,
                       aligned16(cost) && aligned16(goal) && aligned16(passable) ? 1 : 0};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (HW <= 1024) return fields_launch<64>(a, B, s);
-    if (HW <= 4096) return fields_launch<256>(a, B, s);
-    return fields_launch<1024>(a, B, s);
+    const size_t lds = fields_lds_bytes(HW);
+    // one wavefront relaxes a map of up to 1024 cells (16 cells per lane, the barrier of a sweep costs nothing); 4 wavefronts up to 4096 cells,
+    // 16 above -- 16 cells per lane at every limit
+    if (HW <= 1024) return launch_grid(nastar_cost_to_go_kernel<64>, dim3((unsigned)B), dim3(64), lds, s, a);
+    if (HW <= 4096) return launch_grid(nastar_cost_to_go_kernel<256>, dim3((unsigned)B), dim3(256), lds, s, a);
+    return launch_grid(nastar_cost_to_go_kernel<1024>, dim3((unsigned)B), dim3(1024), lds, s, a);
 }
 
 int nastar_cost_to_go(const float* cost, const float* goal, const float* passable, int B, int H, int W, unsigned neighbor_mask, float* dist_out,

@@ -21,15 +21,6 @@ static inline bool tiled_shape_ok(int B, int H, int W)
     return B >= 1 && H >= 1 && W >= 1 && (long long)H * W <= kTiledMaxCells && (long long)B * tiled_tiles(H, W) <= (1ll << 24);   // (x 256 lanes: the 2^32 threads a grid may have)
 }
 
-template <typename K, typename... A>
-static int tiled_launch(K kernel, unsigned grid, hipStream_t stream, const A&... args)
-{
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTileT), 0, stream, args...);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
-}
-
 extern "C" {
 
 int nastar_fields_tiled_abi(void) { return NASTAR_FIELDS_TILED_ABI; }
@@ -62,7 +53,7 @@ int nastar_cost_to_go_tiled_batched(const float* cost, const float* goal, const 
     if (workspace_bytes < nastar_cost_to_go_tiled_workspace_bytes(B, H, W) || (reinterpret_cast<uintptr_t>(workspace) & 3u) != 0) return NASTAR_ERR_WORKSPACE;
 
     const int ty = (H + kTileH - 1) / kTileH, tx = (W + kTileW - 1) / kTileW;
-    const unsigned grid = (unsigned)((long long)B * ty * tx);
+    const dim3 grid((unsigned)((long long)B * ty * tx));
     int32_t* words = reinterpret_cast<int32_t*>(workspace);
     const TiledArgs a{cost, goal, passable, dist_out, policy_out, status_out, visits_out, words, words + (size_t)B * 4, B, H, W, ty, tx, neighbor_mask};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -72,7 +63,7 @@ int nastar_cost_to_go_tiled_batched(const float* cost, const float* goal, const 
 
     hipError_t e = hipMemsetAsync(words, 0, (size_t)B * 16, s);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(per-map words)");
-    int rc = tiled_launch(nastar_fields_tiled_init_kernel, grid, s, a);
+    int rc = launch_grid(nastar_fields_tiled_init_kernel, grid, dim3(kTileT), 0, s, a);
     if (rc) return rc;
 
     // words[0..B): the last round in which the map marked a tile; words[B..2B): the last round in which it relaxed one
@@ -83,7 +74,7 @@ int nastar_cost_to_go_tiled_batched(const float* cost, const float* goal, const 
     while (!quiet && launched < limit) {
         const long long n = std::min((long long)per_batch, limit - launched);
         for (long long k = 0; k < n; ++k) {
-            rc = tiled_launch(nastar_fields_tiled_round_kernel, grid, s, a, (int)(launched + 1));
+            rc = launch_grid(nastar_fields_tiled_round_kernel, grid, dim3(kTileT), 0, s, a, (int)(launched + 1));
             if (rc) return rc;
             ++launched;
         }
@@ -95,10 +86,10 @@ int nastar_cost_to_go_tiled_batched(const float* cost, const float* goal, const 
         active_rounds = *std::max_element(host.begin() + B, host.end());
     }
     if (policy_out) {
-        rc = tiled_launch(nastar_fields_tiled_policy_kernel, grid, s, a);
+        rc = launch_grid(nastar_fields_tiled_policy_kernel, grid, dim3(kTileT), 0, s, a);
         if (rc) return rc;
     }
-    rc = tiled_launch(nastar_fields_tiled_finish_kernel, grid, s, a, (int)launched);
+    rc = launch_grid(nastar_fields_tiled_finish_kernel, grid, dim3(kTileT), 0, s, a, (int)launched);
     if (rc) return rc;
     if (rounds_out) *rounds_out = active_rounds;
     return NASTAR_OK;

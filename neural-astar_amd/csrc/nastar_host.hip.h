@@ -31,15 +31,26 @@ inline int ensure_lds(K kernel, size_t bytes)
     return NASTAR_OK;
 }
 
+// The ONE place a kernel is launched from: raises the dynamic-LDS limit where the launch needs more than 64 KiB, issues the launch and
+// checks it.  A sequence of launches calls this once per kernel and returns at the first failure: nothing more is issued on a stream
+// after a launch on it failed.  (The arguments are forwarded by reference: a null pointer is written `nullptr`, never `0`, and a kernel's
+// trailing arguments are all written out -- a function pointer carries no default arguments.)
 template <typename K, typename... A>
-inline int launch(K kernel, int B, size_t lds, hipStream_t stream, const A&... args)
+inline int launch_grid(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args)
 {
     int rc = ensure_lds(kernel, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64), lds, stream, args...);
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return NASTAR_OK;
+}
+
+// the search and replay kernels: one wavefront per map
+template <typename K, typename... A>
+inline int launch(K kernel, int B, size_t lds, hipStream_t stream, const A&... args)
+{
+    return launch_grid(kernel, dim3((unsigned)B), dim3(64), lds, stream, args...);
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -56,6 +67,5 @@ inline auto with_bools(F&& f, bool b, Bools... rest)
     if (b) return with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
     return with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
-
 
 }  // namespace nastar

@@ -91,12 +91,9 @@ int nastar_policy_rollout(const float* opt_policies, const int32_t* start_idx, c
     if (n_maps <= 0 || starts_per_map <= 0 || H <= 0 || W <= 0 || n_actions <= 0 || n_actions > 8) return NASTAR_ERR_BAD_SHAPE;
     const long long n_roll = (long long)n_maps * starts_per_map;
     if (n_roll > (1ll << 30)) return NASTAR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(nastar_policy_rollout_kernel, dim3((unsigned)((n_roll + 63) / 64)), dim3(64), 0,
+    return launch_grid(nastar_policy_rollout_kernel, dim3((unsigned)((n_roll + 63) / 64)), dim3(64), 0,
                        reinterpret_cast<hipStream_t>(stream), opt_policies, start_idx, goal_idx, (int)n_roll, starts_per_map,
                        n_actions, H, W, opt_trajs_out, status_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
 }
 
 int nastar_l1_loss(const float* histories, const float* opt_trajs, long long numel, float* loss_out, void* workspace,
@@ -107,11 +104,9 @@ int nastar_l1_loss(const float* histories, const float* opt_trajs, long long num
     if (workspace_bytes < (size_t)kL1Blocks * sizeof(double)) return NASTAR_ERR_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(nastar_l1_partial_kernel, dim3(kL1Blocks), dim3(256), 0, s, histories, opt_trajs, numel, part);
-    hipLaunchKernelGGL(nastar_l1_final_kernel, dim3(1), dim3(256), 0, s, part, numel, loss_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    const int rc = launch_grid(nastar_l1_partial_kernel, dim3(kL1Blocks), dim3(256), 0, s, histories, opt_trajs, numel, part);
+    if (rc) return rc;
+    return launch_grid(nastar_l1_final_kernel, dim3(1), dim3(256), 0, s, part, numel, loss_out);
 }
 
 }  // extern "C"

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64, 8) void nastar_solvable_proof_kernel(const floa
         if (proved_out != nullptr && valid && r == 0) proved_out[b] = proved ? 1 : 0;
         all_proved = all_proved && __ballot(valid && !proved) == 0ull;
     }
-    // the terminal word, by the pattern of the search's completion flag (nastar_capi.hip: note_done): release, count, and the workgroup that
+    // the terminal word, by the pattern of the search's completion flag (nastar_search_kernels.hip.h: note_done): release, count, and the workgroup that
     // counts last publishes with a system-scope store.  The counter carries "some map was not proved" in a high bit and is 0 again first.
     if (lane == 0) {
         __threadfence();

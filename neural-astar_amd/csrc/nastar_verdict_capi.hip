@@ -72,12 +72,8 @@ int nastar_solvable_proof(const float* cost, const float* start, const float* go
     if ((e = hipStreamWaitEvent(l->stream, l->event, 0)) != hipSuccess) return hip_fail(e, "hipStreamWaitEvent");
     const int mpw = 64 / W, ngroups = (B + mpw - 1) / mpw;
     const unsigned grid = (unsigned)(ngroups < l->max_grid ? ngroups : l->max_grid);
-    if (W == 32)
-        hipLaunchKernelGGL(nastar_solvable_proof_kernel<5>, dim3(grid), dim3(64), 0, l->stream, cost, start, goal, passable, B, proved_out, word, counter);
-    else
-        hipLaunchKernelGGL(nastar_solvable_proof_kernel<6>, dim3(grid), dim3(64), 0, l->stream, cost, start, goal, passable, B, proved_out, word, counter);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "kernel launch");
-    return NASTAR_OK;
+    if (W == 32) return launch(nastar_solvable_proof_kernel<5>, (int)grid, 0, l->stream, cost, start, goal, passable, B, proved_out, word, counter);
+    return launch(nastar_solvable_proof_kernel<6>, (int)grid, 0, l->stream, cost, start, goal, passable, B, proved_out, word, counter);
 }
 
 int nastar_solvable_proof_sync(void)

@@ -277,6 +277,183 @@ def test_argument_validation_needs_no_gpu():
     assert lib.nastar_unpack_outputs(one, 0, 8, 8, one, one, None) == _native.NASTAR_ERR_BAD_SHAPE
 
 
+def _validation_table():
+    """[(symbol, a call that would pass every check, [(the arguments changed, the status that change must give), ...])] for the entry points
+    of csrc/nastar_encoder_train_capi.hip, csrc/nastar_encoder_capi.hip and nastar_cost_to_go*: one change per status an entry point can
+    return before its first HIP call.  The unchanged call is never made: with these pointers it would reach a launch."""
+    import ctypes
+    from neural_astar import _native as n
+    NULL, SHAPE, UNSUP, WS = n.NASTAR_ERR_NULL, n.NASTAR_ERR_BAD_SHAPE, n.NASTAR_ERR_UNSUPPORTED, n.NASTAR_ERR_WORKSPACE
+    o, o2, odd = 16, 32, 24  # non-NULL pointer values, never dereferenced on these paths; `odd` is not 16-byte aligned
+    arr = (ctypes.c_void_p * 5)(*([o] * 5))
+    big = 1 << 40
+    t = []
+
+    def entry(symbol, base, *cases):
+        t.append((symbol, base, cases))
+
+    def chan(C="C"):  # the channel layout of the streaming kernels: a multiple of 8, at most 2048, C / 8 divides 256
+        return [({C: 12}, UNSUP), ({C: 24}, UNSUP), ({C: 4096}, UNSUP)]
+
+    # ---- csrc/nastar_encoder_train_capi.hip
+    entry("nastar_conv3x3_wgrad_f16",
+          dict(dz=o, a=o, dw=o, B=1, H=32, W=32, co=32, ci=32, co_real=32, ci_real=32, split=0, out_scale=1.0, grad_scale_dev=None, workspace=o,
+               workspace_bytes=big, stream=None),
+          ({"dz": None}, NULL), ({"workspace": None}, NULL), ({"B": 0}, SHAPE), ({"co_real": 33}, SHAPE), ({"ci_real": 0}, SHAPE),
+          ({"co": 48, "co_real": 48}, UNSUP), ({"ci": 16, "ci_real": 16}, UNSUP), ({"dz": odd}, SHAPE), ({"workspace": odd}, SHAPE),
+          ({"workspace_bytes": 0}, WS), ({"split": 1, "workspace_bytes": 9 * 32 * 32 * 4 - 1}, WS))
+    entry("nastar_chan_stats_f16", dict(u=o, v=o, ms=o, mt=o, sums=o, amax_out=o, npix=64, C=8, split=0, stream=None),
+          ({"v": None}, NULL), ({"sums": None}, NULL), ({"ms": None}, NULL), ({"npix": 0}, SHAPE), ({"C": 0}, SHAPE), *chan())
+    entry("nastar_chan_stats_f16_ws",
+          dict(u=o, v=o, ms=o, mt=o, sums=o, amax_out=o, npix=64, C=8, split=0, workspace=o, workspace_bytes=big, stream=None),
+          ({"v": None}, NULL), ({"workspace": None}, NULL), ({"mt": None}, NULL), ({"npix": 0}, SHAPE), *chan(), ({"workspace_bytes": 16}, WS))
+    entry("nastar_bn_stats_coef_fwd_f16",
+          dict(z=o, npix=64, C=8, split=0, gamma=o, beta=o, eps=1e-5, momentum=0.1, running_mean=o, running_var=o, k2=o, k3=o, mean_out=o,
+               invstd_out=o, sums_out=None, workspace=o, workspace_bytes=big, stream=None),
+          ({"z": None}, NULL), ({"k3": None}, NULL), ({"running_var": None}, NULL), ({"C": 0}, SHAPE), *chan(), ({"workspace_bytes": 16}, WS))
+    entry("nastar_bn_stats_coef_bwd_f16",
+          dict(da=o, z=o, ms=o, mt=o, npix=64, C=8, split=0, mean=o, invstd=o, gamma=o, gscale_in=o, gscale_out=o2, dgamma=o, dbeta=o, c1=o, c2=o,
+               c3=o, sums_out=None, workspace=o, workspace_bytes=big, stream=None),
+          ({"da": None}, NULL), ({"c3": None}, NULL), ({"npix": 0}, SHAPE), ({"gscale_out": o}, SHAPE), *chan(), ({"workspace_bytes": 16}, WS))
+    entry("nastar_chan_affine_f16", dict(u=o, v=o, k1=o, k2=o, k3=o, ms=o, mt=o, out=o, npix=64, C=8, relu=1, split=0, stream=None),
+          ({"v": None}, NULL), ({"k1": None}, NULL), ({"npix": 0}, SHAPE), *chan())
+    entry("nastar_pack_conv_weight_f16",
+          dict(w=o, co=32, ci=32, transpose_flip=0, split=0, bias=None, wpack=o, scale_out=o, shift_out=o, scal_out=o, reuse_max=0, stream=None),
+          ({"w": None}, NULL), ({"scal_out": None}, NULL), ({"co": 0}, SHAPE), ({"ci": -1}, SHAPE))
+    entry("nastar_absmax_multi_f32", dict(table=o, n=1, scal=o, stream=None), ({"table": None}, NULL), ({"n": 0}, SHAPE), ({"n": 65536}, SHAPE))
+    entry("nastar_pack_conv_weights_multi_f16", dict(table=o, n=1, max_tiles=1, split=0, scal=o, flat16=o, flatf=o, stream=None),
+          ({"flatf": None}, NULL), ({"n": 0}, SHAPE), ({"max_tiles": 0}, SHAPE), ({"max_tiles": 65536}, SHAPE))
+    entry("nastar_rmsprop_multi_f32", dict(table=o, n=1, lr=1e-3, alpha=0.99, eps=1e-8, stream=None),
+          ({"table": None}, NULL), ({"n": 0}, SHAPE), ({"n": 65536}, SHAPE))
+    entry("nastar_bn_coef_fwd",
+          dict(sums=o, gamma=o, beta=o, eps=1e-5, npix=64, momentum=0.1, running_mean=o, running_var=o, k2=o, k3=o, mean_out=o, invstd_out=o, C=8,
+               stream=None),
+          ({"sums": None}, NULL), ({"running_var": None}, NULL), ({"C": 0}, SHAPE), ({"npix": 0}, SHAPE))
+    entry("nastar_bn_coef_bwd_io",
+          dict(sums=o, amax_dy=o, mean=o, invstd=o, gamma=o, npix=64, gscale_in=o, gscale_out=o2, dgamma=o, dbeta=o, c1=o, c2=o, c3=o, C=8,
+               stream=None),
+          ({"amax_dy": None}, NULL), ({"gscale_in": None}, NULL), ({"C": 0}, SHAPE), ({"npix": 0}, SHAPE))
+    entry("nastar_bn_coef_bwd",
+          dict(sums=o, amax_dy=o, mean=o, invstd=o, gamma=o, npix=64, gscale=o, dgamma=o, dbeta=o, c1=o, c2=o, c3=o, C=8, stream=None),
+          ({"gscale": None}, NULL), ({"C": 0}, SHAPE), ({"npix": 0}, SHAPE))
+    entry("nastar_grad_seed_f16", dict(d=o, npix=64, split=0, dzb=o, gscale=o, amax_scratch=o, stream=None),
+          ({"d": None}, NULL), ({"amax_scratch": None}, NULL), ({"npix": 0}, SHAPE))
+    entry("nastar_maxpool2x2_bwd_f16", dict(r=o, dp=o, dr=o, B=1, H=8, W=8, C=8, split=0, stream=None),
+          ({"dr": None}, NULL), ({"B": 0}, SHAPE), ({"H": 7}, UNSUP), ({"C": 12}, UNSUP))
+    for sym, ptrs in (("nastar_upcat_f16", ("x", "skip", "out")), ("nastar_upcat_bwd_f16", ("dcat", "dx", "dskip"))):
+        opt = ptrs[1] if sym == "nastar_upcat_f16" else ptrs[2]  # the pointer that may be NULL when c2 == 0
+        entry(sym, dict(**{p: o for p in ptrs}, B=1, H=8, W=8, c1=8, c2=8, split=0, stream=None),
+              ({ptrs[0]: None}, NULL), ({opt: None}, NULL), ({"B": 0}, SHAPE), ({"c2": -8}, SHAPE), ({"W": 7}, UNSUP), ({"c1": 12}, UNSUP))
+    entry("nastar_grad_add_f16", dict(a=o, scale_a=o, b=o, scale_b=o, out=o, scale_out=o, npix=64, C=8, split=0, stream=None),
+          ({"b": None}, NULL), ({"scale_out": None}, NULL), ({"npix": 0}, SHAPE), ({"C": 12}, UNSUP))
+    entry("nastar_bn1_fwd_partial", dict(z=o, n=64, part=o, stream=None), ({"z": None}, NULL), ({"part": None}, NULL), ({"n": 0}, SHAPE))
+    entry("nastar_bn1_sigmoid_fwd",
+          dict(z=o, n=64, part=o, nparts=1, n_total=64.0, gamma=o, beta=o, eps=1e-5, cmul=None, momentum=0.1, running_mean=o, running_var=o,
+               cost_out=o, stat_out=o, stream=None),
+          ({"z": None}, NULL), ({"running_var": None}, NULL), ({"n": 0}, SHAPE), ({"nparts": 0}, SHAPE), ({"nparts": 257}, SHAPE),
+          ({"n_total": 63.0}, SHAPE))
+    entry("nastar_bn1_sigmoid_bwd_partial", dict(z=o, dcost=o, n=64, stat=o, gamma=o, beta=o, cmul=None, part=o, stream=None),
+          ({"dcost": None}, NULL), ({"part": None}, NULL), ({"n": 0}, SHAPE))
+    entry("nastar_bn1_sigmoid_bwd",
+          dict(z=o, dcost=o, n=64, stat=o, gamma=o, beta=o, cmul=None, part=o, nparts=1, n_total=64.0, dz_out=o, dgamma_out=o, dbeta_out=o,
+               dconst_out=None, stream=None),
+          ({"stat": None}, NULL), ({"dbeta_out": None}, NULL), ({"n": 0}, SHAPE), ({"nparts": 257}, SHAPE), ({"n_total": 63.0}, SHAPE))
+    co1 = [({"B": 0}, SHAPE), ({"C": 0}, SHAPE), ({"C": 4}, UNSUP), ({"C": 24}, UNSUP), ({"C": 1024}, UNSUP), ({"workspace_bytes": 16}, WS)]
+    entry("nastar_conv3x3_co1_f16",
+          dict(a=o, w=o, bias=None, B=1, H=8, W=8, C=8, split=0, k2=o, k3=o, z_out=o, workspace=o, workspace_bytes=big, stream=None),
+          ({"a": None}, NULL), ({"workspace": None}, NULL), ({"k3": None}, NULL), *co1)
+    entry("nastar_conv3x3_co1_wgrad_f16",
+          dict(d=o, a=o, B=1, H=8, W=8, C=8, split=0, k2=o, k3=o, dw_out=o, workspace=o, workspace_bytes=big, stream=None),
+          ({"d": None}, NULL), ({"dw_out": None}, NULL), ({"k3": None}, NULL), *co1)
+    entry("nastar_grad_scale_f32", dict(d=o, npix=64, gscale=o, amax_scratch=o, stream=None),
+          ({"d": None}, NULL), ({"gscale": None}, NULL), ({"npix": 0}, SHAPE))
+    entry("nastar_chan_stats_u1_f16_ws",
+          dict(d=o, wlast=o, gscale=o, B=1, H=8, W=8, v=o, ms=o, mt=o, sums=o, amax_out=None, C=8, split=0, workspace=o, workspace_bytes=big,
+               stream=None),
+          ({"wlast": None}, NULL), ({"sums": None}, NULL), ({"H": 0}, SHAPE), ({"C": 0}, SHAPE), *chan(), ({"workspace_bytes": 16}, WS))
+    entry("nastar_bn_stats_coef_bwd_u1_f16",
+          dict(d=o, wlast=o, B=1, H=8, W=8, z=o, ms=o, mt=o, C=8, split=0, mean=o, invstd=o, gamma=o, gscale_in=o, gscale_out=o2, dgamma=o,
+               dbeta=o, c1=o, c2=o, c3=o, sums_out=None, workspace=o, workspace_bytes=big, stream=None),
+          ({"d": None}, NULL), ({"workspace": None}, NULL), ({"W": 0}, SHAPE), ({"gscale_out": o}, SHAPE), *chan(), ({"workspace_bytes": 16}, WS))
+    entry("nastar_chan_affine_u1_f16",
+          dict(d=o, wlast=o, gscale=o, B=1, H=8, W=8, z=o, k1=o, k2=o, k3=o, ms=o, mt=o, out=o, C=8, split=0, stream=None),
+          ({"gscale": None}, NULL), ({"out": None}, NULL), ({"B": 0}, SHAPE), *chan())
+    # ---- csrc/nastar_encoder_capi.hip
+    entry("nastar_encoder_cnn_forward",
+          dict(map=o, start=o, goal=o, plus=1, B=1, H=32, W=32, wpack=arr, scale=arr, shift=arr, final_mul=1.0, cost_out=o, workspace=o,
+               workspace_bytes=big, stream=None),
+          ({"cost_out": None}, NULL), ({"wpack": None}, NULL), ({"goal": None}, NULL), ({"B": 0}, SHAPE), ({"W": 40}, UNSUP),
+          ({"workspace_bytes": 32 * 32 * 800 - 1}, WS))
+    for sym, per_pixel in (("nastar_encoder_cnn_forward_f16x3", 2 * 480 * 2 + 4), ("nastar_encoder_cnn_forward_f16", 480 * 2 + 4)):
+        entry(sym,
+              dict(map=o, start=o, goal=o, plus=1, B=1, H=32, W=32, w1_f32=o, wts=arr, scale=arr, shift=arr, final_mul=1.0, cost_out=o,
+                   workspace=o, workspace_bytes=big, stream=None),
+              ({"map": None}, NULL), ({"w1_f32": None}, NULL), ({"start": None}, NULL), ({"shift": None}, NULL), ({"H": 0}, SHAPE),
+              ({"H": 48}, UNSUP), ({"workspace_bytes": 32 * 32 * per_pixel - 1}, WS))
+    entry("nastar_conv3x3_bf16", dict(inp=o, wpack=o, scale=o, shift=o, out=o, B=1, H=32, W=32, cin=32, cout=64, relu=1, stream=None),
+          ({"inp": None}, NULL), ({"B": 0}, SHAPE), ({"H": 30}, SHAPE), ({"cin": 48}, UNSUP), ({"cout": 32}, UNSUP))
+    entry("nastar_encoder_cnn_downsize_forward",
+          dict(image=o, start=o, goal=o, plus=1, B=1, C=3, H=32, W=32, h=4, w=4, depth=3, wts=arr, scale=arr, shift=arr, final_mul=1.0,
+               cost_out=o, workspace=o, workspace_bytes=big, stream=None),
+          ({"image": None}, NULL), ({"goal": None}, NULL), ({"workspace": None}, NULL), ({"depth": 5}, SHAPE), ({"C": 4}, SHAPE),
+          ({"H": 36}, UNSUP), ({"h": 0}, UNSUP), ({"workspace_bytes": 16}, WS))
+    entry("nastar_conv3x3_img32_f16", dict(inp=o, wpack=o, scale=o, shift=o, out=o, B=1, cin=32, cout=64, flags=1, stream=None),
+          ({"scale": None}, NULL), ({"B": 0}, SHAPE), ({"out": odd}, SHAPE), ({"flags": 2}, UNSUP), ({"cin": 48}, UNSUP), ({"cout": 256}, UNSUP))
+    entry("nastar_conv3x3_f16",
+          dict(inp=o, in2=o, wpack=o, scale=o, shift=o, out=o, out_f32=None, B=1, H=8, W=8, c1=32, c2=32, cout=32, flags=1, final_mul=1.0,
+               stream=None),
+          ({"inp": None}, NULL), ({"out": None}, NULL), ({"in2": None}, NULL), ({"flags": 2}, NULL), ({"B": 0}, SHAPE), ({"c2": -32}, SHAPE),
+          ({"c1": 16}, UNSUP), ({"cout": 48}, UNSUP), ({"flags": 2, "out_f32": o, "cout": 64}, UNSUP), ({"flags": 4, "H": 7}, UNSUP),
+          ({"B": 1 << 20, "H": 64, "W": 64}, UNSUP), ({"in2": odd}, SHAPE))
+    entry("nastar_maxpool2x2_f16", dict(inp=o, out=o, B=1, H=8, W=8, C=8, split=0, stream=None),
+          ({"out": None}, NULL), ({"C": 0}, SHAPE), ({"W": 7}, UNSUP), ({"C": 12}, UNSUP))
+    entry("nastar_encoder_prep_f16", dict(map=o, start=o, goal=o, plus=1, npix=64, cp=8, split=0, out=o, stream=None),
+          ({"out": None}, NULL), ({"start": None}, NULL), ({"npix": 0}, SHAPE), ({"cp": 1}, SHAPE), ({"cp": 12}, SHAPE))
+    # ---- nastar_cost_to_go* (include/nastar_fields.h, include/nastar_fields_tiled.h): an invalid neighbor_mask is refused before any other check
+    field = dict(cost=o, goal=o, passable=o, B=1, H=8, W=8, neighbor_mask=0x1EF, dist_out=o, policy_out=None, status_out=o)
+    field_cases = [({"neighbor_mask": 0x10, "cost": None}, UNSUP), ({"neighbor_mask": 0x200}, UNSUP), ({"cost": None}, NULL),
+                   ({"status_out": None}, NULL), ({"B": 0}, SHAPE)]
+    entry("nastar_cost_to_go", dict(field, stream=None), *field_cases, ({"H": 128, "W": 129}, UNSUP))
+    entry("nastar_cost_to_go_sweeps", dict(field, sweeps_out=None, stream=None), *field_cases, ({"H": 128, "W": 129}, UNSUP))
+    tiled = dict(field, visits_out=None, workspace=o, workspace_bytes=big, max_rounds=0)
+    tiled_cases = field_cases + [({"workspace": None}, NULL), ({"max_rounds": -1}, SHAPE), ({"H": 1024, "W": 1153}, UNSUP),
+                                 ({"workspace_bytes": 16}, WS), ({"workspace": 18}, WS)]
+    entry("nastar_cost_to_go_tiled", dict(tiled, rounds_out=None, stream=None), *tiled_cases)
+    entry("nastar_cost_to_go_tiled_batched", dict(tiled, launches_per_batch=0, rounds_out=None, stream=None), *tiled_cases,
+          ({"launches_per_batch": -1}, SHAPE))
+    return t
+
+
+def test_argument_validation_table_needs_no_gpu():
+    """The training, encoder and cost-to-go entry points: every status an entry point can return before its first HIP call, one call each
+    (_validation_table).  Every call differs from a valid one by the change under test, so none gets past the argument checks."""
+    from neural_astar import _native
+    lib = _native.load()
+    signatures = dict(_native.SIGNATURES, **_native.FIELD_SIGNATURES, **_native.TILED_FIELD_SIGNATURES)
+    table = _validation_table()
+    seen = {}
+    for symbol, base, cases in table:
+        assert len(base) == len(signatures[symbol].split(" ")[1]) and list(base)[-1] == "stream", symbol
+        for change, status in cases:
+            assert change and set(change) <= set(base) and any(base[k] != v for k, v in change.items()), (symbol, change)
+            assert status in (_native.NASTAR_ERR_NULL, _native.NASTAR_ERR_BAD_SHAPE, _native.NASTAR_ERR_UNSUPPORTED, _native.NASTAR_ERR_WORKSPACE)
+            assert getattr(lib, symbol)(*dict(base, **change).values()) == status, (symbol, change)
+            seen.setdefault(symbol, set()).add(status)
+    # every status-returning entry point the two encoder translation units define is in the table (nastar_bn1_parts returns a count) ...
+    csrc = os.path.join(ROOT, "neural-astar_amd", "csrc")
+    defined = set()
+    for f in ("nastar_encoder_train_capi.hip", "nastar_encoder_capi.hip"):
+        defined |= set(re.findall(r"^int (nastar_[a-z0-9_]+)\(", open(os.path.join(csrc, f)).read(), flags=re.M))
+    defined |= {s for s in signatures if s.startswith("nastar_cost_to_go") and not s.endswith("_bytes")}
+    assert defined - {"nastar_bn1_parts"} == set(seen) and len(seen) == len(table) == 41
+    # ... with a NULL and a BAD_SHAPE call each, and a WORKSPACE call wherever a workspace size is passed
+    for symbol, base, _ in table:
+        need = {_native.NASTAR_ERR_NULL, _native.NASTAR_ERR_BAD_SHAPE} | ({_native.NASTAR_ERR_WORKSPACE} if "workspace_bytes" in base else set())
+        assert need <= seen[symbol], (symbol, seen[symbol])
+    assert lib.nastar_bn1_parts(0) == 0 and lib.nastar_bn1_parts(1) == 1 and lib.nastar_bn1_parts(1 << 40) == 256
+    assert lib.nastar_last_error() == b""  # no call reached the HIP runtime
+
+
 def test_product_has_no_cpu_fallback_and_never_touches_the_oracle():
     import torch
     from neural_astar.planner import VanillaAstar
