@@ -27,6 +27,7 @@ NASTAR_ERR_NOT_UNIT_COST = 7  # per-map status only
 NASTAR_ERR_BAD_HEURISTIC = 8  # per-map status only
 NASTAR_ERR_BAD_COST = 9  # per-map status of include/nastar_fields.h only
 NASTAR_ERR_NO_CONVERGENCE = 10  # per-map status of include/nastar_fields.h only
+NASTAR_ERR_PLATEAU = 11  # per-map status of include/nastar_fields_grad.h only
 
 _ERR_NAMES = {
     NASTAR_ERR_BAD_SHAPE: "bad shape (B, H, W and max_iters must be positive)",
@@ -199,6 +200,15 @@ VERDICT_SIGNATURES = {
     "nastar_solvable_proof_sync": "i ",
 }
 
+# the signatures of include/nastar_fields_grad.h (the eighth header: the gradient of the cost-to-go field with respect to the cost maps), same
+# letter code; a table of its own (tests/test_fields_grad.py compares it with ITS header)
+FIELD_GRAD_SIGNATURES = {
+    "nastar_fields_grad_abi": "i ",
+    "nastar_fields_grad_max_cells": "i ",
+    # dist, goal, passable, grad_dist, B, H, W, neighbor_mask, grad_cost_out, status_out, sweeps_out, stream
+    "nastar_fields_backward": "i ppppiiiupppp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -330,6 +340,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, TILED_FIELD_SIGNATURES, TILED_FIELD_SIGNATURES)
     if hasattr(lib, "nastar_verdict_abi"):  # (and the seventh)
         _bind(lib, VERDICT_SIGNATURES, VERDICT_SIGNATURES)
+    if hasattr(lib, "nastar_fields_grad_abi"):  # (and the eighth)
+        _bind(lib, FIELD_GRAD_SIGNATURES, FIELD_GRAD_SIGNATURES)
     _lib = lib
     return lib
 

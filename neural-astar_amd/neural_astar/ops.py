@@ -16,7 +16,8 @@ from .status import (CLEAN, PROOF_MAX_G_RATIO, STATUS_BAD_HEURISTIC, STATUS_NOT_
                      SUMMARY_WORDS, StatusBoard, Summary, coupling_possible, needs_exact, proof_covers)  # (a launch's status lives in status.py; the names stay importable from here)
 
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
-           "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput", "cost_to_go_tiled"]
+           "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput", "cost_to_go_tiled",
+           "fields_backward", "FIELD_PLATEAU", "FIELDS_GRAD_MAX_CELLS"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -856,7 +857,7 @@ def _raise_bad_cost(st: torch.Tensor, B: int, what: str) -> None:
 
 
 def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
-               policies: bool = True, sweeps_out: Optional[torch.Tensor] = None, tiled: bool = False) -> FieldOutput:
+               policies: bool = True, sweeps_out: Optional[torch.Tensor] = None, tiled: bool = False, differentiable: bool = False) -> FieldOutput:
     """The cost-to-go field of every map of the batch, and the optimal policy that follows it (include/nastar_fields.h).  What follows
     describes the default, ``tiled=False``: one launch, maps of at most ``FIELDS_MAX_CELLS`` cells; see the last sentence for ``tiled=True``.
 
@@ -866,7 +867,19 @@ def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps:
     synchronisation; not inside a hipGraph capture): a NaN or a negative cost on a passable cell raises ValueError naming the rows; a map
     without a goal is reported in ``status``, not raised.  Maps of more than ``FIELDS_MAX_CELLS`` cells raise NotImplementedError.
     ``sweeps_out``: a [B] int32 tensor that receives the sweeps every map's relaxation took (probes).  ``tiled=True`` computes the same
-    tensors with ``cost_to_go_tiled`` -- at any map size up to ``FIELDS_TILED_MAX_CELLS``; that call blocks and cannot be captured."""
+    tensors with ``cost_to_go_tiled`` -- at any map size up to ``FIELDS_TILED_MAX_CELLS``; that call blocks and cannot be captured.
+
+    ``differentiable=True``: the same launch and the same values, and ``dists`` carries an autograd node when ``cost_maps`` requires a
+    gradient and grad mode is on (include/nastar_fields_grad.h: its backward is one launch of ``nastar_fields_backward`` on the current
+    stream; the gradient goes to ``cost_maps`` alone, in its own shape; ``policies`` and ``status`` are not differentiable).  ``dists``
+    holds +inf on obstacles and unreachable cells: a loss masks them itself (``torch.isfinite``); whatever gradient arrives for those
+    cells, and for goals, is ignored.  A map with a live cell that has no strictly closer neighbour -- a zero-cost plateau -- has no such
+    gradient and raises ValueError naming the rows.  Not with ``tiled=True`` and not inside a stream capture (NotImplementedError)."""
+    if differentiable:
+        if tiled:
+            raise NotImplementedError(f"cost_to_go: differentiable=True is the one-workgroup kernel's (maps of at most {FIELDS_GRAD_MAX_CELLS} cells); "
+                                      "the tiled relaxation has no backward")
+        return _cost_to_go_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, sweeps_out)
     if tiled:
         if sweeps_out is not None:
             raise ValueError("cost_to_go: sweeps_out belongs to the one-workgroup kernel; cost_to_go_tiled() reports rounds and tile visits")
@@ -898,6 +911,97 @@ def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps:
             if stuck:
                 raise RuntimeError(f"cost_to_go: map(s) {stuck[:16]} did not converge within H*W sweeps (NASTAR_ERR_NO_CONVERGENCE)")
     return FieldOutput(dists, pol, status)
+
+
+# ---- include/nastar_fields_grad.h: the gradient of that field with respect to the cost maps -------------------
+FIELD_PLATEAU = 11  # NASTAR_ERR_PLATEAU (per-map status of nastar_fields_backward): a live cell without a strictly closer neighbour
+FIELDS_GRAD_MAX_CELLS = 16384  # nastar_fields_grad_max_cells(): every size nastar_cost_to_go takes
+
+
+def fields_backward(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, grad_dists: torch.Tensor,
+                    neighbor_mask: Optional[int] = None, sweeps_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``nastar_fields_backward`` as it is (include/nastar_fields_grad.h): ``dists`` as ``cost_to_go`` returned them, the goal and obstacle
+    maps and the mask of that call, and an upstream gradient of ``dists``' shape -> ``(grad_cost [B,H,W], status [B] int32)``.  One launch
+    on the current stream, nothing is read back: a map whose status is ``FIELD_PLATEAU`` has an all-zero gradient.  ``grad_dists`` is read
+    on live cells only (not a goal, finite distance); ``grad_cost`` is exactly 0 on every other cell.  What ``cost_to_go(...,
+    differentiable=True)`` runs in its backward; probes and tests call it directly."""
+    maps, mask, (B, H, W) = _field_inputs(dists, goal_maps, obstacles_maps, neighbor_mask)
+    if not torch.is_tensor(grad_dists) or grad_dists.dtype != torch.float32 or grad_dists.numel() != B * H * W or tuple(grad_dists.shape[-2:]) != (H, W):
+        raise ValueError(f"grad_dists must be a float32 tensor of the shape of dists ({B} maps of {H}x{W}), got "
+                         f"{tuple(grad_dists.shape) if torch.is_tensor(grad_dists) else type(grad_dists).__name__}")
+    if H * W > FIELDS_GRAD_MAX_CELLS:
+        raise NotImplementedError(f"fields_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_GRAD_MAX_CELLS} cells")
+    dev = _field_device(maps)
+    _require_device(grad_dists)
+    if grad_dists.device != dev:
+        raise ValueError(f"dists lives on {dev}, grad_dists on {grad_dists.device}: they must share a device")
+    lib = _native.load()
+    if not hasattr(lib, "nastar_fields_backward"):
+        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields_grad.h: rebuild it with `make -C {_native.CSRC_DIR}`")
+    if sweeps_out is not None and (sweeps_out.dtype != torch.int32 or sweeps_out.numel() != B or sweeps_out.device != dev or not sweeps_out.is_contiguous()):
+        raise ValueError(f"sweeps_out must be a contiguous int32 tensor of {B} elements on {dev}")
+    with torch.no_grad():
+        dist, goal, passable = (_maps3(t.detach()) for t in maps)
+        up = grad_dists.detach().reshape(B, H, W).contiguous()
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_fields_backward(dist.data_ptr(), goal.data_ptr(), passable.data_ptr(), up.data_ptr(), B, H, W, mask, grad.data_ptr(),
+                                            status.data_ptr(), sweeps_out.data_ptr() if sweeps_out is not None else None, _stream_ptr(dev))
+        _native.check(rc, "nastar_fields_backward")
+    return grad, status
+
+
+class _CostToGo(torch.autograd.Function):
+    """``cost_to_go`` as an autograd node: forward = nastar_cost_to_go (the evaluation call, status checks included), backward =
+    nastar_fields_backward.  Only ``dists`` carries gradient, and only to ``cost``."""
+
+    @staticmethod
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, mask, policies, sweeps_out):
+        out = cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=mask, policies=policies, sweeps_out=sweeps_out)
+        ctx.save_for_backward(out.dists, goal_maps, obstacles_maps)
+        ctx.mask, ctx.cost_shape = mask, tuple(cost_maps.shape)
+        ctx.mark_non_differentiable(out.status, *((out.policies,) if policies else ()))
+        ctx.set_materialize_grads(False)
+        return (out.dists, out.status) + ((out.policies,) if policies else ())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_dists, *unused):
+        if g_dists is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        dists, goal_maps, obstacles_maps = ctx.saved_tensors
+        grad, _ = fields_backward(dists, goal_maps, obstacles_maps, g_dists, ctx.mask)
+        shape = ctx.cost_shape
+        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
+            full = grad.new_zeros(shape)
+            full[:, 0] = grad
+            grad = full
+        return (grad.reshape(shape), None, None, None, None, None)
+
+
+def _cost_to_go_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, sweeps_out) -> FieldOutput:
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    if H * W > FIELDS_GRAD_MAX_CELLS:
+        raise NotImplementedError(f"cost_to_go: differentiable=True takes maps of at most {FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = {H * W}")
+    dev = _field_device(maps)
+    with torch.cuda.device(dev):
+        capturing = torch.cuda.is_current_stream_capturing()
+    if capturing:
+        raise NotImplementedError("cost_to_go: differentiable=True reads the per-map status before it returns and cannot be captured into a graph")
+    if cost_maps.requires_grad and torch.is_grad_enabled():
+        res = _CostToGo.apply(cost_maps, goal_maps, obstacles_maps, mask, bool(policies), sweeps_out)
+        out = FieldOutput(res[0], res[2] if policies else None, res[1])
+    else:  # nothing to differentiate: the evaluation call, detached outputs -- and the same check
+        out = cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=mask, policies=policies, sweeps_out=sweeps_out)
+    # which maps have no gradient: the backward kernel's own verdict, from a launch with a zero upstream gradient (its set-up and one quiet
+    # sweep: a zero gradient is at its fixed point from the start) -- so the rule lives in one place, the kernel, and covers policies=False
+    _, st = fields_backward(out.dists.detach(), goal_maps, obstacles_maps, torch.zeros_like(out.dists), mask)
+    flat = torch.nonzero(st.cpu() == FIELD_PLATEAU).flatten().tolist()
+    if flat:
+        raise ValueError(f"cost_to_go: a cell with no strictly closer neighbour (a zero-cost plateau) on map(s) {flat[:16]}{' ...' if len(flat) > 16 else ''} "
+                         f"({len(flat)} of {B}): the field has no gradient with respect to the costs there; the other maps were computed")
+    return out
 
 
 # ---- include/nastar_fields_tiled.h: the same field for maps of up to 1179648 cells, by a tiled relaxation (DESIGN.md section 2, item 6f) ------

@@ -85,10 +85,12 @@ class VanillaAstar(nn.Module):
                                       "the MI355X-native hot path; plan_routes() runs the HIP DifferentiableAstar kernel only")
         return self.astar.plan_routes(map_designs, start_maps, goal_maps, map_designs, heuristic_maps, max_route_len)
 
-    def cost_to_go(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True, tiled: bool = False) -> FieldOutput:
+    def cost_to_go(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True, tiled: bool = False,
+                   differentiable: bool = False) -> FieldOutput:
         """The exact cost to the goal from every cell and the optimal policy (``DifferentiableAstar.cost_to_go``) with cost = passable =
-        ``map_designs``: on a binary map the number of moves to the goal."""
-        return self.astar.cost_to_go(map_designs, goal_maps, map_designs, policies, tiled)
+        ``map_designs``: on a binary map the number of moves to the goal.  ``differentiable=True``: ``dists`` carries the gradient to
+        ``map_designs`` as the cost (not as the obstacles)."""
+        return self.astar.cost_to_go(map_designs, goal_maps, map_designs, policies, tiled, differentiable)
 
 
 class NeuralAstar(VanillaAstar):
@@ -260,9 +262,13 @@ class NeuralAstar(VanillaAstar):
         return self.astar.plan_routes(cost_maps, start_maps, goal_maps, obstacles_maps, heuristic_maps, max_route_len)
 
     def cost_to_go(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True,
-                   tiled: bool = False) -> FieldOutput:
+                   tiled: bool = False, differentiable: bool = False) -> FieldOutput:
         """The cost-to-go field and optimal policy of the PREDICTED cost maps: encodes as ``plan_routes()`` does (detached), then
-        ``DifferentiableAstar.cost_to_go``; ``learn_obstacles`` makes every cell passable, as it does for the search."""
-        cost_maps = self.encode(map_designs, start_maps, goal_maps).detach()
+        ``DifferentiableAstar.cost_to_go``; ``learn_obstacles`` makes every cell passable, as it does for the search.
+        ``differentiable=True``: the encoded cost maps are NOT detached, so the gradient of ``dists`` reaches the encoder's parameters
+        (value-function supervision; the loss masks the +inf cells itself).  The encoder route is what ``encode()`` picks in that mode."""
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        if not differentiable:
+            cost_maps = cost_maps.detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
-        return self.astar.cost_to_go(cost_maps, goal_maps, obstacles_maps, policies, tiled)
+        return self.astar.cost_to_go(cost_maps, goal_maps, obstacles_maps, policies, tiled, differentiable)

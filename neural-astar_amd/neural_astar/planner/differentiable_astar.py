@@ -622,12 +622,14 @@ class DifferentiableAstar(nn.Module):
         return RoutedAstarOutput(hist, paths, routes, lengths, costs)
 
     def cost_to_go(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, policies: bool = True,
-                   tiled: bool = False) -> FieldOutput:
+                   tiled: bool = False, differentiable: bool = False) -> FieldOutput:
         """The exact cost to the goal from EVERY cell of every map, and the optimal policy that follows it (``ops.cost_to_go``, the kernel of
         include/nastar_fields.h), under this module's own move set: ``neighbor_filter`` through the cached mask.  A move costs the cell being
         left, as the search's g does; ``g_ratio``, ``Tmax`` and the heuristic play no part.  An evaluation call: no autograd graph, detached
-        tensors, one host synchronisation for the status."""
-        return ops.cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies, tiled=tiled)
+        tensors, one host synchronisation for the status.  ``differentiable=True``: ``dists`` carries the gradient to ``cost_maps``
+        (include/nastar_fields_grad.h; see ``ops.cost_to_go``): a loss masks the +inf cells itself."""
+        return ops.cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies, tiled=tiled,
+                              differentiable=differentiable)
 
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
