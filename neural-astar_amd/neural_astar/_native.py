@@ -209,6 +209,19 @@ FIELD_GRAD_SIGNATURES = {
     "nastar_fields_backward": "i ppppiiiupppp",
 }
 
+# the signatures of include/nastar_fields_grad_tiled.h (the ninth header: that gradient for maps of up to 1179648 cells, by a tiled subtree
+# sum), same letter code; a table of its own (tests/test_fields_grad_tiled.py compares it with ITS header)
+FIELD_GRAD_TILED_SIGNATURES = {
+    "nastar_fields_grad_tiled_abi": "i ",
+    "nastar_fields_grad_tiled_max_cells": "i ",
+    "nastar_fields_backward_tiled_workspace_bytes": "z iii",
+    # dist, goal, passable, grad_dist, B, H, W, neighbor_mask, grad_cost_out, status_out, visits_out, workspace, workspace_bytes, max_rounds,
+    # rounds_out, stream
+    "nastar_fields_backward_tiled": "i ppppiiiuppppzqpp",
+    # dist, goal, passable, B, H, W, neighbor_mask, status_out, workspace, workspace_bytes, stream
+    "nastar_fields_backward_tiled_status": "i pppiiiuppzp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -342,6 +355,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, VERDICT_SIGNATURES, VERDICT_SIGNATURES)
     if hasattr(lib, "nastar_fields_grad_abi"):  # (and the eighth)
         _bind(lib, FIELD_GRAD_SIGNATURES, FIELD_GRAD_SIGNATURES)
+    if hasattr(lib, "nastar_fields_grad_tiled_abi"):  # (and the ninth)
+        _bind(lib, FIELD_GRAD_TILED_SIGNATURES, FIELD_GRAD_TILED_SIGNATURES)
     _lib = lib
     return lib
 

@@ -17,7 +17,7 @@ from .status import (CLEAN, PROOF_MAX_G_RATIO, STATUS_BAD_HEURISTIC, STATUS_NOT_
 
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
            "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput", "cost_to_go_tiled",
-           "fields_backward", "FIELD_PLATEAU", "FIELDS_GRAD_MAX_CELLS"]
+           "fields_backward", "FIELD_PLATEAU", "FIELDS_GRAD_MAX_CELLS", "fields_backward_tiled", "FIELDS_GRAD_TILED_MAX_CELLS"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -874,11 +874,12 @@ def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps:
     stream; the gradient goes to ``cost_maps`` alone, in its own shape; ``policies`` and ``status`` are not differentiable).  ``dists``
     holds +inf on obstacles and unreachable cells: a loss masks them itself (``torch.isfinite``); whatever gradient arrives for those
     cells, and for goals, is ignored.  A map with a live cell that has no strictly closer neighbour -- a zero-cost plateau -- has no such
-    gradient and raises ValueError naming the rows.  Not with ``tiled=True`` and not inside a stream capture (NotImplementedError)."""
+    gradient and raises ValueError naming the rows.  Not with ``tiled=True`` (``cost_to_go_tiled(..., differentiable=True)`` is that call)
+    and not inside a stream capture (NotImplementedError)."""
     if differentiable:
         if tiled:
             raise NotImplementedError(f"cost_to_go: differentiable=True is the one-workgroup kernel's (maps of at most {FIELDS_GRAD_MAX_CELLS} cells); "
-                                      "the tiled relaxation has no backward")
+                                      "the tiled relaxation's backward is cost_to_go_tiled(..., differentiable=True)")
         return _cost_to_go_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, sweeps_out)
     if tiled:
         if sweeps_out is not None:
@@ -930,7 +931,8 @@ def fields_backward(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
         raise ValueError(f"grad_dists must be a float32 tensor of the shape of dists ({B} maps of {H}x{W}), got "
                          f"{tuple(grad_dists.shape) if torch.is_tensor(grad_dists) else type(grad_dists).__name__}")
     if H * W > FIELDS_GRAD_MAX_CELLS:
-        raise NotImplementedError(f"fields_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_GRAD_MAX_CELLS} cells")
+        raise NotImplementedError(f"fields_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_GRAD_MAX_CELLS} cells "
+                                  "(larger maps: fields_backward_tiled, or cost_to_go_tiled(..., differentiable=True))")
     dev = _field_device(maps)
     _require_device(grad_dists)
     if grad_dists.device != dev:
@@ -983,7 +985,8 @@ class _CostToGo(torch.autograd.Function):
 def _cost_to_go_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, sweeps_out) -> FieldOutput:
     maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     if H * W > FIELDS_GRAD_MAX_CELLS:
-        raise NotImplementedError(f"cost_to_go: differentiable=True takes maps of at most {FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = {H * W}")
+        raise NotImplementedError(f"cost_to_go: differentiable=True takes maps of at most {FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = {H * W} "
+                                  "(larger maps: cost_to_go_tiled(..., differentiable=True))")
     dev = _field_device(maps)
     with torch.cuda.device(dev):
         capturing = torch.cuda.is_current_stream_capturing()
@@ -1025,7 +1028,7 @@ def _tiled_lib():
 
 def cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
                      policies: bool = True, max_rounds: Optional[int] = None, visits_out: Optional[torch.Tensor] = None,
-                     launches_per_batch: Optional[int] = None) -> Tuple[FieldOutput, int]:
+                     launches_per_batch: Optional[int] = None, differentiable: bool = False) -> Tuple[FieldOutput, int]:
     """``cost_to_go`` for maps of up to ``FIELDS_TILED_MAX_CELLS`` cells: the same definition and the same BITS, reached by a tiled
     relaxation (include/nastar_fields_tiled.h) -> ``(FieldOutput, rounds)``.
 
@@ -1035,7 +1038,15 @@ def cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles
     tile was active.  ``max_rounds=None``: the bound H*W + 1, which no accepted input reaches; status 10 then raises RuntimeError as in
     ``cost_to_go``.  With an explicit ``max_rounds`` a map that still has an active tile is reported in ``status`` (``FIELD_NO_CONVERGENCE``),
     not raised; its ``dists`` are upper bounds of its field, finite only where the field is.  ``visits_out``: a [B] int32 tensor that
-    receives every map's (tile, round) visits; ``launches_per_batch``: probes only, not a stable part of the interface (None = the library's choice)."""
+    receives every map's (tile, round) visits; ``launches_per_batch``: probes only, not a stable part of the interface (None = the library's choice).
+
+    ``differentiable=True``: the same launches and the same values, and ``dists`` carries an autograd node when ``cost_maps`` requires a
+    gradient and grad mode is on (include/nastar_fields_grad_tiled.h).  Its backward is ``fields_backward_tiled`` on the current stream: it
+    BLOCKS, like this call, and cannot be captured.  The gradient goes to ``cost_maps`` alone, in its own shape; ``policies`` and
+    ``status`` are not differentiable; a loss masks the +inf cells of ``dists`` itself.  A map with a live cell that has no strictly closer
+    neighbour -- a zero-cost plateau -- has no such gradient and raises ValueError naming the rows, also when nothing requires a gradient."""
+    if differentiable:
+        return _cost_to_go_tiled_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, max_rounds, visits_out, launches_per_batch)
     maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     if H * W > FIELDS_TILED_MAX_CELLS:
         raise NotImplementedError(f"cost_to_go_tiled: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_TILED_MAX_CELLS} cells")
@@ -1076,3 +1087,144 @@ def cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles
             if stuck:
                 raise RuntimeError(f"cost_to_go_tiled: map(s) {stuck[:16]} did not converge within H*W + 1 rounds (NASTAR_ERR_NO_CONVERGENCE)")
     return FieldOutput(dists, pol, status), rounds.value
+
+
+# ---- include/nastar_fields_grad_tiled.h: the gradient of the field for maps of up to 1179648 cells, by a tiled subtree sum
+FIELDS_GRAD_TILED_MAX_CELLS = 1179648  # nastar_fields_grad_tiled_max_cells(): every size cost_to_go_tiled takes
+
+
+def _grad_tiled_lib():
+    lib = _native.load()
+    if not hasattr(lib, "nastar_fields_backward_tiled"):
+        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields_grad_tiled.h: rebuild it with `make -C {_native.CSRC_DIR}`")
+    return lib
+
+
+def _refuse_capture(dev: torch.device, what: str) -> None:
+    with torch.cuda.device(dev):
+        capturing = torch.cuda.is_current_stream_capturing()
+    if capturing:
+        raise RuntimeError(f"{what}: the call synchronises its stream between batches of rounds and cannot be captured into a graph")
+
+
+def _grad_tiled_workspace(lib, B: int, H: int, W: int, dev: torch.device, what: str):
+    nbytes = lib.nastar_fields_backward_tiled_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        raise NotImplementedError(f"{what}: a batch of {B} maps of {H}x{W} has more than 2^24 tiles")
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev), nbytes  # (fp64 elements: 8-byte aligned whatever the allocator does)
+
+
+def fields_backward_tiled(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, grad_dists: torch.Tensor,
+                          neighbor_mask: Optional[int] = None, max_rounds: Optional[int] = None,
+                          visits_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """``nastar_fields_backward_tiled`` as it is (include/nastar_fields_grad_tiled.h): ``fields_backward`` for maps of up to
+    ``FIELDS_GRAD_TILED_MAX_CELLS`` cells, the same definition and -- on the sizes both take -- the same BITS ->
+    ``(grad_cost [B,H,W], status [B] int32, rounds)``.
+
+    ``dists`` as ``cost_to_go`` or ``cost_to_go_tiled`` returned them, the goal and obstacle maps and the mask of that call, an upstream
+    gradient of ``dists``' shape, read on live cells only.  The fp64 sums live in a workspace of 9 bytes per cell; a round is one launch in
+    which every active tile recomputes itself to its local fixed point and marks the neighbours that have to look again; the host reads
+    one word per map after each batch of rounds.  The call therefore BLOCKS on the current stream and is refused (RuntimeError) while that
+    stream is capturing a graph, before anything is enqueued.  A map whose status is ``FIELD_PLATEAU`` has an all-zero gradient.
+    ``max_rounds=None``: the bound H*W + 1, which no input reaches; status 10 then raises RuntimeError.  With an explicit ``max_rounds`` a
+    map that still has an active tile is reported in ``status`` (``FIELD_NO_CONVERGENCE``), not raised, and its gradient is all zero.
+    ``visits_out``: a [B] int32 tensor that receives every map's (tile, round) visits."""
+    maps, mask, (B, H, W) = _field_inputs(dists, goal_maps, obstacles_maps, neighbor_mask)
+    if not torch.is_tensor(grad_dists) or grad_dists.dtype != torch.float32 or grad_dists.numel() != B * H * W or tuple(grad_dists.shape[-2:]) != (H, W):
+        raise ValueError(f"grad_dists must be a float32 tensor of the shape of dists ({B} maps of {H}x{W}), got "
+                         f"{tuple(grad_dists.shape) if torch.is_tensor(grad_dists) else type(grad_dists).__name__}")
+    if H * W > FIELDS_GRAD_TILED_MAX_CELLS:
+        raise NotImplementedError(f"fields_backward_tiled: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_GRAD_TILED_MAX_CELLS} cells")
+    if max_rounds is not None and (isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or max_rounds < 1):
+        raise ValueError(f"max_rounds must be a positive int or None, got {max_rounds!r}")
+    dev = _field_device(maps)
+    _require_device(grad_dists)
+    if grad_dists.device != dev:
+        raise ValueError(f"dists lives on {dev}, grad_dists on {grad_dists.device}: they must share a device")
+    lib = _grad_tiled_lib()
+    if visits_out is not None and (visits_out.dtype != torch.int32 or visits_out.numel() != B or visits_out.device != dev or not visits_out.is_contiguous()):
+        raise ValueError(f"visits_out must be a contiguous int32 tensor of {B} elements on {dev}")
+    _refuse_capture(dev, "fields_backward_tiled")
+    import ctypes
+    with torch.no_grad():
+        workspace, nbytes = _grad_tiled_workspace(lib, B, H, W, dev, "fields_backward_tiled")
+        dist, goal, passable = (_maps3(t.detach()) for t in maps)
+        up = grad_dists.detach().reshape(B, H, W).contiguous()
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        rounds = ctypes.c_int(0)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_fields_backward_tiled(dist.data_ptr(), goal.data_ptr(), passable.data_ptr(), up.data_ptr(), B, H, W, mask, grad.data_ptr(),
+                                                  status.data_ptr(), visits_out.data_ptr() if visits_out is not None else None,
+                                                  workspace.data_ptr(), nbytes, 0 if max_rounds is None else max_rounds,
+                                                  ctypes.cast(ctypes.pointer(rounds), ctypes.c_void_p), _stream_ptr(dev))
+        _native.check(rc, "nastar_fields_backward_tiled")
+        if max_rounds is None:
+            stuck = torch.nonzero(status.cpu() == FIELD_NO_CONVERGENCE).flatten().tolist()
+            if stuck:
+                raise RuntimeError(f"fields_backward_tiled: map(s) {stuck[:16]} did not converge within H*W + 1 rounds (NASTAR_ERR_NO_CONVERGENCE)")
+    return grad, status, rounds.value
+
+
+def _fields_plateau_tiled(dists, goal_maps, obstacles_maps, mask) -> torch.Tensor:
+    """``nastar_fields_backward_tiled_status``: [B] int32, ``FIELD_PLATEAU`` for the maps without a gradient -- the kernel's own verdict"""
+    maps, mask, (B, H, W) = _field_inputs(dists, goal_maps, obstacles_maps, mask)
+    dev = _field_device(maps)
+    lib = _grad_tiled_lib()
+    with torch.no_grad():
+        workspace, nbytes = _grad_tiled_workspace(lib, B, H, W, dev, "cost_to_go_tiled")
+        dist, goal, passable = (_maps3(t.detach()) for t in maps)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_fields_backward_tiled_status(dist.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, status.data_ptr(),
+                                                         workspace.data_ptr(), nbytes, _stream_ptr(dev))
+        _native.check(rc, "nastar_fields_backward_tiled_status")
+    return status
+
+
+class _CostToGoTiled(torch.autograd.Function):
+    """``cost_to_go_tiled`` as an autograd node: forward = nastar_cost_to_go_tiled (the evaluation call, status checks included), backward =
+    nastar_fields_backward_tiled.  Only ``dists`` carries gradient, and only to ``cost``."""
+
+    @staticmethod
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, mask, policies, max_rounds, visits_out, launches_per_batch, rounds_box):
+        out, rounds = cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, neighbor_mask=mask, policies=policies, max_rounds=max_rounds,
+                                       visits_out=visits_out, launches_per_batch=launches_per_batch)
+        rounds_box.append(rounds)
+        ctx.save_for_backward(out.dists, goal_maps, obstacles_maps)
+        ctx.mask, ctx.cost_shape = mask, tuple(cost_maps.shape)
+        ctx.mark_non_differentiable(out.status, *((out.policies,) if policies else ()))
+        ctx.set_materialize_grads(False)
+        return (out.dists, out.status) + ((out.policies,) if policies else ())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_dists, *unused):
+        if g_dists is None or not ctx.needs_input_grad[0]:
+            return (None,) * 9
+        dists, goal_maps, obstacles_maps = ctx.saved_tensors
+        grad, _, _ = fields_backward_tiled(dists, goal_maps, obstacles_maps, g_dists, ctx.mask)
+        shape = ctx.cost_shape
+        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
+            full = grad.new_zeros(shape)
+            full[:, 0] = grad
+            grad = full
+        return (grad.reshape(shape),) + (None,) * 8
+
+
+def _cost_to_go_tiled_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, max_rounds, visits_out, launches_per_batch):
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    kw = dict(neighbor_mask=mask, policies=policies, max_rounds=max_rounds, visits_out=visits_out, launches_per_batch=launches_per_batch)
+    if cost_maps.requires_grad and torch.is_grad_enabled():
+        box: list = []
+        res = _CostToGoTiled.apply(cost_maps, goal_maps, obstacles_maps, mask, bool(policies), max_rounds, visits_out, launches_per_batch, box)
+        out, rounds = FieldOutput(res[0], res[2] if policies else None, res[1]), box[0]
+    else:  # nothing to differentiate: the evaluation call, detached outputs -- and the same check
+        out, rounds = cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, **kw)
+    # which maps have no gradient: the backward's own verdict (its init launch and a status write), so the rule lives in one place, the kernel
+    st = _fields_plateau_tiled(out.dists.detach(), goal_maps, obstacles_maps, mask)
+    flat = torch.nonzero(st.cpu() == FIELD_PLATEAU).flatten().tolist()
+    if flat:
+        raise ValueError(f"cost_to_go_tiled: a cell with no strictly closer neighbour (a zero-cost plateau) on map(s) {flat[:16]}{' ...' if len(flat) > 16 else ''} "
+                         f"({len(flat)} of {B}): the field has no gradient with respect to the costs there; the other maps were computed")
+    return out, rounds

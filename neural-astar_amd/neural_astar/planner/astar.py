@@ -92,6 +92,11 @@ class VanillaAstar(nn.Module):
         ``map_designs`` as the cost (not as the obstacles)."""
         return self.astar.cost_to_go(map_designs, goal_maps, map_designs, policies, tiled, differentiable)
 
+    def cost_to_go_tiled(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True, differentiable: bool = False) -> FieldOutput:
+        """``cost_to_go`` by the tiled relaxation (``DifferentiableAstar.cost_to_go_tiled``: maps of up to 1024x1152, the same bits), with
+        cost = passable = ``map_designs``.  ``differentiable=True``: ``dists`` carries the gradient to ``map_designs`` as the cost."""
+        return self.astar.cost_to_go_tiled(map_designs, goal_maps, map_designs, policies, differentiable)
+
 
 class NeuralAstar(VanillaAstar):
     def __init__(self, g_ratio: float = 0.5, Tmax: float = 1.0, encoder_input: str = "m+",
@@ -272,3 +277,14 @@ class NeuralAstar(VanillaAstar):
             cost_maps = cost_maps.detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.astar.cost_to_go(cost_maps, goal_maps, obstacles_maps, policies, tiled, differentiable)
+
+    def cost_to_go_tiled(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True,
+                         differentiable: bool = False) -> FieldOutput:
+        """``cost_to_go`` of the PREDICTED cost maps by the tiled relaxation (maps of up to 1024x1152; the call blocks).
+        ``differentiable=True``: the encoded cost maps are NOT detached, exactly as in ``cost_to_go``, so a loss on ``dists`` trains the
+        encoder on maps of any size the search takes (include/nastar_fields_grad_tiled.h)."""
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        if not differentiable:
+            cost_maps = cost_maps.detach()
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, policies, differentiable)

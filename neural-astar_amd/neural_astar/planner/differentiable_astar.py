@@ -631,6 +631,14 @@ class DifferentiableAstar(nn.Module):
         return ops.cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies, tiled=tiled,
                               differentiable=differentiable)
 
+    def cost_to_go_tiled(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, policies: bool = True,
+                         differentiable: bool = False) -> FieldOutput:
+        """``cost_to_go`` by the tiled relaxation (``ops.cost_to_go_tiled``: maps of up to ``ops.FIELDS_TILED_MAX_CELLS`` cells, the same
+        bits; the call blocks and cannot be captured), under this module's own move set.  ``differentiable=True``: ``dists`` carries the
+        gradient to ``cost_maps`` (include/nastar_fields_grad_tiled.h; its backward blocks too): a loss masks the +inf cells itself."""
+        return ops.cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies,
+                                    differentiable=differentiable)[0]
+
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
                 heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:
