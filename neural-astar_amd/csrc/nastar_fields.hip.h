@@ -10,15 +10,16 @@
 // x -> fl32(c + x) is monotone, min over m of fl32(c + R[m]) == fl32(c + min over m of R[m]) -- one addition per cell -- and every value a lane
 // can read, fresh or stale, is an upper bound of the fixed point, so the order of the updates changes the number of sweeps and never the
 // result.  (R is read and written through relaxed workgroup-scope atomics: plain ds_read_b32 / ds_write_b32, and no data race in the
-// language's sense.)  A sweep that lowered nothing read final values only: the fixed point.  Detection: one ballot per wavefront, a flag in
-// LDS, ONE barrier per sweep -- three flags in rotation, so that the flag of sweep s is cleared during sweep s + 2, when nobody reads it.
-// The trip count is bounded by H*W whatever the data: a shortest route has fewer than H*W hops, and every sweep settles one more hop.
+// language's sense.)  A sweep that lowered nothing read final values only: the fixed point -- fld_sweep (nastar_field_rules.hip.h) owns the
+// loop and its detection.  The trip count is bounded by H*W whatever the data: a shortest route has fewer than H*W hops, and every sweep
+// settles one more hop.  The policy is fld_best_action of the same header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/nastar_fields.h"
+#include "nastar_field_rules.hip.h"
 
 namespace nastar {
 
@@ -42,9 +43,6 @@ inline size_t fields_lds_bytes(int HW) { return ((size_t)HW * 8 + 15) / 16 * 16 
 
 __device__ __forceinline__ float fld_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void fld_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// the mask bit of the move (dy, dx): filter cell (a, b) opens offset (1-a, 1-b) (include/nastar.h)
-__device__ __forceinline__ constexpr uint32_t fld_bit(int dy, int dx) { return 1u << ((1 - dy) * 3 + (1 - dx)); }
 
 template <int T>
 __global__ __launch_bounds__(T) void nastar_cost_to_go_kernel(const FieldArgs a)
@@ -103,41 +101,30 @@ __global__ __launch_bounds__(T) void nastar_cost_to_go_kernel(const FieldArgs a)
     const uint32_t nm = a.nmask;
     const int r0 = tid / W, c0 = tid - r0 * W;    // the cell of this lane in the first round; round k + 1 is T cells on
     const int dr = T / W, dc = T - dr * W;
-    int sweeps = 0;
-    bool quiet = true;
+    Sweeps run{0, true};
     if (!map_bad && map_goal) {
-        quiet = false;
         // the last cell of this lane, for the sweeps that run backwards
         const int ilast = tid < HW ? tid + (HW - 1 - tid) / T * T : 0;
         const int rl = ilast / W, cl = ilast - rl * W;
-        for (int s = 0; s < HW; ++s) {            // the bound: no input moves it
-            bool changed = false;
-            auto relax = [&](int i, int r, int c) {
-                const bool up = r > 0, dn = r < H - 1, lf = c > 0, rt = c < W - 1;
-                float m = INF;
-#define NASTAR_FLD_NB(dy, dx, ok)                                               \
-    if (nm & fld_bit(dy, dx)) {                                                  \
-        const float v = (ok) ? fld_load(R + i + (dy) * W + (dx)) : INF;           \
-        m = fminf(m, v);                                                         \
-    }
-                NASTAR_FLD_NB(-1, -1, up && lf)
-                NASTAR_FLD_NB(-1, 0, up)
-                NASTAR_FLD_NB(-1, 1, up && rt)
-                NASTAR_FLD_NB(0, -1, lf)
-                NASTAR_FLD_NB(0, 1, rt)
-                NASTAR_FLD_NB(1, -1, dn && lf)
-                NASTAR_FLD_NB(1, 0, dn)
-                NASTAR_FLD_NB(1, 1, dn && rt)
-#undef NASTAR_FLD_NB
-                const float cand = C[i] + m;
-                if (cand < fld_load(R + i)) {
-                    fld_store(R + i, cand);
-                    changed = true;
-                }
-            };
-            // even sweeps run down the map, odd sweeps up: a round reads what the round before it wrote, so values travel many rows per
-            // sweep in the direction of the sweep and one row against it
-            if ((s & 1) == 0) {
+        bool changed;
+        auto relax = [&](int i, int r, int c) {
+            const bool up = r > 0, dn = r < H - 1, lf = c > 0, rt = c < W - 1;
+            float m = INF;
+            fld_each<8>([&](auto j) __attribute__((always_inline)) {
+                constexpr Move o = kChildOffsets[decltype(j)::value];
+                if (nm & fld_bit(o.dy, o.dx)) m = fminf(m, fld_inside(o.dy, o.dx, up, dn, lf, rt) ? fld_load(R + i + o.dy * W + o.dx) : INF);
+            });
+            const float cand = C[i] + m;
+            if (cand < fld_load(R + i)) {
+                fld_store(R + i, cand);
+                changed = true;
+            }
+        };
+        // forward sweeps run down the map, backward sweeps up: a round reads what the round before it wrote, so values travel many rows per
+        // sweep in the direction of the sweep and one row against it
+        run = fld_sweep(flags, HW, [&](bool backwards) {
+            changed = false;
+            if (!backwards) {
                 int r = r0, c = c0;
                 for (int i = tid; i < HW; i += T) {
                     relax(i, r, c);
@@ -160,22 +147,14 @@ __global__ __launch_bounds__(T) void nastar_cost_to_go_kernel(const FieldArgs a)
                     }
                 }
             }
-            const int slot = s % 3;
-            if (__ballot(changed) && (tid & 63) == 0) __hip_atomic_store(&flags[slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (tid == 0) __hip_atomic_store(&flags[slot == 2 ? 0 : slot + 1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __syncthreads();
-            ++sweeps;
-            if (__hip_atomic_load(&flags[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
-                quiet = true;
-                break;
-            }
-        }
+            return changed;
+        });
     }
 
     // ---- epilogue: the field, then the policy planes, every store coalesced ---------------------------------------------------------------------
     if (tid == 0) {
-        a.status[blockIdx.x] = map_bad ? NASTAR_ERR_BAD_COST : !map_goal ? NASTAR_ERR_UNSOLVABLE : quiet ? NASTAR_OK : NASTAR_ERR_NO_CONVERGENCE;
-        if (a.sweeps) a.sweeps[blockIdx.x] = sweeps;
+        a.status[blockIdx.x] = map_bad ? NASTAR_ERR_BAD_COST : !map_goal ? NASTAR_ERR_UNSOLVABLE : run.quiet ? NASTAR_OK : NASTAR_ERR_NO_CONVERGENCE;
+        if (a.sweeps) a.sweeps[blockIdx.x] = run.sweeps;
     }
     float* dist = a.dist + base;
     for (int i = tid; i < HW; i += T) dist[i] = map_bad ? INF : (goal[i] != 0.f ? 0.f : R[i]);
@@ -185,29 +164,8 @@ __global__ __launch_bounds__(T) void nastar_cost_to_go_kernel(const FieldArgs a)
         for (int i = tid; i < HW; i += T) {
             const float d = map_bad ? INF : R[i];
             int best = -1;
-            if (d > 0.f && d < INF) {
-                const bool up = r > 0, dn = r < H - 1, lf = c > 0, rt = c < W - 1;
-                float m = INF;
-                // synthetic.ACTION_MOVES order; a strict < keeps the first action among equals
-#define NASTAR_FLD_ACT(k, dy, dx, ok)                                            \
-    if ((nm & fld_bit(dy, dx)) && (ok)) {                                         \
-        const float v = R[i + (dy) * W + (dx)];                                   \
-        if (v < m) {                                                              \
-            m = v;                                                                \
-            best = k;                                                             \
-        }                                                                         \
-    }
-                NASTAR_FLD_ACT(0, -1, 0, up)
-                NASTAR_FLD_ACT(1, 0, 1, rt)
-                NASTAR_FLD_ACT(2, 0, -1, lf)
-                NASTAR_FLD_ACT(3, 1, 0, dn)
-                NASTAR_FLD_ACT(4, -1, 1, up && rt)
-                NASTAR_FLD_ACT(5, -1, -1, up && lf)
-                NASTAR_FLD_ACT(6, 1, 1, dn && rt)
-                NASTAR_FLD_ACT(7, 1, -1, dn && lf)
-#undef NASTAR_FLD_ACT
-                if (!(m < d)) best = -1;
-            }
+            if (d > 0.f && d < INF)
+                best = fld_best_action([&](int dy, int dx) { return R[i + dy * W + dx]; }, nm, r > 0, r < H - 1, c > 0, c < W - 1, d);
 #pragma unroll
             for (int k = 0; k < 8; ++k) pol[(size_t)k * HW + i] = (k == best) ? 1.f : 0.f;
             r += dr;

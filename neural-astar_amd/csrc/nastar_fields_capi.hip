@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "nastar_fields.hip.h"
-#include "nastar_host.hip.h"
+#include "nastar_fields_host.hip.h"
 
 using namespace nastar;
 
@@ -16,7 +16,7 @@ int nastar_fields_max_cells(void) { return kFieldsMaxCells; }
 int nastar_cost_to_go_sweeps(const float* cost, const float* goal, const float* passable, int B, int H, int W, unsigned neighbor_mask,
                              float* dist_out, float* policy_out, int32_t* status_out, int32_t* sweeps_out, void* stream)
 {
-    if ((neighbor_mask & ~0x1FFu) != 0u || (neighbor_mask & 0x10u) != 0u) return NASTAR_ERR_UNSUPPORTED;
+    if (!field_mask_ok(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
     if (!cost || !goal || !passable || !dist_out || !status_out) return NASTAR_ERR_NULL;
     if (B < 1 || H < 1 || W < 1) return NASTAR_ERR_BAD_SHAPE;
     if ((long long)H * W > kFieldsMaxCells) return NASTAR_ERR_UNSUPPORTED;
@@ -25,11 +25,7 @@ int nastar_cost_to_go_sweeps(const float* cost, const float* goal, const float* 
                       aligned16(cost) && aligned16(goal) && aligned16(passable) ? 1 : 0};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = fields_lds_bytes(HW);
-    // one wavefront relaxes a map of up to 1024 cells (16 cells per lane, the barrier of a sweep costs nothing); 4 wavefronts up to 4096 cells,
-    // 16 above -- 16 cells per lane at every limit
-    if (HW <= 1024) return launch_grid(nastar_cost_to_go_kernel<64>, dim3((unsigned)B), dim3(64), lds, s, a);
-    if (HW <= 4096) return launch_grid(nastar_cost_to_go_kernel<256>, dim3((unsigned)B), dim3(256), lds, s, a);
-    return launch_grid(nastar_cost_to_go_kernel<1024>, dim3((unsigned)B), dim3(1024), lds, s, a);
+    return with_field_block(HW, [&](auto T) { return launch_grid(nastar_cost_to_go_kernel<T()>, dim3((unsigned)B), dim3(T()), lds, s, a); });
 }
 
 int nastar_cost_to_go(const float* cost, const float* goal, const float* passable, int B, int H, int W, unsigned neighbor_mask, float* dist_out,

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "nastar_fields_grad.hip.h"
-#include "nastar_host.hip.h"
+#include "nastar_fields_host.hip.h"
 
 using namespace nastar;
 
@@ -19,7 +19,7 @@ int nastar_fields_grad_max_cells(void) { return kFieldsGradMaxCells; }
 int nastar_fields_backward(const float* dist, const float* goal, const float* passable, const float* grad_dist, int B, int H, int W,
                            unsigned neighbor_mask, float* grad_cost_out, int32_t* status_out, int32_t* sweeps_out, void* stream)
 {
-    if ((neighbor_mask & ~0x1FFu) != 0u || (neighbor_mask & 0x10u) != 0u) return NASTAR_ERR_UNSUPPORTED;
+    if (!field_mask_ok(neighbor_mask)) return NASTAR_ERR_UNSUPPORTED;
     if (!dist || !goal || !passable || !grad_dist || !grad_cost_out || !status_out) return NASTAR_ERR_NULL;
     if (B < 1 || H < 1 || W < 1) return NASTAR_ERR_BAD_SHAPE;
     if ((long long)H * W > kFieldsGradMaxCells) return NASTAR_ERR_UNSUPPORTED;
@@ -27,10 +27,7 @@ int nastar_fields_backward(const float* dist, const float* goal, const float* pa
     const FieldGradArgs a{dist, goal, passable, grad_dist, grad_cost_out, status_out, sweeps_out, H, W, neighbor_mask};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = fields_grad_lds_bytes(HW);
-    // the forward's choice: one wavefront up to 1024 cells, 4 up to 4096, 16 above -- at most kGradCellsPerLane cells per lane at every limit
-    if (HW <= 64 * kGradCellsPerLane) return launch_grid(nastar_fields_backward_kernel<64>, dim3((unsigned)B), dim3(64), lds, s, a);
-    if (HW <= 256 * kGradCellsPerLane) return launch_grid(nastar_fields_backward_kernel<256>, dim3((unsigned)B), dim3(256), lds, s, a);
-    return launch_grid(nastar_fields_backward_kernel<1024>, dim3((unsigned)B), dim3(1024), lds, s, a);
+    return with_field_block(HW, [&](auto T) { return launch_grid(nastar_fields_backward_kernel<T()>, dim3((unsigned)B), dim3(T()), lds, s, a); });
 }
 
 }  // extern "C"

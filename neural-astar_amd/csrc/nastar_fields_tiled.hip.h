@@ -8,10 +8,9 @@
 //           tile, only in the next one);
 //   round   a tile that is not active this round exits.  An active one loads its interior and a one-cell
 //           halo of R (+inf outside the map) and C (cost, obstacles folded in as +inf) into LDS, relaxes the interior to the LOCAL fixed
-//           point with the sweep loop of item 6e (bounded by the tile's cell count), stores the cells it lowered and marks, in the NEXT
-//           round's flags, every existing adjacent tile whose halo holds one of them (up to 8); last of all it clears its own flag of
-//           THIS round (behind the barriers: every wavefront decides for itself whether the tile is active, from that word);
-//   policy  the eight planes from the converged R (a goal on an obstacle is still +inf there, as in 6e);
+//           point with fld_sweep (bounded by the tile's cell count), stores the cells it lowered and ends the round with tld_end_round
+//           on every existing adjacent tile whose halo holds one of them (up to 8);
+//   policy  the eight planes, fld_best_action on the converged R (a goal on an obstacle is still +inf there, as in 6e);
 //   finish  the goal cells (0, passable or not), all +inf for a map with a bad cost, and the status.
 // Inside a launch nothing is handed from one workgroup to another: every value a workgroup reads from another tile, old or new, is an upper
 // bound of the fixed point (a 32-bit word is never torn), and a tile that read a stale halo has been marked by the writer and reads it
@@ -31,8 +30,8 @@ namespace nastar {
 
 __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_init_kernel(const TiledArgs a)
 {
-    const TilePos p = tld_pos(a);
-    const int tid = threadIdx.x, H = a.H, W = a.W;
+    const TilePos p = tld_pos(a.g);
+    const int tid = threadIdx.x, H = a.g.H, W = a.g.W;
     const float* cost = a.cost + p.base;
     const float* goal = a.goal + p.base;
     const float* pass = a.passable + p.base;
@@ -55,11 +54,11 @@ __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_init_kernel(const 
     }
     const int any_near = __syncthreads_or(near_goal), any_goal = __syncthreads_or(has_goal), any_bad = __syncthreads_or(bad);
     if (tid == 0) {
-        const size_t nflags = (size_t)a.B * a.ty * a.tx;
+        const size_t nflags = (size_t)a.g.B * a.g.ty * a.g.tx;
         tld_store(a.flags + blockIdx.x, any_near ? 1 : 0);
         tld_store(a.flags + nflags + blockIdx.x, 0);
-        if (any_goal) tld_store(a.words + 2 * (size_t)a.B + p.b, 1);
-        if (any_bad) tld_store(a.words + 3 * (size_t)a.B + p.b, 1);
+        if (any_goal) tld_store(a.words + 2 * (size_t)a.g.B + p.b, 1);
+        if (any_bad) tld_store(a.words + 3 * (size_t)a.g.B + p.b, 1);
         if (p.t == 0 && a.visits) a.visits[p.b] = 0;
     }
 }
@@ -70,15 +69,15 @@ __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_round_kernel(const
     __shared__ float R[kHaloH * kHaloW];          // interior + halo; the halo is never written
     __shared__ float C[kTileH * kTileW];
     __shared__ int flags[8];                      // [0..2] sweep flags, [3] the borders that hold a lowered cell
-    const size_t nflags = (size_t)a.B * a.ty * a.tx;
+    const size_t nflags = (size_t)a.g.B * a.g.ty * a.g.tx;
     int32_t* cur = a.flags + (size_t)((round - 1) & 1) * nflags;
     int32_t* nxt = a.flags + (size_t)(round & 1) * nflags;
-    const TilePos p = tld_pos(a);
+    const TilePos p = tld_pos(a.g);
     // 1. not active this round, or a map with a bad cost: nothing to do.  Every wavefront reads the two words for itself, so the decision is
     // the same in all of them only because NOBODY writes either word before the barriers below: other workgroups write this tile's flag of
     // round r during round r + 1 only, and this workgroup clears it at the very end, behind barriers every wavefront has passed
-    if (tld_load(cur + blockIdx.x) == 0 || tld_load(a.words + 3 * (size_t)a.B + p.b) != 0) return;
-    const int tid = threadIdx.x, H = a.H, W = a.W;
+    if (tld_load(cur + blockIdx.x) == 0 || tld_load(a.words + 3 * (size_t)a.g.B + p.b) != 0) return;
+    const int tid = threadIdx.x, H = a.g.H, W = a.g.W;
     const float INF = INFINITY;
     float* dist = a.dist + p.base;
     const float* cost = a.cost + p.base;
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_round_kernel(const
     }
     __syncthreads();
 
-    // 3. the local fixed point: the sweep loop of item 6e on the interior.  Lane l owns column l % 64 of rows l / 64, l / 64 + 4, ...
+    // 3. the local fixed point on the interior.  Lane l owns column l % 64 of rows l / 64, l / 64 + 4, ...
     const uint32_t nm = a.nmask;
     const int c = tid & (kTileW - 1), r0 = tid / kTileW;
     constexpr int kRowStep = kTileT / kTileW;
@@ -110,17 +109,10 @@ __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_round_kernel(const
     auto relax = [&](int r) -> bool {
         float* q = R + (r + 1) * kHaloW + (c + 1);
         float m = INF;
-#define NASTAR_TLD_NB(dy, dx) \
-    if (nm & fld_bit(dy, dx)) m = fminf(m, fld_load(q + (dy) * kHaloW + (dx)));
-        NASTAR_TLD_NB(-1, -1)
-        NASTAR_TLD_NB(-1, 0)
-        NASTAR_TLD_NB(-1, 1)
-        NASTAR_TLD_NB(0, -1)
-        NASTAR_TLD_NB(0, 1)
-        NASTAR_TLD_NB(1, -1)
-        NASTAR_TLD_NB(1, 0)
-        NASTAR_TLD_NB(1, 1)
-#undef NASTAR_TLD_NB
+        fld_each<8>([&](auto j) __attribute__((always_inline)) {
+            constexpr Move o = kChildOffsets[decltype(j)::value];
+            if (nm & fld_bit(o.dy, o.dx)) m = fminf(m, fld_load(q + o.dy * kHaloW + o.dx));
+        });
         const float cand = C[r * kTileW + c] + m;
         if (cand < fld_load(q)) {
             fld_store(q, cand);
@@ -128,19 +120,15 @@ __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_round_kernel(const
         }
         return false;
     };
-    for (int s = 0; s < kTileH * kTileW; ++s) {   // the bound: no input moves it
+    fld_sweep(flags, kTileH * kTileW, [&](bool backwards) {
         bool changed = false;
-        if ((s & 1) == 0) {
+        if (!backwards) {
             for (int k = 0; k < nk; ++k) changed |= relax(r0 + k * kRowStep);
         } else {
             for (int k = nk - 1; k >= 0; --k) changed |= relax(r0 + k * kRowStep);
         }
-        const int slot = s % 3;
-        if (__ballot(changed) && (tid & 63) == 0) __hip_atomic_store(&flags[slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (tid == 0) __hip_atomic_store(&flags[slot == 2 ? 0 : slot + 1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __syncthreads();
-        if (__hip_atomic_load(&flags[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) break;
-    }
+        return changed;
+    });
 
     // 4. write back what was lowered (nobody else writes this tile's interior: dist still holds what was loaded) and note the borders
     uint32_t edges = 0;   // bit 0 N, 1 S, 2 W, 3 E, 4 NW, 5 NE, 6 SW, 7 SE
@@ -155,36 +143,19 @@ __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_round_kernel(const
                      (s && w ? 64u : 0u) | (s && e ? 128u : 0u);
         }
     }
-    if (edges) __hip_atomic_fetch_or(&flags[3], (int)edges, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __syncthreads();
     // 5, 6. mark the adjacent tiles that exist, and the map
-    if (tid < 8) {
-        const int dy = (tid == 0 || tid == 4 || tid == 5) ? -1 : (tid == 1 || tid == 6 || tid == 7) ? 1 : 0;
-        const int dx = (tid == 2 || tid == 4 || tid == 6) ? -1 : (tid == 3 || tid == 5 || tid == 7) ? 1 : 0;
-        const int tyi = p.t / a.tx, txi = p.t - tyi * a.tx;
-        const int ny = tyi + dy, nx = txi + dx;
-        if (((flags[3] >> tid) & 1) && ny >= 0 && ny < a.ty && nx >= 0 && nx < a.tx) {
-            tld_store(nxt + ((size_t)p.b * a.ty * a.tx + (size_t)(ny * a.tx + nx)), 1);
-            tld_store(a.words + p.b, round);
-        }
-    }
-    if (tid == 0) {
-        // the flag of this round is this workgroup's to clear -- here, after the barriers, when every wavefront has long read it
-        tld_store(cur + blockIdx.x, 0);
-        tld_store(a.words + (size_t)a.B + p.b, round);
-        if (a.visits) atomicAdd(a.visits + p.b, 1);
-    }
+    tld_end_round(a.g, p, edges, flags, cur, nxt, a.words, a.visits, round);
 }
 
 // the policy planes from the converged R; a map with a bad cost gets zeros
 __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_policy_kernel(const TiledArgs a)
 {
-    const TilePos p = tld_pos(a);
-    const int tid = threadIdx.x, H = a.H, W = a.W;
+    const TilePos p = tld_pos(a.g);
+    const int tid = threadIdx.x, H = a.g.H, W = a.g.W;
     const size_t HW = (size_t)H * W;
     const float* R = a.dist + p.base;
     float* pol = a.policy + p.base * 8;
-    const bool map_bad = tld_load(a.words + 3 * (size_t)a.B + p.b) != 0;
+    const bool map_bad = tld_load(a.words + 3 * (size_t)a.g.B + p.b) != 0;
     const uint32_t nm = a.nmask;
     const float INF = INFINITY;
     const int cc = tid & (kTileW - 1);
@@ -195,29 +166,8 @@ __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_policy_kernel(cons
         const ptrdiff_t i = (ptrdiff_t)y * W + x;
         const float d = map_bad ? INF : R[i];
         int best = -1;
-        if (d > 0.f && d < INF) {
-            const bool up = y > 0, dn = y < H - 1, lf = x > 0, rt = x < W - 1;
-            float m = INF;
-            // synthetic.ACTION_MOVES order; a strict < keeps the first action among equals
-#define NASTAR_TLD_ACT(k, dy, dx, ok)                                            \
-    if ((nm & fld_bit(dy, dx)) && (ok)) {                                         \
-        const float v = R[i + (ptrdiff_t)(dy) * W + (dx)];                        \
-        if (v < m) {                                                              \
-            m = v;                                                                \
-            best = k;                                                             \
-        }                                                                         \
-    }
-            NASTAR_TLD_ACT(0, -1, 0, up)
-            NASTAR_TLD_ACT(1, 0, 1, rt)
-            NASTAR_TLD_ACT(2, 0, -1, lf)
-            NASTAR_TLD_ACT(3, 1, 0, dn)
-            NASTAR_TLD_ACT(4, -1, 1, up && rt)
-            NASTAR_TLD_ACT(5, -1, -1, up && lf)
-            NASTAR_TLD_ACT(6, 1, 1, dn && rt)
-            NASTAR_TLD_ACT(7, 1, -1, dn && lf)
-#undef NASTAR_TLD_ACT
-            if (!(m < d)) best = -1;
-        }
+        if (d > 0.f && d < INF)
+            best = fld_best_action([&](int dy, int dx) { return R[i + (ptrdiff_t)dy * W + dx]; }, nm, y > 0, y < H - 1, x > 0, x < W - 1, d);
 #pragma unroll
         for (int k = 0; k < 8; ++k) pol[(size_t)k * HW + (size_t)i] = (k == best) ? 1.f : 0.f;
     }
@@ -227,14 +177,14 @@ __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_policy_kernel(cons
 // last_round: the number of rounds launched; a map that marked a tile in that round still has an active one
 __global__ __launch_bounds__(kTileT) void nastar_fields_tiled_finish_kernel(const TiledArgs a, const int last_round)
 {
-    const TilePos p = tld_pos(a);
-    const int tid = threadIdx.x, W = a.W;
+    const TilePos p = tld_pos(a.g);
+    const int tid = threadIdx.x, W = a.g.W;
     const float* goal = a.goal + p.base;
     float* dist = a.dist + p.base;
-    const bool map_bad = tld_load(a.words + 3 * (size_t)a.B + p.b) != 0;
+    const bool map_bad = tld_load(a.words + 3 * (size_t)a.g.B + p.b) != 0;
     if (p.t == 0 && tid == 0) {
-        const bool map_goal = tld_load(a.words + 2 * (size_t)a.B + p.b) != 0;
-        const bool quiet = last_round == 0 || tld_load(a.words + p.b) < last_round;
+        const bool map_goal = tld_load(a.words + 2 * (size_t)a.g.B + p.b) != 0;
+        const bool quiet = tld_map_quiet(a.words, p.b, last_round);
         a.status[p.b] = map_bad ? NASTAR_ERR_BAD_COST : !map_goal ? NASTAR_ERR_UNSOLVABLE : quiet ? NASTAR_OK : NASTAR_ERR_NO_CONVERGENCE;
     }
     const int cc = tid & (kTileW - 1);

@@ -856,6 +856,61 @@ def _raise_bad_cost(st: torch.Tensor, B: int, what: str) -> None:
                          f"({len(bad)} of {B}); the other maps were computed")
 
 
+def _raise_plateau(st: torch.Tensor, B: int, what: str) -> None:
+    flat = torch.nonzero(st.cpu() == FIELD_PLATEAU).flatten().tolist()
+    if flat:
+        raise ValueError(f"{what}: a cell with no strictly closer neighbour (a zero-cost plateau) on map(s) {flat[:16]}{' ...' if len(flat) > 16 else ''} "
+                         f"({len(flat)} of {B}): the field has no gradient with respect to the costs there; the other maps were computed")
+
+
+def _raise_no_convergence(st: torch.Tensor, what: str, bound: str) -> None:
+    stuck = torch.nonzero(st.cpu() == FIELD_NO_CONVERGENCE).flatten().tolist()
+    if stuck:
+        raise RuntimeError(f"{what}: map(s) {stuck[:16]} did not converge within {bound} (NASTAR_ERR_NO_CONVERGENCE)")
+
+
+def _field_lib(symbol: str, header: str):
+    """the library, which has to export ``symbol`` of include/``header``"""
+    lib = _native.load()
+    if not hasattr(lib, symbol):
+        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/{header}: rebuild it with `make -C {_native.CSRC_DIR}`")
+    return lib
+
+
+def _check_counts_out(t: Optional[torch.Tensor], name: str, B: int, dev: torch.device) -> None:
+    if t is not None and (t.dtype != torch.int32 or t.numel() != B or t.device != dev or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous int32 tensor of {B} elements on {dev}")
+
+
+def _check_max_rounds(max_rounds) -> None:
+    if max_rounds is not None and (isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or max_rounds < 1):
+        raise ValueError(f"max_rounds must be a positive int or None, got {max_rounds!r}")
+
+
+def _check_grad_dists(grad_dists, B: int, H: int, W: int) -> None:
+    if not torch.is_tensor(grad_dists) or grad_dists.dtype != torch.float32 or grad_dists.numel() != B * H * W or tuple(grad_dists.shape[-2:]) != (H, W):
+        raise ValueError(f"grad_dists must be a float32 tensor of the shape of dists ({B} maps of {H}x{W}), got "
+                         f"{tuple(grad_dists.shape) if torch.is_tensor(grad_dists) else type(grad_dists).__name__}")
+
+
+def _grad_device(maps, grad_dists: torch.Tensor) -> torch.device:
+    dev = _field_device(maps)
+    _require_device(grad_dists)
+    if grad_dists.device != dev:
+        raise ValueError(f"dists lives on {dev}, grad_dists on {grad_dists.device}: they must share a device")
+    return dev
+
+
+def _refuse_capture(dev: torch.device, error: type, message: str) -> None:
+    with torch.cuda.device(dev):
+        capturing = torch.cuda.is_current_stream_capturing()
+    if capturing:
+        raise error(message)
+
+
+_BLOCKS = "the call synchronises its stream between batches of rounds and cannot be captured into a graph"
+
+
 def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
                policies: bool = True, sweeps_out: Optional[torch.Tensor] = None, tiled: bool = False, differentiable: bool = False) -> FieldOutput:
     """The cost-to-go field of every map of the batch, and the optimal policy that follows it (include/nastar_fields.h).  What follows
@@ -890,11 +945,8 @@ def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps:
         raise NotImplementedError(f"cost_to_go: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_MAX_CELLS} cells (one workgroup "
                                   "relaxes one map in LDS; larger maps need a tiled kernel: pass tiled=True)")
     dev = _field_device(maps)
-    lib = _native.load()
-    if not hasattr(lib, "nastar_cost_to_go"):
-        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields.h: rebuild it with `make -C {_native.CSRC_DIR}`")
-    if sweeps_out is not None and (sweeps_out.dtype != torch.int32 or sweeps_out.numel() != B or sweeps_out.device != dev or not sweeps_out.is_contiguous()):
-        raise ValueError(f"sweeps_out must be a contiguous int32 tensor of {B} elements on {dev}")
+    lib = _field_lib("nastar_cost_to_go", "nastar_fields.h")
+    _check_counts_out(sweeps_out, "sweeps_out", B, dev)
     with torch.no_grad():
         cost, goal, passable = (_maps3(t.detach()) for t in maps)
         dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
@@ -908,9 +960,7 @@ def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps:
         if not torch.cuda.is_current_stream_capturing():
             st = status.cpu()
             _raise_bad_cost(st, B, "cost_to_go")
-            stuck = torch.nonzero(st == FIELD_NO_CONVERGENCE).flatten().tolist()
-            if stuck:
-                raise RuntimeError(f"cost_to_go: map(s) {stuck[:16]} did not converge within H*W sweeps (NASTAR_ERR_NO_CONVERGENCE)")
+            _raise_no_convergence(st, "cost_to_go", "H*W sweeps")
     return FieldOutput(dists, pol, status)
 
 
@@ -927,21 +977,13 @@ def fields_backward(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
     on live cells only (not a goal, finite distance); ``grad_cost`` is exactly 0 on every other cell.  What ``cost_to_go(...,
     differentiable=True)`` runs in its backward; probes and tests call it directly."""
     maps, mask, (B, H, W) = _field_inputs(dists, goal_maps, obstacles_maps, neighbor_mask)
-    if not torch.is_tensor(grad_dists) or grad_dists.dtype != torch.float32 or grad_dists.numel() != B * H * W or tuple(grad_dists.shape[-2:]) != (H, W):
-        raise ValueError(f"grad_dists must be a float32 tensor of the shape of dists ({B} maps of {H}x{W}), got "
-                         f"{tuple(grad_dists.shape) if torch.is_tensor(grad_dists) else type(grad_dists).__name__}")
+    _check_grad_dists(grad_dists, B, H, W)
     if H * W > FIELDS_GRAD_MAX_CELLS:
         raise NotImplementedError(f"fields_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_GRAD_MAX_CELLS} cells "
                                   "(larger maps: fields_backward_tiled, or cost_to_go_tiled(..., differentiable=True))")
-    dev = _field_device(maps)
-    _require_device(grad_dists)
-    if grad_dists.device != dev:
-        raise ValueError(f"dists lives on {dev}, grad_dists on {grad_dists.device}: they must share a device")
-    lib = _native.load()
-    if not hasattr(lib, "nastar_fields_backward"):
-        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields_grad.h: rebuild it with `make -C {_native.CSRC_DIR}`")
-    if sweeps_out is not None and (sweeps_out.dtype != torch.int32 or sweeps_out.numel() != B or sweeps_out.device != dev or not sweeps_out.is_contiguous()):
-        raise ValueError(f"sweeps_out must be a contiguous int32 tensor of {B} elements on {dev}")
+    dev = _grad_device(maps, grad_dists)
+    lib = _field_lib("nastar_fields_backward", "nastar_fields_grad.h")
+    _check_counts_out(sweeps_out, "sweeps_out", B, dev)
     with torch.no_grad():
         dist, goal, passable = (_maps3(t.detach()) for t in maps)
         up = grad_dists.detach().reshape(B, H, W).contiguous()
@@ -954,32 +996,41 @@ def fields_backward(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
     return grad, status
 
 
-class _CostToGo(torch.autograd.Function):
-    """``cost_to_go`` as an autograd node: forward = nastar_cost_to_go (the evaluation call, status checks included), backward =
-    nastar_fields_backward.  Only ``dists`` carries gradient, and only to ``cost``."""
+class _FieldNode(torch.autograd.Function):
+    """A field call as an autograd node, for ``cost_to_go`` and ``cost_to_go_tiled`` alike: ``field(cost, goal, obstacles) -> FieldOutput``
+    is the evaluation call (status checks included), ``backward(dists, goal, obstacles, grad_dists) -> grad_cost [B,H,W]`` the raw
+    gradient call.  Only ``dists`` carries gradient, and only to ``cost``."""
 
     @staticmethod
-    def forward(ctx, cost_maps, goal_maps, obstacles_maps, mask, policies, sweeps_out):
-        out = cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=mask, policies=policies, sweeps_out=sweeps_out)
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, field, backward):
+        out = field(cost_maps, goal_maps, obstacles_maps)
         ctx.save_for_backward(out.dists, goal_maps, obstacles_maps)
-        ctx.mask, ctx.cost_shape = mask, tuple(cost_maps.shape)
-        ctx.mark_non_differentiable(out.status, *((out.policies,) if policies else ()))
+        ctx.backward_call, ctx.cost_shape = backward, tuple(cost_maps.shape)
+        rest = (out.status,) + (() if out.policies is None else (out.policies,))
+        ctx.mark_non_differentiable(*rest)
         ctx.set_materialize_grads(False)
-        return (out.dists, out.status) + ((out.policies,) if policies else ())
+        return (out.dists,) + rest
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_dists, *unused):
         if g_dists is None or not ctx.needs_input_grad[0]:
-            return (None,) * 6
-        dists, goal_maps, obstacles_maps = ctx.saved_tensors
-        grad, _ = fields_backward(dists, goal_maps, obstacles_maps, g_dists, ctx.mask)
+            return (None,) * 5
+        grad = ctx.backward_call(*ctx.saved_tensors, g_dists)
         shape = ctx.cost_shape
         if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
             full = grad.new_zeros(shape)
             full[:, 0] = grad
             grad = full
-        return (grad.reshape(shape), None, None, None, None, None)
+        return (grad.reshape(shape), None, None, None, None)
+
+
+def _differentiable_field(cost_maps, goal_maps, obstacles_maps, field, backward) -> FieldOutput:
+    """``field(...)``, with the node on ``dists`` when there is something to differentiate"""
+    if cost_maps.requires_grad and torch.is_grad_enabled():
+        res = _FieldNode.apply(cost_maps, goal_maps, obstacles_maps, field, backward)
+        return FieldOutput(res[0], res[2] if len(res) > 2 else None, res[1])
+    return field(cost_maps, goal_maps, obstacles_maps)  # nothing to differentiate: the evaluation call, detached outputs
 
 
 def _cost_to_go_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, sweeps_out) -> FieldOutput:
@@ -987,23 +1038,15 @@ def _cost_to_go_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_ma
     if H * W > FIELDS_GRAD_MAX_CELLS:
         raise NotImplementedError(f"cost_to_go: differentiable=True takes maps of at most {FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = {H * W} "
                                   "(larger maps: cost_to_go_tiled(..., differentiable=True))")
-    dev = _field_device(maps)
-    with torch.cuda.device(dev):
-        capturing = torch.cuda.is_current_stream_capturing()
-    if capturing:
-        raise NotImplementedError("cost_to_go: differentiable=True reads the per-map status before it returns and cannot be captured into a graph")
-    if cost_maps.requires_grad and torch.is_grad_enabled():
-        res = _CostToGo.apply(cost_maps, goal_maps, obstacles_maps, mask, bool(policies), sweeps_out)
-        out = FieldOutput(res[0], res[2] if policies else None, res[1])
-    else:  # nothing to differentiate: the evaluation call, detached outputs -- and the same check
-        out = cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=mask, policies=policies, sweeps_out=sweeps_out)
+    _refuse_capture(_field_device(maps), NotImplementedError,
+                    "cost_to_go: differentiable=True reads the per-map status before it returns and cannot be captured into a graph")
+    out = _differentiable_field(cost_maps, goal_maps, obstacles_maps,
+                                lambda c, g, o: cost_to_go(c, g, o, neighbor_mask=mask, policies=policies, sweeps_out=sweeps_out),
+                                lambda d, g, o, up: fields_backward(d, g, o, up, mask)[0])
     # which maps have no gradient: the backward kernel's own verdict, from a launch with a zero upstream gradient (its set-up and one quiet
     # sweep: a zero gradient is at its fixed point from the start) -- so the rule lives in one place, the kernel, and covers policies=False
     _, st = fields_backward(out.dists.detach(), goal_maps, obstacles_maps, torch.zeros_like(out.dists), mask)
-    flat = torch.nonzero(st.cpu() == FIELD_PLATEAU).flatten().tolist()
-    if flat:
-        raise ValueError(f"cost_to_go: a cell with no strictly closer neighbour (a zero-cost plateau) on map(s) {flat[:16]}{' ...' if len(flat) > 16 else ''} "
-                         f"({len(flat)} of {B}): the field has no gradient with respect to the costs there; the other maps were computed")
+    _raise_plateau(st, B, "cost_to_go")
     return out
 
 
@@ -1015,15 +1058,9 @@ def fields_tile() -> Tuple[int, int]:
     """(rows, columns) of the interior of one tile of ``cost_to_go_tiled`` (nastar_fields_tile)"""
     import ctypes
     th, tw = ctypes.c_int(0), ctypes.c_int(0)
-    _native.check(_tiled_lib().nastar_fields_tile(ctypes.byref(th), ctypes.byref(tw)), "nastar_fields_tile")
+    lib = _field_lib("nastar_cost_to_go_tiled", "nastar_fields_tiled.h")
+    _native.check(lib.nastar_fields_tile(ctypes.byref(th), ctypes.byref(tw)), "nastar_fields_tile")
     return th.value, tw.value
-
-
-def _tiled_lib():
-    lib = _native.load()
-    if not hasattr(lib, "nastar_cost_to_go_tiled"):
-        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields_tiled.h: rebuild it with `make -C {_native.CSRC_DIR}`")
-    return lib
 
 
 def cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
@@ -1050,18 +1087,13 @@ def cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles
     maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     if H * W > FIELDS_TILED_MAX_CELLS:
         raise NotImplementedError(f"cost_to_go_tiled: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_TILED_MAX_CELLS} cells")
-    if max_rounds is not None and (isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or max_rounds < 1):
-        raise ValueError(f"max_rounds must be a positive int or None, got {max_rounds!r}")
+    _check_max_rounds(max_rounds)
     if launches_per_batch is not None and (isinstance(launches_per_batch, bool) or not isinstance(launches_per_batch, int) or launches_per_batch < 1):
         raise ValueError(f"launches_per_batch must be a positive int or None, got {launches_per_batch!r}")
     dev = _field_device(maps)
-    lib = _tiled_lib()
-    if visits_out is not None and (visits_out.dtype != torch.int32 or visits_out.numel() != B or visits_out.device != dev or not visits_out.is_contiguous()):
-        raise ValueError(f"visits_out must be a contiguous int32 tensor of {B} elements on {dev}")
-    with torch.cuda.device(dev):
-        capturing = torch.cuda.is_current_stream_capturing()
-    if capturing:
-        raise RuntimeError("cost_to_go_tiled: the call synchronises its stream between batches of rounds and cannot be captured into a graph")
+    lib = _field_lib("nastar_cost_to_go_tiled", "nastar_fields_tiled.h")
+    _check_counts_out(visits_out, "visits_out", B, dev)
+    _refuse_capture(dev, RuntimeError, f"cost_to_go_tiled: {_BLOCKS}")
     import ctypes
     nbytes = lib.nastar_cost_to_go_tiled_workspace_bytes(B, H, W)
     if nbytes == 0:
@@ -1083,28 +1115,12 @@ def cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles
         st = status.cpu()
         _raise_bad_cost(st, B, "cost_to_go_tiled")
         if max_rounds is None:
-            stuck = torch.nonzero(st == FIELD_NO_CONVERGENCE).flatten().tolist()
-            if stuck:
-                raise RuntimeError(f"cost_to_go_tiled: map(s) {stuck[:16]} did not converge within H*W + 1 rounds (NASTAR_ERR_NO_CONVERGENCE)")
+            _raise_no_convergence(st, "cost_to_go_tiled", "H*W + 1 rounds")
     return FieldOutput(dists, pol, status), rounds.value
 
 
 # ---- include/nastar_fields_grad_tiled.h: the gradient of the field for maps of up to 1179648 cells, by a tiled subtree sum
 FIELDS_GRAD_TILED_MAX_CELLS = 1179648  # nastar_fields_grad_tiled_max_cells(): every size cost_to_go_tiled takes
-
-
-def _grad_tiled_lib():
-    lib = _native.load()
-    if not hasattr(lib, "nastar_fields_backward_tiled"):
-        raise _native.NativeLibraryMissing(f"{_native.LIB_PATH} is older than include/nastar_fields_grad_tiled.h: rebuild it with `make -C {_native.CSRC_DIR}`")
-    return lib
-
-
-def _refuse_capture(dev: torch.device, what: str) -> None:
-    with torch.cuda.device(dev):
-        capturing = torch.cuda.is_current_stream_capturing()
-    if capturing:
-        raise RuntimeError(f"{what}: the call synchronises its stream between batches of rounds and cannot be captured into a graph")
 
 
 def _grad_tiled_workspace(lib, B: int, H: int, W: int, dev: torch.device, what: str):
@@ -1130,21 +1146,14 @@ def fields_backward_tiled(dists: torch.Tensor, goal_maps: torch.Tensor, obstacle
     map that still has an active tile is reported in ``status`` (``FIELD_NO_CONVERGENCE``), not raised, and its gradient is all zero.
     ``visits_out``: a [B] int32 tensor that receives every map's (tile, round) visits."""
     maps, mask, (B, H, W) = _field_inputs(dists, goal_maps, obstacles_maps, neighbor_mask)
-    if not torch.is_tensor(grad_dists) or grad_dists.dtype != torch.float32 or grad_dists.numel() != B * H * W or tuple(grad_dists.shape[-2:]) != (H, W):
-        raise ValueError(f"grad_dists must be a float32 tensor of the shape of dists ({B} maps of {H}x{W}), got "
-                         f"{tuple(grad_dists.shape) if torch.is_tensor(grad_dists) else type(grad_dists).__name__}")
+    _check_grad_dists(grad_dists, B, H, W)
     if H * W > FIELDS_GRAD_TILED_MAX_CELLS:
         raise NotImplementedError(f"fields_backward_tiled: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELDS_GRAD_TILED_MAX_CELLS} cells")
-    if max_rounds is not None and (isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or max_rounds < 1):
-        raise ValueError(f"max_rounds must be a positive int or None, got {max_rounds!r}")
-    dev = _field_device(maps)
-    _require_device(grad_dists)
-    if grad_dists.device != dev:
-        raise ValueError(f"dists lives on {dev}, grad_dists on {grad_dists.device}: they must share a device")
-    lib = _grad_tiled_lib()
-    if visits_out is not None and (visits_out.dtype != torch.int32 or visits_out.numel() != B or visits_out.device != dev or not visits_out.is_contiguous()):
-        raise ValueError(f"visits_out must be a contiguous int32 tensor of {B} elements on {dev}")
-    _refuse_capture(dev, "fields_backward_tiled")
+    _check_max_rounds(max_rounds)
+    dev = _grad_device(maps, grad_dists)
+    lib = _field_lib("nastar_fields_backward_tiled", "nastar_fields_grad_tiled.h")
+    _check_counts_out(visits_out, "visits_out", B, dev)
+    _refuse_capture(dev, RuntimeError, f"fields_backward_tiled: {_BLOCKS}")
     import ctypes
     with torch.no_grad():
         workspace, nbytes = _grad_tiled_workspace(lib, B, H, W, dev, "fields_backward_tiled")
@@ -1160,9 +1169,7 @@ def fields_backward_tiled(dists: torch.Tensor, goal_maps: torch.Tensor, obstacle
                                                   ctypes.cast(ctypes.pointer(rounds), ctypes.c_void_p), _stream_ptr(dev))
         _native.check(rc, "nastar_fields_backward_tiled")
         if max_rounds is None:
-            stuck = torch.nonzero(status.cpu() == FIELD_NO_CONVERGENCE).flatten().tolist()
-            if stuck:
-                raise RuntimeError(f"fields_backward_tiled: map(s) {stuck[:16]} did not converge within H*W + 1 rounds (NASTAR_ERR_NO_CONVERGENCE)")
+            _raise_no_convergence(status, "fields_backward_tiled", "H*W + 1 rounds")
     return grad, status, rounds.value
 
 
@@ -1170,7 +1177,7 @@ def _fields_plateau_tiled(dists, goal_maps, obstacles_maps, mask) -> torch.Tenso
     """``nastar_fields_backward_tiled_status``: [B] int32, ``FIELD_PLATEAU`` for the maps without a gradient -- the kernel's own verdict"""
     maps, mask, (B, H, W) = _field_inputs(dists, goal_maps, obstacles_maps, mask)
     dev = _field_device(maps)
-    lib = _grad_tiled_lib()
+    lib = _field_lib("nastar_fields_backward_tiled", "nastar_fields_grad_tiled.h")
     with torch.no_grad():
         workspace, nbytes = _grad_tiled_workspace(lib, B, H, W, dev, "cost_to_go_tiled")
         dist, goal, passable = (_maps3(t.detach()) for t in maps)
@@ -1182,49 +1189,17 @@ def _fields_plateau_tiled(dists, goal_maps, obstacles_maps, mask) -> torch.Tenso
     return status
 
 
-class _CostToGoTiled(torch.autograd.Function):
-    """``cost_to_go_tiled`` as an autograd node: forward = nastar_cost_to_go_tiled (the evaluation call, status checks included), backward =
-    nastar_fields_backward_tiled.  Only ``dists`` carries gradient, and only to ``cost``."""
-
-    @staticmethod
-    def forward(ctx, cost_maps, goal_maps, obstacles_maps, mask, policies, max_rounds, visits_out, launches_per_batch, rounds_box):
-        out, rounds = cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, neighbor_mask=mask, policies=policies, max_rounds=max_rounds,
-                                       visits_out=visits_out, launches_per_batch=launches_per_batch)
-        rounds_box.append(rounds)
-        ctx.save_for_backward(out.dists, goal_maps, obstacles_maps)
-        ctx.mask, ctx.cost_shape = mask, tuple(cost_maps.shape)
-        ctx.mark_non_differentiable(out.status, *((out.policies,) if policies else ()))
-        ctx.set_materialize_grads(False)
-        return (out.dists, out.status) + ((out.policies,) if policies else ())
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_dists, *unused):
-        if g_dists is None or not ctx.needs_input_grad[0]:
-            return (None,) * 9
-        dists, goal_maps, obstacles_maps = ctx.saved_tensors
-        grad, _, _ = fields_backward_tiled(dists, goal_maps, obstacles_maps, g_dists, ctx.mask)
-        shape = ctx.cost_shape
-        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
-            full = grad.new_zeros(shape)
-            full[:, 0] = grad
-            grad = full
-        return (grad.reshape(shape),) + (None,) * 8
-
-
 def _cost_to_go_tiled_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, max_rounds, visits_out, launches_per_batch):
     maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    kw = dict(neighbor_mask=mask, policies=policies, max_rounds=max_rounds, visits_out=visits_out, launches_per_batch=launches_per_batch)
-    if cost_maps.requires_grad and torch.is_grad_enabled():
-        box: list = []
-        res = _CostToGoTiled.apply(cost_maps, goal_maps, obstacles_maps, mask, bool(policies), max_rounds, visits_out, launches_per_batch, box)
-        out, rounds = FieldOutput(res[0], res[2] if policies else None, res[1]), box[0]
-    else:  # nothing to differentiate: the evaluation call, detached outputs -- and the same check
-        out, rounds = cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, **kw)
+    rounds: list = []
+
+    def field(c, g, o):
+        out, n = cost_to_go_tiled(c, g, o, neighbor_mask=mask, policies=policies, max_rounds=max_rounds, visits_out=visits_out,
+                                  launches_per_batch=launches_per_batch)
+        rounds.append(n)
+        return out
+
+    out = _differentiable_field(cost_maps, goal_maps, obstacles_maps, field, lambda d, g, o, up: fields_backward_tiled(d, g, o, up, mask)[0])
     # which maps have no gradient: the backward's own verdict (its init launch and a status write), so the rule lives in one place, the kernel
-    st = _fields_plateau_tiled(out.dists.detach(), goal_maps, obstacles_maps, mask)
-    flat = torch.nonzero(st.cpu() == FIELD_PLATEAU).flatten().tolist()
-    if flat:
-        raise ValueError(f"cost_to_go_tiled: a cell with no strictly closer neighbour (a zero-cost plateau) on map(s) {flat[:16]}{' ...' if len(flat) > 16 else ''} "
-                         f"({len(flat)} of {B}): the field has no gradient with respect to the costs there; the other maps were computed")
-    return out, rounds
+    _raise_plateau(_fields_plateau_tiled(out.dists.detach(), goal_maps, obstacles_maps, mask), B, "cost_to_go_tiled")
+    return out, rounds[0]

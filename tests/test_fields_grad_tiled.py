@@ -129,8 +129,66 @@ def test_what_is_not_live_is_never_read():
     assert st == 0 and A.tobytes() == want.tobytes() and np.isfinite(grad).all()
 
 
+# ---- 1b: an upstream gradient that SHOWS the order of the children ------------------------------------------------------------------------------------
+ORDER_CASES = [(H, W, mask) for H, W in ((20, 45), (70, 130)) for mask in (HO.MOORE8, DIRECTED)]
+
+
+@functools.lru_cache(maxsize=None)
+def _order_case(H, W, mask):
+    """two maps [2,H,W]: cost U(0.5, 1.5), about 20 % obstacles, one goal on a passable cell, the field, and G drawn per cell from
+    {+2^60, -2^60, 1.0}.  A Gaussian G hides the order of an fp64 sum behind the fp32 rounding of the result; here 2^60 + 1 absorbs the 1
+    (the ulp of 2^60 in binary64 is 256) and 2^60 - 2^60 + 1 keeps it, so the order of the children reaches the fp32 output.  Shared with
+    the GPU pin (tests/test_fields_grad_tiled_gpu.py), never modified."""
+    rng = np.random.default_rng([H, W, mask, 1])
+    passable = (rng.random((2, H, W)) > 0.2).astype(f32)
+    goal = np.zeros((2, H, W), f32)
+    for b in range(2):
+        gy, gx = int(rng.integers(H)), int(rng.integers(W))
+        goal[b, gy, gx] = passable[b, gy, gx] = 1
+    cost = (0.5 + rng.random((2, H, W))).astype(f32)
+    G = rng.choice(np.array([2.0 ** 60, -2.0 ** 60, 1.0], f32), size=(2, H, W))
+    fields = [FO.field(cost[b], goal[b], passable[b], mask) for b in range(2)]
+    assert [st for _, _, st in fields] == [0, 0]
+    dist = np.stack([d for d, _, _ in fields])
+    want = [GT.in_order(dist[b], goal[b], passable[b], G[b], mask) for b in range(2)]
+    assert [st for _, _, st in want] == [0, 0]
+    grad = np.stack([g32 for _, g32, _ in want])
+    for a in (goal, passable, dist, G, grad):
+        a.setflags(write=False)
+    return goal, passable, dist, G, grad
+
+
+def _children_reversed(dist, goal, passable, G, mask):
+    """``GT.in_order`` with one change: every cell adds its children in the REVERSED order"""
+    F = GT.forest(dist, goal, passable, mask)
+    H, W = F.live.shape
+    assert not F.plateau
+    g = np.asarray(G, f32).reshape(-1).astype(np.float64).tolist()
+    A = [0.0] * (H * W)
+    for n in F.order.tolist():
+        v = g[n]
+        for c in reversed(F.kids[n]):
+            v += A[c]
+        A[n] = v
+    A = np.array(A).reshape(H, W)
+    return np.where(F.live, A, 0.0).astype(f32)
+
+
+@pytest.mark.parametrize("H,W,mask", ORDER_CASES)
+def test_the_order_pin_sees_a_reversed_child_order(H, W, mask):
+    """what makes tests/test_fields_grad_tiled_gpu.py::test_gradient_bits_are_the_in_order_sum a pin of the ORDER: on its very inputs, adding
+    the children the other way round changes fp32 cells of the output"""
+    goal, passable, dist, G, grad = _order_case(H, W, mask)
+    assert np.isfinite(grad).all()                                  # at most 9100 addends of magnitude 2^60: far below fp32's 2^128
+    other = np.stack([_children_reversed(dist[b], goal[b], passable[b], G[b], mask) for b in range(2)])
+    assert np.isfinite(other).all()
+    changed = [int((other[b].view(np.uint32) != grad[b].view(np.uint32)).sum()) for b in range(2)]
+    print(f"{H}x{W} {hex(mask)}: a reversed child order changes {changed} fp32 cells of the two maps")
+    assert min(changed) >= 1
+
+
 # ---- 2: header, binding, library ----------------------------------------------------------------------------------------------------------------------
-NAMES = ["nastar_fields_backward_tiled", "nastar_fields_backward_tiled_status", "nastar_fields_backward_tiled_workspace_bytes",
+NAMES =["nastar_fields_backward_tiled", "nastar_fields_backward_tiled_status", "nastar_fields_backward_tiled_workspace_bytes",
          "nastar_fields_grad_tiled_abi", "nastar_fields_grad_tiled_max_cells"]
 
 

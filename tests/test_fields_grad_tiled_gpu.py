@@ -19,6 +19,7 @@ import torch
 import fields_grad_oracle as GO
 import heuristic_oracle as HO
 from test_fields_grad_gpu import _case, _close, _serpentine
+from test_fields_grad_tiled import ORDER_CASES, _order_case
 
 pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
@@ -98,6 +99,24 @@ def test_same_bits_as_the_one_workgroup_kernel(H, W, mask):
         assert rounds >= 1 and all(v >= t for v, t in zip(visits, tiles)), (rounds, visits, tiles)
         if H * W == 4096:
             assert rounds == 1 and visits == tiles                    # one tile: one visit (none for a walled-in goal: no live cell)
+
+
+# ---- the summation order itself: both kernels against the in-order evaluation, on a G that shows the order ------------------------------------------
+@pytest.mark.parametrize("H,W,mask", ORDER_CASES)
+def test_gradient_bits_are_the_in_order_sum(H, W, mask):
+    """20x45: one wavefront (T = 64); 70x130: T = 1024, four ragged tiles.  G in {+2^60, -2^60, 1.0}: a changed order of the children changes
+    fp32 cells of the result (tests/test_fields_grad_tiled.py::test_the_order_pin_sees_a_reversed_child_order), which a Gaussian G hides."""
+    from neural_astar import ops
+    goal, passable, dist, G, want = _order_case(H, W, mask)
+    d, g, p, up = _t(dist), _t(goal), _t(passable), _t(G)
+    one, st1 = ops.fields_backward(d, g, p, up, neighbor_mask=mask)
+    tiled, st2, rounds = ops.fields_backward_tiled(d, g, p, up, neighbor_mask=mask)
+    assert st1.tolist() == st2.tolist() == [0, 0] and rounds >= 1
+    for name, got in (("fields_backward", one), ("fields_backward_tiled", tiled)):
+        got = got.cpu().numpy()
+        differ = int((got.view(np.uint32) != want.view(np.uint32)).sum())
+        print(f"{H}x{W} {hex(mask)} {name}: {differ} of {want.size} fp32 cells differ from the in-order sum")
+        assert got.tobytes() == want.tobytes(), name
 
 
 # ---- above the old limit: the definition ---------------------------------------------------------------------------------------------------------------
