@@ -13,9 +13,15 @@ trunk -- the five convolutions, the four hidden BatchNorm + ReLU blocks and ever
              dW_l = dz_l (*) a_{l-1}                  nastar_conv3x3_wgrad_f16    (fp16 MFMA, LDS transpose reads)
              da_{l-1} = conv(dz_l, W_l^T flipped)    nastar_conv3x3_f16
 
-The last block's 1-channel BatchNorm + sigmoid * const stay ordinary torch ops on a [B,1,H,W] tensor (negligible, and torch's
-autograd then also serves ``const`` and that BatchNorm's parameters).  Gradients travel multiplied by a power of two chosen on the
-device from max|dL/dz5| (no host sync) so that fp16 never under- or overflows; it is divided out of every result.
+The last block's 1-channel BatchNorm + sigmoid * const is a second autograd node (``_LastBlock``: two launches each way, ``nastar_bn1_*``),
+which also serves ``const`` and that BatchNorm's parameters; only a BatchNorm without affine part or an exotic ``const`` takes plain
+tensor ops.  Gradients travel multiplied by a power of two chosen on the device from max|dL/dz5| (no host sync) so that fp16 never
+under- or overflows; it is divided out of every result.
+
+Both trunks (``_CnnTrunk``, and ``_UnetTrunk`` over the launch plan of ``encoder_hip.unet_layer_plan``) take the BatchNorm of a hidden block
+from ONE pair of steps, ``_Lib.bn_forward`` / ``_Lib.bn_backward``: batch statistics in one fused pass, the data-parallel form (statistics ->
+all-reduce -> coefficients, ``SyncBatchNorm``) or eval mode under autograd (running statistics), with the gradient either stored or formed
+on the fly from the streamed closing convolution.
 
 Conv biases sit in front of a BatchNorm, so their true gradient is exactly zero (the batch mean removes them); zeros are returned
 where torch's autograd returns ~1e-10 of rounding noise.
@@ -31,6 +37,29 @@ from . import _native
 from .encoder_hip import CONV_FINAL, CONV_RELU, CONV_SPLIT, _pad32, pack_conv_weight, pack_conv_weight_f16x3
 
 CONV_RAW = 16  # include/nastar.h
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _f32c(t: torch.Tensor) -> torch.Tensor:
+    t = t.detach()
+    return t if t.is_contiguous() and t.dtype == torch.float32 else t.float().contiguous()
+
+
+def _bn_track(bn, eval_bn: bool, tracked: Optional[list] = None) -> Tuple[bool, float]:
+    """(track, momentum) of nn.BatchNorm2d's training-mode side effect (running statistics with the unbiased variance: done inside the
+    coefficient kernels).  The step counter joins ``tracked`` (ONE multi-tensor increment by the caller instead of a launch per layer) or,
+    without a list, is incremented here."""
+    if bn is None or not bn.track_running_stats or bn.running_mean is None or eval_bn:
+        return False, 0.0
+    mom = bn.momentum if bn.momentum is not None else 1.0 / float(int(bn.num_batches_tracked) + 1)
+    if tracked is None:
+        bn.num_batches_tracked += 1
+    else:
+        tracked.append(bn.num_batches_tracked)
+    return True, mom
 
 
 class SyncBatchNorm:
@@ -142,7 +171,8 @@ def pack_flat_weight(w: torch.Tensor, split: bool):  # torch-op reference of nas
 
 
 class _Lib:
-    """thin typed wrappers over the C ABI (all tensors on the current device, launches on torch's current stream)"""
+    """thin typed wrappers over the C ABI (all tensors on the current device, launches on torch's current stream), and on top of them the
+    two BatchNorm steps every hidden block of both trunks takes: ``bn_forward`` / ``bn_backward``"""
 
     def __init__(self, dev):
         self.lib = _native.load()
@@ -162,15 +192,9 @@ class _Lib:
         scale, shift = self.f32(cout_p), self.f32(cout_p)
         reuse = scal is not None
         scal = scal if reuse else self.f32(3)
-        wc = w.detach()
-        wc = wc if wc.is_contiguous() and wc.dtype == torch.float32 else wc.float().contiguous()
-        bc = None
-        if bias is not None:
-            bc = bias.detach()
-            bc = bc if bc.is_contiguous() and bc.dtype == torch.float32 else bc.float().contiguous()
-        rc = self.lib.nastar_pack_conv_weight_f16(wc.data_ptr(), co, ci, int(transpose_flip), int(split),
-                                                  bc.data_ptr() if bc is not None else None, wpack.data_ptr(), scale.data_ptr(),
-                                                  shift.data_ptr(), scal.data_ptr(), int(reuse), self.stream)
+        wc, bc = _f32c(w), (_f32c(bias) if bias is not None else None)
+        rc = self.lib.nastar_pack_conv_weight_f16(wc.data_ptr(), co, ci, int(transpose_flip), int(split), _ptr(bc), wpack.data_ptr(),
+                                                  scale.data_ptr(), shift.data_ptr(), scal.data_ptr(), int(reuse), self.stream)
         _native.check(rc, "nastar_pack_conv_weight_f16")
         return wpack, scale, shift, scal
 
@@ -232,32 +256,43 @@ class _Lib:
         _native.check(rc, "nastar_pack_conv_weights_multi_f16")
         return [(flat16[o:o + n], flatf[f:f + c], flatf[f + c:f + 2 * c], scal[sp[3]]) for (o, n, f, c), sp in zip(lay, specs)]
 
+    def stats_ws(self, npix, C):
+        """(workspace, bytes) of the per-workgroup partial rows of a statistics pass"""
+        n = int(self.lib.nastar_chan_stats_workspace_bytes(npix, C))
+        return torch.empty((n,), dtype=torch.uint8, device=self.dev), n
+
     def bn_fwd(self, z, npix, C, split, gamma, beta, eps, mom, rm, rv):
         """batch statistics of z and the forward BatchNorm coefficients in two launches (partial rows; finish + coefficients):
         (mean, invstd, k2, k3).  Not for SyncBatchNorm (the sums must be all-reduced between the halves)."""
         k2, k3 = self.f32(C), self.f32(C)
         mean = torch.empty((C,), dtype=torch.float64, device=self.dev)
         invstd = torch.empty((C,), dtype=torch.float64, device=self.dev)
-        nbytes = int(self.lib.nastar_chan_stats_workspace_bytes(npix, C))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
+        ws, nbytes = self.stats_ws(npix, C)
         rc = self.lib.nastar_bn_stats_coef_fwd_f16(z.data_ptr(), npix, C, int(split), gamma.data_ptr(), beta.data_ptr(), float(eps), float(mom),
-                                                   rm.data_ptr() if rm is not None else None, rv.data_ptr() if rv is not None else None,
-                                                   k2.data_ptr(), k3.data_ptr(), mean.data_ptr(), invstd.data_ptr(), None, ws.data_ptr(), nbytes,
-                                                   self.stream)
+                                                   _ptr(rm), _ptr(rv), k2.data_ptr(), k3.data_ptr(), mean.data_ptr(), invstd.data_ptr(), None,
+                                                   ws.data_ptr(), nbytes, self.stream)
         _native.check(rc, "nastar_bn_stats_coef_fwd_f16")
         return mean, invstd, k2, k3
+
+    # The gradient ``da`` a BatchNorm backward starts from (``bn_bwd``, ``stats``, ``affine``) is a stored fp16 tensor -- or, for the block in
+    # front of the streamed closing convolution, the tuple (d, wlast, B, H, W): da = gscale_in * (that convolution's input gradient of d),
+    # formed on the fly and never stored (the ``*_u1_*`` entry points)
 
     def bn_bwd(self, da, z, k2f, k3f, npix, C, split, mean, invstd, gamma, gscale_in, gscale_out, sums_out=None):
         """(sum dy, sum dy z), max|dy| and the backward BatchNorm coefficients in two launches: (dgamma, dbeta, c1, c2, c3); the re-centred
         gradient scale goes to ``gscale_out`` (a DIFFERENT tensor than ``gscale_in``: every workgroup of the finishing kernel reads the latter)"""
         dgamma, dbeta, c1, c2, c3 = (self.f32(C) for _ in range(5))
-        nbytes = int(self.lib.nastar_chan_stats_workspace_bytes(npix, C))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
-        rc = self.lib.nastar_bn_stats_coef_bwd_f16(da.data_ptr(), z.data_ptr(), k2f.data_ptr(), k3f.data_ptr(), npix, C, int(split), mean.data_ptr(),
-                                                   invstd.data_ptr(), gamma.data_ptr(), gscale_in.data_ptr(), gscale_out.data_ptr(),
-                                                   dgamma.data_ptr(), dbeta.data_ptr(), c1.data_ptr(), c2.data_ptr(), c3.data_ptr(),
-                                                   sums_out.data_ptr() if sums_out is not None else None, ws.data_ptr(), nbytes, self.stream)
-        _native.check(rc, "nastar_bn_stats_coef_bwd_f16")
+        ws, nbytes = self.stats_ws(npix, C)
+        tail = (mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), gscale_in.data_ptr(), gscale_out.data_ptr(), dgamma.data_ptr(),
+                dbeta.data_ptr(), c1.data_ptr(), c2.data_ptr(), c3.data_ptr(), _ptr(sums_out), ws.data_ptr(), nbytes, self.stream)
+        if isinstance(da, tuple):
+            d, wlast, B, H, W = da
+            rc = self.lib.nastar_bn_stats_coef_bwd_u1_f16(d.data_ptr(), wlast.data_ptr(), B, H, W, z.data_ptr(), k2f.data_ptr(), k3f.data_ptr(), C,
+                                                          int(split), *tail)
+            _native.check(rc, "nastar_bn_stats_coef_bwd_u1_f16")
+        else:
+            rc = self.lib.nastar_bn_stats_coef_bwd_f16(da.data_ptr(), z.data_ptr(), k2f.data_ptr(), k3f.data_ptr(), npix, C, int(split), *tail)
+            _native.check(rc, "nastar_bn_stats_coef_bwd_f16")
         return dgamma, dbeta, c1, c2, c3
 
     IMG32 = {(32, 64), (64, 128), (128, 256), (256, 128), (128, 64)}
@@ -271,31 +306,113 @@ class _Lib:
                                                    cin, cout, flags, self.stream)
             _native.check(rc, "nastar_conv3x3_img32_f16")
             return
-        rc = self.lib.nastar_conv3x3_f16(src.data_ptr(), src2.data_ptr() if src2 is not None else None, wpack.data_ptr(),
-                                         scale.data_ptr(), shift.data_ptr(), out.data_ptr() if out is not None else None,
-                                         out_f32.data_ptr() if out_f32 is not None else None, B, H, W, cin, c2, cout, flags, 1.0, self.stream)
+        rc = self.lib.nastar_conv3x3_f16(src.data_ptr(), _ptr(src2), wpack.data_ptr(), scale.data_ptr(), shift.data_ptr(), _ptr(out), _ptr(out_f32),
+                                         B, H, W, cin, c2, cout, flags, 1.0, self.stream)
         _native.check(rc, "nastar_conv3x3_f16")
 
     def i16(self, n):
         return torch.empty((n,), dtype=torch.int16, device=self.dev)
 
-    def stats(self, u, v, ms, mt, npix, C, split, amax=None):
-        """per-channel double sums [C,2]: two-stage form (per-workgroup partials + a fixed-order finishing launch: deterministic)"""
-        sums = torch.empty((C, 2), dtype=torch.float64, device=self.dev)
-        nbytes = int(self.lib.nastar_chan_stats_workspace_bytes(npix, C))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
-        rc = self.lib.nastar_chan_stats_f16_ws(u.data_ptr() if u is not None else None, v.data_ptr(),
-                                               ms.data_ptr() if ms is not None else None, mt.data_ptr() if mt is not None else None,
-                                               sums.data_ptr(), amax.data_ptr() if amax is not None else None, npix, C, int(split),
-                                               ws.data_ptr(), nbytes, self.stream)
-        _native.check(rc, "nastar_chan_stats_f16_ws")
+    def stats(self, u, v, ms, mt, npix, C, split, amax=None, gscale=None, out=None):
+        """per-channel double sums [C,2]: two-stage form (per-workgroup partials + a fixed-order finishing launch: deterministic);
+        ``gscale``: the scale of an on-the-fly ``u``"""
+        sums = out if out is not None else torch.empty((C, 2), dtype=torch.float64, device=self.dev)
+        ws, nbytes = self.stats_ws(npix, C)
+        if isinstance(u, tuple):
+            d, wlast, B, H, W = u
+            rc = self.lib.nastar_chan_stats_u1_f16_ws(d.data_ptr(), wlast.data_ptr(), gscale.data_ptr(), B, H, W, v.data_ptr(), ms.data_ptr(),
+                                                      mt.data_ptr(), sums.data_ptr(), amax.data_ptr(), C, int(split), ws.data_ptr(), nbytes,
+                                                      self.stream)
+            _native.check(rc, "nastar_chan_stats_u1_f16_ws")
+        else:
+            rc = self.lib.nastar_chan_stats_f16_ws(_ptr(u), v.data_ptr(), _ptr(ms), _ptr(mt), sums.data_ptr(), _ptr(amax), npix, C, int(split),
+                                                   ws.data_ptr(), nbytes, self.stream)
+            _native.check(rc, "nastar_chan_stats_f16_ws")
         return sums
 
-    def affine(self, u, v, k1, k2, k3, ms, mt, out, npix, C, relu, split):
-        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        rc = self.lib.nastar_chan_affine_f16(p(u), p(v), p(k1), p(k2), p(k3), p(ms), p(mt), out.data_ptr(), npix, C, int(relu),
-                                             int(split), self.stream)
+    def affine(self, u, v, k1, k2, k3, ms, mt, out, npix, C, relu, split, gscale=None):
+        if isinstance(u, tuple):  # (the backward form only: no ReLU)
+            d, wlast, B, H, W = u
+            rc = self.lib.nastar_chan_affine_u1_f16(d.data_ptr(), wlast.data_ptr(), gscale.data_ptr(), B, H, W, v.data_ptr(), k1.data_ptr(),
+                                                    k2.data_ptr(), k3.data_ptr(), ms.data_ptr(), mt.data_ptr(), out.data_ptr(), C, int(split),
+                                                    self.stream)
+            _native.check(rc, "nastar_chan_affine_u1_f16")
+            return
+        rc = self.lib.nastar_chan_affine_f16(_ptr(u), _ptr(v), _ptr(k1), _ptr(k2), _ptr(k3), _ptr(ms), _ptr(mt), out.data_ptr(), npix, C,
+                                             int(relu), int(split), self.stream)
         _native.check(rc, "nastar_chan_affine_f16")
+
+    def bn_forward(self, z, npix, C, split, gamma, beta, rm, rv, eps, bn, eval_bn, sync_state, tracked):
+        """forward BatchNorm coefficients of a hidden block with pre-activations ``z``: (mean, invstd, k2, k3), a = relu(k2 z + k3).
+        ``gamma`` / ``beta`` / ``rm`` / ``rv``: the [C] vectors of module ``bn`` (detached; padded copies where C exceeds its channels);
+        its step counter joins ``tracked``."""
+        track, mom = _bn_track(bn, eval_bn, tracked)
+        if eval_bn:
+            # EVAL-mode BatchNorm under autograd (module.eval() with gradients on): the coefficients come from the RUNNING statistics,
+            # nothing is updated; [C]-sized host-side tensor math (a handful of tiny launches on a rare path)
+            gam = gamma.double()
+            invstd = torch.rsqrt(rv.double() + float(eps))
+            mean = rm.double().clone()
+            return mean, invstd, (gam * invstd).float(), (beta.double() - mean * gam * invstd).float()
+        if not track:
+            rm = rv = None
+        if not sync_state[0]:  # partial rows, then finish + coefficients in one kernel
+            return self.bn_fwd(z, npix, C, split, gamma, beta, eps, mom, rm, rv)
+        # data parallel: the sums of the GLOBAL batch go through an all-reduce between the halves
+        sums = self.stats(None, z, None, None, npix, C, split)
+        npix_bn = npix * _sync_sums(sums, state=sync_state)
+        k2, k3 = self.f32(C), self.f32(C)
+        mean = torch.empty((C,), dtype=torch.float64, device=self.dev)
+        invstd = torch.empty((C,), dtype=torch.float64, device=self.dev)
+        rc = self.lib.nastar_bn_coef_fwd(sums.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), npix_bn, float(mom), _ptr(rm), _ptr(rv),
+                                         k2.data_ptr(), k3.data_ptr(), mean.data_ptr(), invstd.data_ptr(), C, self.stream)
+        _native.check(rc, "nastar_bn_coef_fwd")
+        return mean, invstd, k2, k3
+
+    def bn_backward(self, da, z, coef, gamma, S_in, amax, npix, C, split, sync_state, eval_bn, in_place=False, overlap=None, sums_out=None,
+                    bias_n=0):
+        """ReLU mask + BatchNorm backward of a hidden block: (dgamma, dbeta, dz, S, conv-bias gradient or None).  ``da`` (stored, or the
+        on-the-fly tuple) carries the device scale ``S_in``, dz the re-centred ``S``; ``coef``: what ``bn_forward`` returned.  Batch
+        statistics on one rank: partial rows, then finish + coefficients in one kernel.  Data parallel (``sync_state``: the FORWARD's
+        snapshot) or eval mode: statistics -> all-reduce -> coefficients, with ``overlap()`` -- launches that need neither -- issued beside
+        the collective (a small one costs ~80 us of latency even in a 1-rank group).  The finishing kernels never write the scale they
+        read (all their workgroups read it) except the one-workgroup ``nastar_bn_coef_bwd`` (``in_place``: S is S_in).  ``sums_out``:
+        [C,2] doubles that receive (sum dy, sum dy z) * S_in (test probe).  ``bias_n``: eval mode, the convolution in front has a bias
+        of that many elements -- it HAS a gradient then: sum_p dz = gamma invstd sum_p dy."""
+        mean, invstd, k2f, k3f = coef
+        if not (sync_state[0] or eval_bn):
+            S = self.f32(1)
+            dgamma, dbeta, c1, c2, c3 = self.bn_bwd(da, z, k2f, k3f, npix, C, split, mean, invstd, gamma, S_in, S, sums_out=sums_out)
+        else:
+            sums = self.stats(da, z, k2f, k3f, npix, C, split, amax=amax, gscale=S_in, out=sums_out)
+            work = _sync_sums_begin(sums, S_in, sync_state)
+            if overlap is not None:
+                overlap()
+            world = _sync_sums_end(work, sums, S_in, sync_state)
+            assert not (in_place and isinstance(da, tuple)), "an on-the-fly gradient is formed again, with S_in, by the affine pass below"
+            S = S_in if in_place else self.f32(1)
+            dgamma, dbeta, c1, c2, c3 = (self.f32(C) for _ in range(5))
+            # eval-mode BatchNorm = the batch-statistics closed form in the limit of infinitely many pixels (the mean terms vanish), with the
+            # running statistics as mean / invstd; dgamma / dbeta need the same sums
+            name = "nastar_bn_coef_bwd" if in_place else "nastar_bn_coef_bwd_io"
+            rc = getattr(self.lib, name)(sums.data_ptr(), amax.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
+                                         (1 << 62) if eval_bn else npix * world, *((S.data_ptr(),) if in_place else (S_in.data_ptr(), S.data_ptr())),
+                                         dgamma.data_ptr(), dbeta.data_ptr(), c1.data_ptr(), c2.data_ptr(), c3.data_ptr(), C, self.stream)
+            _native.check(rc, name)
+            if world > 1:  # the kernel formed dgamma / dbeta from the GLOBAL sums; the flat gradient all-reduce AVERAGES over the ranks
+                dgamma /= world
+                dbeta /= world
+        bias_grad = (dbeta[:bias_n].double() * gamma.double()[:bias_n] * invstd[:bias_n]).float() if (eval_bn and bias_n) else None
+        dz = self.i16(npix * C * (2 if split else 1))
+        self.affine(da, z, c1, c2, c3, k2f, k3f, dz, npix, C, False, split, gscale=S_in)
+        return dgamma, dbeta, dz, S, bias_grad
+
+    def grad_seed(self, d, npix, split, amax):
+        """the upstream gradient d [npix] fp32 of a head padded to 32 channels as (fp16 gradient, its device scale S); max|d| goes to ``amax``"""
+        dzb, S = self.i16(npix * 32 * (2 if split else 1)), self.f32(1)
+        rc = self.lib.nastar_grad_seed_f16(d.data_ptr(), npix, int(split), dzb.data_ptr(), S.data_ptr(), amax.data_ptr(), self.stream)
+        _native.check(rc, "nastar_grad_seed_f16")
+        return dzb, S
 
     # ---- the 1-channel closing convolution as streams (csrc/nastar_encoder_co1.hip.h) ----
     @staticmethod
@@ -312,47 +429,18 @@ class _Lib:
         z = torch.empty((B, H, W), dtype=torch.float32, device=self.dev)
         ws, n = self.co1_ws(B, H, W, C)
         wc, bc = _f32c(w), (_f32c(bias) if bias is not None else None)
-        rc = self.lib.nastar_conv3x3_co1_f16(a.data_ptr(), wc.data_ptr(), bc.data_ptr() if bc is not None else None, B, H, W, C, int(split),
-                                             k2.data_ptr() if k2 is not None else None, k3.data_ptr() if k3 is not None else None,
-                                             z.data_ptr(), ws.data_ptr(), n, self.stream)
+        rc = self.lib.nastar_conv3x3_co1_f16(a.data_ptr(), wc.data_ptr(), _ptr(bc), B, H, W, C, int(split), _ptr(k2), _ptr(k3), z.data_ptr(),
+                                             ws.data_ptr(), n, self.stream)
         _native.check(rc, "nastar_conv3x3_co1_f16")
         return z
 
     def wgrad_co1(self, d, a, B, H, W, C, split, k2=None, k3=None):
         dw = torch.empty((1, C, 3, 3), dtype=torch.float32, device=self.dev)
         ws, n = self.co1_ws(B, H, W, C)
-        rc = self.lib.nastar_conv3x3_co1_wgrad_f16(d.data_ptr(), a.data_ptr(), B, H, W, C, int(split),
-                                                   k2.data_ptr() if k2 is not None else None, k3.data_ptr() if k3 is not None else None,
-                                                   dw.data_ptr(), ws.data_ptr(), n, self.stream)
+        rc = self.lib.nastar_conv3x3_co1_wgrad_f16(d.data_ptr(), a.data_ptr(), B, H, W, C, int(split), _ptr(k2), _ptr(k3), dw.data_ptr(),
+                                                   ws.data_ptr(), n, self.stream)
         _native.check(rc, "nastar_conv3x3_co1_wgrad_f16")
         return dw
-
-    def bn_bwd_u1(self, d, wlast, B, H, W, z, k2f, k3f, C, split, mean, invstd, gamma, gscale_in, gscale_out):
-        """``bn_bwd`` for the block in front of the closing convolution: da = gscale_in * (its input gradient of d), never stored"""
-        dgamma, dbeta, c1, c2, c3 = (self.f32(C) for _ in range(5))
-        nbytes = int(self.lib.nastar_chan_stats_workspace_bytes(B * H * W, C))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
-        rc = self.lib.nastar_bn_stats_coef_bwd_u1_f16(d.data_ptr(), wlast.data_ptr(), B, H, W, z.data_ptr(), k2f.data_ptr(), k3f.data_ptr(), C, int(split),
-                                                      mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), gscale_in.data_ptr(), gscale_out.data_ptr(),
-                                                      dgamma.data_ptr(), dbeta.data_ptr(), c1.data_ptr(), c2.data_ptr(), c3.data_ptr(), None,
-                                                      ws.data_ptr(), nbytes, self.stream)
-        _native.check(rc, "nastar_bn_stats_coef_bwd_u1_f16")
-        return dgamma, dbeta, c1, c2, c3
-
-    def stats_u1(self, d, wlast, gscale, B, H, W, z, ms, mt, C, split, amax):
-        """``stats`` (backward form) with da formed on the fly: double sums [C,2] for the sync-BN all-reduce"""
-        sums = torch.empty((C, 2), dtype=torch.float64, device=self.dev)
-        nbytes = int(self.lib.nastar_chan_stats_workspace_bytes(B * H * W, C))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
-        rc = self.lib.nastar_chan_stats_u1_f16_ws(d.data_ptr(), wlast.data_ptr(), gscale.data_ptr(), B, H, W, z.data_ptr(), ms.data_ptr(), mt.data_ptr(),
-                                                  sums.data_ptr(), amax.data_ptr(), C, int(split), ws.data_ptr(), nbytes, self.stream)
-        _native.check(rc, "nastar_chan_stats_u1_f16_ws")
-        return sums
-
-    def affine_u1(self, d, wlast, gscale, B, H, W, z, k1, k2, k3, ms, mt, out, C, split):
-        rc = self.lib.nastar_chan_affine_u1_f16(d.data_ptr(), wlast.data_ptr(), gscale.data_ptr(), B, H, W, z.data_ptr(), k1.data_ptr(), k2.data_ptr(),
-                                                k3.data_ptr(), ms.data_ptr(), mt.data_ptr(), out.data_ptr(), C, int(split), self.stream)
-        _native.check(rc, "nastar_chan_affine_u1_f16")
 
     def wgrad(self, dz, a, B, H, W, co, ci, co_real, ci_real, split, gscale):
         """dW in torch's [co_real, ci_real, 3, 3] layout, already divided by the device-side gradient scale"""
@@ -366,11 +454,6 @@ class _Lib:
 
 
 CO1_STREAMS = True  # the 1-channel closing convolution as streams (csrc/nastar_encoder_co1.hip.h); False: padded to 32 channels on the MFMA (A/B, tests)
-
-
-def _f32c(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    return t if t.is_contiguous() and t.dtype == torch.float32 else t.float().contiguous()
 
 
 def wgrad_segment(W: int) -> int:
@@ -433,7 +516,6 @@ class _CnnTrunk(torch.autograd.Function):
             acts, zs, rs, coef, scals = [x0], [], [], [], []
             tracked = []  # the BatchNorm step counters: ONE multi-tensor increment instead of a launch per layer
             ctx.sync_state = SyncBatchNorm.snapshot()  # the backward all-reduces iff this forward did
-            sync = ctx.sync_state[0]
             h, w = H, W
             wmax = L.weight_maxima(ws) if split else None  # one launch for all D + 1 weight maxima
             # the 1-channel closing convolution: a stream over its input (31/32 of a padded matrix product would be zeros); where nothing
@@ -460,32 +542,8 @@ class _CnnTrunk(torch.autograd.Function):
                 z = torch.empty((npix * cout * mult,), dtype=torch.int16, device=dev)
                 L.conv(acts[-1], wpack, scale, shift, B, h, w, cin_p, cout, sflag, out=z)
                 bn = cfg["bns"][l]
-                track = bn is not None and bn.track_running_stats and bn.running_mean is not None and not cfg.get("eval_bn")
-                mom = 0.0
-                if track:  # nn.BatchNorm2d's training-mode side effect (unbiased variance), done inside the coefficient kernel
-                    mom = bn.momentum if bn.momentum is not None else 1.0 / float(int(bn.num_batches_tracked) + 1)
-                    tracked.append(bn.num_batches_tracked)
-                gam, bet = gammas[l].detach(), betas[l].detach()
-                if cfg.get("eval_bn"):
-                    # EVAL-mode BatchNorm under autograd (module.eval() with gradients on): the coefficients come from the RUNNING statistics,
-                    # nothing is updated; [C]-sized host-side tensor math (a handful of tiny launches on a rare path)
-                    invstd = torch.rsqrt(bn.running_var.double() + float(cfg["eps"][l]))
-                    mean = bn.running_mean.double().clone()
-                    k2 = (gam.double() * invstd).float()
-                    k3 = (bet.double() - mean * gam.double() * invstd).float()
-                elif not sync:  # partial rows, then finish + coefficients in one kernel
-                    mean, invstd, k2, k3 = L.bn_fwd(z, npix, cout, split, gam, bet, cfg["eps"][l], mom, bn.running_mean if track else None,
-                                                    bn.running_var if track else None)
-                else:  # data parallel: the sums of the GLOBAL batch go through an all-reduce between the halves
-                    sums = L.stats(None, z, None, None, npix, cout, split)
-                    npix_bn = npix * _sync_sums(sums, state=ctx.sync_state)
-                    k2, k3 = L.f32(cout), L.f32(cout)
-                    mean = torch.empty((cout,), dtype=torch.float64, device=dev)
-                    invstd = torch.empty((cout,), dtype=torch.float64, device=dev)
-                    rc = L.lib.nastar_bn_coef_fwd(sums.data_ptr(), gam.data_ptr(), bet.data_ptr(), float(cfg["eps"][l]), npix_bn, float(mom),
-                                                  bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-                                                  k2.data_ptr(), k3.data_ptr(), mean.data_ptr(), invstd.data_ptr(), cout, L.stream)
-                    _native.check(rc, "nastar_bn_coef_fwd")
+                mean, invstd, k2, k3 = L.bn_forward(z, npix, cout, split, gammas[l].detach(), betas[l].detach(), bn.running_mean, bn.running_var,
+                                                    cfg["eps"][l], bn, bool(cfg.get("eval_bn")), ctx.sync_state, tracked)
                 zs.append(z)
                 coef.append((mean, invstd, k2, k3))
                 if fuse_act and l == D - 1:
@@ -545,77 +603,57 @@ class _CnnTrunk(torch.autograd.Function):
         with torch.cuda.device(dev):
             h, w = (H >> D, W >> D) if pool else (H, W)   # resolution of the last convolution
             npix = B * h * w
-            d = dzl.reshape(npix)
-            d = d if d.is_contiguous() and d.dtype == torch.float32 else d.float().contiguous()
+            d = _f32c(dzl.reshape(npix))
             # gradients travel multiplied by a power of two S (device scalar `gscale`, re-centred per block): scaled values peak near
             # 2^10, so fp16 neither overflows nor loses the small terms; S is divided out inside the weight-gradient / coefficient kernels
-            gscale, amax = L.f32(1), L.f32(1)
+            amax = L.f32(1)
             bias_grads = {}  # eval-mode BatchNorm only: conv-bias gradients of the hidden blocks
+            eval_bn = bool(cfg.get("eval_bn"))
+            # data-parallel (sync) and eval-mode steps take a BatchNorm backward in halves around a collective: the weight gradient of the
+            # layer behind it, which needs neither, is launched BESIDE that collective (``overlap`` of _Lib.bn_backward)
+            unfused = ctx.sync_state[0] or eval_bn
+
+            def bn_block(l, da, C, in_place, overlap):
+                """ReLU mask + BatchNorm backward of the hidden block with pre-activations zs[l]: (dz, its scale)"""
+                grads[4 * l + 2], grads[4 * l + 3], dz, S, bias_grads[l] = L.bn_backward(
+                    da, ctx.zs[l], ctx.coef[l], gammas[l].detach(), gscale, amax, npix, C, split, ctx.sync_state, eval_bn, in_place=in_place,
+                    overlap=overlap, bias_n=params[4 * l + 1].numel())
+                return dz, S
+
             top = D
             # closing convolution as streams: its weight gradient from d itself, its input gradient never stored -- the BatchNorm backward
             # of block D forms it on the fly (not for pooling stacks, whose gradient passes through the max-pool first)
             if getattr(ctx, "co1", False) and D >= 1 and not pool:
                 wl = ws[D]
                 C = wl.shape[1]
+                gscale = L.f32(1)
                 rc = L.lib.nastar_grad_scale_f32(d.data_ptr(), npix, gscale.data_ptr(), amax.data_ptr(), L.stream)
                 _native.check(rc, "nastar_grad_scale_f32")
+
                 def closing_wgrad():
                     if ctx.fuse_act:
-                        return L.wgrad_co1(d, ctx.zs[D - 1], B, h, w, C, split, ctx.coef[D - 1][2], ctx.coef[D - 1][3])
-                    return L.wgrad_co1(d, ctx.acts[D], B, h, w, C, split)
-                # eval-mode BatchNorm = the batch-statistics closed form in the limit of infinitely many pixels (the mean terms vanish): the
-                # unfused path below with npix -> 1e30 and the running statistics as mean / invstd; dgamma / dbeta need the same sums
-                eval_bn = bool(cfg.get("eval_bn"))
-                unfused = ctx.sync_state[0] or eval_bn
+                        grads[4 * D] = L.wgrad_co1(d, ctx.zs[D - 1], B, h, w, C, split, ctx.coef[D - 1][2], ctx.coef[D - 1][3])
+                    else:
+                        grads[4 * D] = L.wgrad_co1(d, ctx.acts[D], B, h, w, C, split)
                 if not unfused:
-                    grads[4 * D] = closing_wgrad()
+                    closing_wgrad()
                 grads[4 * D + 1] = torch.empty_like(params[4 * D + 1])
-                z = ctx.zs[D - 1]
-                mean, invstd, k2f, k3f = ctx.coef[D - 1]
-                wlc = _f32c(wl)
-                gs_new = L.f32(1)
-                if not unfused:
-                    dgamma, dbeta, c1, c2, c3 = L.bn_bwd_u1(d, wlc, B, h, w, z, k2f, k3f, C, split, mean, invstd, gammas[D - 1].detach(), gscale, gs_new)
-                else:  # data parallel: the sums of the GLOBAL batch (all-reduced between the statistics and the coefficients); or eval mode
-                    sums = L.stats_u1(d, wlc, gscale, B, h, w, z, k2f, k3f, C, split, amax)
-                    work = _sync_sums_begin(sums, gscale, ctx.sync_state)
-                    grads[4 * D] = closing_wgrad()  # beside the collective, which it does not need
-                    world = _sync_sums_end(work, sums, gscale, ctx.sync_state)
-                    dgamma, dbeta, c1, c2, c3 = (L.f32(C) for _ in range(5))
-                    rc = L.lib.nastar_bn_coef_bwd_io(sums.data_ptr(), amax.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                     gammas[D - 1].detach().data_ptr(), (1 << 62) if eval_bn else npix * world, gscale.data_ptr(), gs_new.data_ptr(),
-                                                     dgamma.data_ptr(), dbeta.data_ptr(), c1.data_ptr(), c2.data_ptr(), c3.data_ptr(), C, L.stream)
-                    _native.check(rc, "nastar_bn_coef_bwd_io")
-                    if world > 1:  # the flat gradient all-reduce AVERAGES over the ranks
-                        dgamma /= world
-                        dbeta /= world
-                grads[4 * (D - 1) + 2] = dgamma
-                grads[4 * (D - 1) + 3] = dbeta
-                if eval_bn:  # the conv bias in front of an EVAL-mode BatchNorm has a gradient: sum_p dz = gamma invstd sum_p dy
-                    nb = params[4 * (D - 1) + 1].numel()
-                    bias_grads[D - 1] = (dbeta[:nb].double() * gammas[D - 1].detach().double()[:nb] * invstd[:nb]).float()
-                dzb = torch.empty((npix * C * mult,), dtype=torch.int16, device=dev)
-                L.affine_u1(d, wlc, gscale, B, h, w, z, c1, c2, c3, k2f, k3f, dzb, C, split)
-                gscale = gs_new
+                dzb, gscale = bn_block(D - 1, (d, _f32c(wl), B, h, w), C, False, closing_wgrad if unfused else None)
                 cur_co = C
                 top = D - 1
             else:
-                dzb = torch.empty((npix * 32 * mult,), dtype=torch.int16, device=dev)
-                rc = L.lib.nastar_grad_seed_f16(d.data_ptr(), npix, int(split), dzb.data_ptr(), gscale.data_ptr(), amax.data_ptr(), L.stream)
-                _native.check(rc, "nastar_grad_seed_f16")
+                dzb, gscale = L.grad_seed(d, npix, split, amax)
                 cur_co = 32  # padded channel count of the current dz
             for l in range(top, -1, -1):
                 wt = ws[l]
                 cout, cin = wt.shape[:2]
                 cin_p = _pad32(cin)
-                # data-parallel (sync) steps launch this layer's weight gradient BESIDE the all-reduce of the next BatchNorm backward's
-                # sums (below): it needs neither, and a small collective costs ~80 us of latency even in a 1-rank group
-                eval_bn = bool(cfg.get("eval_bn"))
-                unfused = ctx.sync_state[0] or eval_bn
-                late_wgrad = unfused and l > 0
-                wg_h, wg_w = h, w  # (the pooling stacks change h, w before the deferred launch)
-                if not late_wgrad:
+
+                def layer_wgrad(h=h, w=w):  # (the pooling stacks change h, w before a deferred launch)
                     grads[4 * l] = L.wgrad(dzb, ctx.acts[l], B, h, w, cur_co, cin_p, cout, cin, split, gscale)
+                late_wgrad = unfused and l > 0
+                if not late_wgrad:
+                    layer_wgrad()
                 grads[4 * l + 1] = torch.empty_like(params[4 * l + 1])             # conv bias in front of a BatchNorm: exactly 0 (zeroed below)
                 if l == 0:
                     break
@@ -623,45 +661,18 @@ class _CnnTrunk(torch.autograd.Function):
                 wpack, scale, shift, _ = ctx.tpacks[l - 1] if (ctx.tpacks is not None and ctx.tpacks[l - 1] is not None) else L.pack(wt, True, split, scal=ctx.scals[l])
                 da = torch.empty((npix * cin_p * mult,), dtype=torch.int16, device=dev)
                 L.conv(dzb, wpack, scale, shift, B, h, w, cur_co, cin_p, sflag, out=da)
-                C = cin_p
                 if pool:  # da is the gradient w.r.t. the pooled activations: route it to each window's arg-max at the finer resolution
                     h, w = h * 2, w * 2
                     npix = B * h * w
-                    dr = torch.empty((npix * C * mult,), dtype=torch.int16, device=dev)
-                    rc = L.lib.nastar_maxpool2x2_bwd_f16(ctx.rs[l - 1].data_ptr(), da.data_ptr(), dr.data_ptr(), B, h, w, C, int(split), L.stream)
+                    dr = torch.empty((npix * cin_p * mult,), dtype=torch.int16, device=dev)
+                    rc = L.lib.nastar_maxpool2x2_bwd_f16(ctx.rs[l - 1].data_ptr(), da.data_ptr(), dr.data_ptr(), B, h, w, cin_p, int(split), L.stream)
                     _native.check(rc, "nastar_maxpool2x2_bwd_f16")
                     da = dr
-                # ReLU mask + BatchNorm backward of hidden block l (pre-activation zs[l-1])
-                z = ctx.zs[l - 1]
-                mean, invstd, k2f, k3f = ctx.coef[l - 1]
-                if not unfused:  # (sum dy, sum dy z) * S, max|dy| * S: partial rows, then finish + coefficients in one kernel
-                    gs_new = L.f32(1)  # NOT in place: the finishing kernel has many workgroups, all of which read the incoming scale
-                    dgamma, dbeta, c1, c2, c3 = L.bn_bwd(da, z, k2f, k3f, npix, C, split, mean, invstd, gammas[l - 1].detach(), gscale, gs_new)
-                    gscale = gs_new
-                else:
-                    sums = L.stats(da, z, k2f, k3f, npix, C, split, amax=amax)
-                    work = _sync_sums_begin(sums, gscale, ctx.sync_state)
-                    # ... the collective is in flight: this layer's weight gradient (dz of block l+1 x activations of block l) runs now
-                    grads[4 * l] = L.wgrad(dzb, ctx.acts[l], B, wg_h, wg_w, cur_co, cin_p, cout, cin, split, gscale)
-                    world = _sync_sums_end(work, sums, gscale, ctx.sync_state)
-                    dgamma, dbeta, c1, c2, c3 = (L.f32(C) for _ in range(5))
-                    rc = L.lib.nastar_bn_coef_bwd(sums.data_ptr(), amax.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                  gammas[l - 1].detach().data_ptr(), (1 << 62) if eval_bn else npix * world, gscale.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                                  c1.data_ptr(), c2.data_ptr(), c3.data_ptr(), C, L.stream)
-                    _native.check(rc, "nastar_bn_coef_bwd")
-                    if world > 1:  # the kernel formed dgamma / dbeta from the GLOBAL sums; the flat gradient all-reduce AVERAGES over ranks
-                        dgamma /= world
-                        dbeta /= world
-                grads[4 * (l - 1) + 2] = dgamma
-                grads[4 * (l - 1) + 3] = dbeta
-                if eval_bn:
-                    nb = params[4 * (l - 1) + 1].numel()
-                    bias_grads[l - 1] = (dbeta[:nb].double() * gammas[l - 1].detach().double()[:nb] * invstd[:nb]).float()
-                dzb = torch.empty_like(da)
-                L.affine(da, z, c1, c2, c3, k2f, k3f, dzb, npix, C, False, split)
-                cur_co = C
+                # hidden block l; its unfused form finishes with the in-place (one-workgroup) coefficient kernel
+                dzb, gscale = bn_block(l - 1, da, cin_p, True, layer_wgrad if late_wgrad else None)
+                cur_co = cin_p
             torch._foreach_zero_([grads[4 * l + 1] for l in range(D + 1)])  # one launch for all of them
-            if cfg.get("eval_bn"):  # ... except in eval mode, where the biases in front of a BatchNorm on running statistics do get gradients
+            if eval_bn:  # ... except in eval mode, where the biases in front of a BatchNorm on running statistics do get gradients
                 for l, bg in bias_grads.items():
                     grads[4 * l + 1] = bg
                 grads[4 * D + 1] = dzl.float().sum().reshape(1)
@@ -690,7 +701,7 @@ class _LastBlock(torch.autograd.Function):
         dev = z.device
         lib = _native.load()
         st = torch.cuda.current_stream(dev).cuda_stream
-        zc = z if z.is_contiguous() and z.dtype == torch.float32 else z.float().contiguous()
+        zc = _f32c(z)
         n = zc.numel()
         nparts = int(lib.nastar_bn1_parts(n))
         part = torch.empty((nparts, 2), dtype=torch.float64, device=dev)
@@ -721,9 +732,7 @@ class _LastBlock(torch.autograd.Function):
                 world = _sync_sums(part, state=ctx.sync_state)
                 nparts = 1
             _native.check(lib.nastar_bn1_sigmoid_fwd(zc.data_ptr(), n, part.data_ptr(), nparts, float(n * world), g.data_ptr(), b.data_ptr(),
-                                                     float(eps), c.data_ptr(), float(momentum),
-                                                     running_mean.data_ptr() if running_mean is not None else None,
-                                                     running_var.data_ptr() if running_var is not None else None, cost.data_ptr(),
+                                                     float(eps), c.data_ptr(), float(momentum), _ptr(running_mean), _ptr(running_var), cost.data_ptr(),
                                                      stat.data_ptr(), st), "nastar_bn1_sigmoid_fwd")
         ctx.save_for_backward(zc, g, b, c, stat)
         ctx.n_total = float(n * world)
@@ -739,7 +748,7 @@ class _LastBlock(torch.autograd.Function):
         dev = zc.device
         lib = _native.load()
         st = torch.cuda.current_stream(dev).cuda_stream
-        d = dcost if dcost.is_contiguous() and dcost.dtype == torch.float32 else dcost.float().contiguous()
+        d = _f32c(dcost)
         n = zc.numel()
         nparts = int(lib.nastar_bn1_parts(n))
         part = torch.empty((nparts, 3), dtype=torch.float64, device=dev)
@@ -852,11 +861,7 @@ def cnn_train_forward(cnn: nn.Module, map_designs: torch.Tensor, start_maps: tor
             y = (zl - bnl.running_mean) * torch.rsqrt(bnl.running_var + bnl.eps) * bnl.weight + bnl.bias
             return torch.sigmoid(y) * cnn.const
         return _LastBlock.apply(zl, bnl.weight, bnl.bias, const.reshape(1), bnl.eps, None, bnl.running_mean, bnl.running_var)  # momentum None = eval
-    track = bnl.track_running_stats and bnl.running_mean is not None
-    mom = 0.0
-    if track:
-        mom = bnl.momentum if bnl.momentum is not None else 1.0 / float(int(bnl.num_batches_tracked) + 1)
-        bnl.num_batches_tracked += 1
+    track, mom = _bn_track(bnl, False)
     const = cnn.const if isinstance(cnn.const, torch.Tensor) else _const_tensor(float(cnn.const), zl.device)
     if bnl.weight is None or const.numel() != 1 or const.dtype != torch.float32:  # BatchNorm without affine / exotic const: tensor ops
         if SyncBatchNorm.active():
@@ -896,7 +901,7 @@ class _UnetTrunk(torch.autograd.Function):
         saved = []
         tracked = []  # the BatchNorm step counters: ONE multi-tensor increment instead of a launch per layer
         ctx.sync_state = SyncBatchNorm.snapshot()  # the backward all-reduces iff this forward did
-        sync = ctx.sync_state[0]
+        eval_bn = bool(cfg.get("eval_bn"))
         out = None
         with torch.cuda.device(dev):
             conv_steps = [st for st in cfg["plan"] if st["kind"] != "pool"]
@@ -938,41 +943,15 @@ class _UnetTrunk(torch.autograd.Function):
                 z = L.i16(npix * cout * mult)
                 L.conv(src, wpack, scale, shift, B, h, w, c1, cout, sflag | ups, out=z, src2=src2, c2=c2)
                 bn = st["bn"]
-                eval_bn = bool(cfg.get("eval_bn"))
-                track = bn.track_running_stats and bn.running_mean is not None and not eval_bn
-                mom = 0.0
-                if track:
-                    mom = bn.momentum if bn.momentum is not None else 1.0 / float(int(bn.num_batches_tracked) + 1)
-                    tracked.append(bn.num_batches_tracked)
                 padc = cout - cout_r
                 gam_v, bet_v = params[st["g"]].detach(), params[st["be"]].detach()
-                rm_v, rv_v = (bn.running_mean, bn.running_var) if (track or eval_bn) else (None, None)
+                rm_v, rv_v = bn.running_mean, bn.running_var
                 if padc:  # padded copies of the per-channel vectors (the running statistics are copied back below)
                     gam_v, bet_v = torch.nn.functional.pad(gam_v, (0, padc)), torch.nn.functional.pad(bet_v, (0, padc))
                     if rm_v is not None:
                         rm_v, rv_v = torch.nn.functional.pad(rm_v, (0, padc)), torch.nn.functional.pad(rv_v, (0, padc), value=1.0)
-                if eval_bn:
-                    # EVAL-mode BatchNorm under autograd (module.eval() with gradients on): coefficients from the RUNNING statistics, nothing is
-                    # updated; [C]-sized host-side tensor math (as in _CnnTrunk)
-                    gam, bet = gam_v.double(), bet_v.double()
-                    invstd = torch.rsqrt(rv_v.double() + float(bn.eps))
-                    mean = rm_v.double().clone()
-                    k2 = (gam * invstd).float()
-                    k3 = (bet - mean * gam * invstd).float()
-                elif not sync:  # partial rows, then finish + coefficients in one kernel
-                    mean, invstd, k2, k3 = L.bn_fwd(z, npix, cout, split, gam_v, bet_v, bn.eps, mom, rm_v if track else None, rv_v if track else None)
-                else:  # data parallel: statistics of the GLOBAL batch (all-reduce between the halves)
-                    sums = L.stats(None, z, None, None, npix, cout, split)
-                    npix_bn = npix * _sync_sums(sums, state=ctx.sync_state)
-                    k2, k3 = L.f32(cout), L.f32(cout)
-                    mean = torch.empty((cout,), dtype=torch.float64, device=dev)
-                    invstd = torch.empty((cout,), dtype=torch.float64, device=dev)
-                    rc = L.lib.nastar_bn_coef_fwd(sums.data_ptr(), gam_v.data_ptr(), bet_v.data_ptr(),
-                                                  float(bn.eps), npix_bn, float(mom), rm_v.data_ptr() if track else None,
-                                                  rv_v.data_ptr() if track else None, k2.data_ptr(), k3.data_ptr(),
-                                                  mean.data_ptr(), invstd.data_ptr(), cout, L.stream)
-                    _native.check(rc, "nastar_bn_coef_fwd")
-                if padc and track:  # the kernels updated the padded copies
+                mean, invstd, k2, k3 = L.bn_forward(z, npix, cout, split, gam_v, bet_v, rm_v, rv_v, bn.eps, bn, eval_bn, ctx.sync_state, tracked)
+                if padc and rm_v is not None and not eval_bn:  # the kernels updated the padded copies
                     bn.running_mean.copy_(rm_v[:cout_r])
                     bn.running_var.copy_(rv_v[:cout_r])
                 a = L.i16(npix * cout * mult)
@@ -1015,6 +994,7 @@ class _UnetTrunk(torch.autograd.Function):
         zero_bias = []
         with torch.cuda.device(dev):
             amax = L.f32(1)
+            eval_bn = bool(cfg.get("eval_bn"))
             for idx in range(len(cfg["plan"]) - 1, -1, -1):
                 st, sv = cfg["plan"][idx], saved[idx]
                 h, w = H // st["div"], W // st["div"]
@@ -1034,51 +1014,27 @@ class _UnetTrunk(torch.autograd.Function):
                 src, c1 = acts[st["src"]]
                 src2, c2 = acts[st["skip"]] if st["skip"] is not None else (None, 0)
                 if st["final"]:
-                    d = dz.reshape(npix)
-                    d = d if d.is_contiguous() and d.dtype == torch.float32 else d.float().contiguous()
-                    S = L.f32(1)
-                    dzb = L.i16(npix * 32 * mult)
-                    _native.check(L.lib.nastar_grad_seed_f16(d.data_ptr(), npix, int(split), dzb.data_ptr(), S.data_ptr(), amax.data_ptr(), L.stream),
-                                  "nastar_grad_seed_f16")
+                    d = _f32c(dz.reshape(npix))
+                    dzb, S = L.grad_seed(d, npix, split, amax)
                     cur_co = 32
                     if st["b"] is not None:
                         grads_p[st["b"]] = d.sum().reshape(1)  # no BatchNorm behind the head: its bias has a real gradient
                 else:
                     g, S_in = grads.pop(st["dst"])
-                    if cfg.get("debug") is not None:  # dev probe: the gradient w.r.t. this block's output, as it arrives
+                    debug = cfg.get("debug") is not None
+                    if debug:  # dev probe: the gradient w.r.t. this block's output, as it arrives
                         cfg["debug"][st["dst"]] = (g.clone(), S_in.clone(), (B, h, w, cout))
-                    S = L.f32(1)  # the BatchNorm backward re-centres the scale: S_in (possibly shared with a skip branch) -> S
-                    z = sv["z"]
-                    mean, invstd, k2f, k3f = sv["coef"]
-                    sums = None
-                    eval_bn = bool(cfg.get("eval_bn"))
-                    if not ctx.sync_state[0] and not eval_bn:  # partial rows, then finish + coefficients in one kernel
-                        if cfg.get("debug") is not None:
-                            sums = torch.empty((cout, 2), dtype=torch.float64, device=dev)
-                        dgamma, dbeta, c1v, c2v, c3v = L.bn_bwd(g, z, k2f, k3f, npix, cout, split, mean, invstd, sv["gam"], S_in, S, sums_out=sums)
-                    else:
-                        sums = L.stats(g, z, k2f, k3f, npix, cout, split, amax=amax)
-                        world = _sync_sums(sums, S_in, ctx.sync_state)
-                        dgamma, dbeta, c1v, c2v, c3v = (L.f32(cout) for _ in range(5))
-                        # (eval mode: BatchNorm on its running statistics = the batch-statistics closed form with infinitely many pixels)
-                        rc = L.lib.nastar_bn_coef_bwd_io(sums.data_ptr(), amax.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                         sv["gam"].data_ptr(), (1 << 62) if eval_bn else npix * world, S_in.data_ptr(), S.data_ptr(),
-                                                         dgamma.data_ptr(), dbeta.data_ptr(), c1v.data_ptr(), c2v.data_ptr(), c3v.data_ptr(), cout,
-                                                         L.stream)
-                        _native.check(rc, "nastar_bn_coef_bwd_io")
-                        if world > 1:  # formed from the GLOBAL sums; the flat gradient all-reduce averages over ranks
-                            dgamma /= world
-                            dbeta /= world
-                    if cfg.get("debug") is not None:
-                        cfg["debug"][st["dst"] + ":bn"] = (z, k2f, k3f, dbeta.clone(), dgamma.clone(), sums.clone(), S_in.clone())
+                    # the BatchNorm backward re-centres the scale: S_in (possibly shared with a skip branch) -> S
+                    sums = torch.empty((cout, 2), dtype=torch.float64, device=dev) if debug else None
+                    nb = params[st["b"]].numel() if st["b"] is not None else 0
+                    dgamma, dbeta, dzb, S, bias_grad = L.bn_backward(g, sv["z"], sv["coef"], sv["gam"], S_in, amax, npix, cout, split, ctx.sync_state,
+                                                                     eval_bn, sums_out=sums, bias_n=nb)
+                    if debug:
+                        cfg["debug"][st["dst"] + ":bn"] = (sv["z"], sv["coef"][2], sv["coef"][3], dbeta.clone(), dgamma.clone(), sums.clone(), S_in.clone())
                     grads_p[st["g"]], grads_p[st["be"]] = (dgamma, dbeta) if cout == cout_r else (dgamma[:cout_r].contiguous(), dbeta[:cout_r].contiguous())
-                    dzb = L.i16(npix * cout * mult)
-                    L.affine(g, z, c1v, c2v, c3v, k2f, k3f, dzb, npix, cout, False, split)
                     cur_co = cout
-                    if st["b"] is not None and eval_bn:
-                        # ... whose conv bias DOES have a gradient then: sum_p dz = gamma invstd sum_p dy
-                        nb = params[st["b"]].numel()
-                        grads_p[st["b"]] = (dbeta[:nb].double() * sv["gam"].double()[:nb] * invstd[:nb]).float()
+                    if bias_grad is not None:  # eval mode: the conv bias in front of a BatchNorm on running statistics DOES have a gradient
+                        grads_p[st["b"]] = bias_grad
                     elif st["b"] is not None:
                         grads_p[st["b"]] = torch.empty_like(params[st["b"]])  # conv bias in front of a BatchNorm: exactly 0 (zeroed below)
                         zero_bias.append(grads_p[st["b"]])
@@ -1086,7 +1042,7 @@ class _UnetTrunk(torch.autograd.Function):
                 cin_p = c1 + c2
                 if st["ups"]:
                     a_in = L.i16(npix * cin_p * mult)
-                    _native.check(L.lib.nastar_upcat_f16(src.data_ptr(), src2.data_ptr() if src2 is not None else None, a_in.data_ptr(), B, h, w,
+                    _native.check(L.lib.nastar_upcat_f16(src.data_ptr(), _ptr(src2), a_in.data_ptr(), B, h, w,
                                                          c1, c2, int(split), L.stream), "nastar_upcat_f16")
                 else:
                     a_in = src
@@ -1099,7 +1055,7 @@ class _UnetTrunk(torch.autograd.Function):
                 if st["ups"]:
                     dx = L.i16(B * (h // 2) * (w // 2) * c1 * mult)
                     dsk = L.i16(npix * c2 * mult) if c2 else None
-                    _native.check(L.lib.nastar_upcat_bwd_f16(da.data_ptr(), dx.data_ptr(), dsk.data_ptr() if dsk is not None else None, B, h, w,
+                    _native.check(L.lib.nastar_upcat_bwd_f16(da.data_ptr(), dx.data_ptr(), _ptr(dsk), B, h, w,
                                                              c1, c2, int(split), L.stream), "nastar_upcat_bwd_f16")
                     accumulate(st["src"], dx, S, B * (h // 2) * (w // 2), c1)
                     if c2:
