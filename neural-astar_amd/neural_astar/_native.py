@@ -222,6 +222,18 @@ FIELD_GRAD_TILED_SIGNATURES = {
     "nastar_fields_backward_tiled_status": "i pppiiiuppzp",
 }
 
+# the signatures of include/nastar_field_routes.h (the tenth header: ordered optimal routes for many start cells per map, read off a
+# cost-to-go field), same letter code; a table of its own (tests/test_field_routes.py compares it with ITS header)
+FIELD_ROUTE_SIGNATURES = {
+    "nastar_field_routes_abi": "i ",
+    "nastar_field_routes_max_cells": "i ",
+    "nastar_field_routes_lds_cells": "i ",
+    "nastar_field_routes_workspace_bytes": "z iii",
+    # dist, goal, passable, start_idx, B, S, H, W, neighbor_mask, routes_out, route_cap, route_len_out, route_cost_out, status_out, workspace,
+    # workspace_bytes, stream
+    "nastar_field_routes": "i ppppiiiiupippppzp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -357,6 +369,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, FIELD_GRAD_SIGNATURES, FIELD_GRAD_SIGNATURES)
     if hasattr(lib, "nastar_fields_grad_tiled_abi"):  # (and the ninth)
         _bind(lib, FIELD_GRAD_TILED_SIGNATURES, FIELD_GRAD_TILED_SIGNATURES)
+    if hasattr(lib, "nastar_field_routes_abi"):  # (and the tenth)
+        _bind(lib, FIELD_ROUTE_SIGNATURES, FIELD_ROUTE_SIGNATURES)
     _lib = lib
     return lib
 

@@ -17,7 +17,8 @@ from .status import (CLEAN, PROOF_MAX_G_RATIO, STATUS_BAD_HEURISTIC, STATUS_NOT_
 
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
            "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput", "cost_to_go_tiled",
-           "fields_backward", "FIELD_PLATEAU", "FIELDS_GRAD_MAX_CELLS", "fields_backward_tiled", "FIELDS_GRAD_TILED_MAX_CELLS"]
+           "fields_backward", "FIELD_PLATEAU", "FIELDS_GRAD_MAX_CELLS", "fields_backward_tiled", "FIELDS_GRAD_TILED_MAX_CELLS",
+           "field_routes", "FieldRoutes", "FIELD_ROUTES_MAX_CELLS", "FIELD_ROUTES_MAX_QUERIES"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -1203,3 +1204,95 @@ def _cost_to_go_tiled_differentiable(cost_maps, goal_maps, obstacles_maps, neigh
     # which maps have no gradient: the backward's own verdict (its init launch and a status write), so the rule lives in one place, the kernel
     _raise_plateau(_fields_plateau_tiled(out.dists.detach(), goal_maps, obstacles_maps, mask), B, "cost_to_go_tiled")
     return out, rounds[0]
+
+
+# ---- include/nastar_field_routes.h: ordered optimal routes for many start cells per map, read off the field ---
+FIELD_ROUTES_MAX_CELLS = 1179648  # nastar_field_routes_max_cells(): every size cost_to_go_tiled takes
+FIELD_ROUTES_MAX_QUERIES = 1 << 30  # the most (map, start) pairs one call takes
+
+
+class FieldRoutes(NamedTuple):
+    """What ``field_routes()`` returns, per (map, start) query.  ``routes`` [B,S,L] int32: flat cell indices r*W + c in travel order, the
+    goal last, then -1 (``planner.differentiable_astar.route_coords`` turns them into (row, col)); a route longer than L keeps its LAST L
+    cells.  ``route_lengths`` [B,S] int32: the true number of route cells.  ``route_costs`` [B,S] fp32: the field at the start cell, +inf
+    for an obstacle, an unreachable start and an index outside the map.  ``status`` [B,S] int32: 0, ``STATUS_UNSOLVABLE`` (3: the field
+    is not finite at the start), ``FIELD_PLATEAU`` (11: the chain runs into a cell without a strictly closer neighbour) or 1 (the index
+    lies outside [0, H*W)); a failed query has length 0 and a row of -1."""
+
+    routes: torch.Tensor
+    route_lengths: torch.Tensor
+    route_costs: torch.Tensor
+    status: torch.Tensor
+
+
+def _start_indices(starts, B: int, H: int, W: int) -> torch.Tensor:
+    """``starts`` of ``field_routes`` -> [B,S] int32 flat indices: an integer [B,S] tensor as it is; a float [B,S,H,W] tensor (the dataset's
+    ``start_maps`` layout) by the highest-index non-zero cell of every channel, -1 for an all-zero channel"""
+    if not torch.is_tensor(starts) or starts.dtype == torch.bool or starts.is_complex():
+        raise TypeError(f"starts must be an integer [B,S] tensor of flat cell indices or a float [B,S,H,W] tensor of start maps, got "
+                        f"{starts.dtype if torch.is_tensor(starts) else type(starts).__name__}")
+    if starts.is_floating_point():
+        if starts.ndim != 4 or starts.shape[0] != B or starts.shape[1] < 1 or tuple(starts.shape[-2:]) != (H, W):
+            raise ValueError(f"float starts must be [B,S,H,W] start maps with S >= 1 for {B} maps of {H}x{W}, got {tuple(starts.shape)}")
+        cells = torch.arange(1, H * W + 1, dtype=torch.int32, device=starts.device)
+        return ((starts.detach().reshape(B, starts.shape[1], H * W) != 0) * cells).amax(-1) - 1
+    if starts.ndim != 2 or starts.shape[0] != B or starts.shape[1] < 1:
+        raise ValueError(f"integer starts must be [B,S] flat cell indices with S >= 1 for {B} maps, got {tuple(starts.shape)}")
+    if starts.dtype == torch.int32:
+        return starts.detach()
+    return starts.detach().clamp(-1, H * W).to(torch.int32)  # (every index outside the map stays outside it)
+
+
+def field_routes(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor,
+                 neighbor_mask: Optional[int] = None, max_route_len: Optional[int] = None) -> FieldRoutes:
+    """The ORDERED optimal route from each of S start cells per map to its nearest goal, read off the field (include/nastar_field_routes.h)
+    -> ``FieldRoutes``: one field per map answers any number of starts, no search runs.
+
+    ``dists`` as ``cost_to_go`` or ``cost_to_go_tiled`` returned them, the goal and obstacle maps and the mask of that call.  ``starts``:
+    an integer [B,S] tensor of flat cell indices r*W + c, or a float [B,S,H,W] tensor in the dataset's ``start_maps`` layout (a channel's
+    start is its highest-index non-zero cell; an all-zero channel becomes index -1 and gets status 1).  Maps of up to
+    ``FIELD_ROUTES_MAX_CELLS`` cells, at most ``FIELD_ROUTES_MAX_QUERIES`` queries.  An evaluation call on the current stream of the inputs'
+    device, detached outputs; nothing raises for a failed query: read ``status``.
+
+    ``max_route_len=L``: one call into the library (a memset of the rows and one launch; two launches above the LDS limit of the table),
+    nothing is read back -- it can be captured into a graph; a longer route keeps its last L cells and reports its true length.  ``None``: a lengths-only call, ONE host read of the longest route, then the call that fills
+    rows of exactly that length (at least 1); refused while the stream is capturing."""
+    maps, mask, (B, H, W) = _field_inputs(dists, goal_maps, obstacles_maps, neighbor_mask)
+    idx = _start_indices(starts, B, H, W)
+    S = idx.shape[1]
+    if max_route_len is not None and (isinstance(max_route_len, bool) or not isinstance(max_route_len, int) or max_route_len < 1):
+        raise ValueError(f"max_route_len must be an int >= 1 (or None: the longest route of the call), got {max_route_len!r}")
+    if H * W > FIELD_ROUTES_MAX_CELLS:
+        raise NotImplementedError(f"field_routes: maps of {H}x{W} = {H * W} cells exceed the limit of {FIELD_ROUTES_MAX_CELLS} cells")
+    if B * S > FIELD_ROUTES_MAX_QUERIES:
+        raise NotImplementedError(f"field_routes: {B} maps x {S} starts exceed the limit of {FIELD_ROUTES_MAX_QUERIES} queries per call")
+    dev = _field_device(maps)
+    if idx.device != dev:
+        raise ValueError(f"dists lives on {dev}, starts on {idx.device}: they must share a device")
+    lib = _field_lib("nastar_field_routes", "nastar_field_routes.h")
+    if max_route_len is None:
+        _refuse_capture(dev, RuntimeError, "field_routes: max_route_len=None reads the longest route back before it allocates the rows and "
+                                           "cannot be captured into a graph; pass max_route_len")
+    with torch.no_grad():
+        dist, goal, passable = (_maps3(t.detach()) for t in maps)
+        idx = idx.contiguous()
+        lengths = torch.empty((B, S), dtype=torch.int32, device=dev)
+        costs = torch.empty((B, S), dtype=torch.float32, device=dev)
+        status = torch.empty((B, S), dtype=torch.int32, device=dev)
+        nbytes = lib.nastar_field_routes_workspace_bytes(B, H, W)
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+
+        def call(routes: Optional[torch.Tensor]) -> None:
+            with torch.cuda.device(dev):
+                rc = lib.nastar_field_routes(dist.data_ptr(), goal.data_ptr(), passable.data_ptr(), idx.data_ptr(), B, S, H, W, mask,
+                                             routes.data_ptr() if routes is not None else None, routes.shape[2] if routes is not None else 0,
+                                             lengths.data_ptr(), costs.data_ptr(), status.data_ptr(),
+                                             workspace.data_ptr() if workspace is not None else None, nbytes, _stream_ptr(dev))
+            _native.check(rc, "nastar_field_routes")
+
+        if max_route_len is None:
+            call(None)
+            max_route_len = max(1, int(lengths.max()))
+        routes = torch.empty((B, S, max_route_len), dtype=torch.int32, device=dev)
+        call(routes)
+    return FieldRoutes(routes, lengths, costs, status)

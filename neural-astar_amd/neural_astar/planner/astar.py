@@ -17,7 +17,8 @@ import torch
 import torch.nn as nn
 
 from . import encoder
-from .differentiable_astar import AstarOutput, DifferentiableAstar, FieldOutput, RoutedAstarOutput, _checked_heuristic, _checked_route_len
+from .differentiable_astar import (AstarOutput, DifferentiableAstar, FieldOutput, FieldRoutesOutput, RoutedAstarOutput, _checked_heuristic,
+                                    _checked_route_len)
 from .pq_astar import pq_astar  # noqa: F401  (the reference's astar.py imports it here: a stub that fails loudly when called)
 
 
@@ -96,6 +97,12 @@ class VanillaAstar(nn.Module):
         """``cost_to_go`` by the tiled relaxation (``DifferentiableAstar.cost_to_go_tiled``: maps of up to 1024x1152, the same bits), with
         cost = passable = ``map_designs``.  ``differentiable=True``: ``dists`` carries the gradient to ``map_designs`` as the cost."""
         return self.astar.cost_to_go_tiled(map_designs, goal_maps, map_designs, policies, differentiable)
+
+    def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
+                  paths: bool = False) -> FieldRoutesOutput:
+        """The ordered optimal route from each of S start cells per map (``DifferentiableAstar.plan_many``: one field per map, a chase per
+        start) with cost = passable = ``map_designs``: on a binary map, shortest routes.  An evaluation call."""
+        return self.astar.plan_many(map_designs, starts, goal_maps, map_designs, max_route_len, paths)
 
 
 class NeuralAstar(VanillaAstar):
@@ -288,3 +295,18 @@ class NeuralAstar(VanillaAstar):
             cost_maps = cost_maps.detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.astar.cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, policies, differentiable)
+
+    def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
+                  paths: bool = False) -> FieldRoutesOutput:
+        """The ordered optimal route, under the PREDICTED cost maps, from each of S start cells per map (``DifferentiableAstar.plan_many``).
+        For ``encoder_input == "m"`` only: the maps are encoded once (detached, with an all-zero start channel) and one field serves every
+        start.  With "m+" the cost map depends on the start, so one field cannot serve S starts: NotImplementedError.  An evaluation
+        call; ``learn_obstacles`` makes every cell passable, as it does for the search."""
+        _checked_route_len(max_route_len)  # (both refusals before the encoder launches anything)
+        if self.encoder_input != "m":
+            raise NotImplementedError(f"NeuralAstar.plan_many: with encoder_input={self.encoder_input!r} the predicted cost map depends on the "
+                                      "start, so one cost-to-go field cannot serve several starts; encode per start and call "
+                                      "planner.astar.plan_many(cost_maps, starts, goal_maps, obstacles_maps), or use encoder_input='m'")
+        cost_maps = self.encode(map_designs, torch.zeros_like(goal_maps), goal_maps).detach()
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(goal_maps)
+        return self.astar.plan_many(cost_maps, starts, goal_maps, obstacles_maps, max_route_len, paths)

@@ -42,6 +42,19 @@ class RoutedAstarOutput(NamedTuple):
 FieldOutput = ops.FieldOutput  # what ``cost_to_go()`` returns (dists, policies, status): DESIGN.md section 2, item 6e
 
 
+class FieldRoutesOutput(NamedTuple):
+    """What ``plan_many()`` returns: ``dists`` [B,1,H,W], the cost-to-go field the routes were read off, the four tensors of
+    ``ops.FieldRoutes`` -- ``routes`` [B,S,L] int32, ``route_lengths``, ``route_costs`` and ``status`` [B,S] -- and ``paths`` [B,S,H,W]
+    int64, the 0/1 mask of the cells ``routes`` holds, or None.  DESIGN.md section 2, item 6i."""
+
+    dists: torch.Tensor
+    routes: torch.Tensor
+    route_lengths: torch.Tensor
+    route_costs: torch.Tensor
+    status: torch.Tensor
+    paths: Optional[torch.Tensor] = None
+
+
 def route_coords(routes: torch.Tensor, W: int) -> torch.Tensor:
     """``routes`` [B, L] (flat indices r*W + c, -1 = no cell) -> [B, L, 2] (row, col), -1 where the route is -1"""
     none = routes < 0
@@ -638,6 +651,30 @@ class DifferentiableAstar(nn.Module):
         gradient to ``cost_maps`` (include/nastar_fields_grad_tiled.h; its backward blocks too): a loss masks the +inf cells itself."""
         return ops.cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies,
                                     differentiable=differentiable)[0]
+
+    def plan_many(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                  max_route_len: Optional[int] = None, paths: bool = False) -> FieldRoutesOutput:
+        """The ORDERED optimal route from each of S start cells per map to its nearest goal: ONE cost-to-go field per map
+        (``ops.cost_to_go`` without policies; the tiled call above ``ops.FIELDS_MAX_CELLS`` cells), then a chase along its policy forest per
+        start (``ops.field_routes``, include/nastar_field_routes.h), under this module's own move set.  No search runs: ``g_ratio``,
+        ``Tmax`` and the heuristic play no part, the routes are optimal under the search's cost semantics (a move costs the cell being
+        left).  ``starts``: an integer [B,S] tensor of flat cell indices, or a float [B,S,H,W] tensor of start maps.  An EVALUATION call: no
+        autograd graph, detached tensors.  A failed query (an obstacle or unreachable start, an index outside the map, a zero-cost
+        plateau on the way) is reported in ``status``, not raised.  ``max_route_len``: the row length L of ``routes`` (a longer route keeps
+        its last L cells); None = the longest route of the call, one more host read.  ``paths=True`` adds the [B,S,H,W] int64 masks of the
+        cells in ``routes``."""
+        route_cap = _checked_route_len(max_route_len)
+        mask = self.neighbor_mask()
+        cells = cost_maps.shape[-2] * cost_maps.shape[-1] if torch.is_tensor(cost_maps) and cost_maps.ndim >= 2 else 0
+        field = ops.cost_to_go(cost_maps, goal_maps, obstacles_maps, neighbor_mask=mask, policies=False, tiled=cells > ops.FIELDS_MAX_CELLS)
+        r = ops.field_routes(field.dists, goal_maps, obstacles_maps, starts, neighbor_mask=mask, max_route_len=route_cap)
+        masks = None
+        if paths:
+            B, S, _ = r.routes.shape
+            H, W = field.dists.shape[-2:]
+            cell = torch.where(r.routes < 0, H * W, r.routes).long()  # (-1 lands in a spare column)
+            masks = torch.zeros((B, S, H * W + 1), dtype=torch.int64, device=cell.device).scatter_(2, cell, 1)[..., :H * W].reshape(B, S, H, W)
+        return FieldRoutesOutput(field.dists, r.routes, r.route_lengths, r.route_costs, r.status, masks)
 
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
