@@ -4,8 +4,9 @@
  * A checked search call returns once the launch's completion flag is up, i.e. when the LONGEST search of the batch is over (nastar.h:
  * completion_counter), and nothing the host does for the next call can overlap the device.  For a Moore-8 search without heuristic maps,
  * with g_ratio in [0.5, 0.75] and a budget of at least H * W steps, "every map ends with status 0 and no summary cell" is a property of the
- * inputs alone: the goal is reachable from the start over passable cells.  That is a bit-parallel flood fill of a few microseconds, which a
- * caller can wait for instead of the searches.
+ * inputs alone: the goal is reachable from the start over passable cells.  That is a bit-parallel flood fill, which a caller can wait for
+ * instead of the searches.  Alone on the device it takes a few microseconds; beside the search launch it accompanies it issues only in the
+ * slots the searching wavefronts leave and takes a good part of that launch's duration (measured: profiles/lean_proof.json).
  *
  *   proved[b] = 1 only if ALL of
  *     (a) the start map and the goal map each hold a non-zero cell (the cell taken is the one with the highest index, as the search takes it);
