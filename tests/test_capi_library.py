@@ -454,6 +454,36 @@ def test_argument_validation_table_needs_no_gpu():
     assert lib.nastar_last_error() == b""  # no call reached the HIP runtime
 
 
+def test_eval_encoder_refusals_need_no_gpu():
+    """The three forward entry points of the eval-mode CNN encoder refuse, before any HIP call: a workspace smaller than one image (the
+    size is the library's own nastar_encoder_workspace_bytes*(1, H, W)), map heights their kernels do not tile, `plus` without a start
+    map, and an empty batch."""
+    import ctypes
+    from neural_astar import _native as n
+    lib = n.load()
+    o = 16  # a non-NULL pointer value, never dereferenced on these paths
+    arr = (ctypes.c_void_p * 5)(*([o] * 5))
+    big = 1 << 40
+    forms = [("nastar_encoder_cnn_forward", "nastar_encoder_workspace_bytes", (), 20),
+             ("nastar_encoder_cnn_forward_f16", "nastar_encoder_workspace_bytes_f16", (o,), 16),
+             ("nastar_encoder_cnn_forward_f16x3", "nastar_encoder_workspace_bytes_f16x3", (o,), 16)]
+    for fwd_name, ws_name, w1, bad_h in forms:
+        fwd, ws_fn = getattr(lib, fwd_name), getattr(lib, ws_name)
+
+        def call(start=o, plus=1, B=3, H=32, W=32, ws_bytes=big):
+            return fwd(o, start, o, plus, B, H, W, *w1, arr, arr, arr, 1.0, o, o, ws_bytes, None)
+
+        for H, W in ((32, 32), (64, 96)):
+            per_image = int(ws_fn(1, H, W))
+            assert per_image > 0 and int(ws_fn(3, H, W)) == 3 * per_image
+            assert call(H=H, W=W, ws_bytes=per_image - 1) == n.NASTAR_ERR_WORKSPACE, (fwd_name, H, W)
+            assert call(H=H, W=W, ws_bytes=0) == n.NASTAR_ERR_WORKSPACE, (fwd_name, H, W)
+        assert call(H=bad_h) == n.NASTAR_ERR_UNSUPPORTED, fwd_name
+        assert call(start=None) == n.NASTAR_ERR_NULL, fwd_name
+        assert call(B=0) == n.NASTAR_ERR_BAD_SHAPE, fwd_name
+    assert lib.nastar_last_error() == b""  # no call reached the HIP runtime
+
+
 def test_product_has_no_cpu_fallback_and_never_touches_the_oracle():
     import torch
     from neural_astar.planner import VanillaAstar
