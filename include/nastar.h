@@ -408,6 +408,15 @@ int nastar_encoder_cnn_forward_f16(const float* map, const float* start, const f
  *   H, W multiples of 2^depth.  wts[l] device fp32 [9][CINp][COUTp] (tap = ky*3+kx; CINp = 2|4, 32, 64, 128; COUTp = 32, 64, 128,
  *   256 for the hidden blocks and 32 (channel 0 real) for the last one), scale/shift [COUTp] = eval-mode BatchNorm and conv bias folded;
  *   wts/scale/shift are HOST arrays of depth+1 device pointers.  workspace: nastar_encoder_downsize_workspace_bytes(B, C+plus, H, W, depth).
+ *   upsample_nearest is F.interpolate(mode="nearest") on fp32 tensors: source row = min((int)floorf(y * ((float)h / H)), h - 1), columns
+ *   likewise (any h, w > 0; the same cell as (y * h) / H in integers only where H / h is an integer).
+ *   Workspace layout (fp32, NHWC, packed with nothing between the tensors; every element is written by the call before it is read, and
+ *   nothing at or past workspace_bytes(...) is touched even when the caller's workspace is larger):
+ *     [B, H, W, CINp]                        the assembled input: image channels, the upsampled start + goal channel when plus,
+ *                                            zeros up to CINp = 2 when C + plus <= 2, else 4
+ *     [B, H >> (l+1), W >> (l+1), 32 << l]   l = 0 .. depth-1: the pooled output of hidden block l
+ *   nastar_encoder_downsize_workspace_bytes returns 4 * the sum of these element counts (its C argument is C + plus), 0 for arguments the
+ *   forward call refuses as a bad shape.  After the call the tensors stay as the kernels left them (tests/downsize_oracle.py: levels).
  */
 size_t nastar_encoder_downsize_workspace_bytes(int B, int C, int H, int W, int depth);
 int nastar_encoder_cnn_downsize_forward(const float* image, const float* start, const float* goal, int plus, int B, int C, int H,

@@ -103,6 +103,9 @@ __global__ __launch_bounds__(256) void nastar_downsize_prep_kernel(const float* 
                                                                    int H, int W, int h, int w, int plus, int CP)
 {
     const long long total = (long long)B * H * W;
+    // F.interpolate(mode="nearest") on fp32 tensors: source = min((int)floorf(dst * ((float)in / out)), in - 1).  The same cell as
+    // (dst * in) / out in integers when out / in is an integer, another one at some dst otherwise (h = 26, H = 88: row 44).
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int x = (int)(i % W), y = (int)((i / W) % H), b = (int)(i / ((long long)W * H));
         float* o = out + i * CP;
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(256) void nastar_downsize_prep_kernel(const float* 
             float v = 0.f;
             if (c < C) v = image[(((size_t)b * C + c) * H + y) * W + x];
             else if (plus && c == C) {
-                const int ys = (int)(((long long)y * h) / H), xs = (int)(((long long)x * w) / W);  // F.interpolate(mode="nearest")
+                const int ys = min((int)floorf((float)y * sy), h - 1), xs = min((int)floorf((float)x * sx), w - 1);
                 const size_t j = ((size_t)b * h + ys) * w + xs;
                 v = start[j] + goal[j];
             }

@@ -181,8 +181,11 @@ class HipCnnDownSizeEncoder:
         self._refresh()
 
     def _refresh(self) -> None:
+        const = self.cnn.const
         key = tuple((int(t._version), t.data_ptr(), str(t.device), t.dtype)
                     for t in list(self.cnn.parameters()) + list(self.cnn.buffers()))
+        if not isinstance(const, torch.Tensor):
+            key += (float(const),)  # const=None leaves a plain float on the module (reference encoder.py:27): it has no version
         if key == self._key:
             return
         layers = list(self.cnn.model)
@@ -197,7 +200,6 @@ class HipCnnDownSizeEncoder:
             sc, sh = fold_bn(conv, bn, cout_p)
             self.scale.append(sc)
             self.shift.append(sh)
-        const = self.cnn.const
         self._mul = float(const.detach().item()) if isinstance(const, torch.Tensor) else float(const)
         self._key = key
 
