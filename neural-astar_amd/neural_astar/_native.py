@@ -234,6 +234,17 @@ FIELD_ROUTE_SIGNATURES = {
     "nastar_field_routes": "i ppppiiiiupippppzp",
 }
 
+# the signatures of include/nastar_path_masks.h (the eleventh header: the exact shortest path of every map as a 0/1 mask, and its blackbox
+# gradient with respect to the costs), same letter code; a table of its own (tests/test_path_masks.py compares it with ITS header)
+PATH_MASK_SIGNATURES = {
+    "nastar_path_masks_abi": "i ",
+    "nastar_path_masks_max_cells": "i ",
+    # cost, goal, passable, start_idx, B, H, W, neighbor_mask, path_out, path_cost_out, status_out, stream
+    "nastar_path_masks": "i ppppiiiupppp",
+    # cost, goal, passable, start_idx, grad_path, path_fwd, status_fwd, B, H, W, neighbor_mask, lambda, min_cost, grad_cost_out, status_out, stream
+    "nastar_path_masks_backward": "i pppppppiiiuffppp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -371,6 +382,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, FIELD_GRAD_TILED_SIGNATURES, FIELD_GRAD_TILED_SIGNATURES)
     if hasattr(lib, "nastar_field_routes_abi"):  # (and the tenth)
         _bind(lib, FIELD_ROUTE_SIGNATURES, FIELD_ROUTE_SIGNATURES)
+    if hasattr(lib, "nastar_path_masks_abi"):  # (and the eleventh)
+        _bind(lib, PATH_MASK_SIGNATURES, PATH_MASK_SIGNATURES)
     _lib = lib
     return lib
 

@@ -18,7 +18,8 @@ from .status import (CLEAN, PROOF_MAX_G_RATIO, STATUS_BAD_HEURISTIC, STATUS_NOT_
 __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay", "l1_loss", "astar_l1_loss", "heuristic", "max_iters_for", "search_nograd", "order_from_levels", "OrderHint", "attach_order", "attach_levels",
            "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput", "cost_to_go_tiled",
            "fields_backward", "FIELD_PLATEAU", "FIELDS_GRAD_MAX_CELLS", "fields_backward_tiled", "FIELDS_GRAD_TILED_MAX_CELLS",
-           "field_routes", "FieldRoutes", "FIELD_ROUTES_MAX_CELLS", "FIELD_ROUTES_MAX_QUERIES"]
+           "field_routes", "FieldRoutes", "FIELD_ROUTES_MAX_CELLS", "FIELD_ROUTES_MAX_QUERIES",
+           "shortest_paths", "PathOutput", "path_masks", "path_masks_backward", "PATH_MASKS_MAX_CELLS"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -1296,3 +1297,175 @@ def field_routes(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: t
         routes = torch.empty((B, S, max_route_len), dtype=torch.int32, device=dev)
         call(routes)
     return FieldRoutes(routes, lengths, costs, status)
+
+
+# ---- include/nastar_path_masks.h: the exact shortest path as a 0/1 mask, and its blackbox gradient -----------
+PATH_MASKS_MAX_CELLS = 16384  # nastar_path_masks_max_cells(): the one-workgroup limit of cost_to_go
+
+
+class PathOutput(NamedTuple):
+    """What ``shortest_paths()`` returns.  ``paths`` [B,1,H,W] fp32 0/1: the start, the goal cell reached and every cell of the optimal
+    route between them (the convention of ``AstarOutput.paths``); all-zero for a failed map.  ``costs`` [B] fp32: the cost-to-go field at
+    the start, the field's own bits (the costs of the cells the route leaves); +inf for a failed map; not differentiable.  ``status`` [B]
+    int32: 0, 1 (no start cell), ``STATUS_UNSOLVABLE`` (3: no goal, or the start is an obstacle or cannot reach a goal), ``FIELD_BAD_COST``
+    (9), ``FIELD_NO_CONVERGENCE`` (10) or ``FIELD_PLATEAU`` (11: the route runs into a zero-cost plateau)."""
+
+    paths: torch.Tensor
+    costs: torch.Tensor
+    status: torch.Tensor
+
+
+def _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mask, what: str):
+    """the argument checks of the three path-mask calls, in one order -> (the three maps, [B] int32 start indices, the mask, (B, H, W), device)"""
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    if torch.is_tensor(starts) and starts.is_floating_point() and starts.ndim == 3:
+        starts = starts[:, None]
+    if not torch.is_tensor(starts) or starts.ndim not in (1, 2, 4) or (starts.ndim > 1 and starts.shape[1] != 1):
+        raise ValueError(f"{what}: one start per map -- a [B,1,H,W] (or [B,H,W]) float start map or an integer [B] tensor of flat cell indices, got "
+                         f"{tuple(starts.shape) if torch.is_tensor(starts) else type(starts).__name__}")
+    idx = _start_indices(starts[:, None] if starts.ndim == 1 else starts, B, H, W).reshape(B)
+    if H * W > PATH_MASKS_MAX_CELLS:
+        raise NotImplementedError(f"{what}: maps of {H}x{W} = {H * W} cells exceed the limit of {PATH_MASKS_MAX_CELLS} cells (one workgroup solves "
+                                  "one map in LDS; the tiled composition -- cost_to_go_tiled, field_routes, a scatter -- is not built into this call)")
+    dev = _field_device(maps)
+    if idx.device != dev:
+        raise ValueError(f"cost_maps lives on {dev}, the starts on {idx.device}: they must share a device")
+    return maps, idx.contiguous(), mask, (B, H, W), dev
+
+
+def _checked_step(value, name: str) -> float:
+    """``lambda_`` / ``min_cost``: a finite positive number whose fp32 value and (for lambda_) fp32 reciprocal are finite and positive too"""
+    import ctypes
+    ok = isinstance(value, (int, float)) and not isinstance(value, bool) and abs(value) < float("inf")
+    if ok:
+        f = ctypes.c_float(float(value)).value
+        ok = 0.0 < f < float("inf") and (name != "lambda_" or ctypes.c_float(1.0 / f).value < float("inf"))
+    if not ok:
+        raise ValueError(f"{name} must be a finite positive number (in float32 as well), got {value!r}")
+    return float(value)
+
+
+def path_masks(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor,
+               neighbor_mask: Optional[int] = None) -> PathOutput:
+    """``nastar_path_masks`` as it is (include/nastar_path_masks.h): one launch on the current stream, nothing is read back and nothing
+    raises for a failed map -- read ``status``.  ``starts``: a float [B,1,H,W] start map (its highest-index non-zero cell) or an integer
+    [B] tensor of flat cell indices.  Detached outputs.  What ``shortest_paths`` runs; probes and tests call it directly."""
+    maps, idx, mask, (B, H, W), dev = _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mask, "path_masks")
+    lib = _field_lib("nastar_path_masks", "nastar_path_masks.h")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(t.detach()) for t in maps)
+        paths = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        costs = torch.empty((B,), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_path_masks(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), idx.data_ptr(), B, H, W, mask, paths.data_ptr(),
+                                       costs.data_ptr(), status.data_ptr(), _stream_ptr(dev))
+        _native.check(rc, "nastar_path_masks")
+    return PathOutput(paths, costs, status)
+
+
+def path_masks_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor,
+                        grad_paths: torch.Tensor, paths_fwd: torch.Tensor, status_fwd: torch.Tensor, lambda_: float, min_cost: float = 2.0 ** -10,
+                        neighbor_mask: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``nastar_path_masks_backward`` as it is: the inputs of ``path_masks``, the upstream gradient of ``paths``, and ``paths`` and
+    ``status`` as that call returned them -> ``(grad_cost [B,H,W], status [B] int32 of the perturbed solve)``.  One launch on the current
+    stream, nothing is read back.  ``grad_cost`` is 0 or +-fl32(1/lambda_) per cell; all-zero for a map whose ``status_fwd`` is not 0,
+    all-NaN for a map whose perturbed solve failed.  What the backward of ``shortest_paths(..., lambda_=...)`` runs."""
+    lam, floor = _checked_step(lambda_, "lambda_"), _checked_step(min_cost, "min_cost")
+    maps, idx, mask, (B, H, W), dev = _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mask, "path_masks_backward")
+    for name, t in (("grad_paths", grad_paths), ("paths_fwd", paths_fwd)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != B * H * W or tuple(t.shape[-2:]) != (H, W) or t.device != dev:
+            raise ValueError(f"{name} must be a float32 tensor of the shape of the paths ({B} maps of {H}x{W}) on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__}")
+    _check_counts_out(status_fwd, "status_fwd", B, dev)
+    if status_fwd is None:
+        raise ValueError("status_fwd must be the status tensor of the forward call")
+    lib = _field_lib("nastar_path_masks_backward", "nastar_path_masks.h")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(t.detach()) for t in maps)
+        up = grad_paths.detach().reshape(B, H, W).contiguous()
+        fwd = paths_fwd.detach().reshape(B, H, W).contiguous()
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_path_masks_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), idx.data_ptr(), up.data_ptr(), fwd.data_ptr(),
+                                                status_fwd.data_ptr(), B, H, W, mask, lam, floor, grad.data_ptr(), status.data_ptr(), _stream_ptr(dev))
+        _native.check(rc, "nastar_path_masks_backward")
+    return grad, status
+
+
+class _PathNode(torch.autograd.Function):
+    """``path_masks`` as an autograd node: only ``paths`` carries gradient, and only to ``cost_maps`` -- the blackbox gradient, one launch of
+    ``path_masks_backward`` on the current stream, no host read."""
+
+    @staticmethod
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, idx, mask, lam, floor):
+        out = path_masks(cost_maps, goal_maps, obstacles_maps, idx, mask)
+        ctx.save_for_backward(cost_maps, goal_maps, obstacles_maps, idx, out.paths, out.status)
+        ctx.step, ctx.cost_shape = (mask, lam, floor), tuple(cost_maps.shape)
+        ctx.mark_non_differentiable(out.costs, out.status)
+        ctx.set_materialize_grads(False)
+        return out.paths, out.costs, out.status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_paths, *unused):
+        if g_paths is None or not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        cost, goal, obstacles, idx, paths, status = ctx.saved_tensors
+        mask, lam, floor = ctx.step
+        grad, _ = path_masks_backward(cost, goal, obstacles, idx, g_paths, paths, status, lam, floor, mask)
+        shape = ctx.cost_shape
+        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
+            full = grad.new_zeros(shape)
+            full[:, 0] = grad
+            grad = full
+        return (grad.reshape(shape),) + (None,) * 6
+
+
+def shortest_paths(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                   neighbor_mask: Optional[int] = None, lambda_: Optional[float] = None, min_cost: float = 2.0 ** -10) -> PathOutput:
+    """The EXACT optimal path of every map as a 0/1 mask, as a layer (include/nastar_path_masks.h) -> ``PathOutput``: the cost-to-go field
+    of ``cost_to_go`` and the route of ``field_routes`` in ONE launch, no field or policy plane in memory.  A move costs the cell being
+    left; ``g_ratio``, ``Tmax`` and the heuristic play no part: unlike a search with costs below 1, the path IS the minimiser.
+
+    ``cost_maps``, ``start_maps``, ``goal_maps``, ``obstacles_maps``: [B,1,H,W] (or [B,H,W]) float32 on one HIP device, maps of at most
+    ``PATH_MASKS_MAX_CELLS`` cells (NotImplementedError above).  ``start_maps`` is one-hot; of several non-zero cells the one with the
+    highest flat index is the start (the search's own default rule); an all-zero map gets status 1.  Every non-zero cell of a goal map is a
+    goal (the nearest one is reached).  ``neighbor_mask``: the move set as the search takes it (None = Moore-8).
+
+    ``lambda_=None``: an evaluation call -- detached outputs, one host read for the status (none inside a stream capture): a NaN or a
+    negative cost on a passable cell raises ValueError naming the rows; every other failure stays in ``status``.
+
+    ``lambda_`` a positive float: ``paths`` carries an autograd node when ``cost_maps`` requires a gradient (blackbox differentiation of
+    the solver, Vlastelica et al. 2020).  Its backward is ONE launch and reads nothing back: with g = dL/dpaths it solves the costs
+    ``max(fl32(fl32(lambda_ * g) + cost), min_cost)`` and returns ``(paths_lambda - paths) * fl32(1 / lambda_)`` -- 0 or +-1/lambda_ per
+    cell -- to ``cost_maps`` alone.  The forward reads the status once (not inside a capture) and raises ValueError for rows with a bad
+    cost or a plateau; a map that failed otherwise (see ``status``) gets a zero gradient; a map whose PERTURBED solve fails (a NaN in g)
+    gets an all-NaN gradient row.  ``lambda_`` trades the informativeness of the gradient against its faithfulness and is the user's to
+    choose (the blackbox paper uses 20 on WarCraft costs); ``min_cost``, the floor of the perturbed costs, is an API default chosen so
+    that a clamped cell stays strictly positive -- 2^-10 is NOT a tuned number.
+
+    Zero costs: a route that would run through a zero-cost plateau (no strictly closer neighbour) has no defined successor and is reported
+    as ``FIELD_PLATEAU``.  The same holds in float32 for very small costs on long routes: where ``fl32(c + D) == D`` the field does not
+    fall along the move, which is a plateau in the sense of the field rules and is reported as such."""
+    differentiable = lambda_ is not None
+    if differentiable:
+        lam = _checked_step(lambda_, "lambda_")
+    floor = _checked_step(min_cost, "min_cost")
+    maps, idx, mask, (B, H, W), dev = _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, start_maps, neighbor_mask, "shortest_paths")
+    if differentiable and cost_maps.requires_grad and torch.is_grad_enabled():
+        out = PathOutput(*_PathNode.apply(cost_maps, goal_maps, obstacles_maps, idx, mask, lam, floor))
+    else:
+        out = path_masks(cost_maps, goal_maps, obstacles_maps, idx, mask)
+    with torch.cuda.device(dev):
+        capturing = torch.cuda.is_current_stream_capturing()
+    if not capturing:
+        st = out.status.cpu()
+        _raise_bad_cost(st, B, "shortest_paths")
+        _raise_no_convergence(st, "shortest_paths", "H*W sweeps")
+        flat = torch.nonzero(st == FIELD_PLATEAU).flatten().tolist()
+        if differentiable and flat:
+            raise ValueError(f"shortest_paths: the route of map(s) {flat[:16]}{' ...' if len(flat) > 16 else ''} ({len(flat)} of {B}) runs into a cell "
+                             "with no strictly closer neighbour (a zero-cost plateau): no path, so no gradient; the other maps were computed")
+    return out

@@ -17,8 +17,9 @@ import torch
 import torch.nn as nn
 
 from . import encoder
-from .differentiable_astar import (AstarOutput, DifferentiableAstar, FieldOutput, FieldRoutesOutput, RoutedAstarOutput, _checked_heuristic,
-                                    _checked_route_len)
+from .differentiable_astar import (AstarOutput, DifferentiableAstar, FieldOutput, FieldRoutesOutput, PathOutput, RoutedAstarOutput,
+                                    _checked_heuristic, _checked_route_len)
+from .. import ops
 from .pq_astar import pq_astar  # noqa: F401  (the reference's astar.py imports it here: a stub that fails loudly when called)
 
 
@@ -103,6 +104,13 @@ class VanillaAstar(nn.Module):
         """The ordered optimal route from each of S start cells per map (``DifferentiableAstar.plan_many``: one field per map, a chase per
         start) with cost = passable = ``map_designs``: on a binary map, shortest routes.  An evaluation call."""
         return self.astar.plan_many(map_designs, starts, goal_maps, map_designs, max_route_len, paths)
+
+    def shortest_paths(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, lambda_: Optional[float] = None,
+                       min_cost: float = 2.0 ** -10) -> PathOutput:
+        """The exact optimal path of every map as a 0/1 mask (``DifferentiableAstar.shortest_paths``: field and chase in one launch) with
+        cost = passable = ``map_designs``: on a binary map, a shortest route.  ``lambda_``: ``paths`` carries the blackbox gradient to
+        ``map_designs`` as the cost (not as the obstacles)."""
+        return self.astar.shortest_paths(map_designs, start_maps, goal_maps, map_designs, lambda_, min_cost)
 
 
 class NeuralAstar(VanillaAstar):
@@ -310,3 +318,19 @@ class NeuralAstar(VanillaAstar):
         cost_maps = self.encode(map_designs, torch.zeros_like(goal_maps), goal_maps).detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(goal_maps)
         return self.astar.plan_many(cost_maps, starts, goal_maps, obstacles_maps, max_route_len, paths)
+
+    def shortest_paths(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, lambda_: Optional[float] = None,
+                       min_cost: float = 2.0 ** -10) -> PathOutput:
+        """The exact optimal path under the PREDICTED cost maps as a 0/1 mask (``DifferentiableAstar.shortest_paths``): encodes as
+        ``forward()`` does, then one launch solves every map; ``learn_obstacles`` makes every cell passable, as it does for the search.
+        ``lambda_=None``: an evaluation call on the detached cost maps.  ``lambda_`` a positive float: the cost maps are NOT detached and
+        ``paths`` carries the blackbox gradient, so a Hamming or L1 loss on ``paths`` against the demonstration trains the encoder on the
+        device (the "BB-A*" baseline of the Neural A* paper).  The encoder route is what ``encode()`` picks in that mode."""
+        if lambda_ is not None:
+            ops._checked_step(lambda_, "lambda_")  # (both refusals before the encoder launches anything)
+        ops._checked_step(min_cost, "min_cost")
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        if lambda_ is None:
+            cost_maps = cost_maps.detach()
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.shortest_paths(cost_maps, start_maps, goal_maps, obstacles_maps, lambda_, min_cost)

@@ -40,6 +40,7 @@ class RoutedAstarOutput(NamedTuple):
 
 
 FieldOutput = ops.FieldOutput  # what ``cost_to_go()`` returns (dists, policies, status): DESIGN.md section 2, item 6e
+PathOutput = ops.PathOutput  # what ``shortest_paths()`` returns (paths, costs, status): DESIGN.md section 2, item 6j
 
 
 class FieldRoutesOutput(NamedTuple):
@@ -675,6 +676,15 @@ class DifferentiableAstar(nn.Module):
             cell = torch.where(r.routes < 0, H * W, r.routes).long()  # (-1 lands in a spare column)
             masks = torch.zeros((B, S, H * W + 1), dtype=torch.int64, device=cell.device).scatter_(2, cell, 1)[..., :H * W].reshape(B, S, H, W)
         return FieldRoutesOutput(field.dists, r.routes, r.route_lengths, r.route_costs, r.status, masks)
+
+    def shortest_paths(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                       lambda_: Optional[float] = None, min_cost: float = 2.0 ** -10) -> PathOutput:
+        """The EXACT optimal path of every map as a 0/1 mask (``ops.shortest_paths``, the kernel of include/nastar_path_masks.h: field and
+        chase in one launch), under this module's own move set.  No search runs: ``g_ratio``, ``Tmax`` and the heuristic play no part.
+        ``lambda_=None``: an evaluation call.  ``lambda_`` a positive float: ``paths`` carries the blackbox gradient to ``cost_maps`` (one
+        more launch in the backward, no host read), so that a Hamming or L1 loss on ``paths`` trains whatever produced the costs."""
+        return ops.shortest_paths(cost_maps, start_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), lambda_=lambda_,
+                                  min_cost=min_cost)
 
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
