@@ -2,7 +2,8 @@
 // (include/nastar_field_routes.h).
 //
 // The successor of a cell is fld_best_action on the readable field (nastar_field_rules.hip.h): the rule is not written here.  What is
-// here: the SUCCESSOR TABLE, one byte per cell (the action 0..7, kRouteGoal on a goal cell, kRouteNoSucc elsewhere), its builder
+// here: the SUCCESSOR TABLE, one byte per cell (the action 0..7, kRouteGoal on a goal cell, kRouteNoSucc elsewhere: frt_cell and frt_step
+// of nastar_route_table.hip.h, which the tiled path-mask kernels share), its builder
 // (frt_build: coalesced loads, the one-cell halo of a cell read from global memory) and the CHASE of one start along it (frt_chase),
 // written once and handed the table through an accessor at(n), as the field kernels take at().  Two homes for the table:
 //   LDS        nastar_field_routes_lds_kernel<T>: a workgroup of T lanes serves one map and T of its starts; it builds the WHOLE map's
@@ -20,11 +21,10 @@
 
 #include "../../include/nastar_field_routes.h"
 #include "nastar_field_rules.hip.h"
+#include "nastar_route_table.hip.h"
 
 namespace nastar {
 
-constexpr uint8_t kRouteNoSucc = 0xFF;  // no successor: not live, or a plateau (kNoSucc of nastar_fields_grad_tiled.hip.h)
-constexpr uint8_t kRouteGoal = 0xFE;    // a goal cell: the chase ends here without reading goal[] again
 constexpr int kRouteTableT = 256;       // the width of the workspace path's two kernels
 constexpr int kRouteTableCells = kRouteTableT * kFieldCellsPerLane;  // cells one workgroup of the table kernel writes
 
@@ -43,35 +43,6 @@ struct FieldRoutesArgs {
     int groups;              // workgroups per map
     uint32_t nmask;
 };
-
-// dy * W + dx of action k: ACTION_MOVES packed two bits per component (value + 1), so that a step is two shifts, two masks and a mad
-constexpr uint32_t frt_pack(bool want_dy)
-{
-    uint32_t v = 0;
-    for (int k = 0; k < 8; ++k) v |= (uint32_t)((want_dy ? kActionMoves[k].dy : kActionMoves[k].dx) + 1) << (2 * k);
-    return v;
-}
-__device__ __forceinline__ int frt_step(uint32_t k, int W)
-{
-    constexpr uint32_t dys = frt_pack(true), dxs = frt_pack(false);
-    return ((int)((dys >> (2 * k)) & 3u) - 1) * W + ((int)((dxs >> (2 * k)) & 3u) - 1);
-}
-
-// the table byte of cell i of one map
-__device__ __forceinline__ uint8_t frt_cell(const float* dist, const float* goal, const float* pass, int i, int H, int W, uint32_t nm)
-{
-    const float INF = INFINITY;
-    if (goal[i] != 0.f) return kRouteGoal;
-    const float d = dist[i];
-    if (!(d < INF)) return kRouteNoSucc;  // (a NaN is not below +inf)
-    const int y = i / W, x = i - y * W;
-    auto readable = [&](int dy, int dx) {
-        const int j = i + dy * W + dx;
-        return pass[j] != 0.f ? dist[j] : INF;
-    };
-    const int best = fld_best_action(readable, nm, y > 0, y < H - 1, x > 0, x < W - 1, d);
-    return best < 0 ? kRouteNoSucc : (uint8_t)best;
-}
 
 // cells [begin, end) of one map's table, `step` lanes side by side: lane `first` takes begin + first, begin + first + step, ...
 __device__ __forceinline__ void frt_build(uint8_t* table, const float* dist, const float* goal, const float* pass, int begin, int end, int first,

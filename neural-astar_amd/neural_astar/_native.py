@@ -245,6 +245,21 @@ PATH_MASK_SIGNATURES = {
     "nastar_path_masks_backward": "i pppppppiiiuffppp",
 }
 
+# the signatures of include/nastar_path_masks_tiled.h (the twelfth header: that mask and that gradient for maps of up to 1179648 cells, the
+# field by the tiled relaxation), same letter code; a table of its own (tests/test_path_masks_tiled.py compares it with ITS header)
+PATH_MASK_TILED_SIGNATURES = {
+    "nastar_path_masks_tiled_abi": "i ",
+    "nastar_path_masks_tiled_max_cells": "i ",
+    "nastar_path_masks_tiled_workspace_bytes": "z iii",
+    "nastar_path_masks_tiled_backward_workspace_bytes": "z iii",
+    # cost, goal, passable, start_idx, B, H, W, neighbor_mask, path_out, path_cost_out, status_out, workspace, workspace_bytes, max_rounds,
+    # rounds_out, stream
+    "nastar_path_masks_tiled": "i ppppiiiuppppzqpp",
+    # cost, goal, passable, start_idx, grad_path, path_fwd, status_fwd, B, H, W, neighbor_mask, lambda, min_cost, grad_cost_out, status_out,
+    # workspace, workspace_bytes, max_rounds, rounds_out, stream
+    "nastar_path_masks_tiled_backward": "i pppppppiiiuffpppzqpp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -384,6 +399,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, FIELD_ROUTE_SIGNATURES, FIELD_ROUTE_SIGNATURES)
     if hasattr(lib, "nastar_path_masks_abi"):  # (and the eleventh)
         _bind(lib, PATH_MASK_SIGNATURES, PATH_MASK_SIGNATURES)
+    if hasattr(lib, "nastar_path_masks_tiled_abi"):  # (and the twelfth)
+        _bind(lib, PATH_MASK_TILED_SIGNATURES, PATH_MASK_TILED_SIGNATURES)
     _lib = lib
     return lib
 

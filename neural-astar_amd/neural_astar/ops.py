@@ -19,7 +19,8 @@ __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay",
            "StatusBoard", "route_forward_calls", "search_routes", "source_forward_calls", "astar_forward_sources", "cost_to_go", "FieldOutput", "cost_to_go_tiled",
            "fields_backward", "FIELD_PLATEAU", "FIELDS_GRAD_MAX_CELLS", "fields_backward_tiled", "FIELDS_GRAD_TILED_MAX_CELLS",
            "field_routes", "FieldRoutes", "FIELD_ROUTES_MAX_CELLS", "FIELD_ROUTES_MAX_QUERIES",
-           "shortest_paths", "PathOutput", "path_masks", "path_masks_backward", "PATH_MASKS_MAX_CELLS"]
+           "shortest_paths", "PathOutput", "path_masks", "path_masks_backward", "PATH_MASKS_MAX_CELLS",
+           "shortest_paths_tiled", "path_masks_tiled", "path_masks_tiled_backward", "PATH_MASKS_TILED_MAX_CELLS"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -1315,8 +1316,9 @@ class PathOutput(NamedTuple):
     status: torch.Tensor
 
 
-def _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mask, what: str):
-    """the argument checks of the three path-mask calls, in one order -> (the three maps, [B] int32 start indices, the mask, (B, H, W), device)"""
+def _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mask, what: str, max_cells: Optional[int] = None):
+    """the argument checks of the path-mask calls, one-workgroup and tiled (``max_cells``: the tiled limit), in one order -> (the three maps,
+    [B] int32 start indices, the mask, (B, H, W), device)"""
     maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     if torch.is_tensor(starts) and starts.is_floating_point() and starts.ndim == 3:
         starts = starts[:, None]
@@ -1324,9 +1326,11 @@ def _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mas
         raise ValueError(f"{what}: one start per map -- a [B,1,H,W] (or [B,H,W]) float start map or an integer [B] tensor of flat cell indices, got "
                          f"{tuple(starts.shape) if torch.is_tensor(starts) else type(starts).__name__}")
     idx = _start_indices(starts[:, None] if starts.ndim == 1 else starts, B, H, W).reshape(B)
-    if H * W > PATH_MASKS_MAX_CELLS:
+    if max_cells is not None and H * W > max_cells:
+        raise NotImplementedError(f"{what}: maps of {H}x{W} = {H * W} cells exceed the limit of {max_cells} cells")
+    if max_cells is None and H * W > PATH_MASKS_MAX_CELLS:
         raise NotImplementedError(f"{what}: maps of {H}x{W} = {H * W} cells exceed the limit of {PATH_MASKS_MAX_CELLS} cells (one workgroup solves "
-                                  "one map in LDS; the tiled composition -- cost_to_go_tiled, field_routes, a scatter -- is not built into this call)")
+                                  "one map in LDS; larger maps are shortest_paths_tiled's / path_masks_tiled's)")
     dev = _field_device(maps)
     if idx.device != dev:
         raise ValueError(f"cost_maps lives on {dev}, the starts on {idx.device}: they must share a device")
@@ -1343,6 +1347,17 @@ def _checked_step(value, name: str) -> float:
     if not ok:
         raise ValueError(f"{name} must be a finite positive number (in float32 as well), got {value!r}")
     return float(value)
+
+
+def _check_path_planes(grad_paths, paths_fwd, status_fwd, B: int, H: int, W: int, dev: torch.device) -> None:
+    """what a path-mask backward call takes beside the forward's inputs: the upstream gradient, and the forward's paths and status"""
+    for name, t in (("grad_paths", grad_paths), ("paths_fwd", paths_fwd)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != B * H * W or tuple(t.shape[-2:]) != (H, W) or t.device != dev:
+            raise ValueError(f"{name} must be a float32 tensor of the shape of the paths ({B} maps of {H}x{W}) on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__}")
+    _check_counts_out(status_fwd, "status_fwd", B, dev)
+    if status_fwd is None:
+        raise ValueError("status_fwd must be the status tensor of the forward call")
 
 
 def path_masks(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor,
@@ -1373,13 +1388,7 @@ def path_masks_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstac
     all-NaN for a map whose perturbed solve failed.  What the backward of ``shortest_paths(..., lambda_=...)`` runs."""
     lam, floor = _checked_step(lambda_, "lambda_"), _checked_step(min_cost, "min_cost")
     maps, idx, mask, (B, H, W), dev = _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mask, "path_masks_backward")
-    for name, t in (("grad_paths", grad_paths), ("paths_fwd", paths_fwd)):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != B * H * W or tuple(t.shape[-2:]) != (H, W) or t.device != dev:
-            raise ValueError(f"{name} must be a float32 tensor of the shape of the paths ({B} maps of {H}x{W}) on {dev}, got "
-                             f"{(tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t).__name__}")
-    _check_counts_out(status_fwd, "status_fwd", B, dev)
-    if status_fwd is None:
-        raise ValueError("status_fwd must be the status tensor of the forward call")
+    _check_path_planes(grad_paths, paths_fwd, status_fwd, B, H, W, dev)
     lib = _field_lib("nastar_path_masks_backward", "nastar_path_masks.h")
     with torch.no_grad():
         cost, goal, passable = (_maps3(t.detach()) for t in maps)
@@ -1396,13 +1405,14 @@ def path_masks_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstac
 
 class _PathNode(torch.autograd.Function):
     """``path_masks`` as an autograd node: only ``paths`` carries gradient, and only to ``cost_maps`` -- the blackbox gradient, one launch of
-    ``path_masks_backward`` on the current stream, no host read."""
+    ``path_masks_backward`` on the current stream, no host read.  ``tiled``: ``path_masks_tiled`` and ``path_masks_tiled_backward`` in their
+    place -- both block."""
 
     @staticmethod
-    def forward(ctx, cost_maps, goal_maps, obstacles_maps, idx, mask, lam, floor):
-        out = path_masks(cost_maps, goal_maps, obstacles_maps, idx, mask)
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, idx, mask, lam, floor, tiled):
+        out = (path_masks_tiled if tiled else path_masks)(cost_maps, goal_maps, obstacles_maps, idx, mask)
         ctx.save_for_backward(cost_maps, goal_maps, obstacles_maps, idx, out.paths, out.status)
-        ctx.step, ctx.cost_shape = (mask, lam, floor), tuple(cost_maps.shape)
+        ctx.step, ctx.cost_shape, ctx.tiled = (mask, lam, floor), tuple(cost_maps.shape), tiled
         ctx.mark_non_differentiable(out.costs, out.status)
         ctx.set_materialize_grads(False)
         return out.paths, out.costs, out.status
@@ -1411,16 +1421,28 @@ class _PathNode(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_paths, *unused):
         if g_paths is None or not ctx.needs_input_grad[0]:
-            return (None,) * 7
+            return (None,) * 8
         cost, goal, obstacles, idx, paths, status = ctx.saved_tensors
         mask, lam, floor = ctx.step
-        grad, _ = path_masks_backward(cost, goal, obstacles, idx, g_paths, paths, status, lam, floor, mask)
+        grad, _ = (path_masks_tiled_backward if ctx.tiled else path_masks_backward)(cost, goal, obstacles, idx, g_paths, paths, status, lam, floor, mask)
         shape = ctx.cost_shape
         if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
             full = grad.new_zeros(shape)
             full[:, 0] = grad
             grad = full
-        return (grad.reshape(shape),) + (None,) * 6
+        return (grad.reshape(shape),) + (None,) * 7
+
+
+def _raise_path_failures(status: torch.Tensor, B: int, what: str, bound: str, differentiable: bool) -> None:
+    """the one status read of ``shortest_paths`` / ``shortest_paths_tiled``: a bad cost and a relaxation that hit its bound raise; with a
+    gradient asked for, so does a plateau"""
+    st = status.cpu()
+    _raise_bad_cost(st, B, what)
+    _raise_no_convergence(st, what, bound)
+    flat = torch.nonzero(st == FIELD_PLATEAU).flatten().tolist()
+    if differentiable and flat:
+        raise ValueError(f"{what}: the route of map(s) {flat[:16]}{' ...' if len(flat) > 16 else ''} ({len(flat)} of {B}) runs into a cell "
+                         "with no strictly closer neighbour (a zero-cost plateau): no path, so no gradient; the other maps were computed")
 
 
 def shortest_paths(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
@@ -1455,17 +1477,119 @@ def shortest_paths(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps:
     floor = _checked_step(min_cost, "min_cost")
     maps, idx, mask, (B, H, W), dev = _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, start_maps, neighbor_mask, "shortest_paths")
     if differentiable and cost_maps.requires_grad and torch.is_grad_enabled():
-        out = PathOutput(*_PathNode.apply(cost_maps, goal_maps, obstacles_maps, idx, mask, lam, floor))
+        out = PathOutput(*_PathNode.apply(cost_maps, goal_maps, obstacles_maps, idx, mask, lam, floor, False))
     else:
         out = path_masks(cost_maps, goal_maps, obstacles_maps, idx, mask)
     with torch.cuda.device(dev):
         capturing = torch.cuda.is_current_stream_capturing()
     if not capturing:
-        st = out.status.cpu()
-        _raise_bad_cost(st, B, "shortest_paths")
-        _raise_no_convergence(st, "shortest_paths", "H*W sweeps")
-        flat = torch.nonzero(st == FIELD_PLATEAU).flatten().tolist()
-        if differentiable and flat:
-            raise ValueError(f"shortest_paths: the route of map(s) {flat[:16]}{' ...' if len(flat) > 16 else ''} ({len(flat)} of {B}) runs into a cell "
-                             "with no strictly closer neighbour (a zero-cost plateau): no path, so no gradient; the other maps were computed")
+        _raise_path_failures(out.status, B, "shortest_paths", "H*W sweeps", differentiable)
+    return out
+
+
+# ---- include/nastar_path_masks_tiled.h: that mask and that gradient for maps of up to 1179648 cells ------------
+PATH_MASKS_TILED_MAX_CELLS = 1179648  # nastar_path_masks_tiled_max_cells(): every size cost_to_go_tiled takes
+
+
+def _path_tiled_workspace(lib, backward: bool, B: int, H: int, W: int, dev: torch.device, what: str):
+    sizer = lib.nastar_path_masks_tiled_backward_workspace_bytes if backward else lib.nastar_path_masks_tiled_workspace_bytes
+    nbytes = sizer(B, H, W)
+    if nbytes == 0:
+        raise NotImplementedError(f"{what}: a batch of {B} maps of {H}x{W} has more than 2^24 tiles")
+    return torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=dev), nbytes  # (int32 elements: 4-byte aligned whatever the allocator does)
+
+
+def path_masks_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor,
+                     neighbor_mask: Optional[int] = None, max_rounds: Optional[int] = None, return_rounds: bool = False):
+    """``nastar_path_masks_tiled`` as it is (include/nastar_path_masks_tiled.h): ``path_masks`` for maps of up to
+    ``PATH_MASKS_TILED_MAX_CELLS`` cells, the same definition and -- on the sizes both take -- the same BITS -> ``PathOutput``, or
+    ``(PathOutput, rounds)`` with ``return_rounds=True`` (the rounds of the relaxation in which some tile was active).
+
+    The field is ``cost_to_go_tiled``'s, written into a workspace this call allocates (4 bytes per cell and the relaxation's own words);
+    one more launch turns it into the mask.  The relaxation synchronises its stream between batches of rounds: the call BLOCKS and is
+    refused (RuntimeError) while that stream is capturing a graph, before anything is enqueued.  Nothing raises for a failed map -- read
+    ``status``.  ``max_rounds=None``: the bound H*W + 1, which no accepted input reaches; with an explicit ``max_rounds`` a map that still
+    has an active tile gets ``FIELD_NO_CONVERGENCE``, a zero mask and a cost of +inf.  Detached outputs."""
+    _check_max_rounds(max_rounds)
+    maps, idx, mask, (B, H, W), dev = _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mask, "path_masks_tiled",
+                                                        PATH_MASKS_TILED_MAX_CELLS)
+    lib = _field_lib("nastar_path_masks_tiled", "nastar_path_masks_tiled.h")
+    _refuse_capture(dev, RuntimeError, f"path_masks_tiled: {_BLOCKS}")
+    import ctypes
+    with torch.no_grad():
+        workspace, nbytes = _path_tiled_workspace(lib, False, B, H, W, dev, "path_masks_tiled")
+        cost, goal, passable = (_maps3(t.detach()) for t in maps)
+        paths = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        costs = torch.empty((B,), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        rounds = ctypes.c_int(0)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_path_masks_tiled(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), idx.data_ptr(), B, H, W, mask, paths.data_ptr(),
+                                             costs.data_ptr(), status.data_ptr(), workspace.data_ptr(), nbytes, 0 if max_rounds is None else max_rounds,
+                                             ctypes.cast(ctypes.pointer(rounds), ctypes.c_void_p), _stream_ptr(dev))
+        _native.check(rc, "nastar_path_masks_tiled")
+    out = PathOutput(paths, costs, status)
+    return (out, rounds.value) if return_rounds else out
+
+
+def path_masks_tiled_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor,
+                              grad_paths: torch.Tensor, paths_fwd: torch.Tensor, status_fwd: torch.Tensor, lambda_: float,
+                              min_cost: float = 2.0 ** -10, neighbor_mask: Optional[int] = None, max_rounds: Optional[int] = None,
+                              return_rounds: bool = False):
+    """``nastar_path_masks_tiled_backward`` as it is: ``path_masks_backward`` for maps of up to ``PATH_MASKS_TILED_MAX_CELLS`` cells, the
+    same definition and -- on the sizes both take -- the same BITS -> ``(grad_cost [B,H,W], status [B] int32 of the perturbed solve)``, and
+    the rounds of the perturbed relaxation as a third element with ``return_rounds=True``.  One elementwise launch writes the perturbed
+    costs into the workspace, ``cost_to_go_tiled``'s relaxation solves them, one launch writes the rows.  The call BLOCKS and is refused
+    (RuntimeError) while its stream is capturing.  ``grad_cost`` is all-zero for a map whose ``status_fwd`` is not 0 (the map is relaxed
+    with the batch all the same; its field is not looked at), all-NaN for a map whose perturbed solve failed -- a map cut short by an
+    explicit ``max_rounds`` among them (``FIELD_NO_CONVERGENCE``).  What the backward of ``shortest_paths_tiled(..., lambda_=...)`` runs."""
+    lam, floor = _checked_step(lambda_, "lambda_"), _checked_step(min_cost, "min_cost")
+    _check_max_rounds(max_rounds)
+    maps, idx, mask, (B, H, W), dev = _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, starts, neighbor_mask, "path_masks_tiled_backward",
+                                                        PATH_MASKS_TILED_MAX_CELLS)
+    _check_path_planes(grad_paths, paths_fwd, status_fwd, B, H, W, dev)
+    lib = _field_lib("nastar_path_masks_tiled_backward", "nastar_path_masks_tiled.h")
+    _refuse_capture(dev, RuntimeError, f"path_masks_tiled_backward: {_BLOCKS}")
+    import ctypes
+    with torch.no_grad():
+        workspace, nbytes = _path_tiled_workspace(lib, True, B, H, W, dev, "path_masks_tiled_backward")
+        cost, goal, passable = (_maps3(t.detach()) for t in maps)
+        up = grad_paths.detach().reshape(B, H, W).contiguous()
+        fwd = paths_fwd.detach().reshape(B, H, W).contiguous()
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        rounds = ctypes.c_int(0)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_path_masks_tiled_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), idx.data_ptr(), up.data_ptr(),
+                                                      fwd.data_ptr(), status_fwd.data_ptr(), B, H, W, mask, lam, floor, grad.data_ptr(),
+                                                      status.data_ptr(), workspace.data_ptr(), nbytes, 0 if max_rounds is None else max_rounds,
+                                                      ctypes.cast(ctypes.pointer(rounds), ctypes.c_void_p), _stream_ptr(dev))
+        _native.check(rc, "nastar_path_masks_tiled_backward")
+    return (grad, status, rounds.value) if return_rounds else (grad, status)
+
+
+def shortest_paths_tiled(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                         neighbor_mask: Optional[int] = None, lambda_: Optional[float] = None, min_cost: float = 2.0 ** -10) -> PathOutput:
+    """``shortest_paths`` for maps of up to ``PATH_MASKS_TILED_MAX_CELLS`` cells (include/nastar_path_masks_tiled.h) -> ``PathOutput``: the
+    same definition, the same arguments, the same conventions for failed maps and -- on the sizes both take -- the same BITS, forward and
+    backward.  The contract is that of ``shortest_paths`` with three differences.  The limit is ``PATH_MASKS_TILED_MAX_CELLS`` cells
+    (NotImplementedError above).  The field comes from the tiled relaxation of ``cost_to_go_tiled``, which synchronises its stream between
+    batches of rounds: the call BLOCKS and raises RuntimeError inside a stream capture, before any launch.  And with ``lambda_`` the
+    backward of the autograd node on ``paths`` -- one elementwise launch, the same relaxation on the perturbed costs, one launch for the
+    rows -- blocks too.  The status is always read once: a NaN or a negative cost on a passable cell raises ValueError naming the rows, and
+    so does, with ``lambda_``, a route that runs into a zero-cost plateau; every other failure stays in ``status``.  ``min_cost`` is an API
+    default, NOT a tuned number."""
+    differentiable = lambda_ is not None
+    if differentiable:
+        lam = _checked_step(lambda_, "lambda_")
+    _checked_step(min_cost, "min_cost")
+    floor = float(min_cost)
+    maps, idx, mask, (B, H, W), dev = _path_mask_inputs(cost_maps, goal_maps, obstacles_maps, start_maps, neighbor_mask, "shortest_paths_tiled",
+                                                        PATH_MASKS_TILED_MAX_CELLS)
+    _refuse_capture(dev, RuntimeError, f"shortest_paths_tiled: {_BLOCKS}")
+    if differentiable and cost_maps.requires_grad and torch.is_grad_enabled():
+        out = PathOutput(*_PathNode.apply(cost_maps, goal_maps, obstacles_maps, idx, mask, lam, floor, True))
+    else:
+        out = path_masks_tiled(cost_maps, goal_maps, obstacles_maps, idx, mask)
+    _raise_path_failures(out.status, B, "shortest_paths_tiled", "H*W + 1 rounds", differentiable)
     return out

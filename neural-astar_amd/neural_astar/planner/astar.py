@@ -112,6 +112,12 @@ class VanillaAstar(nn.Module):
         ``map_designs`` as the cost (not as the obstacles)."""
         return self.astar.shortest_paths(map_designs, start_maps, goal_maps, map_designs, lambda_, min_cost)
 
+    def shortest_paths_tiled(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, lambda_: Optional[float] = None,
+                             min_cost: float = 2.0 ** -10) -> PathOutput:
+        """``shortest_paths`` by the tiled relaxation (``DifferentiableAstar.shortest_paths_tiled``: maps of up to 1024x1152, the same bits);
+        the call blocks."""
+        return self.astar.shortest_paths_tiled(map_designs, start_maps, goal_maps, map_designs, lambda_, min_cost)
+
 
 class NeuralAstar(VanillaAstar):
     def __init__(self, g_ratio: float = 0.5, Tmax: float = 1.0, encoder_input: str = "m+",
@@ -326,6 +332,17 @@ class NeuralAstar(VanillaAstar):
         ``lambda_=None``: an evaluation call on the detached cost maps.  ``lambda_`` a positive float: the cost maps are NOT detached and
         ``paths`` carries the blackbox gradient, so a Hamming or L1 loss on ``paths`` against the demonstration trains the encoder on the
         device (the "BB-A*" baseline of the Neural A* paper).  The encoder route is what ``encode()`` picks in that mode."""
+        return self.astar.shortest_paths(*self._path_inputs(map_designs, start_maps, goal_maps, lambda_, min_cost), lambda_, min_cost)
+
+    def shortest_paths_tiled(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, lambda_: Optional[float] = None,
+                             min_cost: float = 2.0 ** -10) -> PathOutput:
+        """``shortest_paths`` under the PREDICTED cost maps by the tiled relaxation (``DifferentiableAstar.shortest_paths_tiled``: maps of
+        up to 1024x1152, the same bits; the call blocks, and so does its backward).  With ``lambda_`` the cost maps are NOT detached: a loss
+        on ``paths`` trains the encoder on maps of any size the search takes (include/nastar_path_masks_tiled.h)."""
+        return self.astar.shortest_paths_tiled(*self._path_inputs(map_designs, start_maps, goal_maps, lambda_, min_cost), lambda_, min_cost)
+
+    def _path_inputs(self, map_designs, start_maps, goal_maps, lambda_, min_cost):
+        """the (cost, start, goal, obstacles) maps of ``shortest_paths`` / ``shortest_paths_tiled``"""
         if lambda_ is not None:
             ops._checked_step(lambda_, "lambda_")  # (both refusals before the encoder launches anything)
         ops._checked_step(min_cost, "min_cost")
@@ -333,4 +350,4 @@ class NeuralAstar(VanillaAstar):
         if lambda_ is None:
             cost_maps = cost_maps.detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
-        return self.astar.shortest_paths(cost_maps, start_maps, goal_maps, obstacles_maps, lambda_, min_cost)
+        return cost_maps, start_maps, goal_maps, obstacles_maps

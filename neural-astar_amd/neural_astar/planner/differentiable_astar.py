@@ -686,6 +686,14 @@ class DifferentiableAstar(nn.Module):
         return ops.shortest_paths(cost_maps, start_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), lambda_=lambda_,
                                   min_cost=min_cost)
 
+    def shortest_paths_tiled(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                             lambda_: Optional[float] = None, min_cost: float = 2.0 ** -10) -> PathOutput:
+        """``shortest_paths`` for maps of up to ``ops.PATH_MASKS_TILED_MAX_CELLS`` cells (``ops.shortest_paths_tiled``, include/
+        nastar_path_masks_tiled.h: the field by the tiled relaxation, the same bits), under this module's own move set.  The call blocks
+        and cannot be captured into a graph; with ``lambda_`` the backward of ``paths`` blocks too."""
+        return ops.shortest_paths_tiled(cost_maps, start_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), lambda_=lambda_,
+                                        min_cost=min_cost)
+
     def forward(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor,
                 obstacles_maps: torch.Tensor, store_intermediate_results: bool = False,
                 heuristic_maps: Optional[torch.Tensor] = None) -> AstarOutput:
