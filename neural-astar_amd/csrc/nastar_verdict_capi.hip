@@ -33,8 +33,14 @@ int proof_lane(ProofLane** out)
     if (l.stream == nullptr) {
         int cus = 0;
         if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute");
+        // The event only orders the side stream behind the caller's stream ON THIS DEVICE: nobody synchronises with it from the host or asks
+        // it for a time.  Recorded with the default flags, its marker packet sits between two consecutive search launches of the caller's
+        // stream and performs a system-scope release there (L2 written back and invalidated for the host) -- 2.4 us per checked step,
+        // for a consumer that is a kernel of the same device.  hipEventDisableSystemFence leaves the marker as the plain barrier it needs to
+        // be: what earlier kernels of the stream wrote is released at device scope by those kernels' own ends, and the proof kernel begins
+        // with its own acquire.  (hipEventReleaseToDevice was measured too: no different from the default.  DESIGN 4.1 "The gap", profiles/writethrough_outputs.json)
         hipEvent_t ev = nullptr;
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return hip_fail(e, "hipEventCreateWithFlags");
+        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventDisableSystemFence)) != hipSuccess) return hip_fail(e, "hipEventCreateWithFlags");
         hipStream_t s = nullptr;
         if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess) {
             (void)hipEventDestroy(ev);
