@@ -10,7 +10,8 @@
 //   * the (A, B) history sits behind the records, 16 B per step: 16 KiB + 4 KiB = 20,480 B for 32x32 at the training budget
 //     (256 steps) -> 8 maps per CU.  S, D (fp64) alias the LAST history slot: that slot is only written by step max_steps-1,
 //     i.e. when the budget ran out, after which S and D are not needed any more, and it is never read (cells opened by the last
-//     executed step take their stamp from registers);
+//     executed step take their stamp from registers) -- EXCEPT with a budget of one step, where the last slot is also the first
+//     and the start cell, closed by step 0, reads it (stamp 1): a budget of one step gets a second slot for S, D (bwdr_asm_slots);
 //   * "opened" lanes add (+v_new, +G v_new), "left the open list / re-keyed" lanes add (-v_old, -G v_old) with ds_add_f64 under
 //     EXEC masks (no select-with-zero arithmetic), the interval of a leaving cell is closed one step later (its history entry is
 //     fetched by a ds_read_b128 issued in the step that closes it);
@@ -33,7 +34,9 @@ struct BwdAsmLayout {
     static constexpr int HW = W * W;
     static constexpr int HIST = HW * 16;
 };
-__host__ __device__ inline size_t bwdr_asm_lds_bytes(int HW, int max_steps) { return (size_t)HW * 16 + (size_t)max_steps * 16; }
+// history slots: one per step of the budget, and never fewer than two (S, D must not share slot 0 with the entry the start cell reads)
+__host__ __device__ inline int bwdr_asm_slots(int max_steps) { return max_steps < 2 ? 2 : max_steps; }
+__host__ __device__ inline size_t bwdr_asm_lds_bytes(int HW, int max_steps) { return (size_t)HW * 16 + (size_t)bwdr_asm_slots(max_steps) * 16; }
 
 #define NASTAR_BWD_ASM_LOOP \
         "v_mov_b32 v60, 0\n\tv_mov_b32 v61, 0\n\tv_mov_b32 v62, 0\n\tv_mov_b32 v63, 0\n\t" /* A = B = 0 */ \
@@ -195,7 +198,8 @@ __global__ __launch_bounds__(64) void nastar_backward_replay_asm_kernel(const Bw
     BwdRec* rec = reinterpret_cast<BwdRec*>(smem);
     const int max_steps = a.hist_len - 2;                      // min(max_iters, HW + 1)
     double* hist = reinterpret_cast<double*>(smem + L::HIST);  // entry e at hist[2*(e-1)]
-    double* sd = hist + 2 * (max_steps - 1);                   // S, D alias the last history slot (see the header)
+    const int sd_slot = bwdr_asm_slots(max_steps) - 1;
+    double* sd = hist + 2 * sd_slot;                           // S, D alias the last history slot (see the header)
     const size_t off = (size_t)b * (size_t)L::HW;
     float* gout = a.grad_cost + off;
 
@@ -252,7 +256,7 @@ __global__ __launch_bounds__(64) void nastar_backward_replay_asm_kernel(const Bw
     const bool is_nb = lane < 8;
     const int v_dr = is_nb ? dr : 0, v_dc = is_nb ? dc : 0, v_off = is_nb ? dr * L::W + dc : 0;
     const float v_inf = NASTAR_POS_INF, v_minf = NASTAR_NEG_INF;
-    const uint32_t v_l4 = (uint32_t)lane * 4u, v_sda = (uint32_t)(L::HIST + (max_steps - 1) * 16);
+    const uint32_t v_l4 = (uint32_t)lane * 4u, v_sda = (uint32_t)(L::HIST + sd_slot * 16);
     const uint32_t v_logmax = (uint32_t)(a.max_iters - 1) * 4u;
     const unsigned long long m_nb = 0xFFull;
     int t = 0;

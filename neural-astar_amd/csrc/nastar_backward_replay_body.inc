@@ -86,7 +86,10 @@
         if constexpr (kGlobal) global_step_fence();
         wave_sync();
         double dS = 0.0, dD = 0.0;
+        int n_open = 0, last_open = 0;
         auto open = [&](int i) {
+            ++n_open;
+            last_open = i;
             const int r = i / d.W, c = i - r * d.W;
             const float hh = d.omg * (h0(i, r, c, goal_r, goal_c) + st_ld<kGlobal>(&cst[i]));
             const float v = bwdr_v<kFastDiv>(d, 0.0f, hh, rcp_sqrtW);
@@ -129,6 +132,8 @@
         }
         for (int i = done + lane; i < d.HW; i += 64)
             if (sm[i] != 0.f) open(i);
+        // ONE source in all: the single-source replay's open list, whose start carries stamp 1 (below) -- the same bits for a one-hot start map
+        if ((int)wave_sum_f32((float)n_open) == 1 && n_open == 1) st_st<kGlobal>(&t0[last_open], (stamp_t)1);
         const uint32_t sda0 = (uint32_t)(uintptr_t)sd;
         asm volatile("ds_add_f64 %0, %1\n\tds_add_f64 %0, %2 offset:8" ::"v"(sda0), "v"(dS), "v"(dD) : "memory");
     } else
@@ -139,6 +144,10 @@
         const float hh = d.omg * (h0(sidx, r, c, goal_r, goal_c) + st_ld<kGlobal>(&cst[sidx]));
         const float v = bwdr_v<kFastDiv>(d, 0.0f, hh, rcp_sqrtW);
         st_st<kGlobal>(&g[sidx], 0.0f);
+        // ... with stamp 1, not 0: at step 0 the open list is {start}, y = 1 and G - <G, y> is exactly zero (the oracle's reverse mode gives
+        // 0.0 there), but kfac v (G rS - (G v) rS rS) in fp32 is not -- 1e-11 .. 1e-8 of noise on the start cell, all there is of a
+        // gradient that must be exactly zero (a budget of one step, a start == goal map on its own).  Entry 1 is what step 0 writes.
+        st_st<kGlobal>(&t0[sidx], (stamp_t)1);
         sd[0] = (double)v;
         sd[1] = (double)(st_ld<kGlobal>(&G[sidx]) * v);
     }
@@ -172,6 +181,10 @@
         const float rS = __builtin_amdgcn_rcpf((float)S);
         A += (double)rS;
         B += (double)((float)D * rS * rS);
+        if (lane == 0) {  // history entry t+1 = (A, B) after step t (also of the step that ends the loop: an open start cell's stamp is 1)
+            hist_st<kHistLds>(&hist[2 * (t + 1)], A);
+            hist_st<kHistLds>(&hist[2 * (t + 1) + 1], B);
+        }
         const bool goal_step = s == gidx;
         const bool last_step = t == n_steps - 1;
         if (goal_step && last_step && extra <= 0) {  // the step that ends the batch loop: its softmax counted, nothing follows
@@ -215,18 +228,15 @@
             st_st<kGlobal>(&G[s], goal_up);
             st_st<kGlobal>(&t0[s], (stamp_t)(t + 1));
         }
-        if (lane == 0) {  // history entry t+1 = (A, B) after step t
-            hist_st<kHistLds>(&hist[2 * (t + 1)], A);
-            hist_st<kHistLds>(&hist[2 * (t + 1) + 1], B);
-        }
         // close the interval of every cell that left the open list or was re-keyed: load its opening stamp, consume next step
-        pend = flushing;
+        // (the start cell closed by step 0 carries stamp 1 = this step's own entry: an empty interval, nothing to add)
+        pend = flushing & (tl != t + 1);
         pv = v_old;
         pG = Gl;
         pcell = il;
         pA = A;
         pB = B;
-        if (flushing) {
+        if (pend) {
             pA0 = hist_ld<kHistLds>(&hist[2 * tl]);
             pB0 = hist_ld<kHistLds>(&hist[2 * tl + 1]);
         }

@@ -158,6 +158,10 @@ __device__ __forceinline__ float ord_to_f32(uint32_t k)
 
 // exact n / d for n, d < 2^16 with magic = floor(2^32 / d) + 1
 __device__ __forceinline__ uint32_t div_magic(uint32_t n, uint32_t magic) { return __umulhi(n, magic); }
+// row n / W of cell n in a map W wide.  W == 1 has no 32-bit magic -- floor(2^32 / 1) + 1 wraps to 1, and __umulhi(n, 1) is 0 for every
+// cell: a one-column map's rows all came out as row 0 (unseen while its budget W * W is one step; any longer budget through the C ABI
+// searched a wrong neighbourhood, and nastar_heuristic measured every distance from row 0) -- there the row is the cell itself
+__device__ __forceinline__ uint32_t row_magic(uint32_t n, uint32_t magic, int W) { return W == 1 ? n : div_magic(n, magic); }
 
 // ---- correctly rounded square root of an exactly representable integer >= 0 ------------------------------------------------------------
 // v_sqrt_f32 is a 1-ulp instruction: NOT correctly rounded for ~15 % of the integers (first miss at 6; tools/ubench/sqrt_check.hip,

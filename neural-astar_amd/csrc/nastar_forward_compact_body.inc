@@ -45,7 +45,7 @@
         bad_h0 = compact_load_heuristic<kVec4>(d, l, hhv, h0 + off, lane);
     }
     const int gi = goal_idx < 0 ? 0 : goal_idx;
-    const int goal_r = (int)div_magic((uint32_t)gi, d.magicW);
+    const int goal_r = (int)row_magic((uint32_t)gi, d.magicW, d.W);
     const int goal_c = gi - goal_r * d.W;
 
     const CompactLane lc = make_compact_lane<kMasked>(d, lane, nmask);  // (kMasked: lanes 0-7 gated by the mask -- the goal-expansion test of the COUPLED note reads them too)

@@ -227,7 +227,7 @@ __device__ __forceinline__ void compact_open_start(const CompactDims& d, const C
                                                    int goal_c, float rcp_sqrtW, bool raw_key = false, bool half_key = false)
 {
     if (lane == 0) {
-        const int r = (int)div_magic((uint32_t)sidx, d.magicW);
+        const int r = (int)row_magic((uint32_t)sidx, d.magicW, d.W);
         const int c = sidx - r * d.W;
         const float hh = (half_key ? 1.0f : d.omg) * (heuristic0_fast(r, c, goal_r, goal_c) + l.gc[sidx].y);  // :191-192 h = h0 + cost ; :206
         uint32_t k0 = compact_key<kFastDiv>(d, 0.0f, hh, rcp_sqrtW);
@@ -252,7 +252,7 @@ __device__ __forceinline__ void compact_open_sources(const CompactDims& d, const
         if constexpr (kHeur) {
             hh = hhv[i];
         } else {
-            const int r = (int)div_magic((uint32_t)i, d.magicW);
+            const int r = (int)row_magic((uint32_t)i, d.magicW, d.W);
             const int c = i - r * d.W;
             hh = d.omg * (heuristic0_fast(r, c, goal_r, goal_c) + l.gc[i].y);  // :191-192 h = h0 + cost ; :206
         }
@@ -349,7 +349,7 @@ __device__ __forceinline__ void compact_expand(const CompactDims& d, const Compa
         r = s >> LOGW;
         c = s & ((1 << LOGW) - 1);
     } else {
-        r = (int)div_magic((uint32_t)s, d.magicW);
+        r = (int)row_magic((uint32_t)s, d.magicW, d.W);
         c = s - r * d.W;
     }
     const int cbase = s & ~(CCSZ - 1);
@@ -370,7 +370,7 @@ __device__ __forceinline__ void compact_expand(const CompactDims& d, const Compa
         rl = il >> LOGW;
         cl = il & ((1 << LOGW) - 1);
     } else {
-        rl = (int)div_magic((uint32_t)il, d.magicW);
+        rl = (int)row_magic((uint32_t)il, d.magicW, d.W);
         cl = il - rl * d.W;
     }
     const float h0 = heuristic0_fast(rl, cl, goal_r, goal_c);

@@ -237,9 +237,9 @@ __global__ __launch_bounds__(64) void nastar_heuristic_kernel(const float* goal,
         if (gm[i] != 0.f) gidx = i;
     gidx = wave_max_i32(gidx);
     if (gidx < 0) gidx = 0;
-    const int gr = (int)div_magic((uint32_t)gidx, magicW), gc = gidx - gr * W;
+    const int gr = (int)row_magic((uint32_t)gidx, magicW, W), gc = gidx - gr * W;
     for (int i = lane; i < HW; i += 64) {
-        int r = (int)div_magic((uint32_t)i, magicW), c = i - r * W;
+        int r = (int)row_magic((uint32_t)i, magicW, W), c = i - r * W;
         out[(size_t)b * HW + i] = heuristic0(r, c, gr, gc);
     }
 }
