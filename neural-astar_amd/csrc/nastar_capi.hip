@@ -18,6 +18,7 @@
 #include "nastar_dev_flags.h"  // A/B switches of the development build (make dev): round-3 / round-2 streams, no dive, compiled step
 #endif
 #include "nastar_search_asm4.hip.h"  // (reuses the instruction sections of nastar_search_asm3.hip.h; the round-3 LOOP itself is only instantiated by the development build)
+#include "nastar_search_asm5.hip.h"  // (the round-4 stream for maps that keep the heuristic where the cost word was)
 #include "nastar_search_unit.hip.h"
 #include "nastar_placement.hip.h"
 #include "nastar_backward_replay.hip.h"

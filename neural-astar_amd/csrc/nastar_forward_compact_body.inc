@@ -7,6 +7,9 @@
 // `constexpr bool kMulti` -- every non-zero cell of the start map is a source, and a parent walk ends at an unset parent only.
 // nastar_forward_compact_ranked_kernel (include/nastar_levels.h) is the fifth: `constexpr bool kRanked` / `levels` -- the workgroup finds its
 // map from the batch's levels (ranked_map, nastar_placement.hip.h) instead of an order array; everything behind that line is the first kernel's.
+// The hand-scheduled instantiations (kAsm: the first and the fifth kernel only) decide per map whether its cost word can hold the heuristic
+// instead (`stored_h`, nastar_search_asm5.hip.h); every such line sits behind `if constexpr (kAsm)` or folds away with kAsm, so the other
+// kernels keep their machine code (tools/compare_device_code.py).
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = kRanked ? ranked_map(levels, a.B) : placed_map(a.order, a.order_bad, a.B);
     if ((unsigned)b >= (unsigned)a.B) return;  // not a permutation (and not checked: NASTAR_FLAG_CHECK_ORDER): never read or write outside the batch
@@ -30,9 +33,10 @@
     int start_idx, goal_idx;
     constexpr int kLoadIter = (kVec4 && LOGH > 0 && LOGW > 0 && LOGH + LOGW >= 8) ? (1 << (LOGH + LOGW - 8)) : 0;
     bool any_signed = true;
+    bool all_unit = false;  // kAsm: every cost is exactly 0.0 or 1.0
     // round-3 instruction stream (raw-bit keys): every cost >= +0 and 0 <= g_ratio <= 1 so that every priority is >= +0
     compact_load_map<kVec4, kLoadIter>(d, l, a.cost + off, a.start + off, a.goal + off, a.passable + off, lane, start_idx, goal_idx,
-                                       kAsm ? &any_signed : nullptr);
+                                       kAsm ? &any_signed : nullptr, kAsm ? &all_unit : nullptr);
 #ifdef NASTAR_DEV
     const bool raw = kAsm && !any_signed && !(a.flags & NASTAR_FLAG_ASM_V2) && d.gr >= 0.f && d.omg >= 0.f;
 #else
@@ -53,6 +57,7 @@
     int iters = 0;
     bool solved = false, coupled = false;
     bool goal_hit = false;
+    bool stored_h = false;  // kAsm: this map keeps fl(h0 + 1.0) where its cost word was (nastar_search_asm5.hip.h); wave-uniform
     const bool probe = lockstep && a.bitmap != nullptr;
     const int budget = (lockstep && a.t_end != nullptr) ? __builtin_amdgcn_readfirstlane(*a.t_end + 1) : a.max_iters;
     uint32_t bits = 0u;  // probe: goal selections of the current 32 steps
@@ -86,6 +91,21 @@
         compact_open_start<kFastDiv>(d, l, lane, start_idx, goal_r, goal_c, rcp_sqrtW, raw, half);
         int s = 0;
         if constexpr (kAsm) {
+            // ONE binary tensor as cost map and obstacle map (VanillaAstar, reference astar.py:93-94): every cell the search can relax costs
+            // 1.0, the cost word carries nothing and takes hh = fl(h0 + 1.0) instead -- decided here, per map, from what the load saw; no
+            // flag, no status.  A start on an obstacle (cost 0, expanded all the same, :187) is opened with g = -1.0: fl(-1.0 + 1.0) = fl(0 + 0)
+            // is what its first step hands on (nastar_search_unit.hip.h); its key above was formed from its cost word before that word goes.
+#ifdef NASTAR_DEV
+            stored_h = asm4 && !no_dive && all_unit && a.cost == a.passable;
+#else
+            stored_h = asm4 && all_unit && a.cost == a.passable;
+#endif
+            if (stored_h) {
+                const bool start_blocked = l.gc[start_idx].y == 0.0f;
+                compact_store_heuristic<LOGW>(l, lane, goal_r, goal_c);
+                if (start_blocked && lane == 0) l.gc[start_idx].x = -1.0f;
+                wave_sync();
+            }
             static_assert(LOGW > 0 && LOGW == LOGH && (CPL_T == 1 || CPL_T == 4) && kFastDiv, "asm loop: 16x16, 32x32, 64x64");
             int* const log_row = kLog ? a.sel_log + (size_t)b * (size_t)a.max_iters : nullptr;
             // searching wavefronts issue ahead of the ones still loading their map or already storing their result (the launch waits for the
@@ -102,7 +122,10 @@
                 s = compact_search_loop_asm3<LOGW, kLog>(d, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
             } else
 #endif
-            if (asm4) {
+            if (stored_h) {
+                s = half ? search_loop_asm5<LOGW, kLog, kD, true>(d.gr, d.omg, d.sqrtW, lane, goal_idx, a.max_iters, iters, rcp_sqrtW, log_row)
+                         : search_loop_asm5<LOGW, kLog, kD, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, a.max_iters, iters, rcp_sqrtW, log_row);
+            } else if (asm4) {
                 s = half ? search_loop_asm4<LOGW, kLog, kD, true, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row)
                          : search_loop_asm4<LOGW, kLog, kD, false, false>(d.gr, d.omg, d.sqrtW, lane, goal_idx, goal_r, goal_c, a.max_iters, iters, rcp_sqrtW, log_row);
             } else {
@@ -158,7 +181,14 @@
                     const int nr = goal_r + lc.dr, nc = goal_c + lc.dc;
                     const bool inb = lc.is_nb & ((unsigned)nr < (unsigned)d.H) & ((unsigned)nc < (unsigned)d.W);
                     const int n = inb ? s + lc.off : s;
-                    const float2 gg = l.gc[s], gn = l.gc[n];
+                    float2 gg = l.gc[s], gn = l.gc[n];
+                    if constexpr (kAsm) {
+                        if (stored_h) {  // the words read above hold hh: a cell that can be relaxed costs 1.0, a goal that is the start what the caller's map says (and its g was 0)
+                            gn.y = 1.0f;
+                            gg.y = 1.0f;
+                            if (s == start_idx) gg = make_float2(0.0f, a.cost[off + s]);
+                        }
+                    }
                     const float g2 = gg.x + gg.y;
                     uint32_t kn, kg;
                     if constexpr (kHeur) {  // the stored values, for the neighbour AND the goal (h0(goal) need not be 0)
@@ -195,7 +225,10 @@
                                         a.packed ? a.packed + (size_t)b * (size_t)(d.HW >> 2) : nullptr);
     const RouteOut ro = kernel_route_args<offsetof(FwdCArgs, route)>();  // (a.route, read here: nastar_routes.hip.h)
     if (ro.routes != nullptr) {  // wave-uniform; null unless the launch came through include/nastar_routes.h
+        // (a stored_h map has no cost word: every cell the search opened is passable and costs 1, the start's cost is read from the caller's map)
+        const float start_cost = (kAsm && stored_h) ? a.cost[off + start_idx] : 0.f;
         const int n = route_walk(l.pdir, lane, kMulti ? -1 : start_idx, goal_idx, solved ? d.HW : iters - 1, goal_idx >= 0 && !(kHeur && bad_h0),
-                                 [&](int c, uint32_t code) { return compact_parent_of(d, c, code); }, [&](int c) { return l.gc[c].y; }, ro, b);
+                                 [&](int c, uint32_t code) { return compact_parent_of(d, c, code); },
+                                 [&](int c) { return (kAsm && stored_h) ? (c == start_idx ? start_cost : 1.0f) : l.gc[c].y; }, ro, b);
         route_fill_tail(ro, b, n, lane);
     }

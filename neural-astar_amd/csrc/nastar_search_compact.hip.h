@@ -97,14 +97,15 @@ __device__ __forceinline__ float heuristic0_fast(int r, int c, int goal_r, int g
 // ITER > 0: the map has exactly ITER * 256 cells (compile-time size): the loads of up to 4 iterations (16 x 16 B per lane) are all
 // issued before the first is consumed, so a map costs ~one HBM latency to load instead of one per iteration.
 // any_signed (optional): set when some cost is < 0 or NaN (wave-uniform) -- the round-3 instruction stream keys on raw float bits
+// all_unit (optional): set when every cost is exactly 0.0 or 1.0 (wave-uniform; the test of unit_load_map) -- nastar_search_asm5.hip.h
 template <bool kVec4, int ITER = 0>
 __device__ __forceinline__ void compact_load_map(const CompactDims& d, const CompactLds& l, const float* __restrict__ cost,
                                                  const float* __restrict__ start, const float* __restrict__ goal,
                                                  const float* __restrict__ passable, int lane, int& start_idx, int& goal_idx,
-                                                 bool* any_signed = nullptr)
+                                                 bool* any_signed = nullptr, bool* all_unit = nullptr)
 {
     int sidx = -1, gidx = -1;
-    bool sgn = false;
+    bool sgn = false, nun = false;
     if constexpr (kVec4) {
         const float4* s4 = reinterpret_cast<const float4*>(start);
         const float4* g4 = reinterpret_cast<const float4*>(goal);
@@ -121,6 +122,7 @@ __device__ __forceinline__ void compact_load_map(const CompactDims& d, const Com
             if (gv.z != 0.f) gidx = i + 2;
             if (gv.w != 0.f) gidx = i + 3;
             sgn |= !(cv.x >= 0.f) | !(cv.y >= 0.f) | !(cv.z >= 0.f) | !(cv.w >= 0.f);
+            nun |= ((cv.x != 0.f) & (cv.x != 1.f)) | ((cv.y != 0.f) & (cv.y != 1.f)) | ((cv.z != 0.f) & (cv.z != 1.f)) | ((cv.w != 0.f) & (cv.w != 1.f));
             float4 lo, hi;
             lo.x = pv.x != 0.f ? NASTAR_POS_INF : NASTAR_NEG_INF;
             lo.y = cv.x;
@@ -171,6 +173,7 @@ __device__ __forceinline__ void compact_load_map(const CompactDims& d, const Com
             if (goal[i] != 0.f) gidx = i;
             const float pv = passable[i];
             sgn |= !(cost[i] >= 0.f);
+            nun |= (cost[i] != 0.f) & (cost[i] != 1.f);
             l.gc[i] = make_float2(pv != 0.f ? NASTAR_POS_INF : NASTAR_NEG_INF, cost[i]);
             l.pdir[i] = (uint8_t)(PARENT_UNSET | (pv != 0.f ? P_PASS : 0u));
         }
@@ -183,6 +186,7 @@ __device__ __forceinline__ void compact_load_map(const CompactDims& d, const Com
     const unsigned long long idle = cmin_entry(0xFFFFFFFFu, (uint32_t)(goal_idx < 0 ? 0 : goal_idx));
     for (int c = lane; c < d.NCp; c += 64) l.cmin[c] = idle;
     if (any_signed != nullptr) *any_signed = __ballot(sgn) != 0ull;
+    if (all_unit != nullptr) *all_unit = __ballot(nun) == 0ull;
     wave_sync();
 }
 
