@@ -81,8 +81,8 @@ struct FwdHybridArgs {
     RouteOut route;        // optional (include/nastar_routes.h): ordered routes, lengths, costs; null for every entry point of nastar.h
 };
 
-// row of flat index i (< 2^21): (i + 0.5) / W in fp32 lands within one row of the true quotient (the product's error is ~2^-23 of a row
-// index below 2^11); one correction step either way makes it exact
+// row of flat index i (< 2^21, rows up to 393215 on a 393216x3 map): the product is within (r + 1) 2^-23 of (i + 0.5) / W, which lies 0.5 / W
+// from an integer -- already the row while H W < 2^22; the one correction step either way is a margin no accepted map uses
 __device__ __forceinline__ int hybrid_row(int i, const HybridDims& d, int& c)
 {
     int r = (int)(((float)i + 0.5f) * d.inv_W);
