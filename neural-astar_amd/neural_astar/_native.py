@@ -260,6 +260,20 @@ PATH_MASK_TILED_SIGNATURES = {
     "nastar_path_masks_tiled_backward": "i pppppppiiiuffpppzqpp",
 }
 
+# the signatures of include/nastar_soft_fields.h (the thirteenth header: the entropy-regularised cost-to-go field over a finite horizon, its
+# soft policy and its gradient with respect to the costs), same letter code; a table of its own (tests/test_soft_fields.py compares it with
+# ITS header)
+SOFT_FIELD_SIGNATURES = {
+    "nastar_soft_fields_abi": "i ",
+    "nastar_soft_fields_max_cells": "i ",
+    "nastar_soft_fields_grad_max_cells": "i ",
+    "nastar_soft_fields_tape_bytes": "z iiii",
+    # cost, goal, passable, B, H, W, neighbor_mask, tau, horizon, dist_out, policy_out, status_out, tape, tape_bytes, stream
+    "nastar_soft_cost_to_go": "i pppiiiudippppzp",
+    # cost, goal, passable, tape, tape_bytes, grad_dist, B, H, W, neighbor_mask, tau, horizon, grad_cost_out, status_out, stream
+    "nastar_soft_fields_backward": "i ppppzpiiiudippp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -401,6 +415,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, PATH_MASK_SIGNATURES, PATH_MASK_SIGNATURES)
     if hasattr(lib, "nastar_path_masks_tiled_abi"):  # (and the twelfth)
         _bind(lib, PATH_MASK_TILED_SIGNATURES, PATH_MASK_TILED_SIGNATURES)
+    if hasattr(lib, "nastar_soft_fields_abi"):  # (and the thirteenth)
+        _bind(lib, SOFT_FIELD_SIGNATURES, SOFT_FIELD_SIGNATURES)
     _lib = lib
     return lib
 

@@ -20,7 +20,9 @@ __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay",
            "fields_backward", "FIELD_PLATEAU", "FIELDS_GRAD_MAX_CELLS", "fields_backward_tiled", "FIELDS_GRAD_TILED_MAX_CELLS",
            "field_routes", "FieldRoutes", "FIELD_ROUTES_MAX_CELLS", "FIELD_ROUTES_MAX_QUERIES",
            "shortest_paths", "PathOutput", "path_masks", "path_masks_backward", "PATH_MASKS_MAX_CELLS",
-           "shortest_paths_tiled", "path_masks_tiled", "path_masks_tiled_backward", "PATH_MASKS_TILED_MAX_CELLS"]
+           "shortest_paths_tiled", "path_masks_tiled", "path_masks_tiled_backward", "PATH_MASKS_TILED_MAX_CELLS",
+           "soft_cost_to_go", "SoftFieldOutput", "maxent_path_nll", "soft_fields_forward", "soft_fields_backward", "SOFT_FIELDS_MAX_CELLS",
+           "SOFT_FIELDS_GRAD_MAX_CELLS"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -1593,3 +1595,160 @@ def shortest_paths_tiled(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal
         out = path_masks_tiled(cost_maps, goal_maps, obstacles_maps, idx, mask)
     _raise_path_failures(out.status, B, "shortest_paths_tiled", "H*W + 1 rounds", differentiable)
     return out
+
+
+# ---- include/nastar_soft_fields.h: the entropy-regularised cost-to-go field over a finite horizon and its gradient
+SOFT_FIELDS_MAX_CELLS = 12288  # nastar_soft_fields_max_cells(): the cost and two planes of one map in the LDS of one workgroup
+SOFT_FIELDS_GRAD_MAX_CELLS = 6144  # nastar_soft_fields_grad_max_cells(): the backward keeps 25 bytes per cell
+
+
+class SoftFieldOutput(NamedTuple):
+    """What ``soft_cost_to_go()`` returns.  ``dists`` [B,1,H,W] fp32: the soft-min cost-to-go V_K (0 on goals, +inf on obstacles and where
+    no goal lies within ``horizon`` moves); ``policies`` [B,8,H,W] fp32 (action k = ``utils.synthetic.ACTION_MOVES[k]``: the softmax over
+    the allowed moves with a finite target of -V_{K-1} / tau; all-zero on goals, obstacles and cells with an infinite ``dists``), detached,
+    or None; ``status`` [B] int32: 0, or ``STATUS_UNSOLVABLE`` for a map without a goal cell."""
+
+    dists: torch.Tensor
+    policies: Optional[torch.Tensor]
+    status: torch.Tensor
+
+
+def _checked_tau(tau) -> float:
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0.0 < float(tau) < float("inf"):
+        raise ValueError(f"tau must be a finite positive Python float (the temperature; it has no gradient), got {tau!r}")
+    return float(tau)
+
+
+def _checked_horizon(horizon, H: int, W: int) -> int:
+    if horizon is None:
+        return 2 * (H + W)
+    if isinstance(horizon, bool) or not isinstance(horizon, int) or not 1 <= horizon < 2 ** 31:
+        raise ValueError(f"horizon must be a positive int or None (= 2 * (H + W)), got {horizon!r}")
+    return horizon
+
+
+def soft_fields_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                        neighbor_mask: Optional[int] = None, policies: bool = False, tape: bool = False):
+    """``nastar_soft_cost_to_go`` as it is (include/nastar_soft_fields.h) -> ``(SoftFieldOutput, tape)``: one launch on the current stream,
+    nothing is read back, detached outputs.  ``tape=True`` allocates the tape of ``nastar_soft_fields_tape_bytes`` bytes (the planes
+    V_1 .. V_K, what ``soft_fields_backward`` reads) and returns it as a uint8 tensor; None otherwise.  What ``soft_cost_to_go`` runs;
+    probes and tests call it directly."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    limit = SOFT_FIELDS_GRAD_MAX_CELLS if tape else SOFT_FIELDS_MAX_CELLS
+    if H * W > limit:
+        raise NotImplementedError(f"soft_cost_to_go: maps of {H}x{W} = {H * W} cells exceed the limit of {limit} cells"
+                                  f"{' of its backward' if tape else ''} (one workgroup keeps one map in LDS; there is no tiled soft field)")
+    dev = _field_device(maps)
+    lib = _field_lib("nastar_soft_cost_to_go", "nastar_soft_fields.h")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        tape_bytes = int(lib.nastar_soft_fields_tape_bytes(B, H, W, K)) if tape else 0
+        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
+        with torch.cuda.device(dev):
+            rc = lib.nastar_soft_cost_to_go(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(),
+                                            pol.data_ptr() if pol is not None else None, status.data_ptr(),
+                                            buf.data_ptr() if buf is not None else None, tape_bytes, _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_cost_to_go")
+    return SoftFieldOutput(dists, pol, status), buf
+
+
+def soft_fields_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
+                         grad_dists: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                         neighbor_mask: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``nastar_soft_fields_backward`` as it is: the maps, ``tau``, ``horizon`` and mask of the ``soft_fields_forward(..., tape=True)`` call
+    that wrote ``tape``, and an upstream gradient of ``dists``' shape -> ``(grad_cost [B,H,W], status [B] int32)``.  One launch on the
+    current stream, nothing is read back.  ``grad_dists`` is read on the cells live at the horizon only (passable, no goal, finite
+    ``dists``); ``grad_cost`` is exactly 0 on a cell that was never live.  What the backward of ``soft_cost_to_go(...,
+    differentiable=True)`` runs."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    _check_grad_dists(grad_dists, B, H, W)
+    if H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
+        raise NotImplementedError(f"soft_fields_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_FIELDS_GRAD_MAX_CELLS} cells")
+    dev = _grad_device(maps, grad_dists)
+    lib = _field_lib("nastar_soft_fields_backward", "nastar_soft_fields.h")
+    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
+        raise ValueError(f"tape must be the contiguous uint8 tensor soft_fields_forward(..., tape=True) returned, on {dev}")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        up = grad_dists.detach().reshape(B, H, W).contiguous()
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_soft_fields_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(), up.data_ptr(),
+                                                 B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr(), _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_fields_backward")
+    return grad, status
+
+
+def soft_cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                    neighbor_mask: Optional[int] = None, policies: bool = False, differentiable: bool = False) -> SoftFieldOutput:
+    """The entropy-regularised (soft-min) cost-to-go field of every map of the batch over a finite horizon (include/nastar_soft_fields.h)
+    -> ``SoftFieldOutput``: V_k(n) = cost[n] + softmin_tau over the allowed moves n -> m of V_{k-1}(m), ``horizon`` sweeps from "0 on the
+    goals, +inf elsewhere" -- minus tau times the log of the sum of exp(-cost / tau) over the routes that reach a goal within ``horizon``
+    moves.  The value function of maximum-entropy inverse RL; as ``tau`` goes to 0 it is ``cost_to_go``.  Defined for every cost >= 0
+    (zero costs too), every ``tau`` > 0 and every ``horizon`` >= 1; exactly ``horizon`` sweeps run.
+
+    ``cost_maps``, ``goal_maps``, ``obstacles_maps``: [B,1,H,W] (or [B,H,W]) float32 on one HIP device, maps of at most
+    ``SOFT_FIELDS_MAX_CELLS`` cells (NotImplementedError above); a move costs the cell being left; every non-zero cell of a goal map is a
+    goal.  ``tau``: a Python float, the temperature (no gradient).  ``horizon``: None = 2 * (H + W).  ``neighbor_mask``: the move set as
+    the search takes it (None = Moore-8).  ``policies=True`` also returns the soft policy of the last sweep (detached).  One launch on the
+    current stream; the per-map status is read before returning (one host synchronisation; not inside a stream capture): a NaN or a
+    negative cost on a passable cell raises ValueError naming the rows; a map without a goal is reported in ``status``.
+
+    ``differentiable=True``: maps of at most ``SOFT_FIELDS_GRAD_MAX_CELLS`` cells (NotImplementedError above, before anything is
+    launched); the same launch also writes its tape (B * horizon * H * W fp32), and ``dists`` carries an autograd node when ``cost_maps``
+    requires a gradient and grad mode is on.  Its backward is ONE launch of ``nastar_soft_fields_backward`` on the current stream and
+    reads nothing back; the gradient goes to ``cost_maps`` alone and is smooth in the costs: for ``dists[b, 0, y, x]`` it is the expected
+    number of visits of the soft policy on its way from (y, x) to a goal.  ``dists`` holds +inf where no goal lies within ``horizon``
+    moves: a loss masks those cells itself; whatever gradient arrives for them, for goals and for obstacles is ignored."""
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
+    if differentiable and H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
+        raise NotImplementedError(f"soft_cost_to_go: differentiable=True takes maps of at most {SOFT_FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = "
+                                  f"{H * W} (there is no tiled soft field)")
+    taped: dict = {}  # what the backward needs beside _FieldNode's saved tensors: the tape and the costs; lives as long as the graph does
+    want_tape = differentiable and cost_maps.requires_grad and torch.is_grad_enabled()  # (asked here: inside the node grad mode is off)
+
+    def field(c, g, o):
+        out, taped["tape"] = soft_fields_forward(c, g, o, t, K, mask, policies, tape=want_tape)
+        taped["cost"] = c.detach()
+        if not torch.cuda.is_current_stream_capturing():
+            _raise_bad_cost(out.status.cpu(), B, "soft_cost_to_go")
+        return out
+
+    if not differentiable:
+        return field(cost_maps, goal_maps, obstacles_maps)
+    return SoftFieldOutput(*_differentiable_field(cost_maps, goal_maps, obstacles_maps, field,
+                                                  lambda d, g, o, up: soft_fields_backward(taped["cost"], g, o, taped["tape"], up, t, K, mask)[0]))
+
+
+def maxent_path_nll(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                    opt_trajs: torch.Tensor, tau: float, horizon: Optional[int] = None, neighbor_mask: Optional[int] = None) -> torch.Tensor:
+    """The negative log-likelihood of a demonstration under the maximum-entropy route distribution of ``cost_maps`` -> [B]:
+    ``(sum of cost * opt_trajs * (1 - goal) - V_K(start)) / tau`` with V_K the field of ``soft_cost_to_go(..., differentiable=True)`` --
+    the demonstration pays every cell it leaves, and exp(-V_K(start) / tau) is the partition function over the routes from the start that
+    reach a goal within ``horizon`` moves, so the value is >= 0 for a demonstration among them.  Composed in torch on top of that node: the
+    gradient with respect to ``cost_maps`` is (demonstration - expected visits) / tau.  ``start_maps`` is one-hot, ``opt_trajs`` the 0/1
+    mask of the demonstrated route (start and goal included), both of the maps' shape.  Reads the field at the starts once (a host
+    synchronisation): a start whose V_K is +inf -- no goal within ``horizon`` moves, or none at all -- raises ValueError naming the maps."""
+    out = soft_cost_to_go(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies=False, differentiable=True)
+    B, _, H, W = out.dists.shape
+    for name, m in (("start_maps", start_maps), ("opt_trajs", opt_trajs)):
+        if not torch.is_tensor(m) or m.ndim not in (3, 4) or (m.shape[0],) + tuple(m.shape[-2:]) != (B, H, W) or m.device != out.dists.device:
+            raise ValueError(f"{name} must be a [B,1,H,W] or [B,H,W] tensor of {B} maps of {H}x{W} on {out.dists.device}")
+    at_start = torch.where(_maps3(start_maps) != 0, out.dists[:, 0], torch.zeros_like(out.dists[:, 0])).sum((1, 2))
+    lost = torch.nonzero(~torch.isfinite(at_start.detach())).flatten().tolist()
+    if lost:
+        raise ValueError(f"maxent_path_nll: no goal within horizon = {_checked_horizon(horizon, H, W)} moves of the start of map(s) {lost[:16]}"
+                         f"{' ...' if len(lost) > 16 else ''} ({len(lost)} of {B}): the soft cost-to-go there is +inf (a longer horizon, or an "
+                         "unreachable goal)")
+    leaves = _maps3(opt_trajs).to(torch.float32) * (_maps3(goal_maps) == 0).to(torch.float32)
+    demo = (_maps3(cost_maps) * leaves).sum((1, 2))
+    return (demo - at_start) / _checked_tau(tau)

@@ -99,6 +99,12 @@ class VanillaAstar(nn.Module):
         cost = passable = ``map_designs``.  ``differentiable=True``: ``dists`` carries the gradient to ``map_designs`` as the cost."""
         return self.astar.cost_to_go_tiled(map_designs, goal_maps, map_designs, policies, differentiable)
 
+    def soft_cost_to_go(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                        policies: bool = False, differentiable: bool = False):
+        """The entropy-regularised cost-to-go field over ``horizon`` moves (``DifferentiableAstar.soft_cost_to_go``) with cost = passable =
+        ``map_designs``.  ``differentiable=True``: ``dists`` carries the gradient to ``map_designs`` as the cost (not as the obstacles)."""
+        return self.astar.soft_cost_to_go(map_designs, goal_maps, map_designs, tau, horizon, policies, differentiable)
+
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
                   paths: bool = False) -> FieldRoutesOutput:
         """The ordered optimal route from each of S start cells per map (``DifferentiableAstar.plan_many``: one field per map, a chase per
@@ -309,6 +315,27 @@ class NeuralAstar(VanillaAstar):
             cost_maps = cost_maps.detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.astar.cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, policies, differentiable)
+
+    def soft_cost_to_go(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, tau: float,
+                        horizon: Optional[int] = None, policies: bool = False, differentiable: bool = False):
+        """The entropy-regularised cost-to-go field of the PREDICTED cost maps: encodes as ``cost_to_go()`` does (detached unless
+        ``differentiable``), then ``DifferentiableAstar.soft_cost_to_go``; ``learn_obstacles`` makes every cell passable."""
+        ops._checked_tau(tau)  # (before the encoder launches anything)
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        if not differentiable:
+            cost_maps = cost_maps.detach()
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.soft_cost_to_go(cost_maps, goal_maps, obstacles_maps, tau, horizon, policies, differentiable)
+
+    def maxent_path_nll(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, opt_trajs: torch.Tensor,
+                        tau: float, horizon: Optional[int] = None) -> torch.Tensor:
+        """The maximum-entropy IRL loss of the demonstrations ``opt_trajs`` under the PREDICTED cost maps -> [B]
+        (``ops.maxent_path_nll``): encodes as ``forward()`` does, NOT detached, so ``.sum().backward()`` trains the encoder with the
+        gradient (demonstration - expected visits) / tau; ``learn_obstacles`` makes every cell passable."""
+        ops._checked_tau(tau)  # (before the encoder launches anything)
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.maxent_path_nll(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon)
 
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
                   paths: bool = False) -> FieldRoutesOutput:

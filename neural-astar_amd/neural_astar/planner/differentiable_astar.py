@@ -653,6 +653,20 @@ class DifferentiableAstar(nn.Module):
         return ops.cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, neighbor_mask=self.neighbor_mask(), policies=policies,
                                     differentiable=differentiable)[0]
 
+    def soft_cost_to_go(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
+                        horizon: Optional[int] = None, policies: bool = False, differentiable: bool = False) -> "ops.SoftFieldOutput":
+        """The entropy-regularised (soft-min) cost-to-go field over ``horizon`` moves and, with ``policies``, its soft policy
+        (``ops.soft_cost_to_go``, the kernel of include/nastar_soft_fields.h), under this module's own move set.  ``g_ratio``, ``Tmax`` and
+        the heuristic play no part.  ``differentiable=True``: ``dists`` carries a gradient to ``cost_maps`` that is smooth in the costs."""
+        return ops.soft_cost_to_go(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask=self.neighbor_mask(), policies=policies,
+                                   differentiable=differentiable)
+
+    def maxent_path_nll(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                        opt_trajs: torch.Tensor, tau: float, horizon: Optional[int] = None) -> torch.Tensor:
+        """The negative log-likelihood [B] of the demonstrations ``opt_trajs`` under the maximum-entropy route distribution of
+        ``cost_maps`` (``ops.maxent_path_nll``), under this module's own move set."""
+        return ops.maxent_path_nll(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon, neighbor_mask=self.neighbor_mask())
+
     def plan_many(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
                   max_route_len: Optional[int] = None, paths: bool = False) -> FieldRoutesOutput:
         """The ORDERED optimal route from each of S start cells per map to its nearest goal: ONE cost-to-go field per map
