@@ -274,6 +274,25 @@ SOFT_FIELD_SIGNATURES = {
     "nastar_soft_fields_backward": "i ppppzpiiiudippp",
 }
 
+# the signatures of include/nastar_soft_fields_tiled.h (the fourteenth header: the same field and gradient by tiled sweeps, with a checkpointed
+# tape, for maps of up to 1024 x 1152), same letter code; a table of its own (tests/test_soft_fields_tiled.py compares it with ITS header)
+SOFT_FIELD_TILED_SIGNATURES = {
+    "nastar_soft_fields_tiled_abi": "i ",
+    "nastar_soft_fields_tiled_max_cells": "i ",
+    "nastar_soft_fields_tile": "i ppp",                                # th, tw, sweeps: host ints
+    "nastar_soft_fields_tiled_workspace_bytes": "z iii",
+    "nastar_soft_fields_tiled_tape_bytes": "z iiiii",                  # B, H, W, horizon, checkpoint_every
+    "nastar_soft_fields_tiled_backward_workspace_bytes": "z iiiii",
+    # cost, goal, passable, B, H, W, neighbor_mask, tau, horizon, dist_out, policy_out, status_out, tape, tape_bytes, checkpoint_every, workspace,
+    # workspace_bytes, stream
+    "nastar_soft_cost_to_go_tiled": "i pppiiiudippppzipzp",
+    # ... workspace_bytes, sweeps_per_launch, stream
+    "nastar_soft_cost_to_go_tiled_with_sweeps": "i pppiiiudippppzipzip",
+    # cost, goal, passable, tape, tape_bytes, checkpoint_every, grad_dist, B, H, W, neighbor_mask, tau, horizon, grad_cost_out, status_out,
+    # workspace, workspace_bytes, stream
+    "nastar_soft_fields_backward_tiled": "i ppppzipiiiudipppzp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -417,6 +436,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, PATH_MASK_TILED_SIGNATURES, PATH_MASK_TILED_SIGNATURES)
     if hasattr(lib, "nastar_soft_fields_abi"):  # (and the thirteenth)
         _bind(lib, SOFT_FIELD_SIGNATURES, SOFT_FIELD_SIGNATURES)
+    if hasattr(lib, "nastar_soft_fields_tiled_abi"):  # (and the fourteenth)
+        _bind(lib, SOFT_FIELD_TILED_SIGNATURES, SOFT_FIELD_TILED_SIGNATURES)
     _lib = lib
     return lib
 

@@ -6,6 +6,7 @@ the hand-written HIP kernel.  There is no CPU path: CPU tensors raise.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import NamedTuple, Optional, Tuple
 
@@ -22,7 +23,8 @@ __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay",
            "shortest_paths", "PathOutput", "path_masks", "path_masks_backward", "PATH_MASKS_MAX_CELLS",
            "shortest_paths_tiled", "path_masks_tiled", "path_masks_tiled_backward", "PATH_MASKS_TILED_MAX_CELLS",
            "soft_cost_to_go", "SoftFieldOutput", "maxent_path_nll", "soft_fields_forward", "soft_fields_backward", "SOFT_FIELDS_MAX_CELLS",
-           "SOFT_FIELDS_GRAD_MAX_CELLS"]
+           "SOFT_FIELDS_GRAD_MAX_CELLS", "soft_cost_to_go_tiled", "maxent_path_nll_tiled", "soft_fields_tiled_forward",
+           "soft_fields_tiled_backward", "SOFT_FIELDS_TILED_MAX_CELLS"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -1639,7 +1641,7 @@ def soft_fields_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstac
     limit = SOFT_FIELDS_GRAD_MAX_CELLS if tape else SOFT_FIELDS_MAX_CELLS
     if H * W > limit:
         raise NotImplementedError(f"soft_cost_to_go: maps of {H}x{W} = {H * W} cells exceed the limit of {limit} cells"
-                                  f"{' of its backward' if tape else ''} (one workgroup keeps one map in LDS; there is no tiled soft field)")
+                                  f"{' of its backward' if tape else ''} (one workgroup keeps one map in LDS; larger maps: soft_cost_to_go_tiled)")
     dev = _field_device(maps)
     lib = _field_lib("nastar_soft_cost_to_go", "nastar_soft_fields.h")
     with torch.no_grad():
@@ -1712,7 +1714,7 @@ def soft_cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_
     t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
     if differentiable and H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
         raise NotImplementedError(f"soft_cost_to_go: differentiable=True takes maps of at most {SOFT_FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = "
-                                  f"{H * W} (there is no tiled soft field)")
+                                  f"{H * W} (larger maps: soft_cost_to_go_tiled(..., differentiable=True))")
     taped: dict = {}  # what the backward needs beside _FieldNode's saved tensors: the tape and the costs; lives as long as the graph does
     want_tape = differentiable and cost_maps.requires_grad and torch.is_grad_enabled()  # (asked here: inside the node grad mode is off)
 
@@ -1739,6 +1741,11 @@ def maxent_path_nll(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps
     mask of the demonstrated route (start and goal included), both of the maps' shape.  Reads the field at the starts once (a host
     synchronisation): a start whose V_K is +inf -- no goal within ``horizon`` moves, or none at all -- raises ValueError naming the maps."""
     out = soft_cost_to_go(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies=False, differentiable=True)
+    return _nll_of_field(out, cost_maps, start_maps, goal_maps, opt_trajs, tau, horizon)
+
+
+def _nll_of_field(out: SoftFieldOutput, cost_maps, start_maps, goal_maps, opt_trajs, tau, horizon) -> torch.Tensor:
+    """what ``maxent_path_nll`` and ``maxent_path_nll_tiled`` compose on top of their field node"""
     B, _, H, W = out.dists.shape
     for name, m in (("start_maps", start_maps), ("opt_trajs", opt_trajs)):
         if not torch.is_tensor(m) or m.ndim not in (3, 4) or (m.shape[0],) + tuple(m.shape[-2:]) != (B, H, W) or m.device != out.dists.device:
@@ -1752,3 +1759,137 @@ def maxent_path_nll(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps
     leaves = _maps3(opt_trajs).to(torch.float32) * (_maps3(goal_maps) == 0).to(torch.float32)
     demo = (_maps3(cost_maps) * leaves).sum((1, 2))
     return (demo - at_start) / _checked_tau(tau)
+
+
+# ---- include/nastar_soft_fields_tiled.h: the same field and gradient by tiled sweeps, with a checkpointed tape
+SOFT_FIELDS_TILED_MAX_CELLS = 1179648  # nastar_soft_fields_tiled_max_cells(): 1024 x 1152, every map size the search takes
+
+
+def _checked_checkpoint_every(checkpoint_every, K: int) -> int:
+    if checkpoint_every is None:
+        return max(1, math.isqrt(K - 1) + 1)  # ceil(sqrt(K)): about 2 sqrt(K) planes per map instead of K, for one more forward
+    if isinstance(checkpoint_every, bool) or not isinstance(checkpoint_every, int) or not 1 <= checkpoint_every < 2 ** 31:
+        raise ValueError(f"checkpoint_every must be a positive int or None (= ceil(sqrt(horizon))), got {checkpoint_every!r}")
+    return checkpoint_every
+
+
+def _soft_tiled_limit(H: int, W: int, what: str) -> None:
+    if H * W > SOFT_FIELDS_TILED_MAX_CELLS:
+        raise NotImplementedError(f"{what}: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_FIELDS_TILED_MAX_CELLS} cells")
+
+
+def soft_fields_tiled_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
+                              horizon: Optional[int] = None, neighbor_mask: Optional[int] = None, policies: bool = False, tape: bool = False,
+                              checkpoint_every: Optional[int] = None, sweeps_per_launch: Optional[int] = None):
+    """``nastar_soft_cost_to_go_tiled`` as it is (include/nastar_soft_fields_tiled.h) -> ``(SoftFieldOutput, tape)``: one prepare launch and
+    ceil(horizon / S) sweep launches on the current stream, nothing is read back, detached outputs.  ``tape=True`` allocates the tape of
+    ``nastar_soft_fields_tiled_tape_bytes`` bytes (the planes at the multiples of ``checkpoint_every`` and plane K; None = ceil(sqrt(K)))
+    and returns it as a uint8 tensor; None otherwise.  ``sweeps_per_launch``: 1 .. S instead of S, the same bits in more launches (probes
+    and tests only).  What ``soft_cost_to_go_tiled`` runs."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    c = _checked_checkpoint_every(checkpoint_every, K)
+    if sweeps_per_launch is not None and (isinstance(sweeps_per_launch, bool) or not isinstance(sweeps_per_launch, int) or sweeps_per_launch < 1):
+        raise ValueError(f"sweeps_per_launch must be a positive int or None, got {sweeps_per_launch!r}")
+    _soft_tiled_limit(H, W, "soft_cost_to_go_tiled")
+    dev = _field_device(maps)
+    lib = _field_lib("nastar_soft_cost_to_go_tiled", "nastar_soft_fields_tiled.h")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        tape_bytes = int(lib.nastar_soft_fields_tiled_tape_bytes(B, H, W, K, c)) if tape else 0
+        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
+        ws_bytes = int(lib.nastar_soft_fields_tiled_workspace_bytes(B, H, W))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(),
+                pol.data_ptr() if pol is not None else None, status.data_ptr(), buf.data_ptr() if buf is not None else None, tape_bytes, c,
+                ws.data_ptr(), ws_bytes)
+        with torch.cuda.device(dev):
+            if sweeps_per_launch is None:
+                rc = lib.nastar_soft_cost_to_go_tiled(*args, _stream_ptr(dev))
+            else:
+                rc = lib.nastar_soft_cost_to_go_tiled_with_sweeps(*args, sweeps_per_launch, _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_cost_to_go_tiled")
+    return SoftFieldOutput(dists, pol, status), buf
+
+
+def soft_fields_tiled_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
+                               grad_dists: torch.Tensor, tau: float, horizon: Optional[int] = None, neighbor_mask: Optional[int] = None,
+                               checkpoint_every: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``nastar_soft_fields_backward_tiled`` as it is: the maps, ``tau``, ``horizon``, mask and ``checkpoint_every`` of the
+    ``soft_fields_tiled_forward(..., tape=True)`` call that wrote ``tape``, and an upstream gradient of ``dists``' shape ->
+    ``(grad_cost [B,H,W], status [B] int32)``.  One launch per step and the recomputation of every segment on the current stream, nothing
+    is read back.  ``grad_dists`` is read on the cells live at the horizon only; ``grad_cost`` is exactly 0 on a cell that was never
+    live.  What the backward of ``soft_cost_to_go_tiled(..., differentiable=True)`` runs."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    c = _checked_checkpoint_every(checkpoint_every, K)
+    _check_grad_dists(grad_dists, B, H, W)
+    _soft_tiled_limit(H, W, "soft_fields_tiled_backward")
+    dev = _grad_device(maps, grad_dists)
+    lib = _field_lib("nastar_soft_fields_backward_tiled", "nastar_soft_fields_tiled.h")
+    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
+        raise ValueError(f"tape must be the contiguous uint8 tensor soft_fields_tiled_forward(..., tape=True) returned, on {dev}")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        up = grad_dists.detach().reshape(B, H, W).contiguous()
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        ws_bytes = int(lib.nastar_soft_fields_tiled_backward_workspace_bytes(B, H, W, K, c))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_soft_fields_backward_tiled(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(), c,
+                                                       up.data_ptr(), B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                                       ws_bytes, _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_fields_backward_tiled")
+    return grad, status
+
+
+def soft_cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
+                          horizon: Optional[int] = None, neighbor_mask: Optional[int] = None, policies: bool = False,
+                          differentiable: bool = False, checkpoint_every: Optional[int] = None) -> SoftFieldOutput:
+    """``soft_cost_to_go`` for maps of up to ``SOFT_FIELDS_TILED_MAX_CELLS`` cells (1024x1152: every map size the search takes), by tiled
+    sweeps (include/nastar_soft_fields_tiled.h) -> ``SoftFieldOutput``.  The same definition and, on the maps both take, the same bits in
+    ``dists``, ``policies``, ``status`` and the gradient; the planes live in device memory, a launch runs several sweeps on every tile of
+    every map, and ceil(horizon / S) + 1 launches are enqueued on the current stream.  The per-map status is read before returning as
+    ``soft_cost_to_go`` reads it (not inside a stream capture), with the same ValueError for a NaN or a negative cost.
+
+    ``differentiable=True``: the launches also keep a CHECKPOINTED tape -- the planes at the multiples of ``checkpoint_every`` and the
+    last one -- and ``dists`` carries an autograd node when ``cost_maps`` requires a gradient and grad mode is on.  The backward rebuilds
+    each segment of planes from its checkpoint (the forward is a pure function: the same bits) and walks it back, one launch per step,
+    reading nothing back.  ``checkpoint_every=None`` is ceil(sqrt(horizon)): about 2 sqrt(horizon) planes per map instead of ``horizon``,
+    for one more forward; ``checkpoint_every=1`` keeps every plane, for the caller who has the memory.  The gradient does not depend on
+    it."""
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
+    c = _checked_checkpoint_every(checkpoint_every, K)
+    _soft_tiled_limit(H, W, "soft_cost_to_go_tiled")
+    taped: dict = {}  # what the backward needs beside _FieldNode's saved tensors: the tape and the costs; lives as long as the graph does
+    want_tape = differentiable and cost_maps.requires_grad and torch.is_grad_enabled()  # (asked here: inside the node grad mode is off)
+
+    def field(cm, g, o):
+        out, taped["tape"] = soft_fields_tiled_forward(cm, g, o, t, K, mask, policies, tape=want_tape, checkpoint_every=c)
+        taped["cost"] = cm.detach()
+        if not torch.cuda.is_current_stream_capturing():
+            _raise_bad_cost(out.status.cpu(), B, "soft_cost_to_go_tiled")
+        return out
+
+    if not differentiable:
+        return field(cost_maps, goal_maps, obstacles_maps)
+    return SoftFieldOutput(*_differentiable_field(cost_maps, goal_maps, obstacles_maps, field,
+                                                  lambda d, g, o, up: soft_fields_tiled_backward(taped["cost"], g, o, taped["tape"], up, t, K, mask, c)[0]))
+
+
+def maxent_path_nll_tiled(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                          opt_trajs: torch.Tensor, tau: float, horizon: Optional[int] = None, neighbor_mask: Optional[int] = None,
+                          checkpoint_every: Optional[int] = None) -> torch.Tensor:
+    """``maxent_path_nll`` composed on ``soft_cost_to_go_tiled(..., differentiable=True, checkpoint_every=checkpoint_every)``: the same
+    loss and gradient for maps of up to ``SOFT_FIELDS_TILED_MAX_CELLS`` cells.  What the planners' ``maxent_path_nll(..., tiled=True)``
+    calls."""
+    out = soft_cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies=False, differentiable=True,
+                                checkpoint_every=checkpoint_every)
+    return _nll_of_field(out, cost_maps, start_maps, goal_maps, opt_trajs, tau, horizon)

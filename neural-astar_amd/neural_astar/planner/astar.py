@@ -105,6 +105,17 @@ class VanillaAstar(nn.Module):
         ``map_designs``.  ``differentiable=True``: ``dists`` carries the gradient to ``map_designs`` as the cost (not as the obstacles)."""
         return self.astar.soft_cost_to_go(map_designs, goal_maps, map_designs, tau, horizon, policies, differentiable)
 
+    def soft_cost_to_go_tiled(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                              policies: bool = False, differentiable: bool = False, checkpoint_every: Optional[int] = None):
+        """``soft_cost_to_go`` by tiled sweeps (``DifferentiableAstar.soft_cost_to_go_tiled``: maps of up to 1024x1152, the same bits)."""
+        return self.astar.soft_cost_to_go_tiled(map_designs, goal_maps, map_designs, tau, horizon, policies, differentiable, checkpoint_every)
+
+    def maxent_path_nll(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, opt_trajs: torch.Tensor, tau: float,
+                        horizon: Optional[int] = None, tiled: bool = False, checkpoint_every: Optional[int] = None) -> torch.Tensor:
+        """The maximum-entropy negative log-likelihood [B] of the demonstrations ``opt_trajs`` (``DifferentiableAstar.maxent_path_nll``)
+        with cost = passable = ``map_designs``; ``tiled=True`` for maps of up to 1024x1152."""
+        return self.astar.maxent_path_nll(map_designs, start_maps, goal_maps, map_designs, opt_trajs, tau, horizon, tiled, checkpoint_every)
+
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
                   paths: bool = False) -> FieldRoutesOutput:
         """The ordered optimal route from each of S start cells per map (``DifferentiableAstar.plan_many``: one field per map, a chase per
@@ -327,15 +338,28 @@ class NeuralAstar(VanillaAstar):
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.astar.soft_cost_to_go(cost_maps, goal_maps, obstacles_maps, tau, horizon, policies, differentiable)
 
+    def soft_cost_to_go_tiled(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, tau: float,
+                              horizon: Optional[int] = None, policies: bool = False, differentiable: bool = False,
+                              checkpoint_every: Optional[int] = None):
+        """``soft_cost_to_go`` of the PREDICTED cost maps by tiled sweeps (``DifferentiableAstar.soft_cost_to_go_tiled``: maps of up to
+        1024x1152, the same bits)."""
+        ops._checked_tau(tau)  # (before the encoder launches anything)
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        if not differentiable:
+            cost_maps = cost_maps.detach()
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.soft_cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, policies, differentiable, checkpoint_every)
+
     def maxent_path_nll(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, opt_trajs: torch.Tensor,
-                        tau: float, horizon: Optional[int] = None) -> torch.Tensor:
+                        tau: float, horizon: Optional[int] = None, tiled: bool = False, checkpoint_every: Optional[int] = None) -> torch.Tensor:
         """The maximum-entropy IRL loss of the demonstrations ``opt_trajs`` under the PREDICTED cost maps -> [B]
         (``ops.maxent_path_nll``): encodes as ``forward()`` does, NOT detached, so ``.sum().backward()`` trains the encoder with the
-        gradient (demonstration - expected visits) / tau; ``learn_obstacles`` makes every cell passable."""
+        gradient (demonstration - expected visits) / tau; ``learn_obstacles`` makes every cell passable.  ``tiled=True``: on the tiled
+        field (maps of up to 1024x1152), with its ``checkpoint_every``."""
         ops._checked_tau(tau)  # (before the encoder launches anything)
         cost_maps = self.encode(map_designs, start_maps, goal_maps)
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
-        return self.astar.maxent_path_nll(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon)
+        return self.astar.maxent_path_nll(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon, tiled, checkpoint_every)
 
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
                   paths: bool = False) -> FieldRoutesOutput:

@@ -661,11 +661,27 @@ class DifferentiableAstar(nn.Module):
         return ops.soft_cost_to_go(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask=self.neighbor_mask(), policies=policies,
                                    differentiable=differentiable)
 
+    def soft_cost_to_go_tiled(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
+                              horizon: Optional[int] = None, policies: bool = False, differentiable: bool = False,
+                              checkpoint_every: Optional[int] = None) -> "ops.SoftFieldOutput":
+        """``soft_cost_to_go`` by tiled sweeps (``ops.soft_cost_to_go_tiled``, the kernels of include/nastar_soft_fields_tiled.h): maps of
+        up to 1024x1152, the same bits where both apply.  ``checkpoint_every``: the spacing of the planes the differentiable call keeps
+        (None = ceil(sqrt(horizon)); 1 = every plane)."""
+        return ops.soft_cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask=self.neighbor_mask(), policies=policies,
+                                         differentiable=differentiable, checkpoint_every=checkpoint_every)
+
     def maxent_path_nll(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
-                        opt_trajs: torch.Tensor, tau: float, horizon: Optional[int] = None) -> torch.Tensor:
+                        opt_trajs: torch.Tensor, tau: float, horizon: Optional[int] = None, tiled: bool = False,
+                        checkpoint_every: Optional[int] = None) -> torch.Tensor:
         """The negative log-likelihood [B] of the demonstrations ``opt_trajs`` under the maximum-entropy route distribution of
-        ``cost_maps`` (``ops.maxent_path_nll``), under this module's own move set."""
-        return ops.maxent_path_nll(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon, neighbor_mask=self.neighbor_mask())
+        ``cost_maps`` (``ops.maxent_path_nll``), under this module's own move set.  ``tiled=True``: on the tiled field
+        (``ops.maxent_path_nll_tiled``: maps of up to 1024x1152), with its ``checkpoint_every``."""
+        if not tiled:
+            if checkpoint_every is not None:
+                raise ValueError("checkpoint_every belongs to tiled=True: the one-workgroup field keeps every plane")
+            return ops.maxent_path_nll(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon, neighbor_mask=self.neighbor_mask())
+        return ops.maxent_path_nll_tiled(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon,
+                                         neighbor_mask=self.neighbor_mask(), checkpoint_every=checkpoint_every)
 
     def plan_many(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
                   max_route_len: Optional[int] = None, paths: bool = False) -> FieldRoutesOutput:
