@@ -18,10 +18,15 @@
 // a barrier behind each: every n writes P(n) = A_k(n) / S_k(n) and M_k(n); every m gathers, in the row-major order of kChildOffsets, adds the
 // result to its fp64 sum and fetches its value of the next plane from the tape.  LDS per cell: the fp64 sum, A, P, M, the plane, and one byte
 // that says "passable and no goal".  No floating-point atomics.
+//
+// Both kernels are thin wrappers of a body (sfl_forward, sfl_backward) with a compile-time switch: nastar_soft_policy.hip.h instantiates the
+// other side of it, the log-policy and its adjoint.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/nastar_soft_fields.h"
 #include "nastar_field_rules.hip.h"
@@ -50,7 +55,7 @@ struct SoftFieldGradArgs {
     const float* goal;
     const float* passable;
     const float* tape;      // [B,horizon,HW]
-    const float* grad_dist;
+    const float* grad_dist; // [B,HW] (sfl_backward<T, true>: or nullptr = zeros)
     float* grad_cost;       // [B,HW]
     int32_t* status;        // [B]
     int H, W, horizon;
@@ -105,8 +110,10 @@ __device__ __forceinline__ void sfl_cells(int HW, int W, F&& f)
     }
 }
 
-template <int T>
-__global__ __launch_bounds__(T) void nastar_soft_cost_to_go_kernel(const SoftFieldArgs a)
+// THE FORWARD of one map.  LOGP: the epilogue also writes the log-policy of include/nastar_soft_policy.h to log_policy [B,8,HW], from the M, S
+// and plane K-1 the policy is formed from (nastar_soft_policy.hip.h); everything else is the same statements, so the same bits.
+template <int T, bool LOGP>
+__device__ __forceinline__ void sfl_forward(const SoftFieldArgs& a, float* log_policy)
 {
     extern __shared__ __attribute__((aligned(16))) char sfl_smem[];
     const int H = a.H, W = a.W, HW = H * W, K = a.horizon;
@@ -167,26 +174,50 @@ __global__ __launch_bounds__(T) void nastar_soft_cost_to_go_kernel(const SoftFie
     if (tid == 0) a.status[blockIdx.x] = map_bad ? NASTAR_ERR_BAD_COST : !map_goal ? NASTAR_ERR_UNSOLVABLE : NASTAR_OK;
     float* dist = a.dist + base;
     for (int i = tid; i < HW; i += T) dist[i] = map_bad ? INF : goal[i] != 0.f ? 0.f : prev[i] * a.from_units;
-    if (a.policy) {
-        float* pol = a.policy + base * 8;
+    if (LOGP || a.policy) {
+        float* pol = (!LOGP || a.policy) ? a.policy + base * 8 : nullptr;
+        float* lpol = LOGP ? log_policy + base * 8 : nullptr;
         sfl_cells<T>(HW, W, [&](int i, int r, int c) {
             const bool up = r > 0, dn = r < H - 1, lf = c > 0, rt = c < W - 1;
             const float* at = next + i;
             const SoftMin sm = sfl_softmin([&](int dy, int dx) { return at[dy * W + dx]; }, nm, up, dn, lf, rt);
             const float cc = C[i];
             const bool live = cc >= 0.f && cc < INF && sm.m < INF;
+            float log2s = 0.f;
+            if constexpr (LOGP) log2s = sfl_log2(sm.s);
             fld_each<8>([&](auto k) __attribute__((always_inline)) {
                 constexpr Move mv = kActionMoves[decltype(k)::value];
-                float w = 0.f;
-                if (live && (nm & fld_bit(mv.dy, mv.dx)) && fld_inside(mv.dy, mv.dx, up, dn, lf, rt)) w = sfl_exp2(sm.m - at[mv.dy * W + mv.dx]) / sm.s;
-                pol[(size_t) decltype(k)::value * HW + i] = w;
+                float w = 0.f, lw = -INF;
+                if (live && (nm & fld_bit(mv.dy, mv.dx)) && fld_inside(mv.dy, mv.dx, up, dn, lf, rt)) {
+                    w = sfl_exp2(sm.m - at[mv.dy * W + mv.dx]) / sm.s;
+                    // the minimum and the sum kept apart, as in w: -inf by itself for a target of +inf
+                    if constexpr (LOGP) lw = ((sm.m - at[mv.dy * W + mv.dx]) - log2s) * (float)M_LN2;
+                }
+                if (!LOGP || pol) pol[(size_t) decltype(k)::value * HW + i] = w;
+                if constexpr (LOGP) lpol[(size_t) decltype(k)::value * HW + i] = lw;
             });
         });
     }
 }
 
 template <int T>
-__global__ __launch_bounds__(T) void nastar_soft_fields_backward_kernel(const SoftFieldGradArgs a)
+__global__ __launch_bounds__(T) void nastar_soft_cost_to_go_kernel(const SoftFieldArgs a)
+{
+    sfl_forward<T, false>(a, nullptr);
+}
+
+// the second seed of the backward (include/nastar_soft_policy.h): the upstream gradient of the log-policy of ONE map, [8,HW], or nullptr
+struct SoftPolicySeed {
+    const float* grad_log_policy;
+    float neg_inv_tau;  // -1 / tau
+};
+
+// THE BACKWARD of one map.  POLICY: a.grad_dist may be nullptr (zeros), and a log-policy seed GL is INJECTED AT STEP K (nastar_soft_policy.hip.h):
+// A_{K-1} = the gather + Z.  Step K's first pass also leaves Q(n) = gsum(n) / S_K(n) and A_K(n) in the two halves of the cell's fp64 slot --
+// the sum is A_K alone until that step's gather has run, so the slot is free -- the gather adds GL(a,n) - exp2(M(n) - u) Q(n) over the
+// predecessors live at K, and a third pass makes the slot the sum again.  Without a seed every statement is the plain backward's: the same bits.
+template <int T, bool POLICY>
+__device__ __forceinline__ void sfl_backward(const SoftFieldGradArgs& a, const SoftPolicySeed seed)
 {
     extern __shared__ __attribute__((aligned(16))) char sfg_smem[];
     const int H = a.H, W = a.W, HW = H * W, K = a.horizon;
@@ -213,8 +244,8 @@ __global__ __launch_bounds__(T) void nastar_soft_fields_backward_kernel(const So
         const bool e = ok && a.goal[base + i] == 0.f;
         const bool live = e && tape[(size_t)(K - 1) * HW + i] < INF;
         float g = 0.f;
-        if (live) g = a.grad_dist[base + i];
-        elig[i] = e;
+        if (live && (!POLICY || a.grad_dist)) g = a.grad_dist[base + i];
+        elig[i] = POLICY ? e | (live ? 2 : 0) : e;  // (bit 1: live at K, what the injected step asks of a predecessor)
         A[i] = g;
         sum[i] = (double)g;
         U[i] = K >= 2 ? tape[(size_t)(K - 2) * HW + i] : INF;
@@ -223,41 +254,82 @@ __global__ __launch_bounds__(T) void nastar_soft_fields_backward_kernel(const So
     __syncthreads();
     const bool map_bad = flags[1] != 0;
 
-    // ---- steps k = K .. 2: U holds plane k - 1 ----------------------------------------------------------------------------------------------------
+    // ---- one step k: U holds plane k - 1; `inject` (a std::bool_constant) adds the log-policy seed, at step K only -----------------------------------
     const uint32_t nm = a.nmask;
-    for (int k = K; k >= 2; --k) {
+    const float* gl = seed.grad_log_policy;
+    float* slot = reinterpret_cast<float*>(sum);  // slot[2 i] = Q(i), slot[2 i + 1] = A_K(i) while the injected step runs
+    auto step = [&](int k, auto inject) __attribute__((always_inline)) {
+        constexpr bool kInject = decltype(inject)::value;
         sfl_cells<T>(HW, W, [&](int i, int r, int c) {
+            const bool up = r > 0, dn = r < H - 1, lf = c > 0, rt = c < W - 1;
             const float* at = U + i;
-            const SoftMin sm = sfl_softmin([&](int dy, int dx) { return at[dy * W + dx]; }, nm, r > 0, r < H - 1, c > 0, c < W - 1);
+            const SoftMin sm = sfl_softmin([&](int dy, int dx) { return at[dy * W + dx]; }, nm, up, dn, lf, rt);
             const bool any = sm.m < INF;  // (A is 0 on a cell that is not live at k, whatever its soft-min)
             P[i] = any ? A[i] / sm.s : 0.f;
             M[i] = any ? sm.m : -INF;     // exp2(-inf - u) = 0
+            if constexpr (kInject) {
+                float gsum = 0.f;
+                if (elig[i] & 2) {  // live at K: GL is read on Act(i) only, in the row-major order of the move offsets
+                    fld_each<8>([&](auto j) __attribute__((always_inline)) {
+                        constexpr Move o = kChildOffsets[decltype(j)::value];
+                        if ((nm & fld_bit(o.dy, o.dx)) && fld_inside(o.dy, o.dx, up, dn, lf, rt) && at[o.dy * W + o.dx] < INF)
+                            gsum += gl[(size_t)kOppositeAction[7 - decltype(j)::value] * HW + i];
+                    });
+                }
+                slot[2 * i] = gsum / sm.s;  // (S >= 1 on a live cell; what is not live is 0 / S or 0 / 0 and is never read)
+                slot[2 * i + 1] = A[i];
+            }
         });
         __syncthreads();
         const float* below = k > 2 ? tape + (size_t)(k - 3) * HW : nullptr;  // plane k - 2
         sfl_cells<T>(HW, W, [&](int i, int r, int c) {
             const bool up = r > 0, dn = r < H - 1, lf = c > 0, rt = c < W - 1;
             const float u = U[i];
-            float acc = 0.f;
+            float acc = 0.f, z = 0.f;
             // the predecessor at kChildOffsets[j] steps onto this cell by the opposite move
             fld_each<8>([&](auto j) __attribute__((always_inline)) {
                 constexpr Move o = kChildOffsets[decltype(j)::value];
                 if ((nm & fld_bit(-o.dy, -o.dx)) && fld_inside(o.dy, o.dx, up, dn, lf, rt)) {
                     const int n = i + o.dy * W + o.dx;
-                    acc += P[n] * sfl_exp2(M[n] - u);
+                    const float w = sfl_exp2(M[n] - u);
+                    acc += P[n] * w;
+                    if constexpr (kInject) {
+                        if ((elig[n] & 2) && u < INF) z += gl[(size_t)kOppositeAction[decltype(j)::value] * HW + n] - w * slot[2 * n];
+                    }
                 }
             });
-            const float v = (elig[i] && u < INF) ? acc : 0.f;
+            float v = acc;
+            if constexpr (kInject) v = acc + z * seed.neg_inv_tau;
+            v = (elig[i] && u < INF) ? v : 0.f;
             A[i] = v;
-            sum[i] += (double)v;
+            if constexpr (!kInject) sum[i] += (double)v;
             if (below) U[i] = below[i];
         });
         __syncthreads();
+        if constexpr (kInject) {  // the slot is the sum again: A_K + A_{K-1}, the two additions the plain step makes
+            for (int i = tid; i < HW; i += T) {
+                const float g = slot[2 * i + 1];
+                sum[i] = (double)g + (double)A[i];
+            }
+        }
+    };
+
+    // ---- steps k = K .. 2 -------------------------------------------------------------------------------------------------------------------------
+    int k = K;
+    if constexpr (POLICY) {
+        if (gl && k >= 2) step(k--, std::true_type{});
     }
+    for (; k >= 2; --k) step(k, std::false_type{});
 
     // ---- epilogue: one rounding per cell -----------------------------------------------------------------------------------------------------
     if (tid == 0) a.status[blockIdx.x] = map_bad ? NASTAR_ERR_BAD_COST : NASTAR_OK;
     for (int i = tid; i < HW; i += T) a.grad_cost[base + i] = map_bad ? 0.f : (float)sum[i];
+}
+
+template <int T>
+__global__ __launch_bounds__(T) void nastar_soft_fields_backward_kernel(const SoftFieldGradArgs a)
+{
+    sfl_backward<T, false>(a, SoftPolicySeed{nullptr, 0.f});
 }
 
 }  // namespace nastar

@@ -293,6 +293,16 @@ SOFT_FIELD_TILED_SIGNATURES = {
     "nastar_soft_fields_backward_tiled": "i ppppzipiiiudipppzp",
 }
 
+# the signatures of include/nastar_soft_policy.h (the fifteenth header: the log-policy of the thirteenth's field and the gradient through
+# it), same letter code; a table of its own (tests/test_soft_policy.py compares it with ITS header)
+SOFT_POLICY_SIGNATURES = {
+    "nastar_soft_policy_abi": "i ",
+    # cost, goal, passable, B, H, W, neighbor_mask, tau, horizon, dist_out, policy_out, log_policy_out, status_out, tape, tape_bytes, stream
+    "nastar_soft_policy_forward": "i pppiiiudipppppzp",
+    # cost, goal, passable, tape, tape_bytes, grad_dist, grad_log_policy, B, H, W, neighbor_mask, tau, horizon, grad_cost_out, status_out, stream
+    "nastar_soft_policy_backward": "i ppppzppiiiudippp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -438,6 +448,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, SOFT_FIELD_SIGNATURES, SOFT_FIELD_SIGNATURES)
     if hasattr(lib, "nastar_soft_fields_tiled_abi"):  # (and the fourteenth)
         _bind(lib, SOFT_FIELD_TILED_SIGNATURES, SOFT_FIELD_TILED_SIGNATURES)
+    if hasattr(lib, "nastar_soft_policy_abi"):  # (and the fifteenth)
+        _bind(lib, SOFT_POLICY_SIGNATURES, SOFT_POLICY_SIGNATURES)
     _lib = lib
     return lib
 

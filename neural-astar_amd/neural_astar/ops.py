@@ -24,7 +24,8 @@ __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay",
            "shortest_paths_tiled", "path_masks_tiled", "path_masks_tiled_backward", "PATH_MASKS_TILED_MAX_CELLS",
            "soft_cost_to_go", "SoftFieldOutput", "maxent_path_nll", "soft_fields_forward", "soft_fields_backward", "SOFT_FIELDS_MAX_CELLS",
            "SOFT_FIELDS_GRAD_MAX_CELLS", "soft_cost_to_go_tiled", "maxent_path_nll_tiled", "soft_fields_tiled_forward",
-           "soft_fields_tiled_backward", "SOFT_FIELDS_TILED_MAX_CELLS"]
+           "soft_fields_tiled_backward", "SOFT_FIELDS_TILED_MAX_CELLS",
+           "soft_policy", "SoftPolicyOutput", "soft_policy_nll", "soft_policy_forward", "soft_policy_backward"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -1893,3 +1894,175 @@ def maxent_path_nll_tiled(cost_maps: torch.Tensor, start_maps: torch.Tensor, goa
     out = soft_cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies=False, differentiable=True,
                                 checkpoint_every=checkpoint_every)
     return _nll_of_field(out, cost_maps, start_maps, goal_maps, opt_trajs, tau, horizon)
+
+
+# ---- include/nastar_soft_policy.h: the log-policy of the soft field and the gradient through it ---------------
+class SoftPolicyOutput(NamedTuple):
+    """What ``soft_policy()`` returns.  ``dists`` [B,1,H,W] fp32: the field of ``soft_cost_to_go``; ``log_policies`` [B,8,H,W] fp32: the log
+    of the soft policy of the last sweep (action k = ``utils.synthetic.ACTION_MOVES[k]``), -inf for a move the mask, the border or an
+    obstacle forbids or whose target has no goal within ``horizon`` - 1 moves, and for all eight actions of a goal, an obstacle and a cell
+    with an infinite ``dists``; ``policies`` [B,8,H,W] fp32: that policy itself, detached (0 where the log is -inf), or None; ``status``
+    [B] int32 as in ``SoftFieldOutput``."""
+
+    dists: torch.Tensor
+    log_policies: torch.Tensor
+    policies: Optional[torch.Tensor]
+    status: torch.Tensor
+
+
+def soft_policy_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                        neighbor_mask: Optional[int] = None, policies: bool = True, tape: bool = False):
+    """``nastar_soft_policy_forward`` as it is (include/nastar_soft_policy.h) -> ``(SoftPolicyOutput, tape)``: ``soft_fields_forward`` with
+    the log-policy beside its outputs -- one launch on the current stream, nothing is read back, detached outputs, the same bits in
+    ``dists``, ``policies``, ``status`` and the tape.  What ``soft_policy`` runs; probes and tests call it directly."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    limit = SOFT_FIELDS_GRAD_MAX_CELLS if tape else SOFT_FIELDS_MAX_CELLS
+    if H * W > limit:
+        raise NotImplementedError(f"soft_policy: maps of {H}x{W} = {H * W} cells exceed the limit of {limit} cells"
+                                  f"{' of its backward' if tape else ''} (one workgroup keeps one map in LDS)")
+    dev = _field_device(maps)
+    lib = _field_lib("nastar_soft_policy_forward", "nastar_soft_policy.h")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
+        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        tape_bytes = int(lib.nastar_soft_fields_tape_bytes(B, H, W, K)) if tape else 0
+        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
+        with torch.cuda.device(dev):
+            rc = lib.nastar_soft_policy_forward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(),
+                                                pol.data_ptr() if pol is not None else None, logp.data_ptr(), status.data_ptr(),
+                                                buf.data_ptr() if buf is not None else None, tape_bytes, _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_policy_forward")
+    return SoftPolicyOutput(dists, logp, pol, status), buf
+
+
+def soft_policy_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
+                         grad_dists: Optional[torch.Tensor], grad_log_policies: Optional[torch.Tensor], tau: float,
+                         horizon: Optional[int] = None, neighbor_mask: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``nastar_soft_policy_backward`` as it is: the maps, ``tau``, ``horizon`` and mask of the forward that wrote ``tape``
+    (``soft_policy_forward`` or ``soft_fields_forward``, ``tape=True``), an upstream gradient of ``dists`` and one of ``log_policies``
+    ([B,8,H,W]); either may be None (zeros) -> ``(grad_cost [B,H,W], status [B] int32)``.  One launch on the current stream, nothing is read
+    back.  ``grad_log_policies`` is read only where the log-policy is finite; with None for it the result is ``soft_fields_backward``'s, bit
+    for bit.  What the backward of ``soft_policy`` runs."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    if grad_dists is not None:
+        _check_grad_dists(grad_dists, B, H, W)
+    if grad_log_policies is not None and (not torch.is_tensor(grad_log_policies) or grad_log_policies.dtype != torch.float32
+                                          or tuple(grad_log_policies.shape) != (B, 8, H, W)):
+        raise ValueError(f"grad_log_policies must be a float32 tensor of the shape of log_policies ({B}, 8, {H}, {W}), got "
+                         f"{tuple(grad_log_policies.shape) if torch.is_tensor(grad_log_policies) else type(grad_log_policies).__name__}")
+    if H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
+        raise NotImplementedError(f"soft_policy_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_FIELDS_GRAD_MAX_CELLS} cells")
+    dev = _field_device(maps)
+    for name, g in (("grad_dists", grad_dists), ("grad_log_policies", grad_log_policies)):
+        if g is not None and g.device != dev:
+            raise ValueError(f"the maps live on {dev}, {name} on {g.device}: they must share a device")
+    lib = _field_lib("nastar_soft_policy_backward", "nastar_soft_policy.h")
+    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
+        raise ValueError(f"tape must be the contiguous uint8 tensor soft_policy_forward(..., tape=True) returned, on {dev}")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        up = grad_dists.detach().reshape(B, H, W).contiguous() if grad_dists is not None else None
+        upl = grad_log_policies.detach().contiguous() if grad_log_policies is not None else None
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_soft_policy_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(),
+                                                 up.data_ptr() if up is not None else None, upl.data_ptr() if upl is not None else None,
+                                                 B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr(), _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_policy_backward")
+    return grad, status
+
+
+class _SoftPolicyNode(torch.autograd.Function):
+    """``soft_policy_forward`` as ONE autograd node with two differentiable outputs, ``dists`` and ``log_policies``: its backward is one
+    launch of ``nastar_soft_policy_backward`` with whichever of the two upstream gradients arrived, and reads nothing back."""
+
+    @staticmethod
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, tau, horizon, mask):
+        out, tape = soft_policy_forward(cost_maps, goal_maps, obstacles_maps, tau, horizon, mask, policies=True, tape=True)
+        if not torch.cuda.is_current_stream_capturing():
+            _raise_bad_cost(out.status.cpu(), out.status.numel(), "soft_policy")
+        ctx.save_for_backward(cost_maps, goal_maps, obstacles_maps, tape)
+        ctx.call = (tau, horizon, mask)
+        ctx.mark_non_differentiable(out.policies, out.status)
+        ctx.set_materialize_grads(False)
+        return out.dists, out.log_policies, out.policies, out.status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_dists, g_logp, *unused):
+        if (g_dists is None and g_logp is None) or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        cost_maps, goal_maps, obstacles_maps, tape = ctx.saved_tensors
+        grad = soft_policy_backward(cost_maps, goal_maps, obstacles_maps, tape, g_dists, g_logp, *ctx.call)[0]
+        shape = tuple(cost_maps.shape)
+        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
+            full = grad.new_zeros(shape)
+            full[:, 0] = grad
+            grad = full
+        return (grad.reshape(shape), None, None, None, None, None)
+
+
+def soft_policy(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                neighbor_mask: Optional[int] = None) -> SoftPolicyOutput:
+    """The soft field of ``soft_cost_to_go`` together with the LOG of its soft policy, both differentiable (include/nastar_soft_policy.h)
+    -> ``SoftPolicyOutput``: ``log_policies[b, a, y, x]`` = -(V_{K-1}(target of a) - min) / tau - ln(S) with min and S the soft-min's
+    minimum and sum at (y, x), formed inside the kernel from the two kept apart -- finite where ``log(policies)`` has underflowed to -inf,
+    and free of the rounding of |V| that a log-probability rebuilt from ``dists`` carries.  The arguments are those of
+    ``soft_cost_to_go``; ``tau`` has no gradient.
+
+    When ``cost_maps`` requires a gradient and grad mode is on, ``dists`` and ``log_policies`` are the two outputs of ONE autograd node
+    (maps of at most ``SOFT_FIELDS_GRAD_MAX_CELLS`` cells, NotImplementedError above, before anything is launched; the launch also
+    writes the tape of ``soft_cost_to_go``): its backward is one launch on the current stream and reads nothing back.  The gradient of
+    ``log_policies`` is read only where they are finite, so a loss may leave anything -- a NaN too -- on the -inf entries' gradient; it
+    masks the -inf VALUES itself (``torch.where``, not a product).  Otherwise no graph is built and maps of up to
+    ``SOFT_FIELDS_MAX_CELLS`` cells are taken.  ``policies`` is detached either way.  The per-map status is read before returning as
+    ``soft_cost_to_go`` reads it (one host synchronisation; not inside a stream capture), with the same ValueError for a NaN or a
+    negative cost."""
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
+    if cost_maps.requires_grad and torch.is_grad_enabled():
+        if H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
+            raise NotImplementedError(f"soft_policy: a differentiable call takes maps of at most {SOFT_FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = "
+                                      f"{H * W}")
+        return SoftPolicyOutput(*_SoftPolicyNode.apply(cost_maps, goal_maps, obstacles_maps, t, K, mask))
+    out, _ = soft_policy_forward(cost_maps, goal_maps, obstacles_maps, t, K, mask, policies=True)
+    if not torch.cuda.is_current_stream_capturing():
+        _raise_bad_cost(out.status.cpu(), B, "soft_policy")
+    return out
+
+
+def soft_policy_nll(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, opt_policies: torch.Tensor, tau: float,
+                    horizon: Optional[int] = None, neighbor_mask: Optional[int] = None) -> torch.Tensor:
+    """The per-cell imitation loss of the soft policy of ``cost_maps`` against the demonstrated actions ``opt_policies`` -> [B]: per map the
+    mean over the counted cells of ``-sum over a of opt_policies[a, n] * log_policies[a, n]``, the cross-entropy the planning datasets'
+    ``opt_policies`` were made for.  ``opt_policies`` is [B,8,H,W] in the action order of ``policies`` / ``FieldOutput.policies`` / the
+    dataset (one-hot, or any non-negative weights).  A cell is counted when it is live at the horizon (passable, no goal, a finite
+    ``dists``) and its ``opt_policies`` row is not all zero; a map with no counted cell gives 0.  Composed in torch on the node of
+    ``soft_policy``: the gradient goes to ``cost_maps``.  Reads one flag back (a host synchronisation): a counted cell whose demonstrated
+    action has a log-probability of -inf -- a move the mask or an obstacle forbids, or onto a cell with no goal within ``horizon`` - 1
+    moves -- raises ValueError naming the maps."""
+    _, _, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    if not torch.is_tensor(opt_policies) or tuple(opt_policies.shape) != (B, 8, H, W) or opt_policies.device != cost_maps.device:
+        raise ValueError(f"opt_policies must be a [B,8,H,W] tensor for {B} maps of {H}x{W} on {cost_maps.device}, got "
+                         f"{(tuple(opt_policies.shape), str(opt_policies.device)) if torch.is_tensor(opt_policies) else type(opt_policies).__name__}")
+    out = soft_policy(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask)
+    logp = out.log_policies
+    weights = opt_policies.to(torch.float32)
+    shown = weights != 0
+    counted = torch.isfinite(logp.detach()).any(1) & shown.any(1)        # live at the horizon: some action has a finite log-probability
+    pick = shown & counted[:, None]
+    lost = torch.nonzero((pick & torch.isinf(logp.detach())).flatten(1).any(1)).flatten().tolist()
+    if lost:
+        raise ValueError(f"soft_policy_nll: a demonstrated action of map(s) {lost[:16]}{' ...' if len(lost) > 16 else ''} ({len(lost)} of {B}) has "
+                         f"probability 0 under the soft policy: the move is outside the mask or onto an obstacle, or its target has no goal within "
+                         f"horizon - 1 = {_checked_horizon(horizon, H, W) - 1} moves")
+    terms = weights * torch.where(pick, logp, torch.zeros_like(logp))     # (where, not a product: no 0 * -inf)
+    return -terms.sum((1, 2, 3)) / counted.sum((1, 2)).clamp(min=1).to(torch.float32)

@@ -116,6 +116,17 @@ class VanillaAstar(nn.Module):
         with cost = passable = ``map_designs``; ``tiled=True`` for maps of up to 1024x1152."""
         return self.astar.maxent_path_nll(map_designs, start_maps, goal_maps, map_designs, opt_trajs, tau, horizon, tiled, checkpoint_every)
 
+    def soft_policy(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, tau: float, horizon: Optional[int] = None):
+        """The soft field and the log of its soft policy (``DifferentiableAstar.soft_policy``) with cost = passable = ``map_designs``; both
+        carry the gradient to ``map_designs`` as the cost when it requires one."""
+        return self.astar.soft_policy(map_designs, goal_maps, map_designs, tau, horizon)
+
+    def policy_nll(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, opt_policies: torch.Tensor, tau: float,
+                   horizon: Optional[int] = None) -> torch.Tensor:
+        """The per-cell imitation loss [B] against the demonstrated actions ``opt_policies`` [B,8,H,W] (``DifferentiableAstar.policy_nll``)
+        with cost = passable = ``map_designs``."""
+        return self.astar.policy_nll(map_designs, goal_maps, map_designs, opt_policies, tau, horizon)
+
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
                   paths: bool = False) -> FieldRoutesOutput:
         """The ordered optimal route from each of S start cells per map (``DifferentiableAstar.plan_many``: one field per map, a chase per
@@ -360,6 +371,27 @@ class NeuralAstar(VanillaAstar):
         cost_maps = self.encode(map_designs, start_maps, goal_maps)
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.astar.maxent_path_nll(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon, tiled, checkpoint_every)
+
+    def soft_policy(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, tau: float,
+                    horizon: Optional[int] = None):
+        """The soft field of the PREDICTED cost maps and the log of its soft policy (``ops.soft_policy``): encodes as ``forward()`` does,
+        NOT detached, so a loss on ``dists`` or ``log_policies`` trains the encoder (no graph under ``torch.no_grad()``);
+        ``learn_obstacles`` makes every cell passable."""
+        ops._checked_tau(tau)  # (before the encoder launches anything)
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.soft_policy(cost_maps, goal_maps, obstacles_maps, tau, horizon)
+
+    def policy_nll(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, opt_policies: torch.Tensor,
+                   tau: float, horizon: Optional[int] = None) -> torch.Tensor:
+        """The per-cell imitation loss of the demonstrated actions ``opt_policies`` [B,8,H,W] under the PREDICTED cost maps -> [B]
+        (``ops.soft_policy_nll``): the cross-entropy between the soft policy and the optimal action of every cell, thousands of
+        supervised cells per map.  Encodes as ``forward()`` does, NOT detached, so ``.sum().backward()`` trains the encoder;
+        ``learn_obstacles`` makes every cell passable."""
+        ops._checked_tau(tau)  # (before the encoder launches anything)
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.policy_nll(cost_maps, goal_maps, obstacles_maps, opt_policies, tau, horizon)
 
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
                   paths: bool = False) -> FieldRoutesOutput:

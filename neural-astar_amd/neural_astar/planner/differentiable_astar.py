@@ -683,6 +683,18 @@ class DifferentiableAstar(nn.Module):
         return ops.maxent_path_nll_tiled(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon,
                                          neighbor_mask=self.neighbor_mask(), checkpoint_every=checkpoint_every)
 
+    def soft_policy(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
+                    horizon: Optional[int] = None) -> "ops.SoftPolicyOutput":
+        """The soft field together with the LOG of its soft policy, both differentiable with respect to ``cost_maps``
+        (``ops.soft_policy``, the kernels of include/nastar_soft_policy.h), under this module's own move set."""
+        return ops.soft_policy(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask=self.neighbor_mask())
+
+    def policy_nll(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, opt_policies: torch.Tensor,
+                   tau: float, horizon: Optional[int] = None) -> torch.Tensor:
+        """The per-cell imitation loss [B] of the soft policy of ``cost_maps`` against the demonstrated actions ``opt_policies``
+        [B,8,H,W] (``ops.soft_policy_nll``), under this module's own move set."""
+        return ops.soft_policy_nll(cost_maps, goal_maps, obstacles_maps, opt_policies, tau, horizon, neighbor_mask=self.neighbor_mask())
+
     def plan_many(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
                   max_route_len: Optional[int] = None, paths: bool = False) -> FieldRoutesOutput:
         """The ORDERED optimal route from each of S start cells per map to its nearest goal: ONE cost-to-go field per map
