@@ -1007,12 +1007,18 @@ def fields_backward(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
 class _FieldNode(torch.autograd.Function):
     """A field call as an autograd node, for ``cost_to_go`` and ``cost_to_go_tiled`` alike: ``field(cost, goal, obstacles) -> FieldOutput``
     is the evaluation call (status checks included), ``backward(dists, goal, obstacles, grad_dists) -> grad_cost [B,H,W]`` the raw
-    gradient call.  Only ``dists`` carries gradient, and only to ``cost``."""
+    gradient call.  Only ``dists`` carries gradient, and only to ``cost``.  ``taped`` (the soft fields): ``field`` returns ``(output,
+    tape)`` and the backward reads the costs again, so both are SAVED beside the other three -- ``cost_maps`` itself, not a copy, under
+    autograd's version check -- and the call is ``backward(dists, goal, obstacles, cost, tape, grad_dists)``."""
 
     @staticmethod
-    def forward(ctx, cost_maps, goal_maps, obstacles_maps, field, backward):
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, field, backward, taped):
         out = field(cost_maps, goal_maps, obstacles_maps)
-        ctx.save_for_backward(out.dists, goal_maps, obstacles_maps)
+        kept = ()
+        if taped:
+            out, tape = out
+            kept = (cost_maps, tape)
+        ctx.save_for_backward(out.dists, goal_maps, obstacles_maps, *kept)
         ctx.backward_call, ctx.cost_shape = backward, tuple(cost_maps.shape)
         rest = (out.status,) + (() if out.policies is None else (out.policies,))
         ctx.mark_non_differentiable(*rest)
@@ -1023,22 +1029,23 @@ class _FieldNode(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_dists, *unused):
         if g_dists is None or not ctx.needs_input_grad[0]:
-            return (None,) * 5
+            return (None,) * 6
         grad = ctx.backward_call(*ctx.saved_tensors, g_dists)
         shape = ctx.cost_shape
         if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
             full = grad.new_zeros(shape)
             full[:, 0] = grad
             grad = full
-        return (grad.reshape(shape), None, None, None, None)
+        return (grad.reshape(shape), None, None, None, None, None)
 
 
-def _differentiable_field(cost_maps, goal_maps, obstacles_maps, field, backward) -> FieldOutput:
+def _differentiable_field(cost_maps, goal_maps, obstacles_maps, field, backward, taped: bool = False) -> FieldOutput:
     """``field(...)``, with the node on ``dists`` when there is something to differentiate"""
     if cost_maps.requires_grad and torch.is_grad_enabled():
-        res = _FieldNode.apply(cost_maps, goal_maps, obstacles_maps, field, backward)
+        res = _FieldNode.apply(cost_maps, goal_maps, obstacles_maps, field, backward, taped)
         return FieldOutput(res[0], res[2] if len(res) > 2 else None, res[1])
-    return field(cost_maps, goal_maps, obstacles_maps)  # nothing to differentiate: the evaluation call, detached outputs
+    out = field(cost_maps, goal_maps, obstacles_maps)  # nothing to differentiate: the evaluation call, detached outputs
+    return out[0] if taped else out
 
 
 def _cost_to_go_differentiable(cost_maps, goal_maps, obstacles_maps, neighbor_mask, policies, sweeps_out) -> FieldOutput:
@@ -1716,20 +1723,18 @@ def soft_cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_
     if differentiable and H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
         raise NotImplementedError(f"soft_cost_to_go: differentiable=True takes maps of at most {SOFT_FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = "
                                   f"{H * W} (larger maps: soft_cost_to_go_tiled(..., differentiable=True))")
-    taped: dict = {}  # what the backward needs beside _FieldNode's saved tensors: the tape and the costs; lives as long as the graph does
     want_tape = differentiable and cost_maps.requires_grad and torch.is_grad_enabled()  # (asked here: inside the node grad mode is off)
 
-    def field(c, g, o):
-        out, taped["tape"] = soft_fields_forward(c, g, o, t, K, mask, policies, tape=want_tape)
-        taped["cost"] = c.detach()
+    def field(c, g, o):  # -> (output, tape): the node saves the tape and the costs it was made from (_FieldNode, ``taped``)
+        out, tape = soft_fields_forward(c, g, o, t, K, mask, policies, tape=want_tape)
         if not torch.cuda.is_current_stream_capturing():
             _raise_bad_cost(out.status.cpu(), B, "soft_cost_to_go")
-        return out
+        return out, tape
 
     if not differentiable:
-        return field(cost_maps, goal_maps, obstacles_maps)
+        return field(cost_maps, goal_maps, obstacles_maps)[0]
     return SoftFieldOutput(*_differentiable_field(cost_maps, goal_maps, obstacles_maps, field,
-                                                  lambda d, g, o, up: soft_fields_backward(taped["cost"], g, o, taped["tape"], up, t, K, mask)[0]))
+                                                  lambda d, g, o, c, tape, up: soft_fields_backward(c, g, o, tape, up, t, K, mask)[0], taped=True))
 
 
 def maxent_path_nll(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
@@ -1869,20 +1874,19 @@ def soft_cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obst
     t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
     c = _checked_checkpoint_every(checkpoint_every, K)
     _soft_tiled_limit(H, W, "soft_cost_to_go_tiled")
-    taped: dict = {}  # what the backward needs beside _FieldNode's saved tensors: the tape and the costs; lives as long as the graph does
     want_tape = differentiable and cost_maps.requires_grad and torch.is_grad_enabled()  # (asked here: inside the node grad mode is off)
 
-    def field(cm, g, o):
-        out, taped["tape"] = soft_fields_tiled_forward(cm, g, o, t, K, mask, policies, tape=want_tape, checkpoint_every=c)
-        taped["cost"] = cm.detach()
+    def field(cm, g, o):  # -> (output, tape): the node saves the tape and the costs it was made from (_FieldNode, ``taped``)
+        out, tape = soft_fields_tiled_forward(cm, g, o, t, K, mask, policies, tape=want_tape, checkpoint_every=c)
         if not torch.cuda.is_current_stream_capturing():
             _raise_bad_cost(out.status.cpu(), B, "soft_cost_to_go_tiled")
-        return out
+        return out, tape
 
     if not differentiable:
-        return field(cost_maps, goal_maps, obstacles_maps)
+        return field(cost_maps, goal_maps, obstacles_maps)[0]
     return SoftFieldOutput(*_differentiable_field(cost_maps, goal_maps, obstacles_maps, field,
-                                                  lambda d, g, o, up: soft_fields_tiled_backward(taped["cost"], g, o, taped["tape"], up, t, K, mask, c)[0]))
+                                                  lambda d, g, o, cm, tape, up: soft_fields_tiled_backward(cm, g, o, tape, up, t, K, mask, c)[0],
+                                                  taped=True))
 
 
 def maxent_path_nll_tiled(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
