@@ -28,6 +28,7 @@
 #include "../../include/nastar_sources.h"
 #include "../../include/nastar_levels.h"
 #include "nastar_search_kernels.hip.h"
+#include "nastar_ticket.hip.h"
 
 namespace nastar {
 
@@ -261,6 +262,11 @@ struct FwdLaunch {
     Neighbourhood nb = {};
     RouteOut route = {};  // routes_out, route_cap, route_len_out, route_cost_out of include/nastar_routes.h
     const int32_t* levels = nullptr;  // include/nastar_levels.h: the placement is ranked from these inside the launch (no order, no order_out)
+    // include/nastar_ticket.h: the word the search launch stores ticket_value to when it starts, and where forward_lds says that the kernel
+    // it launched carries the ticket (the first and the ranked compact kernel do; null for every other entry point)
+    unsigned long long* ticket_word = nullptr;
+    unsigned long long ticket_value = 0;
+    bool* ticket_carried = nullptr;
 
     // the group nastar_forward_ex adds to nastar_forward, for it and the entry points that extend it
     void set_ex(uint8_t* packed, const int32_t* order_in, int32_t* order_o, int32_t* status_summary, int32_t* completion_counter)
@@ -390,12 +396,15 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     // (longest first; the trailing counter cell is not used and stays 0)
     const bool rank_after = f.order_out && (long long)f.B > resident_capacity(kernel_lds);
     if (rank_after) c.order_out = nullptr;
+    unsigned long long* const tw = f.ticket_word;
+    const unsigned long long tv = f.ticket_value;
     if (f.levels) {  // (nastar_forward_levels checked the shape, the flags and the log: what is left is the alignment of the caller's pointers)
         if (!vec4 || !fast || !use_asm || unit) return NASTAR_ERR_UNSUPPORTED;
         const int* lv = f.levels;
-        rc = f.W == 32   ? launch(&nastar_forward_compact_ranked_kernel<true, 5, 5, 1, true, false, true>, f.B, lds, s, c, rcp, lv)
-             : f.W == 16 ? launch(&nastar_forward_compact_ranked_kernel<true, 4, 4, 1, true, false, true>, f.B, lds, s, c, rcp, lv)
-                         : launch(&nastar_forward_compact_ranked_kernel<true, 6, 6, 4, true, false, true>, f.B, lds, s, c, rcp, lv);
+        rc = f.W == 32   ? launch(&nastar_forward_compact_ranked_kernel<true, 5, 5, 1, true, false, true>, f.B, lds, s, c, rcp, lv, tw, tv)
+             : f.W == 16 ? launch(&nastar_forward_compact_ranked_kernel<true, 4, 4, 1, true, false, true>, f.B, lds, s, c, rcp, lv, tw, tv)
+                         : launch(&nastar_forward_compact_ranked_kernel<true, 6, 6, 4, true, false, true>, f.B, lds, s, c, rcp, lv, tw, tv);
+        if (rc == NASTAR_OK && f.ticket_carried) *f.ticket_carried = true;  // (a launch that was accepted: only that one will store the ticket)
     } else
     if (unit) rc = forward_unit(c, marks_out, kernel_lds, rcp, s);
     else if (f.nb.multi) rc = with_bools([&](auto heur, auto lg) {  // (always masked: Moore-8 is a mask like any other here)
@@ -405,7 +414,11 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
         const auto kern = compact_kernel<(heur ? 2 : masked ? 1 : 0), lg>(c.d, vec4, fast, use_asm);
         if constexpr (heur) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask, f.nb.h0);
         else if constexpr (masked) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask);
-        else return launch(kern, f.B, lds, s, c, rcp);
+        else {
+            const int lrc = launch(kern, f.B, lds, s, c, rcp, tw, tv);
+            if (lrc == NASTAR_OK && f.ticket_carried) *f.ticket_carried = true;
+            return lrc;
+        }
     }, f.nb.masked, f.nb.h0 != nullptr, f.sel_log_out != nullptr);
     return (rc == NASTAR_OK && rank_after) ? nastar_placement_from_levels(f.iters_out, f.B, f.order_out, f.stream) : rc;
 }
@@ -975,7 +988,7 @@ int nastar_debug_occupancy(int H, int W, int* lds_bytes_out)
     const size_t lds = compact_lds_bytes(d.HWp, d.NCp);
     if (lds_bytes_out) *lds_bytes_out = (int)lds;
     if (lds > kMaxLdsBytes) return 0;
-    void (*kern)(const FwdCArgs, const float) = &nastar_forward_compact_kernel<true, 0, 0, 0, false, false>;
+    void (*kern)(const FwdCArgs, const float, unsigned long long*, const unsigned long long) = &nastar_forward_compact_kernel<true, 0, 0, 0, false, false>;
     if (H == 32 && W == 32) kern = &nastar_forward_compact_kernel<true, 5, 5, 1, true, false>;
     if (H == 64 && W == 64) kern = &nastar_forward_compact_kernel<true, 6, 6, 4, true, false>;
     if (ensure_lds(kern, lds)) return -1;
@@ -996,3 +1009,24 @@ int nastar_heuristic(const float* goal, int B, int H, int W, float* h0_out, void
 }
 
 }  // extern "C"
+
+// ---- csrc/nastar_ticket.hip.h: the search launch of include/nastar_ticket.h (its entry point is in nastar_verdict_capi.hip) -----------------
+bool nastar::search_carries_ticket(int H, int W, int flags)
+{
+    return H > 0 && W > 0 && (long long)H * W <= kMaxGlobalCells && !needs_global_state(H, W) && !(flags & NASTAR_FLAG_UNIT_COST);
+}
+
+int nastar::forward_ticketed(const TicketedSearch& t, bool* carried)
+{
+    *carried = false;
+    if (t.levels && !levels_in_launch(t.H, t.W, t.flags, t.sel_log_out != nullptr)) return NASTAR_ERR_UNSUPPORTED;  // (as nastar_forward_levels)
+    FwdLaunch f{t.cost, t.start, t.goal, t.passable, t.B, t.H, t.W, t.g_ratio, t.max_iters, t.histories_out, t.paths_out, t.sel_log_out, t.iters_out,
+                t.status_out, t.workspace, t.workspace_bytes, t.flags, t.stream};
+    if (t.levels) f.set_ex(t.packed_out, nullptr, nullptr, t.status_summary, t.completion_counter);
+    else f.set_ex(t.packed_out, t.order, t.order_out, t.status_summary, t.completion_counter);
+    f.levels = t.levels;
+    f.ticket_word = t.ticket_word;
+    f.ticket_value = t.ticket_value;
+    f.ticket_carried = carried;
+    return forward(f);
+}

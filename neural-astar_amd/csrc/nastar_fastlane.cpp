@@ -6,7 +6,7 @@
 // data_ptr(), one 23-argument ctypes call, the status-board bookkeeping).  This file is that host work in C++, behind the SAME C ABI:
 //
 //   search(fn, cost, start, goal, passable | None, g_ratio, max_iters, want_log, flags, order | None, order_out | None, ws_bytes,
-//          summary_host, counter_dev, stream, spin_us, levels | None, sort_fn, packed | None, levels_fn, proof_fn, proof_word, proof_counter)
+//          summary_host, counter_dev, stream, spin_us, levels | None, sort_fn, packed | None, levels_fn, proof_fn, proof_word, proof_counter, proved_fn)
 //     0. (a batch that carries its loader's levels instead of an order: `levels_fn` != 0 -- the address of nastar_forward_levels,
 //        include/nastar_levels.h, given when nastar_levels_in_launch says so -- replaces `fn` and the search launch ranks the levels itself;
 //        otherwise nastar_placement_from_levels is launched in front of the search)
@@ -28,6 +28,10 @@
 //        retires it); NASTAR_PROOF_SOME goes on polling the search's flag as before.  The call never returns verdict >= 0 while the proof may
 //        still read the inputs.  The tuple's last element says what happened: 0 = no proof launched, 1 = proved (early return), 2 = proof
 //        over, not all maps proved, 3 = launched but its word was not seen within the spin budget (the caller waits for the side stream).
+//        `proved_fn` != 0 (the address of nastar_forward_proved, include/nastar_ticket.h): ONE call issues both launches in place of the
+//        proof_fn + fn / levels_fn pair -- the search first, the proof ordered behind that launch's own start (a ticket) instead of an event
+//        in front of it, so the caller's stream holds no marker between two searches.  Same conditions, same codes; a call whose search
+//        launch fails reports that rc and has no proof pending.
 // The torch.library custom ops stay for autograd / torch.compile / fake tensors (neural_astar/ops.py); this is the lane a no-grad call takes.
 #include <torch/extension.h>
 
@@ -44,6 +48,10 @@ using fwd_ex_t = int (*)(const float*, const float*, const float*, const float*,
 using fwd_levels_t = int (*)(const float*, const float*, const float*, const float*, int, int, int, double, int, float*, int64_t*, int32_t*, int32_t*,
                              int32_t*, uint8_t*, void*, size_t, int, const int32_t*, int32_t*, int32_t*, void*);  // nastar_forward_levels
 
+using proved_t = int (*)(const float*, const float*, const float*, const float*, int, int, int, double, int, float*, int64_t*, int32_t*, int32_t*,
+                         int32_t*, uint8_t*, void*, size_t, int, const int32_t*, int32_t*, int32_t*, int32_t*, const int32_t*, int32_t*, int32_t*, int32_t*,
+                         int*, void*);  // nastar_forward_proved
+
 using proof_t = int (*)(const float*, const float*, const float*, const float*, int, int, int, int32_t*, int32_t*, int32_t*, void*);  // nastar_solvable_proof
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -54,7 +62,7 @@ py::tuple search(uintptr_t fn, const at::Tensor& cost, const at::Tensor& start, 
                  double g_ratio, int64_t max_iters, bool want_log, int64_t flags, const c10::optional<at::Tensor>& order,
                  const c10::optional<at::Tensor>& order_out, int64_t ws_bytes, uintptr_t summary_host, uintptr_t counter_dev, uintptr_t stream,
                  int64_t spin_us, const c10::optional<at::Tensor>& levels, uintptr_t sort_fn, const c10::optional<at::Tensor>& packed,
-                 uintptr_t levels_fn, uintptr_t proof_fn, uintptr_t proof_word, uintptr_t proof_counter)
+                 uintptr_t levels_fn, uintptr_t proof_fn, uintptr_t proof_word, uintptr_t proof_counter, uintptr_t proved_fn)
 {
     const at::Tensor& pas = passable.has_value() ? *passable : cost;
     // anything the fast lane does not take goes back to the Python path, which raises the proper errors: rc = -1
@@ -115,12 +123,25 @@ py::tuple search(uintptr_t fn, const at::Tensor& cost, const at::Tensor& start, 
     // A refusal (an unsupported size, unaligned maps) simply leaves the call on the late verdict
     int proof = 0;
     volatile int32_t* pword = reinterpret_cast<volatile int32_t*>(proof_word);
-    if (proof_fn != 0 && pword != nullptr && proof_counter != 0 && summ != nullptr && counter_dev != 0 && spin_us > 0 && !want_log &&
+    const bool want_proof = proof_fn != 0 && pword != nullptr && proof_counter != 0 && summ != nullptr && counter_dev != 0 && spin_us > 0 && !want_log;
+    int rc;
+    if (want_proof && proved_fn != 0) {
+        // both launches from one native call: the search, then the proof behind the search launch's ticket (include/nastar_ticket.h)
+        int prc = -1;
+        rc = reinterpret_cast<proved_t>(proved_fn)(cost.data_ptr<float>(), start.data_ptr<float>(), goal.data_ptr<float>(), pas.data_ptr<float>(), (int)B, (int)H,
+                                                   (int)W, g_ratio, (int)max_iters, hist.data_ptr<float>(), paths.data_ptr<int64_t>(), nullptr, iters, status, pk,
+                                                   ws_bytes > 0 ? ws.data_ptr() : nullptr, (size_t)ws_bytes, (int)flags, op, oo,
+                                                   reinterpret_cast<int32_t*>(summary_host), reinterpret_cast<int32_t*>(counter_dev), in_launch, nullptr,
+                                                   reinterpret_cast<int32_t*>(proof_word), reinterpret_cast<int32_t*>(proof_counter), &prc,
+                                                   reinterpret_cast<void*>(stream));
+        if (prc == 0) proof = 3;
+    } else {
+    if (want_proof &&
         reinterpret_cast<proof_t>(proof_fn)(cost.data_ptr<float>(), start.data_ptr<float>(), goal.data_ptr<float>(), pas.data_ptr<float>(), (int)B, (int)H,
                                             (int)W, nullptr, reinterpret_cast<int32_t*>(proof_word), reinterpret_cast<int32_t*>(proof_counter),
                                             reinterpret_cast<void*>(stream)) == 0)
         proof = 3;
-    const int rc = in_launch != nullptr
+    rc = in_launch != nullptr
         ? reinterpret_cast<fwd_levels_t>(levels_fn)(cost.data_ptr<float>(), start.data_ptr<float>(), goal.data_ptr<float>(), pas.data_ptr<float>(), (int)B, (int)H,
                                                     (int)W, g_ratio, (int)max_iters, hist.data_ptr<float>(), paths.data_ptr<int64_t>(), nullptr, iters, status, pk,
                                                     ws_bytes > 0 ? ws.data_ptr() : nullptr, (size_t)ws_bytes, (int)flags, in_launch,
@@ -132,6 +153,7 @@ py::tuple search(uintptr_t fn, const at::Tensor& cost, const at::Tensor& start, 
                                                   ws_bytes > 0 ? ws.data_ptr() : nullptr, (size_t)ws_bytes, (int)flags, op, oo,
                                                   reinterpret_cast<int32_t*>(summary_host), summary_host ? reinterpret_cast<int32_t*>(counter_dev) : nullptr,
                                                   reinterpret_cast<void*>(stream));
+    }
     int verdict = -1;
     const bool flagged = rc == 0 && summ != nullptr && counter_dev != 0 && spin_us > 0;
     if (flagged || proof == 3) {
@@ -181,5 +203,6 @@ PYBIND11_MODULE(_nastar_fastlane, m)
     m.def("search", &search, py::arg("fn"), py::arg("cost"), py::arg("start"), py::arg("goal"), py::arg("passable"), py::arg("g_ratio"),
           py::arg("max_iters"), py::arg("want_log"), py::arg("flags"), py::arg("order"), py::arg("order_out"), py::arg("ws_bytes"),
           py::arg("summary_host"), py::arg("counter_dev"), py::arg("stream"), py::arg("spin_us"), py::arg("levels") = py::none(), py::arg("sort_fn") = 0,
-          py::arg("packed") = py::none(), py::arg("levels_fn") = 0, py::arg("proof_fn") = 0, py::arg("proof_word") = 0, py::arg("proof_counter") = 0);
+          py::arg("packed") = py::none(), py::arg("levels_fn") = 0, py::arg("proof_fn") = 0, py::arg("proof_word") = 0, py::arg("proof_counter") = 0,
+          py::arg("proved_fn") = 0);
 }

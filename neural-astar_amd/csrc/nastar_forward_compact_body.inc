@@ -9,9 +9,29 @@
 // map from the batch's levels (ranked_map, nastar_placement.hip.h) instead of an order array; everything behind that line is the first kernel's.
 // The hand-scheduled instantiations (kAsm: the first and the fifth kernel only) decide per map whether its cost word can hold the heuristic
 // instead (`stored_h`, nastar_search_asm5.hip.h); every such line sits behind `if constexpr (kAsm)` or folds away with kAsm, so the other
-// kernels keep their machine code (tools/compare_device_code.py).
+// kernels keep their machine code (tools/compare_device_code.py).  `constexpr bool kTicket` / `ticket_word`, `ticket_value` (the first and the
+// fifth kernel only; a constexpr null elsewhere): the launch announces its own start (include/nastar_ticket.h).
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // The launch announces that it has STARTED (include/nastar_ticket.h): it was dispatched behind a barrier, so everything queued on its stream
+    // before it is complete and the maps are final -- the store orders no data, hence relaxed; system scope because the command processor
+    // reads the word.  Before the first return, so that a wait for this ticket is always satisfied.  The ranked kernel stores first thing.
+    // The plain kernel stores BEHIND the reads of `order` / `order_bad`: a store ahead of them makes the compiler read both with vector
+    // loads instead of scalar ones and hold the kernel-argument loads back behind it -- a chain of dependent memory latencies ahead of
+    // the map load, 2.5 us on a launch with a lone wavefront per CU (measured: profiles/proof_ticket.json).  Without an order (the common
+    // call) nothing is read in front of the store.
+    if constexpr (kTicket && kRanked) {
+        if (ticket_word != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+            __hip_atomic_store(ticket_word, ticket_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     const int b = kRanked ? ranked_map(levels, a.B) : placed_map(a.order, a.order_bad, a.B);
+    if constexpr (kTicket && !kRanked) {
+        if (ticket_word != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+            __hip_atomic_store(ticket_word, ticket_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        // the 18 instructions above are 72 bytes; 14 more make it 128, so that every loop behind the prologue starts where it started without
+        // the ticket, modulo the 64-byte fetch line (the hand-scheduled step loops are 390 .. 480 bytes long: 8 bytes further on, some of
+        // them reach into one more line per trip, which a lone wavefront per CU does not hide -- measured: profiles/proof_ticket.json)
+        asm volatile("s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0");
+    }
     if ((unsigned)b >= (unsigned)a.B) return;  // not a permutation (and not checked: NASTAR_FLAG_CHECK_ORDER): never read or write outside the batch
     const bool lockstep = !kAsm && (a.flags & NASTAR_FLAG_LOCKSTEP);  // (forward_impl picks a compiled instantiation for it)
     if (lockstep && a.marks != nullptr && a.marks[b] == 0) return;    // not in the batch-coupled class: the early-exit launch's outputs stand

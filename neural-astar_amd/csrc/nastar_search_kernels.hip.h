@@ -99,10 +99,15 @@ __global__ __launch_bounds__(1024) void nastar_order_check_kernel(const int* __r
 // kAsm: the selection/expansion loop is a hand-scheduled instruction stream (nastar_search_asm4 / _asm3 / _asm.hip.h; 16x16, 32x32, 64x64)
 // kMasked: the neighbourhood is DifferentiableAstar.neighbor_filter (nmask, see neighbour_enabled) instead of the Moore-8 stencil; compiled
 // step loops only (kAsm = false).  Both kernels share one body, nastar_forward_compact_body.inc.
+// ticket_word / ticket_value (this kernel and the ranked one only: `constexpr bool kTicket`): the launch announces its own START -- workgroup 0
+// stores the value to the word before anything else (include/nastar_ticket.h: what the proof's side stream waits for instead of an event
+// in front of this launch).  Null for every entry point but nastar_forward_proved.  Kernel arguments of their own behind rcp_sqrtW, for the
+// reason given at `levels` below.
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, bool kAsm = false>
-__global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCArgs a, const float rcp_sqrtW)
+__global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCArgs a, const float rcp_sqrtW, unsigned long long* __restrict__ ticket_word,
+                                                                    const unsigned long long ticket_value)
 {
-    constexpr bool kMasked = false, kHeur = false, kMulti = false, kRanked = false;
+    constexpr bool kMasked = false, kHeur = false, kMulti = false, kRanked = false, kTicket = true;
     constexpr uint32_t nmask = NASTAR_NEIGHBORS_MOORE8;
     constexpr const float* h0 = nullptr;
     constexpr const int* levels = nullptr;
@@ -114,9 +119,10 @@ __global__ __launch_bounds__(64) void nastar_forward_compact_kernel(const FwdCAr
 // `levels` is a kernel argument of its own, behind rcp_sqrtW: a member appended to FwdCArgs would move rcp_sqrtW (and nmask, h0) in the
 // argument segment of EVERY kernel that takes the struct, and with it their scalar-load offsets.
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, bool kAsm>
-__global__ __launch_bounds__(64) void nastar_forward_compact_ranked_kernel(const FwdCArgs a, const float rcp_sqrtW, const int* __restrict__ levels)
+__global__ __launch_bounds__(64) void nastar_forward_compact_ranked_kernel(const FwdCArgs a, const float rcp_sqrtW, const int* __restrict__ levels,
+                                                                           unsigned long long* __restrict__ ticket_word, const unsigned long long ticket_value)
 {
-    constexpr bool kMasked = false, kHeur = false, kMulti = false, kRanked = true;
+    constexpr bool kMasked = false, kHeur = false, kMulti = false, kRanked = true, kTicket = true;
     constexpr uint32_t nmask = NASTAR_NEIGHBORS_MOORE8;
     constexpr const float* h0 = nullptr;
 #include "nastar_forward_compact_body.inc"
@@ -126,7 +132,9 @@ __global__ __launch_bounds__(64) void nastar_forward_compact_ranked_kernel(const
 template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 __global__ __launch_bounds__(64) void nastar_forward_compact_masked_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask)
 {
-    constexpr bool kAsm = false, kMasked = true, kHeur = false, kMulti = false, kRanked = false;
+    constexpr bool kAsm = false, kMasked = true, kHeur = false, kMulti = false, kRanked = false, kTicket = false;
+    constexpr unsigned long long* ticket_word = nullptr;
+    constexpr unsigned long long ticket_value = 0;
     constexpr const float* h0 = nullptr;
     constexpr const int* levels = nullptr;
 #include "nastar_forward_compact_body.inc"
@@ -139,7 +147,9 @@ template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog>
 __global__ __launch_bounds__(64) void nastar_forward_compact_heuristic_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask,
                                                                               const float* __restrict__ h0)
 {
-    constexpr bool kAsm = false, kMasked = true, kHeur = true, kMulti = false, kRanked = false;
+    constexpr bool kAsm = false, kMasked = true, kHeur = true, kMulti = false, kRanked = false, kTicket = false;
+    constexpr unsigned long long* ticket_word = nullptr;
+    constexpr unsigned long long ticket_value = 0;
     constexpr const int* levels = nullptr;
 #include "nastar_forward_compact_body.inc"
 }
@@ -151,7 +161,9 @@ template <bool kVec4, int LOGW, int LOGH, int CPL_T, bool kFastDiv, bool kLog, b
 __global__ __launch_bounds__(64) void nastar_forward_compact_sources_kernel(const FwdCArgs a, const float rcp_sqrtW, const uint32_t nmask,
                                                                             const float* __restrict__ h0)
 {
-    constexpr bool kAsm = false, kMasked = true, kMulti = true, kRanked = false;
+    constexpr bool kAsm = false, kMasked = true, kMulti = true, kRanked = false, kTicket = false;
+    constexpr unsigned long long* ticket_word = nullptr;
+    constexpr unsigned long long ticket_value = 0;
     constexpr const int* levels = nullptr;
 #include "nastar_forward_compact_body.inc"
 }

@@ -200,6 +200,16 @@ VERDICT_SIGNATURES = {
     "nastar_solvable_proof_sync": "i ",
 }
 
+# the signatures of include/nastar_ticket.h (the sixteenth header: a search launch and the proof of its batch from one call, the proof ordered
+# behind the search launch's own start), same letter code; a table of its own (tests/test_proof_ticket.py compares it with ITS header)
+TICKET_SIGNATURES = {
+    "nastar_ticket_abi": "i ",
+    "nastar_proof_ticket_available": "i ",
+    "nastar_proof_order_counts": "i pp",
+    # the arguments of nastar_forward_ex up to completion_counter, levels, proved_out, proof_word, proof_counter, proof_rc, stream
+    "nastar_forward_proved": "i " + _FORWARD + "p" + _WORKSPACE + "ipppp" + "ppppp" + "p",
+}
+
 # the signatures of include/nastar_fields_grad.h (the eighth header: the gradient of the cost-to-go field with respect to the cost maps), same
 # letter code; a table of its own (tests/test_fields_grad.py compares it with ITS header)
 FIELD_GRAD_SIGNATURES = {
@@ -414,6 +424,20 @@ def solvable_proof_address(H: int, W: int) -> int:
     return v
 
 
+_proved_entry: Optional[int] = None
+
+
+def forward_proved_address() -> int:
+    """the address of nastar_forward_proved (include/nastar_ticket.h), or 0 when the library lacks the symbol: what the native host lane takes
+    as ``proved_fn`` -- it then issues a search and its proof from that one entry point (whether the proof is ordered by ticket or by event
+    is the library's decision, per call)."""
+    global _proved_entry
+    if _proved_entry is None:
+        lib = load()
+        _proved_entry = int(ctypes.cast(lib.nastar_forward_proved, ctypes.c_void_p).value) if hasattr(lib, "nastar_forward_proved") else 0
+    return _proved_entry
+
+
 def load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
@@ -450,6 +474,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, SOFT_FIELD_TILED_SIGNATURES, SOFT_FIELD_TILED_SIGNATURES)
     if hasattr(lib, "nastar_soft_policy_abi"):  # (and the fifteenth)
         _bind(lib, SOFT_POLICY_SIGNATURES, SOFT_POLICY_SIGNATURES)
+    if hasattr(lib, "nastar_ticket_abi"):  # (and the sixteenth)
+        _bind(lib, TICKET_SIGNATURES, TICKET_SIGNATURES)
     _lib = lib
     return lib
 

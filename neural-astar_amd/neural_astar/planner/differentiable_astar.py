@@ -531,7 +531,8 @@ class DifferentiableAstar(nn.Module):
                 max_iters, False, flags, order, order_out, ws_bytes, board.ptr(row), board.counter_ptr(row),
                 torch._C._cuda_getCurrentRawStream(dev.index), 2000, levels, fl[2], sink,
                 0 if levels is None else _native.forward_levels_address(H, W, flags),
-                proof_fn, board.ptr(prow) if proof_fn else 0, board.counter_ptr(prow) if proof_fn else 0)
+                proof_fn, board.ptr(prow) if proof_fn else 0, board.counter_ptr(prow) if proof_fn else 0,
+                _native.forward_proved_address() if proof_fn else 0)  # (search + proof from one entry point: include/nastar_ticket.h)
         except BaseException:
             board.release(row)
             if prow >= 0:
