@@ -18,6 +18,9 @@
 // STEP of the backward (one workgroup per tile, one launch per k): plane k - 1 on the tile and two rings and A_k on one ring; every cell n
 // of the tile and one ring writes P(n) = A_k(n) / S_k(n) and M_k(n); every cell m of the interior gathers in kChildOffsets order, stores
 // A_{k-1}(m) into the other A plane and adds it to its fp64 sum in device memory.  One workgroup owns a cell: no atomics.
+//
+// The sweeps, init and step kernels carry a compile-time switch, off by default: nastar_soft_policy_tiled.hip.h instantiates the other side
+// of it, the log-policy and its adjoint (item 6o).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -37,6 +40,8 @@ constexpr int kSoftPlaneT = 256;     // ... of the cell-wise kernels
 constexpr size_t soft_tile_lds_bytes(int n) { return (size_t)(kTileH + 2 * n) * (kTileW + 2 * n) * 12; }
 // ... of a step launch: plane k - 1 on two rings, A (then P) and M on one
 constexpr size_t soft_tile_grad_lds_bytes() { return ((size_t)(kTileH + 4) * (kTileW + 4) + 2 * (size_t)(kTileH + 2) * (kTileW + 2)) * 4; }
+// ... of the step that injects the log-policy seed: Q beside P and M, and a byte "live at K" per cell of the one ring
+constexpr size_t soft_tile_inject_lds_bytes() { return soft_tile_grad_lds_bytes() + (size_t)(kTileH + 2) * (kTileW + 2) * 5; }
 
 struct SoftPrepareArgs {
     const float* cost;      // [B,HW]
@@ -132,8 +137,12 @@ __device__ __forceinline__ void sft_cells(int rows, int cols, F&& f)
     }
 }
 
-template <int T>
-__global__ __launch_bounds__(T) void nastar_soft_tiled_sweeps_kernel(const SoftTileArgs a)
+// THE SWEEPS of one tile.  LOGP: the epilogue of the launch that reaches plane K also writes the log-policy of include/nastar_soft_policy.h to
+// log_policy [B,8,HW], from the M, S and plane K-1 the policy is formed from (nastar_soft_policy_tiled.hip.h); everything else is the same
+// statements, so the same bits.  The switch sits on the KERNEL, not on a body behind a wrapper: the plain instantiation then keeps its
+// instruction stream too (tools/compare_device_code.py; log_policy is nullptr there and never looked at).
+template <int T, bool LOGP = false>
+__global__ __launch_bounds__(T) void nastar_soft_tiled_sweeps_kernel(const SoftTileArgs a, float* log_policy)
 {
     extern __shared__ __attribute__((aligned(16))) char sft_smem[];
     const TilePos p = tld_pos(a.g);
@@ -191,29 +200,39 @@ __global__ __launch_bounds__(T) void nastar_soft_tiled_sweeps_kernel(const SoftT
     const bool map_bad = a.flags[2 * p.b + 1] != 0;
     const size_t HW = (size_t)H * W;
     float* pol = a.policy ? a.policy + p.base * 8 : nullptr;
+    float* lpol = LOGP ? log_policy + p.base * 8 : nullptr;
     sft_cells<T>(p.rows, p.cols, [&](int r, int c) {
         const int i = (r + n) * RW + (c + n);
         const int y = p.y0 + r, x = p.x0 + c;
         const size_t cell = (size_t)(y * W + x);
         a.dist[p.base + cell] = map_bad ? INF : a.goal[p.base + cell] != 0.f ? 0.f : prev[i] * a.from_units;
-        if (pol) {
+        if (LOGP || pol) {
             const bool up = y > 0, dn = y < H - 1, lf = x > 0, rt = x < W - 1;
             const float* at = next + i;
             const SoftMin sm = sfl_softmin([&](int dy, int dx) { return at[dy * RW + dx]; }, nm, up, dn, lf, rt);
             const float cc = C[i];
             const bool live = cc >= 0.f && cc < INF && sm.m < INF;
+            float log2s = 0.f;
+            if constexpr (LOGP) log2s = sfl_log2(sm.s);
             fld_each<8>([&](auto k) __attribute__((always_inline)) {
                 constexpr Move mv = kActionMoves[decltype(k)::value];
-                float w = 0.f;
-                if (live && (nm & fld_bit(mv.dy, mv.dx)) && fld_inside(mv.dy, mv.dx, up, dn, lf, rt)) w = sfl_exp2(sm.m - at[mv.dy * RW + mv.dx]) / sm.s;
-                pol[(size_t) decltype(k)::value * HW + cell] = w;
+                float w = 0.f, lw = -INF;
+                if (live && (nm & fld_bit(mv.dy, mv.dx)) && fld_inside(mv.dy, mv.dx, up, dn, lf, rt)) {
+                    w = sfl_exp2(sm.m - at[mv.dy * RW + mv.dx]) / sm.s;
+                    // the minimum and the sum kept apart, as in w: -inf by itself for a target of +inf
+                    if constexpr (LOGP) lw = ((sm.m - at[mv.dy * RW + mv.dx]) - log2s) * (float)M_LN2;
+                }
+                if (!LOGP || pol) pol[(size_t) decltype(k)::value * HW + cell] = w;
+                if constexpr (LOGP) lpol[(size_t) decltype(k)::value * HW + cell] = lw;
             });
         }
     });
 }
 
+
 // A_K = the upstream gradient on the cells live at K (U is plane K), 0 elsewhere; the fp64 sums start there
-template <int T>
+// (POLICY: a.grad_dist may be nullptr = zeros)
+template <int T, bool POLICY = false>
 __global__ __launch_bounds__(T) void nastar_soft_tiled_grad_init_kernel(const SoftTileGradArgs a)
 {
     const TilePos p = tld_pos(a.g);
@@ -223,14 +242,26 @@ __global__ __launch_bounds__(T) void nastar_soft_tiled_grad_init_kernel(const So
         const float cc = a.C[idx];
         const bool live = cc >= 0.f && cc < INFINITY && a.U[idx] < INFINITY;  // passable, no goal, finite at K
         float g = 0.f;
-        if (live) g = a.grad_dist[idx];
+        if (live && (!POLICY || a.grad_dist)) g = a.grad_dist[idx];
         a.A_out[idx] = g;
         a.sum[idx] = (double)g;
     });
 }
 
-template <int T>
-__global__ __launch_bounds__(T) void nastar_soft_tiled_grad_step_kernel(const SoftTileGradArgs a)
+// the second seed of the tiled backward (include/nastar_soft_policy_tiled.h): the upstream gradient of the log-policy [B,8,HW], and plane K,
+// which says where a cell is live at K
+struct SoftTilePolicySeed {
+    const float* grad_log_policy;
+    const float* UK;
+    float neg_inv_tau;  // -1 / tau
+};
+
+// ONE STEP k of the backward on one tile.  INJECT (step K only, nastar_soft_policy_tiled.hip.h): the log-policy seed GL joins the gather,
+// A_{K-1} = the gather + Z.  The first pass also leaves Q(n) = gsum(n) / S_K(n) and a byte "live at K" (from C and plane K) on the tile and
+// one ring; the gather adds GL(a,n) - exp2(M(n) - u) Q(n) over the predecessors live at K: the statements of sfl_backward<T, true>.  Without
+// it every statement is the plain step's, and `seed` is never looked at: the same instruction stream, the same bits.
+template <int T, bool INJECT = false>
+__global__ __launch_bounds__(T) void nastar_soft_tiled_grad_step_kernel(const SoftTileGradArgs a, const SoftTilePolicySeed seed)
 {
     extern __shared__ __attribute__((aligned(16))) char sfg_tile_smem[];
     const TilePos p = tld_pos(a.g);
@@ -239,6 +270,10 @@ __global__ __launch_bounds__(T) void nastar_soft_tiled_grad_step_kernel(const So
     float* U = reinterpret_cast<float*>(sfg_tile_smem);  // plane k - 1; its cell (0, 0) is the map's (y0 - 2, x0 - 2)
     float* P = U + UH * UW;                               // A_k, then P; its cell (0, 0) is the map's (y0 - 1, x0 - 1)
     float* M = P + PH * PW;
+    float* Q = M + PH * PW;                               // (INJECT) as P
+    uint8_t* liveK = reinterpret_cast<uint8_t*>(Q + PH * PW);
+    const size_t HW = (size_t)H * W;
+    const float* gl = INJECT ? seed.grad_log_policy + p.base * 8 : nullptr;
     const float INF = INFINITY;
 
     sft_cells<T>(UH, UW, [&](int r, int c) {
@@ -257,10 +292,29 @@ __global__ __launch_bounds__(T) void nastar_soft_tiled_grad_step_kernel(const So
     sft_cells<T>(PH, PW, [&](int r, int c) {
         const int y = p.y0 - 1 + r, x = p.x0 - 1 + c, i = r * PW + c;
         const float* at = U + (r + 1) * UW + (c + 1);
-        const SoftMin sm = sfl_softmin([&](int dy, int dx) { return at[dy * UW + dx]; }, nm, y > 0, y < H - 1, x > 0, x < W - 1);
+        const bool up = y > 0, dn = y < H - 1, lf = x > 0, rt = x < W - 1;
+        const SoftMin sm = sfl_softmin([&](int dy, int dx) { return at[dy * UW + dx]; }, nm, up, dn, lf, rt);
         const bool any = sm.m < INF;  // (A is 0 on a cell that is not live at k, whatever its soft-min)
         P[i] = any ? P[i] / sm.s : 0.f;
         M[i] = any ? sm.m : -INF;     // exp2(-inf - u) = 0
+        if constexpr (INJECT) {
+            bool live = false;
+            const size_t cell = (size_t)(y * W + x);  // (inside the map wherever it is used)
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const float cc = a.C[p.base + cell];
+                live = cc >= 0.f && cc < INF && seed.UK[p.base + cell] < INF;  // passable, no goal, finite at K: what the init kernel asks
+            }
+            float gsum = 0.f;
+            if (live) {  // GL is read on Act(n) only, in the row-major order of the move offsets
+                fld_each<8>([&](auto j) __attribute__((always_inline)) {
+                    constexpr Move o = kChildOffsets[decltype(j)::value];
+                    if ((nm & fld_bit(o.dy, o.dx)) && fld_inside(o.dy, o.dx, up, dn, lf, rt) && at[o.dy * UW + o.dx] < INF)
+                        gsum += gl[(size_t)kOppositeAction[7 - decltype(j)::value] * HW + cell];
+                });
+            }
+            Q[i] = gsum / sm.s;  // (S >= 1 on a live cell; what is not live is 0 / S or 0 / 0 and is never read)
+            liveK[i] = live;
+        }
     });
     __syncthreads();
 
@@ -268,22 +322,32 @@ __global__ __launch_bounds__(T) void nastar_soft_tiled_grad_step_kernel(const So
         const int y = p.y0 + r, x = p.x0 + c, i = (r + 1) * PW + (c + 1);
         const bool up = y > 0, dn = y < H - 1, lf = x > 0, rt = x < W - 1;
         const float u = U[(r + 2) * UW + (c + 2)];
-        float acc = 0.f;
+        float acc = 0.f, z = 0.f;
         // the predecessor at kChildOffsets[j] steps onto this cell by the opposite move
         fld_each<8>([&](auto j) __attribute__((always_inline)) {
             constexpr Move o = kChildOffsets[decltype(j)::value];
             if ((nm & fld_bit(-o.dy, -o.dx)) && fld_inside(o.dy, o.dx, up, dn, lf, rt)) {
                 const int n = i + o.dy * PW + o.dx;
-                acc += P[n] * sfl_exp2(M[n] - u);
+                if constexpr (INJECT) {
+                    const float w = sfl_exp2(M[n] - u);
+                    acc += P[n] * w;
+                    if (liveK[n] && u < INF)
+                        z += gl[(size_t)kOppositeAction[decltype(j)::value] * HW + (size_t)((y + o.dy) * W + (x + o.dx))] - w * Q[n];
+                } else {
+                    acc += P[n] * sfl_exp2(M[n] - u);
+                }
             }
         });
         const size_t idx = p.base + (size_t)(y * W + x);
         const float cc = a.C[idx];
-        const float v = (cc >= 0.f && cc < INF && u < INF) ? acc : 0.f;
+        float v = acc;
+        if constexpr (INJECT) v = acc + z * seed.neg_inv_tau;
+        v = (cc >= 0.f && cc < INF && u < INF) ? v : 0.f;
         a.A_out[idx] = v;
-        a.sum[idx] += (double)v;
+        a.sum[idx] += (double)v;  // (INJECT: the sum is A_K alone until here)
     });
 }
+
 
 // one rounding per cell
 template <int T>

@@ -313,6 +313,21 @@ SOFT_POLICY_SIGNATURES = {
     "nastar_soft_policy_backward": "i ppppzppiiiudippp",
 }
 
+# the signatures of include/nastar_soft_policy_tiled.h (the seventeenth header: the fifteenth's log-policy and gradient by the fourteenth's
+# tiled sweeps and checkpointed tape), same letter code; a table of its own (tests/test_soft_policy_tiled.py compares it with ITS header)
+SOFT_POLICY_TILED_SIGNATURES = {
+    "nastar_soft_policy_tiled_abi": "i ",
+    "nastar_soft_policy_tiled_backward_workspace_bytes": "z iiiii",   # B, H, W, horizon, checkpoint_every
+    # cost, goal, passable, B, H, W, neighbor_mask, tau, horizon, dist_out, policy_out, log_policy_out, status_out, tape, tape_bytes,
+    # checkpoint_every, workspace, workspace_bytes, stream
+    "nastar_soft_policy_forward_tiled": "i pppiiiudipppppzipzp",
+    # ... workspace_bytes, sweeps_per_launch, stream
+    "nastar_soft_policy_forward_tiled_with_sweeps": "i pppiiiudipppppzipzip",
+    # cost, goal, passable, tape, tape_bytes, checkpoint_every, grad_dist, grad_log_policy, B, H, W, neighbor_mask, tau, horizon,
+    # grad_cost_out, status_out, workspace, workspace_bytes, stream
+    "nastar_soft_policy_backward_tiled": "i ppppzippiiiudipppzp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -476,6 +491,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, SOFT_POLICY_SIGNATURES, SOFT_POLICY_SIGNATURES)
     if hasattr(lib, "nastar_ticket_abi"):  # (and the sixteenth)
         _bind(lib, TICKET_SIGNATURES, TICKET_SIGNATURES)
+    if hasattr(lib, "nastar_soft_policy_tiled_abi"):  # (and the seventeenth)
+        _bind(lib, SOFT_POLICY_TILED_SIGNATURES, SOFT_POLICY_TILED_SIGNATURES)
     _lib = lib
     return lib
 

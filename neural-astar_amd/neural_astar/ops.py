@@ -25,7 +25,8 @@ __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay",
            "soft_cost_to_go", "SoftFieldOutput", "maxent_path_nll", "soft_fields_forward", "soft_fields_backward", "SOFT_FIELDS_MAX_CELLS",
            "SOFT_FIELDS_GRAD_MAX_CELLS", "soft_cost_to_go_tiled", "maxent_path_nll_tiled", "soft_fields_tiled_forward",
            "soft_fields_tiled_backward", "SOFT_FIELDS_TILED_MAX_CELLS",
-           "soft_policy", "SoftPolicyOutput", "soft_policy_nll", "soft_policy_forward", "soft_policy_backward"]
+           "soft_policy", "SoftPolicyOutput", "soft_policy_nll", "soft_policy_forward", "soft_policy_backward",
+           "soft_policy_tiled", "soft_policy_nll_tiled", "soft_policy_tiled_forward", "soft_policy_tiled_backward"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -2053,11 +2054,21 @@ def soft_policy_nll(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_
     ``soft_policy``: the gradient goes to ``cost_maps``.  Reads one flag back (a host synchronisation): a counted cell whose demonstrated
     action has a log-probability of -inf -- a move the mask or an obstacle forbids, or onto a cell with no goal within ``horizon`` - 1
     moves -- raises ValueError naming the maps."""
+    _check_opt_policies(cost_maps, goal_maps, obstacles_maps, opt_policies, neighbor_mask)
+    out = soft_policy(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask)
+    return _nll_of_policy(out, opt_policies, horizon)
+
+
+def _check_opt_policies(cost_maps, goal_maps, obstacles_maps, opt_policies, neighbor_mask) -> None:
     _, _, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     if not torch.is_tensor(opt_policies) or tuple(opt_policies.shape) != (B, 8, H, W) or opt_policies.device != cost_maps.device:
         raise ValueError(f"opt_policies must be a [B,8,H,W] tensor for {B} maps of {H}x{W} on {cost_maps.device}, got "
                          f"{(tuple(opt_policies.shape), str(opt_policies.device)) if torch.is_tensor(opt_policies) else type(opt_policies).__name__}")
-    out = soft_policy(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask)
+
+
+def _nll_of_policy(out: SoftPolicyOutput, opt_policies: torch.Tensor, horizon) -> torch.Tensor:
+    """what ``soft_policy_nll`` and ``soft_policy_nll_tiled`` compose on top of their policy node"""
+    B, _, H, W = out.dists.shape
     logp = out.log_policies
     weights = opt_policies.to(torch.float32)
     shown = weights != 0
@@ -2070,3 +2081,155 @@ def soft_policy_nll(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_
                          f"horizon - 1 = {_checked_horizon(horizon, H, W) - 1} moves")
     terms = weights * torch.where(pick, logp, torch.zeros_like(logp))     # (where, not a product: no 0 * -inf)
     return -terms.sum((1, 2, 3)) / counted.sum((1, 2)).clamp(min=1).to(torch.float32)
+
+
+# ---- include/nastar_soft_policy_tiled.h: the log-policy and its gradient by tiled sweeps, with the checkpointed tape
+def soft_policy_tiled_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
+                              horizon: Optional[int] = None, neighbor_mask: Optional[int] = None, policies: bool = True, tape: bool = False,
+                              checkpoint_every: Optional[int] = None, sweeps_per_launch: Optional[int] = None):
+    """``nastar_soft_policy_forward_tiled`` as it is (include/nastar_soft_policy_tiled.h) -> ``(SoftPolicyOutput, tape)``:
+    ``soft_fields_tiled_forward`` with the log-policy beside its outputs, written by the launch that reaches the horizon -- the same
+    launches on the current stream, nothing is read back, detached outputs, the same bits in ``dists``, ``policies``, ``status`` and the
+    tape.  ``tape``, ``checkpoint_every`` and ``sweeps_per_launch`` as there.  What ``soft_policy_tiled`` runs."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    c = _checked_checkpoint_every(checkpoint_every, K)
+    if sweeps_per_launch is not None and (isinstance(sweeps_per_launch, bool) or not isinstance(sweeps_per_launch, int) or sweeps_per_launch < 1):
+        raise ValueError(f"sweeps_per_launch must be a positive int or None, got {sweeps_per_launch!r}")
+    _soft_tiled_limit(H, W, "soft_policy_tiled")
+    dev = _field_device(maps)
+    lib = _field_lib("nastar_soft_policy_forward_tiled", "nastar_soft_policy_tiled.h")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
+        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        tape_bytes = int(lib.nastar_soft_fields_tiled_tape_bytes(B, H, W, K, c)) if tape else 0
+        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
+        ws_bytes = int(lib.nastar_soft_fields_tiled_workspace_bytes(B, H, W))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(),
+                pol.data_ptr() if pol is not None else None, logp.data_ptr(), status.data_ptr(), buf.data_ptr() if buf is not None else None,
+                tape_bytes, c, ws.data_ptr(), ws_bytes)
+        with torch.cuda.device(dev):
+            if sweeps_per_launch is None:
+                rc = lib.nastar_soft_policy_forward_tiled(*args, _stream_ptr(dev))
+            else:
+                rc = lib.nastar_soft_policy_forward_tiled_with_sweeps(*args, sweeps_per_launch, _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_policy_forward_tiled")
+    return SoftPolicyOutput(dists, logp, pol, status), buf
+
+
+def soft_policy_tiled_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
+                               grad_dists: Optional[torch.Tensor], grad_log_policies: Optional[torch.Tensor], tau: float,
+                               horizon: Optional[int] = None, neighbor_mask: Optional[int] = None,
+                               checkpoint_every: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``nastar_soft_policy_backward_tiled`` as it is: the maps, ``tau``, ``horizon``, mask and ``checkpoint_every`` of the tiled forward
+    that wrote ``tape`` (``soft_policy_tiled_forward`` or ``soft_fields_tiled_forward``, ``tape=True``), an upstream gradient of ``dists``
+    and one of ``log_policies`` ([B,8,H,W]); either may be None (zeros) -> ``(grad_cost [B,H,W], status [B] int32)``.  The launches of
+    ``soft_fields_tiled_backward`` on the current stream, the one of step ``horizon`` carrying the log-policy seed; nothing is read back.
+    ``grad_log_policies`` is read only where the log-policy is finite; with None for it the result is ``soft_fields_tiled_backward``'s,
+    bit for bit.  What the backward of ``soft_policy_tiled`` runs."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    c = _checked_checkpoint_every(checkpoint_every, K)
+    if grad_dists is not None:
+        _check_grad_dists(grad_dists, B, H, W)
+    if grad_log_policies is not None and (not torch.is_tensor(grad_log_policies) or grad_log_policies.dtype != torch.float32
+                                          or tuple(grad_log_policies.shape) != (B, 8, H, W)):
+        raise ValueError(f"grad_log_policies must be a float32 tensor of the shape of log_policies ({B}, 8, {H}, {W}), got "
+                         f"{tuple(grad_log_policies.shape) if torch.is_tensor(grad_log_policies) else type(grad_log_policies).__name__}")
+    _soft_tiled_limit(H, W, "soft_policy_tiled_backward")
+    dev = _field_device(maps)
+    for name, g in (("grad_dists", grad_dists), ("grad_log_policies", grad_log_policies)):
+        if g is not None and g.device != dev:
+            raise ValueError(f"the maps live on {dev}, {name} on {g.device}: they must share a device")
+    lib = _field_lib("nastar_soft_policy_backward_tiled", "nastar_soft_policy_tiled.h")
+    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
+        raise ValueError(f"tape must be the contiguous uint8 tensor soft_policy_tiled_forward(..., tape=True) returned, on {dev}")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        up = grad_dists.detach().reshape(B, H, W).contiguous() if grad_dists is not None else None
+        upl = grad_log_policies.detach().contiguous() if grad_log_policies is not None else None
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        ws_bytes = int(lib.nastar_soft_policy_tiled_backward_workspace_bytes(B, H, W, K, c))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_soft_policy_backward_tiled(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(), c,
+                                                       up.data_ptr() if up is not None else None, upl.data_ptr() if upl is not None else None,
+                                                       B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                       _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_policy_backward_tiled")
+    return grad, status
+
+
+class _SoftPolicyTiledNode(torch.autograd.Function):
+    """``soft_policy_tiled_forward`` as ONE autograd node with two differentiable outputs, ``dists`` and ``log_policies``: its backward is
+    one call of ``nastar_soft_policy_backward_tiled`` with whichever of the two upstream gradients arrived, and reads nothing back."""
+
+    @staticmethod
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, tau, horizon, mask, checkpoint_every):
+        out, tape = soft_policy_tiled_forward(cost_maps, goal_maps, obstacles_maps, tau, horizon, mask, policies=True, tape=True,
+                                              checkpoint_every=checkpoint_every)
+        if not torch.cuda.is_current_stream_capturing():
+            _raise_bad_cost(out.status.cpu(), out.status.numel(), "soft_policy_tiled")
+        ctx.save_for_backward(cost_maps, goal_maps, obstacles_maps, tape)
+        ctx.call = (tau, horizon, mask, checkpoint_every)
+        ctx.mark_non_differentiable(out.policies, out.status)
+        ctx.set_materialize_grads(False)
+        return out.dists, out.log_policies, out.policies, out.status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_dists, g_logp, *unused):
+        if (g_dists is None and g_logp is None) or not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        cost_maps, goal_maps, obstacles_maps, tape = ctx.saved_tensors
+        grad = soft_policy_tiled_backward(cost_maps, goal_maps, obstacles_maps, tape, g_dists, g_logp, *ctx.call)[0]
+        shape = tuple(cost_maps.shape)
+        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
+            full = grad.new_zeros(shape)
+            full[:, 0] = grad
+            grad = full
+        return (grad.reshape(shape), None, None, None, None, None, None)
+
+
+def soft_policy_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                      neighbor_mask: Optional[int] = None, checkpoint_every: Optional[int] = None) -> SoftPolicyOutput:
+    """``soft_policy`` for maps of up to ``SOFT_FIELDS_TILED_MAX_CELLS`` cells (1024x1152: every map size the search takes), by tiled sweeps
+    (include/nastar_soft_policy_tiled.h) -> ``SoftPolicyOutput``.  The same definition and, on the maps both take, the same bits in
+    ``dists``, ``log_policies``, ``policies``, ``status`` and the gradient; NotImplementedError above the limit, before anything is
+    launched.  The log-policy is written by the sweep launch that reaches the horizon: the launches are those of
+    ``soft_cost_to_go_tiled``.
+
+    When ``cost_maps`` requires a gradient and grad mode is on, ``dists`` and ``log_policies`` are the two outputs of ONE autograd node
+    that keeps the CHECKPOINTED tape of ``soft_cost_to_go_tiled`` (``checkpoint_every``: None = ceil(sqrt(horizon)), 1 keeps every plane;
+    the gradient does not depend on it).  Its backward is that call's backward, one launch per step, with the launch of step ``horizon``
+    carrying the gradient of ``log_policies``; it reads nothing back.  The gradient of ``log_policies`` is read only where they are
+    finite.  Otherwise no graph is built and no tape is kept.  ``policies`` is detached either way.  The per-map status is read once
+    before returning (not inside a stream capture), with the ValueError of ``soft_policy`` for a NaN or a negative cost."""
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
+    c = _checked_checkpoint_every(checkpoint_every, K)
+    _soft_tiled_limit(H, W, "soft_policy_tiled")
+    if cost_maps.requires_grad and torch.is_grad_enabled():
+        return SoftPolicyOutput(*_SoftPolicyTiledNode.apply(cost_maps, goal_maps, obstacles_maps, t, K, mask, c))
+    out, _ = soft_policy_tiled_forward(cost_maps, goal_maps, obstacles_maps, t, K, mask, policies=True, checkpoint_every=c)
+    if not torch.cuda.is_current_stream_capturing():
+        _raise_bad_cost(out.status.cpu(), B, "soft_policy_tiled")
+    return out
+
+
+def soft_policy_nll_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, opt_policies: torch.Tensor, tau: float,
+                          horizon: Optional[int] = None, neighbor_mask: Optional[int] = None,
+                          checkpoint_every: Optional[int] = None) -> torch.Tensor:
+    """``soft_policy_nll`` composed on ``soft_policy_tiled(..., checkpoint_every=checkpoint_every)``: the same loss and gradient for maps of
+    up to ``SOFT_FIELDS_TILED_MAX_CELLS`` cells -- the size ``cost_to_go_tiled`` builds ``opt_policies`` for.  What the planners'
+    ``policy_nll(..., tiled=True)`` calls."""
+    _check_opt_policies(cost_maps, goal_maps, obstacles_maps, opt_policies, neighbor_mask)
+    out = soft_policy_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, checkpoint_every)
+    return _nll_of_policy(out, opt_policies, horizon)

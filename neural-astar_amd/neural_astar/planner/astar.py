@@ -121,11 +121,16 @@ class VanillaAstar(nn.Module):
         carry the gradient to ``map_designs`` as the cost when it requires one."""
         return self.astar.soft_policy(map_designs, goal_maps, map_designs, tau, horizon)
 
+    def soft_policy_tiled(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                          checkpoint_every: Optional[int] = None):
+        """``soft_policy`` by tiled sweeps (``DifferentiableAstar.soft_policy_tiled``: maps of up to 1024x1152, the same bits)."""
+        return self.astar.soft_policy_tiled(map_designs, goal_maps, map_designs, tau, horizon, checkpoint_every)
+
     def policy_nll(self, map_designs: torch.Tensor, goal_maps: torch.Tensor, opt_policies: torch.Tensor, tau: float,
-                   horizon: Optional[int] = None) -> torch.Tensor:
+                   horizon: Optional[int] = None, tiled: bool = False, checkpoint_every: Optional[int] = None) -> torch.Tensor:
         """The per-cell imitation loss [B] against the demonstrated actions ``opt_policies`` [B,8,H,W] (``DifferentiableAstar.policy_nll``)
-        with cost = passable = ``map_designs``."""
-        return self.astar.policy_nll(map_designs, goal_maps, map_designs, opt_policies, tau, horizon)
+        with cost = passable = ``map_designs``; ``tiled=True`` for maps of up to 1024x1152."""
+        return self.astar.policy_nll(map_designs, goal_maps, map_designs, opt_policies, tau, horizon, tiled, checkpoint_every)
 
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
                   paths: bool = False) -> FieldRoutesOutput:
@@ -382,16 +387,26 @@ class NeuralAstar(VanillaAstar):
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.astar.soft_policy(cost_maps, goal_maps, obstacles_maps, tau, horizon)
 
-    def policy_nll(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, opt_policies: torch.Tensor,
-                   tau: float, horizon: Optional[int] = None) -> torch.Tensor:
-        """The per-cell imitation loss of the demonstrated actions ``opt_policies`` [B,8,H,W] under the PREDICTED cost maps -> [B]
-        (``ops.soft_policy_nll``): the cross-entropy between the soft policy and the optimal action of every cell, thousands of
-        supervised cells per map.  Encodes as ``forward()`` does, NOT detached, so ``.sum().backward()`` trains the encoder;
-        ``learn_obstacles`` makes every cell passable."""
+    def soft_policy_tiled(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, tau: float,
+                          horizon: Optional[int] = None, checkpoint_every: Optional[int] = None):
+        """``soft_policy`` of the PREDICTED cost maps by tiled sweeps (``DifferentiableAstar.soft_policy_tiled``: maps of up to 1024x1152,
+        the same bits): encodes as ``soft_policy`` does, NOT detached."""
         ops._checked_tau(tau)  # (before the encoder launches anything)
         cost_maps = self.encode(map_designs, start_maps, goal_maps)
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
-        return self.astar.policy_nll(cost_maps, goal_maps, obstacles_maps, opt_policies, tau, horizon)
+        return self.astar.soft_policy_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, checkpoint_every)
+
+    def policy_nll(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, opt_policies: torch.Tensor,
+                   tau: float, horizon: Optional[int] = None, tiled: bool = False, checkpoint_every: Optional[int] = None) -> torch.Tensor:
+        """The per-cell imitation loss of the demonstrated actions ``opt_policies`` [B,8,H,W] under the PREDICTED cost maps -> [B]
+        (``ops.soft_policy_nll``): the cross-entropy between the soft policy and the optimal action of every cell, thousands of
+        supervised cells per map.  Encodes as ``forward()`` does, NOT detached, so ``.sum().backward()`` trains the encoder;
+        ``learn_obstacles`` makes every cell passable.  ``tiled=True``: on the tiled policy (maps of up to 1024x1152), with its
+        ``checkpoint_every``."""
+        ops._checked_tau(tau)  # (before the encoder launches anything)
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return self.astar.policy_nll(cost_maps, goal_maps, obstacles_maps, opt_policies, tau, horizon, tiled, checkpoint_every)
 
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
                   paths: bool = False) -> FieldRoutesOutput:

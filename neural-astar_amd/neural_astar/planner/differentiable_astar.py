@@ -690,11 +690,25 @@ class DifferentiableAstar(nn.Module):
         (``ops.soft_policy``, the kernels of include/nastar_soft_policy.h), under this module's own move set."""
         return ops.soft_policy(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask=self.neighbor_mask())
 
+    def soft_policy_tiled(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
+                          horizon: Optional[int] = None, checkpoint_every: Optional[int] = None) -> "ops.SoftPolicyOutput":
+        """``soft_policy`` by tiled sweeps (``ops.soft_policy_tiled``, the kernels of include/nastar_soft_policy_tiled.h): maps of up to
+        1024x1152, the same bits where both apply.  ``checkpoint_every``: the spacing of the planes a differentiable call keeps (None =
+        ceil(sqrt(horizon)); 1 = every plane)."""
+        return ops.soft_policy_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask=self.neighbor_mask(),
+                                     checkpoint_every=checkpoint_every)
+
     def policy_nll(self, cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, opt_policies: torch.Tensor,
-                   tau: float, horizon: Optional[int] = None) -> torch.Tensor:
+                   tau: float, horizon: Optional[int] = None, tiled: bool = False, checkpoint_every: Optional[int] = None) -> torch.Tensor:
         """The per-cell imitation loss [B] of the soft policy of ``cost_maps`` against the demonstrated actions ``opt_policies``
-        [B,8,H,W] (``ops.soft_policy_nll``), under this module's own move set."""
-        return ops.soft_policy_nll(cost_maps, goal_maps, obstacles_maps, opt_policies, tau, horizon, neighbor_mask=self.neighbor_mask())
+        [B,8,H,W] (``ops.soft_policy_nll``), under this module's own move set.  ``tiled=True``: on the tiled policy
+        (``ops.soft_policy_nll_tiled``: maps of up to 1024x1152), with its ``checkpoint_every``."""
+        if not tiled:
+            if checkpoint_every is not None:
+                raise ValueError("checkpoint_every belongs to tiled=True: the one-workgroup field keeps every plane")
+            return ops.soft_policy_nll(cost_maps, goal_maps, obstacles_maps, opt_policies, tau, horizon, neighbor_mask=self.neighbor_mask())
+        return ops.soft_policy_nll_tiled(cost_maps, goal_maps, obstacles_maps, opt_policies, tau, horizon, neighbor_mask=self.neighbor_mask(),
+                                         checkpoint_every=checkpoint_every)
 
     def plan_many(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
                   max_route_len: Optional[int] = None, paths: bool = False) -> FieldRoutesOutput:
