@@ -920,6 +920,34 @@ def _refuse_capture(dev: torch.device, error: type, message: str) -> None:
 _BLOCKS = "the call synchronises its stream between batches of rounds and cannot be captured into a graph"
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """the address of an optional tensor of a C call: None (NULL) for a tensor that is not there"""
+    return None if t is None else t.data_ptr()
+
+
+def _field_outputs(B: int, H: int, W: int, dev: torch.device, policies: bool):
+    """what a field call writes -> (dists [B,1,H,W], policies [B,8,H,W] or None, status [B] int32), uninitialised"""
+    dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
+    return dists, pol, torch.empty((B,), dtype=torch.int32, device=dev)
+
+
+def _backward_planes(upstream: Optional[torch.Tensor], B: int, H: int, W: int, dev: torch.device):
+    """what a backward call of the family reads and writes -> (the upstream gradient as a contiguous [B,H,W] plane, or None for None;
+    grad_cost [B,H,W] and status [B] int32, uninitialised)"""
+    up = None if upstream is None else upstream.detach().reshape(B, H, W).contiguous()
+    return up, torch.empty((B, H, W), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev)
+
+
+def _widen_grad(grad: torch.Tensor, shape) -> torch.Tensor:
+    """a [B,H,W] gradient in the shape of the ``cost_maps`` it belongs to: of several channels, channel 0 is the cost map (``_maps3``)"""
+    if len(shape) == 4 and shape[1] > 1:
+        full = grad.new_zeros(shape)
+        full[:, 0] = grad
+        return full
+    return grad.reshape(shape)
+
+
 def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, neighbor_mask: Optional[int] = None,
                policies: bool = True, sweeps_out: Optional[torch.Tensor] = None, tiled: bool = False, differentiable: bool = False) -> FieldOutput:
     """The cost-to-go field of every map of the batch, and the optimal policy that follows it (include/nastar_fields.h).  What follows
@@ -958,13 +986,10 @@ def cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps:
     _check_counts_out(sweeps_out, "sweeps_out", B, dev)
     with torch.no_grad():
         cost, goal, passable = (_maps3(t.detach()) for t in maps)
-        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        dists, pol, status = _field_outputs(B, H, W, dev, policies)
         with torch.cuda.device(dev):
             rc = lib.nastar_cost_to_go_sweeps(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, dists.data_ptr(),
-                                              pol.data_ptr() if pol is not None else None, status.data_ptr(),
-                                              sweeps_out.data_ptr() if sweeps_out is not None else None, _stream_ptr(dev))
+                                              _ptr(pol), status.data_ptr(), _ptr(sweeps_out), _stream_ptr(dev))
         _native.check(rc, "nastar_cost_to_go")
         if not torch.cuda.is_current_stream_capturing():
             st = status.cpu()
@@ -995,12 +1020,10 @@ def fields_backward(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
     _check_counts_out(sweeps_out, "sweeps_out", B, dev)
     with torch.no_grad():
         dist, goal, passable = (_maps3(t.detach()) for t in maps)
-        up = grad_dists.detach().reshape(B, H, W).contiguous()
-        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        up, grad, status = _backward_planes(grad_dists, B, H, W, dev)
         with torch.cuda.device(dev):
             rc = lib.nastar_fields_backward(dist.data_ptr(), goal.data_ptr(), passable.data_ptr(), up.data_ptr(), B, H, W, mask, grad.data_ptr(),
-                                            status.data_ptr(), sweeps_out.data_ptr() if sweeps_out is not None else None, _stream_ptr(dev))
+                                            status.data_ptr(), _ptr(sweeps_out), _stream_ptr(dev))
         _native.check(rc, "nastar_fields_backward")
     return grad, status
 
@@ -1032,12 +1055,7 @@ class _FieldNode(torch.autograd.Function):
         if g_dists is None or not ctx.needs_input_grad[0]:
             return (None,) * 6
         grad = ctx.backward_call(*ctx.saved_tensors, g_dists)
-        shape = ctx.cost_shape
-        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
-            full = grad.new_zeros(shape)
-            full[:, 0] = grad
-            grad = full
-        return (grad.reshape(shape), None, None, None, None, None)
+        return (_widen_grad(grad, ctx.cost_shape), None, None, None, None, None)
 
 
 def _differentiable_field(cost_maps, goal_maps, obstacles_maps, field, backward, taped: bool = False) -> FieldOutput:
@@ -1116,15 +1134,12 @@ def cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles
         raise NotImplementedError(f"cost_to_go_tiled: a batch of {B} maps of {H}x{W} has more than 2^24 tiles")
     with torch.no_grad():
         cost, goal, passable = (_maps3(t.detach()) for t in maps)
-        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        dists, pol, status = _field_outputs(B, H, W, dev, policies)
         workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         rounds = ctypes.c_int(0)
         with torch.cuda.device(dev):
             rc = lib.nastar_cost_to_go_tiled_batched(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, dists.data_ptr(),
-                                                     pol.data_ptr() if pol is not None else None, status.data_ptr(),
-                                                     visits_out.data_ptr() if visits_out is not None else None, workspace.data_ptr(), nbytes,
+                                                     _ptr(pol), status.data_ptr(), _ptr(visits_out), workspace.data_ptr(), nbytes,
                                                      0 if max_rounds is None else max_rounds, launches_per_batch or 0,
                                                      ctypes.cast(ctypes.pointer(rounds), ctypes.c_void_p), _stream_ptr(dev))
         _native.check(rc, "nastar_cost_to_go_tiled")
@@ -1174,14 +1189,11 @@ def fields_backward_tiled(dists: torch.Tensor, goal_maps: torch.Tensor, obstacle
     with torch.no_grad():
         workspace, nbytes = _grad_tiled_workspace(lib, B, H, W, dev, "fields_backward_tiled")
         dist, goal, passable = (_maps3(t.detach()) for t in maps)
-        up = grad_dists.detach().reshape(B, H, W).contiguous()
-        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        up, grad, status = _backward_planes(grad_dists, B, H, W, dev)
         rounds = ctypes.c_int(0)
         with torch.cuda.device(dev):
             rc = lib.nastar_fields_backward_tiled(dist.data_ptr(), goal.data_ptr(), passable.data_ptr(), up.data_ptr(), B, H, W, mask, grad.data_ptr(),
-                                                  status.data_ptr(), visits_out.data_ptr() if visits_out is not None else None,
-                                                  workspace.data_ptr(), nbytes, 0 if max_rounds is None else max_rounds,
+                                                  status.data_ptr(), _ptr(visits_out), workspace.data_ptr(), nbytes, 0 if max_rounds is None else max_rounds,
                                                   ctypes.cast(ctypes.pointer(rounds), ctypes.c_void_p), _stream_ptr(dev))
         _native.check(rc, "nastar_fields_backward_tiled")
         if max_rounds is None:
@@ -1300,9 +1312,8 @@ def field_routes(dists: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: t
         def call(routes: Optional[torch.Tensor]) -> None:
             with torch.cuda.device(dev):
                 rc = lib.nastar_field_routes(dist.data_ptr(), goal.data_ptr(), passable.data_ptr(), idx.data_ptr(), B, S, H, W, mask,
-                                             routes.data_ptr() if routes is not None else None, routes.shape[2] if routes is not None else 0,
-                                             lengths.data_ptr(), costs.data_ptr(), status.data_ptr(),
-                                             workspace.data_ptr() if workspace is not None else None, nbytes, _stream_ptr(dev))
+                                             _ptr(routes), routes.shape[2] if routes is not None else 0,
+                                             lengths.data_ptr(), costs.data_ptr(), status.data_ptr(), _ptr(workspace), nbytes, _stream_ptr(dev))
             _native.check(rc, "nastar_field_routes")
 
         if max_route_len is None:
@@ -1405,10 +1416,8 @@ def path_masks_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstac
     lib = _field_lib("nastar_path_masks_backward", "nastar_path_masks.h")
     with torch.no_grad():
         cost, goal, passable = (_maps3(t.detach()) for t in maps)
-        up = grad_paths.detach().reshape(B, H, W).contiguous()
+        up, grad, status = _backward_planes(grad_paths, B, H, W, dev)
         fwd = paths_fwd.detach().reshape(B, H, W).contiguous()
-        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             rc = lib.nastar_path_masks_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), idx.data_ptr(), up.data_ptr(), fwd.data_ptr(),
                                                 status_fwd.data_ptr(), B, H, W, mask, lam, floor, grad.data_ptr(), status.data_ptr(), _stream_ptr(dev))
@@ -1438,12 +1447,7 @@ class _PathNode(torch.autograd.Function):
         cost, goal, obstacles, idx, paths, status = ctx.saved_tensors
         mask, lam, floor = ctx.step
         grad, _ = (path_masks_tiled_backward if ctx.tiled else path_masks_backward)(cost, goal, obstacles, idx, g_paths, paths, status, lam, floor, mask)
-        shape = ctx.cost_shape
-        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
-            full = grad.new_zeros(shape)
-            full[:, 0] = grad
-            grad = full
-        return (grad.reshape(shape),) + (None,) * 7
+        return (_widen_grad(grad, ctx.cost_shape),) + (None,) * 7
 
 
 def _raise_path_failures(status: torch.Tensor, B: int, what: str, bound: str, differentiable: bool) -> None:
@@ -1567,10 +1571,8 @@ def path_masks_tiled_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, 
     with torch.no_grad():
         workspace, nbytes = _path_tiled_workspace(lib, True, B, H, W, dev, "path_masks_tiled_backward")
         cost, goal, passable = (_maps3(t.detach()) for t in maps)
-        up = grad_paths.detach().reshape(B, H, W).contiguous()
+        up, grad, status = _backward_planes(grad_paths, B, H, W, dev)
         fwd = paths_fwd.detach().reshape(B, H, W).contiguous()
-        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
         rounds = ctypes.c_int(0)
         with torch.cuda.device(dev):
             rc = lib.nastar_path_masks_tiled_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), idx.data_ptr(), up.data_ptr(),
@@ -1638,33 +1640,122 @@ def _checked_horizon(horizon, H: int, W: int) -> int:
     return horizon
 
 
+# The four headers of the family by (tiled, log-policy): the header, its forward and its backward entry point -- each variant calls ITS
+# OWN: they are other kernel instantiations, and the field's are not the policy's with a NULL pointer -- and the names its refusals carry:
+# the public call in the forward's, the stem of ``<stem>_forward`` / ``<stem>_backward`` in the backward's.
+_SOFT_VARIANTS = {
+    (False, False): ("nastar_soft_fields.h", "nastar_soft_cost_to_go", "nastar_soft_fields_backward", "soft_cost_to_go", "soft_fields"),
+    (True, False): ("nastar_soft_fields_tiled.h", "nastar_soft_cost_to_go_tiled", "nastar_soft_fields_backward_tiled", "soft_cost_to_go_tiled",
+                    "soft_fields_tiled"),
+    (False, True): ("nastar_soft_policy.h", "nastar_soft_policy_forward", "nastar_soft_policy_backward", "soft_policy", "soft_policy"),
+    (True, True): ("nastar_soft_policy_tiled.h", "nastar_soft_policy_forward_tiled", "nastar_soft_policy_backward_tiled", "soft_policy_tiled",
+                   "soft_policy_tiled"),
+}
+
+
+def _soft_forward(tiled: bool, logp: bool, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies: bool, tape: bool,
+                  checkpoint_every=None, sweeps_per_launch=None):
+    """the raw forward call of the four variants: the refusals in the family's one order, the outputs, ONE C call with its arguments in
+    header order -> ``(dists, log_policies or None, policies or None, status, tape or None)``.  ``logp``: the log-policy beside the
+    other outputs; ``tiled``: ``checkpoint_every``, ``sweeps_per_launch`` and a workspace, which the one-workgroup call does not have."""
+    header, symbol, _, what, _ = _SOFT_VARIANTS[tiled, logp]
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    if tiled:
+        c = _checked_checkpoint_every(checkpoint_every, K)
+        if sweeps_per_launch is not None and (isinstance(sweeps_per_launch, bool) or not isinstance(sweeps_per_launch, int) or sweeps_per_launch < 1):
+            raise ValueError(f"sweeps_per_launch must be a positive int or None, got {sweeps_per_launch!r}")
+        _soft_tiled_limit(H, W, what)
+    else:
+        limit = SOFT_FIELDS_GRAD_MAX_CELLS if tape else SOFT_FIELDS_MAX_CELLS
+        if H * W > limit:
+            raise NotImplementedError(f"{what}: maps of {H}x{W} = {H * W} cells exceed the limit of {limit} cells{' of its backward' if tape else ''} "
+                                      f"(one workgroup keeps one map in LDS{'' if logp else '; larger maps: soft_cost_to_go_tiled'})")
+    dev = _field_device(maps)
+    lib = _field_lib(symbol, header)
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        dists, pol, status = _field_outputs(B, H, W, dev, policies)
+        log_pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if logp else None
+        tape_bytes = 0
+        if tape:
+            tape_bytes = int(lib.nastar_soft_fields_tiled_tape_bytes(B, H, W, K, c) if tiled else lib.nastar_soft_fields_tape_bytes(B, H, W, K))
+        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
+        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(), _ptr(pol))
+        if logp:
+            args += (log_pol.data_ptr(),)
+        args += (status.data_ptr(), _ptr(buf), tape_bytes)
+        entry = symbol
+        if tiled:
+            ws_bytes = int(lib.nastar_soft_fields_tiled_workspace_bytes(B, H, W))
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            args += (c, ws.data_ptr(), ws_bytes)
+            if sweeps_per_launch is not None:  # nastar_soft_cost_to_go_tiled_with_sweeps / nastar_soft_policy_forward_tiled_with_sweeps
+                entry, args = symbol + "_with_sweeps", args + (sweeps_per_launch,)
+        with torch.cuda.device(dev):
+            rc = getattr(lib, entry)(*args, _stream_ptr(dev))
+        _native.check(rc, symbol)
+    return dists, log_pol, pol, status, buf
+
+
+def _soft_backward(tiled: bool, logp: bool, cost_maps, goal_maps, obstacles_maps, tape, grad_dists, grad_log_policies, tau, horizon, neighbor_mask,
+                   checkpoint_every=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the raw backward call of the four variants, as ``_soft_forward`` is their forward -> ``(grad_cost [B,H,W], status [B] int32)``.
+    ``logp``: a second upstream gradient, and either may be None; without it ``grad_dists`` is required (``grad_log_policies`` is not
+    looked at).  ``tiled``: ``checkpoint_every`` and a workspace of the variant's own size."""
+    header, _, symbol, _, name = _SOFT_VARIANTS[tiled, logp]
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    if tiled:
+        c = _checked_checkpoint_every(checkpoint_every, K)
+    if grad_dists is not None or not logp:
+        _check_grad_dists(grad_dists, B, H, W)
+    if logp and grad_log_policies is not None and (not torch.is_tensor(grad_log_policies) or grad_log_policies.dtype != torch.float32
+                                                   or tuple(grad_log_policies.shape) != (B, 8, H, W)):
+        raise ValueError(f"grad_log_policies must be a float32 tensor of the shape of log_policies ({B}, 8, {H}, {W}), got "
+                         f"{tuple(grad_log_policies.shape) if torch.is_tensor(grad_log_policies) else type(grad_log_policies).__name__}")
+    if tiled:
+        _soft_tiled_limit(H, W, f"{name}_backward")
+    elif H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
+        raise NotImplementedError(f"{name}_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_FIELDS_GRAD_MAX_CELLS} cells")
+    if logp:
+        dev = _field_device(maps)
+        for which, g in (("grad_dists", grad_dists), ("grad_log_policies", grad_log_policies)):
+            if g is not None and g.device != dev:
+                raise ValueError(f"the maps live on {dev}, {which} on {g.device}: they must share a device")
+    else:
+        dev = _grad_device(maps, grad_dists)
+    lib = _field_lib(symbol, header)
+    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
+        raise ValueError(f"tape must be the contiguous uint8 tensor {name}_forward(..., tape=True) returned, on {dev}")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        up, grad, status = _backward_planes(grad_dists, B, H, W, dev)
+        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel()) + ((c,) if tiled else ()) + (_ptr(up),)
+        if logp:
+            upl = None if grad_log_policies is None else grad_log_policies.detach().contiguous()  # (named: it lives until the call is enqueued)
+            args += (_ptr(upl),)
+        args += (B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr())
+        if tiled:
+            sizer = lib.nastar_soft_policy_tiled_backward_workspace_bytes if logp else lib.nastar_soft_fields_tiled_backward_workspace_bytes
+            ws_bytes = int(sizer(B, H, W, K, c))
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            args += (ws.data_ptr(), ws_bytes)
+        with torch.cuda.device(dev):
+            rc = getattr(lib, symbol)(*args, _stream_ptr(dev))
+        _native.check(rc, symbol)
+    return grad, status
+
+
 def soft_fields_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
                         neighbor_mask: Optional[int] = None, policies: bool = False, tape: bool = False):
     """``nastar_soft_cost_to_go`` as it is (include/nastar_soft_fields.h) -> ``(SoftFieldOutput, tape)``: one launch on the current stream,
     nothing is read back, detached outputs.  ``tape=True`` allocates the tape of ``nastar_soft_fields_tape_bytes`` bytes (the planes
     V_1 .. V_K, what ``soft_fields_backward`` reads) and returns it as a uint8 tensor; None otherwise.  What ``soft_cost_to_go`` runs;
     probes and tests call it directly."""
-    t = _checked_tau(tau)
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    K = _checked_horizon(horizon, H, W)
-    limit = SOFT_FIELDS_GRAD_MAX_CELLS if tape else SOFT_FIELDS_MAX_CELLS
-    if H * W > limit:
-        raise NotImplementedError(f"soft_cost_to_go: maps of {H}x{W} = {H * W} cells exceed the limit of {limit} cells"
-                                  f"{' of its backward' if tape else ''} (one workgroup keeps one map in LDS; larger maps: soft_cost_to_go_tiled)")
-    dev = _field_device(maps)
-    lib = _field_lib("nastar_soft_cost_to_go", "nastar_soft_fields.h")
-    with torch.no_grad():
-        cost, goal, passable = (_maps3(m.detach()) for m in maps)
-        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        tape_bytes = int(lib.nastar_soft_fields_tape_bytes(B, H, W, K)) if tape else 0
-        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
-        with torch.cuda.device(dev):
-            rc = lib.nastar_soft_cost_to_go(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(),
-                                            pol.data_ptr() if pol is not None else None, status.data_ptr(),
-                                            buf.data_ptr() if buf is not None else None, tape_bytes, _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_cost_to_go")
+    dists, _, pol, status, buf = _soft_forward(False, False, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies, tape)
     return SoftFieldOutput(dists, pol, status), buf
 
 
@@ -1676,26 +1767,7 @@ def soft_fields_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obsta
     current stream, nothing is read back.  ``grad_dists`` is read on the cells live at the horizon only (passable, no goal, finite
     ``dists``); ``grad_cost`` is exactly 0 on a cell that was never live.  What the backward of ``soft_cost_to_go(...,
     differentiable=True)`` runs."""
-    t = _checked_tau(tau)
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    K = _checked_horizon(horizon, H, W)
-    _check_grad_dists(grad_dists, B, H, W)
-    if H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
-        raise NotImplementedError(f"soft_fields_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_FIELDS_GRAD_MAX_CELLS} cells")
-    dev = _grad_device(maps, grad_dists)
-    lib = _field_lib("nastar_soft_fields_backward", "nastar_soft_fields.h")
-    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
-        raise ValueError(f"tape must be the contiguous uint8 tensor soft_fields_forward(..., tape=True) returned, on {dev}")
-    with torch.no_grad():
-        cost, goal, passable = (_maps3(m.detach()) for m in maps)
-        up = grad_dists.detach().reshape(B, H, W).contiguous()
-        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nastar_soft_fields_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(), up.data_ptr(),
-                                                 B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr(), _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_fields_backward")
-    return grad, status
+    return _soft_backward(False, False, cost_maps, goal_maps, obstacles_maps, tape, grad_dists, None, tau, horizon, neighbor_mask)
 
 
 def soft_cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
@@ -1719,23 +1791,43 @@ def soft_cost_to_go(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_
     reads nothing back; the gradient goes to ``cost_maps`` alone and is smooth in the costs: for ``dists[b, 0, y, x]`` it is the expected
     number of visits of the soft policy on its way from (y, x) to a goal.  ``dists`` holds +inf where no goal lies within ``horizon``
     moves: a loss masks those cells itself; whatever gradient arrives for them, for goals and for obstacles is ignored."""
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    return _soft_cost_to_go(False, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies, differentiable)
+
+
+def _soft_call(tiled: bool, what: str, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, checkpoint_every):
+    """what ``soft_cost_to_go``, ``soft_policy`` and their tiled siblings refuse before anything else, in their one order -> (B, H, W) and the
+    checked ``(tau, horizon, mask, checkpoint_every)`` every raw call of the variant then takes (``checkpoint_every``: None unless tiled)"""
+    _, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
-    if differentiable and H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
+    c = None
+    if tiled:
+        c = _checked_checkpoint_every(checkpoint_every, K)
+        _soft_tiled_limit(H, W, what)
+    return (B, H, W), (t, K, mask, c)
+
+
+def _soft_cost_to_go(tiled: bool, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies, differentiable,
+                     checkpoint_every=None) -> SoftFieldOutput:
+    """the body of ``soft_cost_to_go`` and ``soft_cost_to_go_tiled``"""
+    what = "soft_cost_to_go_tiled" if tiled else "soft_cost_to_go"
+    (B, H, W), call = _soft_call(tiled, what, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, checkpoint_every)
+    if not tiled and differentiable and H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
         raise NotImplementedError(f"soft_cost_to_go: differentiable=True takes maps of at most {SOFT_FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = "
                                   f"{H * W} (larger maps: soft_cost_to_go_tiled(..., differentiable=True))")
     want_tape = differentiable and cost_maps.requires_grad and torch.is_grad_enabled()  # (asked here: inside the node grad mode is off)
+    t, K, mask, c = call
 
-    def field(c, g, o):  # -> (output, tape): the node saves the tape and the costs it was made from (_FieldNode, ``taped``)
-        out, tape = soft_fields_forward(c, g, o, t, K, mask, policies, tape=want_tape)
+    def field(cm, g, o):  # -> (output, tape): the node saves the tape and the costs it was made from (_FieldNode, ``taped``)
+        dists, _, pol, status, tape = _soft_forward(tiled, False, cm, g, o, t, K, mask, policies, want_tape, c)
         if not torch.cuda.is_current_stream_capturing():
-            _raise_bad_cost(out.status.cpu(), B, "soft_cost_to_go")
-        return out, tape
+            _raise_bad_cost(status.cpu(), B, what)
+        return SoftFieldOutput(dists, pol, status), tape
 
     if not differentiable:
         return field(cost_maps, goal_maps, obstacles_maps)[0]
     return SoftFieldOutput(*_differentiable_field(cost_maps, goal_maps, obstacles_maps, field,
-                                                  lambda d, g, o, c, tape, up: soft_fields_backward(c, g, o, tape, up, t, K, mask)[0], taped=True))
+                                                  lambda d, g, o, cm, tape, up: _soft_backward(tiled, False, cm, g, o, tape, up, None, *call)[0],
+                                                  taped=True))
 
 
 def maxent_path_nll(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
@@ -1793,33 +1885,8 @@ def soft_fields_tiled_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, 
     ``nastar_soft_fields_tiled_tape_bytes`` bytes (the planes at the multiples of ``checkpoint_every`` and plane K; None = ceil(sqrt(K)))
     and returns it as a uint8 tensor; None otherwise.  ``sweeps_per_launch``: 1 .. S instead of S, the same bits in more launches (probes
     and tests only).  What ``soft_cost_to_go_tiled`` runs."""
-    t = _checked_tau(tau)
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    K = _checked_horizon(horizon, H, W)
-    c = _checked_checkpoint_every(checkpoint_every, K)
-    if sweeps_per_launch is not None and (isinstance(sweeps_per_launch, bool) or not isinstance(sweeps_per_launch, int) or sweeps_per_launch < 1):
-        raise ValueError(f"sweeps_per_launch must be a positive int or None, got {sweeps_per_launch!r}")
-    _soft_tiled_limit(H, W, "soft_cost_to_go_tiled")
-    dev = _field_device(maps)
-    lib = _field_lib("nastar_soft_cost_to_go_tiled", "nastar_soft_fields_tiled.h")
-    with torch.no_grad():
-        cost, goal, passable = (_maps3(m.detach()) for m in maps)
-        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        tape_bytes = int(lib.nastar_soft_fields_tiled_tape_bytes(B, H, W, K, c)) if tape else 0
-        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
-        ws_bytes = int(lib.nastar_soft_fields_tiled_workspace_bytes(B, H, W))
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(),
-                pol.data_ptr() if pol is not None else None, status.data_ptr(), buf.data_ptr() if buf is not None else None, tape_bytes, c,
-                ws.data_ptr(), ws_bytes)
-        with torch.cuda.device(dev):
-            if sweeps_per_launch is None:
-                rc = lib.nastar_soft_cost_to_go_tiled(*args, _stream_ptr(dev))
-            else:
-                rc = lib.nastar_soft_cost_to_go_tiled_with_sweeps(*args, sweeps_per_launch, _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_cost_to_go_tiled")
+    dists, _, pol, status, buf = _soft_forward(True, False, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies, tape,
+                                               checkpoint_every, sweeps_per_launch)
     return SoftFieldOutput(dists, pol, status), buf
 
 
@@ -1831,29 +1898,7 @@ def soft_fields_tiled_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor,
     ``(grad_cost [B,H,W], status [B] int32)``.  One launch per step and the recomputation of every segment on the current stream, nothing
     is read back.  ``grad_dists`` is read on the cells live at the horizon only; ``grad_cost`` is exactly 0 on a cell that was never
     live.  What the backward of ``soft_cost_to_go_tiled(..., differentiable=True)`` runs."""
-    t = _checked_tau(tau)
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    K = _checked_horizon(horizon, H, W)
-    c = _checked_checkpoint_every(checkpoint_every, K)
-    _check_grad_dists(grad_dists, B, H, W)
-    _soft_tiled_limit(H, W, "soft_fields_tiled_backward")
-    dev = _grad_device(maps, grad_dists)
-    lib = _field_lib("nastar_soft_fields_backward_tiled", "nastar_soft_fields_tiled.h")
-    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
-        raise ValueError(f"tape must be the contiguous uint8 tensor soft_fields_tiled_forward(..., tape=True) returned, on {dev}")
-    with torch.no_grad():
-        cost, goal, passable = (_maps3(m.detach()) for m in maps)
-        up = grad_dists.detach().reshape(B, H, W).contiguous()
-        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        ws_bytes = int(lib.nastar_soft_fields_tiled_backward_workspace_bytes(B, H, W, K, c))
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nastar_soft_fields_backward_tiled(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(), c,
-                                                       up.data_ptr(), B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                                       ws_bytes, _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_fields_backward_tiled")
-    return grad, status
+    return _soft_backward(True, False, cost_maps, goal_maps, obstacles_maps, tape, grad_dists, None, tau, horizon, neighbor_mask, checkpoint_every)
 
 
 def soft_cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
@@ -1871,23 +1916,7 @@ def soft_cost_to_go_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obst
     reading nothing back.  ``checkpoint_every=None`` is ceil(sqrt(horizon)): about 2 sqrt(horizon) planes per map instead of ``horizon``,
     for one more forward; ``checkpoint_every=1`` keeps every plane, for the caller who has the memory.  The gradient does not depend on
     it."""
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
-    c = _checked_checkpoint_every(checkpoint_every, K)
-    _soft_tiled_limit(H, W, "soft_cost_to_go_tiled")
-    want_tape = differentiable and cost_maps.requires_grad and torch.is_grad_enabled()  # (asked here: inside the node grad mode is off)
-
-    def field(cm, g, o):  # -> (output, tape): the node saves the tape and the costs it was made from (_FieldNode, ``taped``)
-        out, tape = soft_fields_tiled_forward(cm, g, o, t, K, mask, policies, tape=want_tape, checkpoint_every=c)
-        if not torch.cuda.is_current_stream_capturing():
-            _raise_bad_cost(out.status.cpu(), B, "soft_cost_to_go_tiled")
-        return out, tape
-
-    if not differentiable:
-        return field(cost_maps, goal_maps, obstacles_maps)[0]
-    return SoftFieldOutput(*_differentiable_field(cost_maps, goal_maps, obstacles_maps, field,
-                                                  lambda d, g, o, cm, tape, up: soft_fields_tiled_backward(cm, g, o, tape, up, t, K, mask, c)[0],
-                                                  taped=True))
+    return _soft_cost_to_go(True, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies, differentiable, checkpoint_every)
 
 
 def maxent_path_nll_tiled(cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
@@ -1920,29 +1949,8 @@ def soft_policy_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstac
     """``nastar_soft_policy_forward`` as it is (include/nastar_soft_policy.h) -> ``(SoftPolicyOutput, tape)``: ``soft_fields_forward`` with
     the log-policy beside its outputs -- one launch on the current stream, nothing is read back, detached outputs, the same bits in
     ``dists``, ``policies``, ``status`` and the tape.  What ``soft_policy`` runs; probes and tests call it directly."""
-    t = _checked_tau(tau)
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    K = _checked_horizon(horizon, H, W)
-    limit = SOFT_FIELDS_GRAD_MAX_CELLS if tape else SOFT_FIELDS_MAX_CELLS
-    if H * W > limit:
-        raise NotImplementedError(f"soft_policy: maps of {H}x{W} = {H * W} cells exceed the limit of {limit} cells"
-                                  f"{' of its backward' if tape else ''} (one workgroup keeps one map in LDS)")
-    dev = _field_device(maps)
-    lib = _field_lib("nastar_soft_policy_forward", "nastar_soft_policy.h")
-    with torch.no_grad():
-        cost, goal, passable = (_maps3(m.detach()) for m in maps)
-        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        logp = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
-        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        tape_bytes = int(lib.nastar_soft_fields_tape_bytes(B, H, W, K)) if tape else 0
-        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
-        with torch.cuda.device(dev):
-            rc = lib.nastar_soft_policy_forward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(),
-                                                pol.data_ptr() if pol is not None else None, logp.data_ptr(), status.data_ptr(),
-                                                buf.data_ptr() if buf is not None else None, tape_bytes, _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_policy_forward")
-    return SoftPolicyOutput(dists, logp, pol, status), buf
+    out = _soft_forward(False, True, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies, tape)
+    return SoftPolicyOutput(*out[:4]), out[4]
 
 
 def soft_policy_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
@@ -1953,66 +1961,53 @@ def soft_policy_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obsta
     ([B,8,H,W]); either may be None (zeros) -> ``(grad_cost [B,H,W], status [B] int32)``.  One launch on the current stream, nothing is read
     back.  ``grad_log_policies`` is read only where the log-policy is finite; with None for it the result is ``soft_fields_backward``'s, bit
     for bit.  What the backward of ``soft_policy`` runs."""
-    t = _checked_tau(tau)
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    K = _checked_horizon(horizon, H, W)
-    if grad_dists is not None:
-        _check_grad_dists(grad_dists, B, H, W)
-    if grad_log_policies is not None and (not torch.is_tensor(grad_log_policies) or grad_log_policies.dtype != torch.float32
-                                          or tuple(grad_log_policies.shape) != (B, 8, H, W)):
-        raise ValueError(f"grad_log_policies must be a float32 tensor of the shape of log_policies ({B}, 8, {H}, {W}), got "
-                         f"{tuple(grad_log_policies.shape) if torch.is_tensor(grad_log_policies) else type(grad_log_policies).__name__}")
-    if H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
-        raise NotImplementedError(f"soft_policy_backward: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_FIELDS_GRAD_MAX_CELLS} cells")
-    dev = _field_device(maps)
-    for name, g in (("grad_dists", grad_dists), ("grad_log_policies", grad_log_policies)):
-        if g is not None and g.device != dev:
-            raise ValueError(f"the maps live on {dev}, {name} on {g.device}: they must share a device")
-    lib = _field_lib("nastar_soft_policy_backward", "nastar_soft_policy.h")
-    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
-        raise ValueError(f"tape must be the contiguous uint8 tensor soft_policy_forward(..., tape=True) returned, on {dev}")
-    with torch.no_grad():
-        cost, goal, passable = (_maps3(m.detach()) for m in maps)
-        up = grad_dists.detach().reshape(B, H, W).contiguous() if grad_dists is not None else None
-        upl = grad_log_policies.detach().contiguous() if grad_log_policies is not None else None
-        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nastar_soft_policy_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(),
-                                                 up.data_ptr() if up is not None else None, upl.data_ptr() if upl is not None else None,
-                                                 B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr(), _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_policy_backward")
-    return grad, status
+    return _soft_backward(False, True, cost_maps, goal_maps, obstacles_maps, tape, grad_dists, grad_log_policies, tau, horizon, neighbor_mask)
+
+
+def _soft_policy_checked(tiled: bool, cost_maps, goal_maps, obstacles_maps, call, tape: bool):
+    """the raw forward of ``soft_policy`` / ``soft_policy_tiled`` (``call``: ``_soft_call``'s) and their one status read (none inside a stream
+    capture) -> ``(dists, log_policies, policies, status, tape or None)``"""
+    t, K, mask, c = call
+    out = _soft_forward(tiled, True, cost_maps, goal_maps, obstacles_maps, t, K, mask, True, tape, c)
+    if not torch.cuda.is_current_stream_capturing():
+        _raise_bad_cost(out[3].cpu(), out[3].numel(), "soft_policy_tiled" if tiled else "soft_policy")
+    return out
 
 
 class _SoftPolicyNode(torch.autograd.Function):
-    """``soft_policy_forward`` as ONE autograd node with two differentiable outputs, ``dists`` and ``log_policies``: its backward is one
-    launch of ``nastar_soft_policy_backward`` with whichever of the two upstream gradients arrived, and reads nothing back."""
+    """``soft_policy_forward`` -- ``tiled``: ``soft_policy_tiled_forward`` -- as ONE autograd node with two differentiable outputs, ``dists``
+    and ``log_policies``: its backward is one call of ``nastar_soft_policy_backward`` (``nastar_soft_policy_backward_tiled``) with whichever
+    of the two upstream gradients arrived, and reads nothing back.  ``call``: the checked ``(tau, horizon, mask, checkpoint_every)``."""
 
     @staticmethod
-    def forward(ctx, cost_maps, goal_maps, obstacles_maps, tau, horizon, mask):
-        out, tape = soft_policy_forward(cost_maps, goal_maps, obstacles_maps, tau, horizon, mask, policies=True, tape=True)
-        if not torch.cuda.is_current_stream_capturing():
-            _raise_bad_cost(out.status.cpu(), out.status.numel(), "soft_policy")
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, tiled, call):
+        dists, log_policies, policies, status, tape = _soft_policy_checked(tiled, cost_maps, goal_maps, obstacles_maps, call, tape=True)
         ctx.save_for_backward(cost_maps, goal_maps, obstacles_maps, tape)
-        ctx.call = (tau, horizon, mask)
-        ctx.mark_non_differentiable(out.policies, out.status)
+        ctx.tiled, ctx.call = tiled, call
+        ctx.mark_non_differentiable(policies, status)
         ctx.set_materialize_grads(False)
-        return out.dists, out.log_policies, out.policies, out.status
+        return dists, log_policies, policies, status
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_dists, g_logp, *unused):
         if (g_dists is None and g_logp is None) or not ctx.needs_input_grad[0]:
-            return (None,) * 6
+            return (None,) * 5
         cost_maps, goal_maps, obstacles_maps, tape = ctx.saved_tensors
-        grad = soft_policy_backward(cost_maps, goal_maps, obstacles_maps, tape, g_dists, g_logp, *ctx.call)[0]
-        shape = tuple(cost_maps.shape)
-        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
-            full = grad.new_zeros(shape)
-            full[:, 0] = grad
-            grad = full
-        return (grad.reshape(shape), None, None, None, None, None)
+        grad = _soft_backward(ctx.tiled, True, cost_maps, goal_maps, obstacles_maps, tape, g_dists, g_logp, *ctx.call)[0]
+        return (_widen_grad(grad, tuple(cost_maps.shape)), None, None, None, None)
+
+
+def _soft_policy(tiled: bool, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, checkpoint_every=None) -> SoftPolicyOutput:
+    """the body of ``soft_policy`` and ``soft_policy_tiled``"""
+    what = "soft_policy_tiled" if tiled else "soft_policy"
+    (B, H, W), call = _soft_call(tiled, what, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, checkpoint_every)
+    if cost_maps.requires_grad and torch.is_grad_enabled():
+        if not tiled and H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
+            raise NotImplementedError(f"soft_policy: a differentiable call takes maps of at most {SOFT_FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = "
+                                      f"{H * W}")
+        return SoftPolicyOutput(*_SoftPolicyNode.apply(cost_maps, goal_maps, obstacles_maps, tiled, call))
+    return SoftPolicyOutput(*_soft_policy_checked(tiled, cost_maps, goal_maps, obstacles_maps, call, tape=False)[:4])
 
 
 def soft_policy(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
@@ -2031,17 +2026,7 @@ def soft_policy(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
     ``SOFT_FIELDS_MAX_CELLS`` cells are taken.  ``policies`` is detached either way.  The per-map status is read before returning as
     ``soft_cost_to_go`` reads it (one host synchronisation; not inside a stream capture), with the same ValueError for a NaN or a
     negative cost."""
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
-    if cost_maps.requires_grad and torch.is_grad_enabled():
-        if H * W > SOFT_FIELDS_GRAD_MAX_CELLS:
-            raise NotImplementedError(f"soft_policy: a differentiable call takes maps of at most {SOFT_FIELDS_GRAD_MAX_CELLS} cells, got {H}x{W} = "
-                                      f"{H * W}")
-        return SoftPolicyOutput(*_SoftPolicyNode.apply(cost_maps, goal_maps, obstacles_maps, t, K, mask))
-    out, _ = soft_policy_forward(cost_maps, goal_maps, obstacles_maps, t, K, mask, policies=True)
-    if not torch.cuda.is_current_stream_capturing():
-        _raise_bad_cost(out.status.cpu(), B, "soft_policy")
-    return out
+    return _soft_policy(False, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask)
 
 
 def soft_policy_nll(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, opt_policies: torch.Tensor, tau: float,
@@ -2091,35 +2076,9 @@ def soft_policy_tiled_forward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, 
     ``soft_fields_tiled_forward`` with the log-policy beside its outputs, written by the launch that reaches the horizon -- the same
     launches on the current stream, nothing is read back, detached outputs, the same bits in ``dists``, ``policies``, ``status`` and the
     tape.  ``tape``, ``checkpoint_every`` and ``sweeps_per_launch`` as there.  What ``soft_policy_tiled`` runs."""
-    t = _checked_tau(tau)
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    K = _checked_horizon(horizon, H, W)
-    c = _checked_checkpoint_every(checkpoint_every, K)
-    if sweeps_per_launch is not None and (isinstance(sweeps_per_launch, bool) or not isinstance(sweeps_per_launch, int) or sweeps_per_launch < 1):
-        raise ValueError(f"sweeps_per_launch must be a positive int or None, got {sweeps_per_launch!r}")
-    _soft_tiled_limit(H, W, "soft_policy_tiled")
-    dev = _field_device(maps)
-    lib = _field_lib("nastar_soft_policy_forward_tiled", "nastar_soft_policy_tiled.h")
-    with torch.no_grad():
-        cost, goal, passable = (_maps3(m.detach()) for m in maps)
-        dists = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        logp = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
-        pol = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev) if policies else None
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        tape_bytes = int(lib.nastar_soft_fields_tiled_tape_bytes(B, H, W, K, c)) if tape else 0
-        buf = torch.empty((tape_bytes,), dtype=torch.uint8, device=dev) if tape else None
-        ws_bytes = int(lib.nastar_soft_fields_tiled_workspace_bytes(B, H, W))
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), B, H, W, mask, t, K, dists.data_ptr(),
-                pol.data_ptr() if pol is not None else None, logp.data_ptr(), status.data_ptr(), buf.data_ptr() if buf is not None else None,
-                tape_bytes, c, ws.data_ptr(), ws_bytes)
-        with torch.cuda.device(dev):
-            if sweeps_per_launch is None:
-                rc = lib.nastar_soft_policy_forward_tiled(*args, _stream_ptr(dev))
-            else:
-                rc = lib.nastar_soft_policy_forward_tiled_with_sweeps(*args, sweeps_per_launch, _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_policy_forward_tiled")
-    return SoftPolicyOutput(dists, logp, pol, status), buf
+    out = _soft_forward(True, True, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies, tape, checkpoint_every,
+                        sweeps_per_launch)
+    return SoftPolicyOutput(*out[:4]), out[4]
 
 
 def soft_policy_tiled_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
@@ -2132,70 +2091,8 @@ def soft_policy_tiled_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor,
     ``soft_fields_tiled_backward`` on the current stream, the one of step ``horizon`` carrying the log-policy seed; nothing is read back.
     ``grad_log_policies`` is read only where the log-policy is finite; with None for it the result is ``soft_fields_tiled_backward``'s,
     bit for bit.  What the backward of ``soft_policy_tiled`` runs."""
-    t = _checked_tau(tau)
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    K = _checked_horizon(horizon, H, W)
-    c = _checked_checkpoint_every(checkpoint_every, K)
-    if grad_dists is not None:
-        _check_grad_dists(grad_dists, B, H, W)
-    if grad_log_policies is not None and (not torch.is_tensor(grad_log_policies) or grad_log_policies.dtype != torch.float32
-                                          or tuple(grad_log_policies.shape) != (B, 8, H, W)):
-        raise ValueError(f"grad_log_policies must be a float32 tensor of the shape of log_policies ({B}, 8, {H}, {W}), got "
-                         f"{tuple(grad_log_policies.shape) if torch.is_tensor(grad_log_policies) else type(grad_log_policies).__name__}")
-    _soft_tiled_limit(H, W, "soft_policy_tiled_backward")
-    dev = _field_device(maps)
-    for name, g in (("grad_dists", grad_dists), ("grad_log_policies", grad_log_policies)):
-        if g is not None and g.device != dev:
-            raise ValueError(f"the maps live on {dev}, {name} on {g.device}: they must share a device")
-    lib = _field_lib("nastar_soft_policy_backward_tiled", "nastar_soft_policy_tiled.h")
-    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
-        raise ValueError(f"tape must be the contiguous uint8 tensor soft_policy_tiled_forward(..., tape=True) returned, on {dev}")
-    with torch.no_grad():
-        cost, goal, passable = (_maps3(m.detach()) for m in maps)
-        up = grad_dists.detach().reshape(B, H, W).contiguous() if grad_dists is not None else None
-        upl = grad_log_policies.detach().contiguous() if grad_log_policies is not None else None
-        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        ws_bytes = int(lib.nastar_soft_policy_tiled_backward_workspace_bytes(B, H, W, K, c))
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.nastar_soft_policy_backward_tiled(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(), c,
-                                                       up.data_ptr() if up is not None else None, upl.data_ptr() if upl is not None else None,
-                                                       B, H, W, mask, t, K, grad.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes,
-                                                       _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_policy_backward_tiled")
-    return grad, status
-
-
-class _SoftPolicyTiledNode(torch.autograd.Function):
-    """``soft_policy_tiled_forward`` as ONE autograd node with two differentiable outputs, ``dists`` and ``log_policies``: its backward is
-    one call of ``nastar_soft_policy_backward_tiled`` with whichever of the two upstream gradients arrived, and reads nothing back."""
-
-    @staticmethod
-    def forward(ctx, cost_maps, goal_maps, obstacles_maps, tau, horizon, mask, checkpoint_every):
-        out, tape = soft_policy_tiled_forward(cost_maps, goal_maps, obstacles_maps, tau, horizon, mask, policies=True, tape=True,
-                                              checkpoint_every=checkpoint_every)
-        if not torch.cuda.is_current_stream_capturing():
-            _raise_bad_cost(out.status.cpu(), out.status.numel(), "soft_policy_tiled")
-        ctx.save_for_backward(cost_maps, goal_maps, obstacles_maps, tape)
-        ctx.call = (tau, horizon, mask, checkpoint_every)
-        ctx.mark_non_differentiable(out.policies, out.status)
-        ctx.set_materialize_grads(False)
-        return out.dists, out.log_policies, out.policies, out.status
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_dists, g_logp, *unused):
-        if (g_dists is None and g_logp is None) or not ctx.needs_input_grad[0]:
-            return (None,) * 7
-        cost_maps, goal_maps, obstacles_maps, tape = ctx.saved_tensors
-        grad = soft_policy_tiled_backward(cost_maps, goal_maps, obstacles_maps, tape, g_dists, g_logp, *ctx.call)[0]
-        shape = tuple(cost_maps.shape)
-        if len(shape) == 4 and shape[1] > 1:  # channel 0 is the cost map (``_maps3``)
-            full = grad.new_zeros(shape)
-            full[:, 0] = grad
-            grad = full
-        return (grad.reshape(shape), None, None, None, None, None, None)
+    return _soft_backward(True, True, cost_maps, goal_maps, obstacles_maps, tape, grad_dists, grad_log_policies, tau, horizon, neighbor_mask,
+                          checkpoint_every)
 
 
 def soft_policy_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float, horizon: Optional[int] = None,
@@ -2212,16 +2109,7 @@ def soft_policy_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacle
     carrying the gradient of ``log_policies``; it reads nothing back.  The gradient of ``log_policies`` is read only where they are
     finite.  Otherwise no graph is built and no tape is kept.  ``policies`` is detached either way.  The per-map status is read once
     before returning (not inside a stream capture), with the ValueError of ``soft_policy`` for a NaN or a negative cost."""
-    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    t, K = _checked_tau(tau), _checked_horizon(horizon, H, W)
-    c = _checked_checkpoint_every(checkpoint_every, K)
-    _soft_tiled_limit(H, W, "soft_policy_tiled")
-    if cost_maps.requires_grad and torch.is_grad_enabled():
-        return SoftPolicyOutput(*_SoftPolicyTiledNode.apply(cost_maps, goal_maps, obstacles_maps, t, K, mask, c))
-    out, _ = soft_policy_tiled_forward(cost_maps, goal_maps, obstacles_maps, t, K, mask, policies=True, checkpoint_every=c)
-    if not torch.cuda.is_current_stream_capturing():
-        _raise_bad_cost(out.status.cpu(), B, "soft_policy_tiled")
-    return out
+    return _soft_policy(True, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, checkpoint_every)
 
 
 def soft_policy_nll_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, opt_policies: torch.Tensor, tau: float,

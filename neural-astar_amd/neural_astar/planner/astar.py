@@ -320,16 +320,20 @@ class NeuralAstar(VanillaAstar):
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
         return self.astar.plan_routes(cost_maps, start_maps, goal_maps, obstacles_maps, heuristic_maps, max_route_len)
 
+    def _field_inputs(self, map_designs, start_maps, goal_maps, detach: bool):
+        """``(cost_maps, obstacles_maps)`` of a field call: the PREDICTED cost maps -- ``detach``: cut from the encoder -- and the obstacles
+        the search would see (``learn_obstacles``: every cell passable)"""
+        cost_maps = self.encode(map_designs, start_maps, goal_maps)
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        return (cost_maps.detach() if detach else cost_maps), obstacles_maps
+
     def cost_to_go(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True,
                    tiled: bool = False, differentiable: bool = False) -> FieldOutput:
         """The cost-to-go field and optimal policy of the PREDICTED cost maps: encodes as ``plan_routes()`` does (detached), then
         ``DifferentiableAstar.cost_to_go``; ``learn_obstacles`` makes every cell passable, as it does for the search.
         ``differentiable=True``: the encoded cost maps are NOT detached, so the gradient of ``dists`` reaches the encoder's parameters
         (value-function supervision; the loss masks the +inf cells itself).  The encoder route is what ``encode()`` picks in that mode."""
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        if not differentiable:
-            cost_maps = cost_maps.detach()
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=not differentiable)
         return self.astar.cost_to_go(cost_maps, goal_maps, obstacles_maps, policies, tiled, differentiable)
 
     def cost_to_go_tiled(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, policies: bool = True,
@@ -337,10 +341,7 @@ class NeuralAstar(VanillaAstar):
         """``cost_to_go`` of the PREDICTED cost maps by the tiled relaxation (maps of up to 1024x1152; the call blocks).
         ``differentiable=True``: the encoded cost maps are NOT detached, exactly as in ``cost_to_go``, so a loss on ``dists`` trains the
         encoder on maps of any size the search takes (include/nastar_fields_grad_tiled.h)."""
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        if not differentiable:
-            cost_maps = cost_maps.detach()
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=not differentiable)
         return self.astar.cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, policies, differentiable)
 
     def soft_cost_to_go(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, tau: float,
@@ -348,10 +349,7 @@ class NeuralAstar(VanillaAstar):
         """The entropy-regularised cost-to-go field of the PREDICTED cost maps: encodes as ``cost_to_go()`` does (detached unless
         ``differentiable``), then ``DifferentiableAstar.soft_cost_to_go``; ``learn_obstacles`` makes every cell passable."""
         ops._checked_tau(tau)  # (before the encoder launches anything)
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        if not differentiable:
-            cost_maps = cost_maps.detach()
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=not differentiable)
         return self.astar.soft_cost_to_go(cost_maps, goal_maps, obstacles_maps, tau, horizon, policies, differentiable)
 
     def soft_cost_to_go_tiled(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, tau: float,
@@ -360,10 +358,7 @@ class NeuralAstar(VanillaAstar):
         """``soft_cost_to_go`` of the PREDICTED cost maps by tiled sweeps (``DifferentiableAstar.soft_cost_to_go_tiled``: maps of up to
         1024x1152, the same bits)."""
         ops._checked_tau(tau)  # (before the encoder launches anything)
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        if not differentiable:
-            cost_maps = cost_maps.detach()
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=not differentiable)
         return self.astar.soft_cost_to_go_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, policies, differentiable, checkpoint_every)
 
     def maxent_path_nll(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, opt_trajs: torch.Tensor,
@@ -373,8 +368,7 @@ class NeuralAstar(VanillaAstar):
         gradient (demonstration - expected visits) / tau; ``learn_obstacles`` makes every cell passable.  ``tiled=True``: on the tiled
         field (maps of up to 1024x1152), with its ``checkpoint_every``."""
         ops._checked_tau(tau)  # (before the encoder launches anything)
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=False)
         return self.astar.maxent_path_nll(cost_maps, start_maps, goal_maps, obstacles_maps, opt_trajs, tau, horizon, tiled, checkpoint_every)
 
     def soft_policy(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, tau: float,
@@ -383,8 +377,7 @@ class NeuralAstar(VanillaAstar):
         NOT detached, so a loss on ``dists`` or ``log_policies`` trains the encoder (no graph under ``torch.no_grad()``);
         ``learn_obstacles`` makes every cell passable."""
         ops._checked_tau(tau)  # (before the encoder launches anything)
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=False)
         return self.astar.soft_policy(cost_maps, goal_maps, obstacles_maps, tau, horizon)
 
     def soft_policy_tiled(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, tau: float,
@@ -392,8 +385,7 @@ class NeuralAstar(VanillaAstar):
         """``soft_policy`` of the PREDICTED cost maps by tiled sweeps (``DifferentiableAstar.soft_policy_tiled``: maps of up to 1024x1152,
         the same bits): encodes as ``soft_policy`` does, NOT detached."""
         ops._checked_tau(tau)  # (before the encoder launches anything)
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=False)
         return self.astar.soft_policy_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, checkpoint_every)
 
     def policy_nll(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, opt_policies: torch.Tensor,
@@ -404,8 +396,7 @@ class NeuralAstar(VanillaAstar):
         ``learn_obstacles`` makes every cell passable.  ``tiled=True``: on the tiled policy (maps of up to 1024x1152), with its
         ``checkpoint_every``."""
         ops._checked_tau(tau)  # (before the encoder launches anything)
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=False)
         return self.astar.policy_nll(cost_maps, goal_maps, obstacles_maps, opt_policies, tau, horizon, tiled, checkpoint_every)
 
     def plan_many(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, max_route_len: Optional[int] = None,
@@ -444,8 +435,5 @@ class NeuralAstar(VanillaAstar):
         if lambda_ is not None:
             ops._checked_step(lambda_, "lambda_")  # (both refusals before the encoder launches anything)
         ops._checked_step(min_cost, "min_cost")
-        cost_maps = self.encode(map_designs, start_maps, goal_maps)
-        if lambda_ is None:
-            cost_maps = cost_maps.detach()
-        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(start_maps)
+        cost_maps, obstacles_maps = self._field_inputs(map_designs, start_maps, goal_maps, detach=lambda_ is None)
         return cost_maps, start_maps, goal_maps, obstacles_maps

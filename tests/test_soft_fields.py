@@ -7,7 +7,8 @@
 4. the numpy definition (tests/soft_fields_oracle.py) against ``torch.logsumexp`` and torch autograd in float64;
 5. the sandwich D - K tau ln(moves) <= V_K <= D against the exact field, and V_K = +inf exactly where no goal lies within K hops;
 6. the negative log-likelihood of a demonstration is >= 0; the float32 restatement stays inside the committed bounds;
-7. the Python refusals made before a launch, and the planner methods.
+7. the Python refusals made before a launch, and the planner methods;
+8. the signatures of the family's public functions and of the planners' soft methods, as literal strings.
 """
 import inspect
 import math
@@ -304,3 +305,143 @@ def test_refusals_before_a_launch_and_the_planner_methods():
         NeuralAstar().maxent_path_nll(m, m, m, m, -1.0)
     with pytest.raises(RuntimeError, match="HIP device"):
         DifferentiableAstar().soft_cost_to_go(m, m, m, 0.5)
+
+
+# ---- 8: the public signatures of the soft family, ops and planners: what callers, probes and the planners' pass-through rely on -----------------
+OPS_SIGNATURES = {
+    "soft_fields_forward":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, policies: 'bool' = False, tape: 'bool' = False)",
+    "soft_fields_backward":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tape: 'torch.Tensor', "
+        "grad_dists: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None) -> "
+        "'Tuple[torch.Tensor, torch.Tensor]'",
+    "soft_fields_tiled_forward":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, policies: 'bool' = False, tape: 'bool' = False, "
+        "checkpoint_every: 'Optional[int]' = None, sweeps_per_launch: 'Optional[int]' = None)",
+    "soft_fields_tiled_backward":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tape: 'torch.Tensor', "
+        "grad_dists: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, "
+        "checkpoint_every: 'Optional[int]' = None) -> 'Tuple[torch.Tensor, torch.Tensor]'",
+    "soft_policy_forward":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, policies: 'bool' = True, tape: 'bool' = False)",
+    "soft_policy_backward":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tape: 'torch.Tensor', "
+        "grad_dists: 'Optional[torch.Tensor]', grad_log_policies: 'Optional[torch.Tensor]', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None) -> 'Tuple[torch.Tensor, torch.Tensor]'",
+    "soft_policy_tiled_forward":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, policies: 'bool' = True, tape: 'bool' = False, "
+        "checkpoint_every: 'Optional[int]' = None, sweeps_per_launch: 'Optional[int]' = None)",
+    "soft_policy_tiled_backward":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tape: 'torch.Tensor', "
+        "grad_dists: 'Optional[torch.Tensor]', grad_log_policies: 'Optional[torch.Tensor]', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, checkpoint_every: 'Optional[int]' = None) -> "
+        "'Tuple[torch.Tensor, torch.Tensor]'",
+    "soft_cost_to_go":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, policies: 'bool' = False, differentiable: 'bool' = "
+        "False) -> 'SoftFieldOutput'",
+    "soft_cost_to_go_tiled":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, policies: 'bool' = False, differentiable: 'bool' = "
+        "False, checkpoint_every: 'Optional[int]' = None) -> 'SoftFieldOutput'",
+    "soft_policy":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None) -> 'SoftPolicyOutput'",
+    "soft_policy_tiled":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, checkpoint_every: 'Optional[int]' = None) -> "
+        "'SoftPolicyOutput'",
+    "maxent_path_nll":
+        "(cost_maps: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', "
+        "opt_trajs: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None) -> "
+        "'torch.Tensor'",
+    "maxent_path_nll_tiled":
+        "(cost_maps: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', "
+        "opt_trajs: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, "
+        "checkpoint_every: 'Optional[int]' = None) -> 'torch.Tensor'",
+    "soft_policy_nll":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', opt_policies: 'torch.Tensor', "
+        "tau: 'float', horizon: 'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None) -> 'torch.Tensor'",
+    "soft_policy_nll_tiled":
+        "(cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', opt_policies: 'torch.Tensor', "
+        "tau: 'float', horizon: 'Optional[int]' = None, neighbor_mask: 'Optional[int]' = None, checkpoint_every: "
+        "'Optional[int]' = None) -> 'torch.Tensor'",
+}
+PLANNER_SIGNATURES = {
+    ("DifferentiableAstar", "soft_cost_to_go"):
+        "(self, cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, policies: 'bool' = False, differentiable: 'bool' = False) -> " '"\'ops.SoftFieldOutput\'"',
+    ("DifferentiableAstar", "soft_cost_to_go_tiled"):
+        "(self, cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, policies: 'bool' = False, differentiable: 'bool' = False, checkpoint_every: 'Optional[int]' = "
+        "None) -> " '"\'ops.SoftFieldOutput\'"',
+    ("DifferentiableAstar", "maxent_path_nll"):
+        "(self, cost_maps: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: "
+        "'torch.Tensor', opt_trajs: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, tiled: 'bool' = False, "
+        "checkpoint_every: 'Optional[int]' = None) -> 'torch.Tensor'",
+    ("DifferentiableAstar", "soft_policy"):
+        "(self, cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None) -> " '"\'ops.SoftPolicyOutput\'"',
+    ("DifferentiableAstar", "soft_policy_tiled"):
+        "(self, cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, checkpoint_every: 'Optional[int]' = None) -> " '"\'ops.SoftPolicyOutput\'"',
+    ("DifferentiableAstar", "policy_nll"):
+        "(self, cost_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', obstacles_maps: 'torch.Tensor', opt_policies: "
+        "'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, tiled: 'bool' = False, checkpoint_every: "
+        "'Optional[int]' = None) -> 'torch.Tensor'",
+    ("VanillaAstar", "soft_cost_to_go"):
+        "(self, map_designs: 'torch.Tensor', goal_maps: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, "
+        "policies: 'bool' = False, differentiable: 'bool' = False)",
+    ("VanillaAstar", "soft_cost_to_go_tiled"):
+        "(self, map_designs: 'torch.Tensor', goal_maps: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, "
+        "policies: 'bool' = False, differentiable: 'bool' = False, checkpoint_every: 'Optional[int]' = None)",
+    ("VanillaAstar", "maxent_path_nll"):
+        "(self, map_designs: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', opt_trajs: 'torch.Tensor', "
+        "tau: 'float', horizon: 'Optional[int]' = None, tiled: 'bool' = False, checkpoint_every: 'Optional[int]' = None) -> "
+        "'torch.Tensor'",
+    ("VanillaAstar", "soft_policy"):
+        "(self, map_designs: 'torch.Tensor', goal_maps: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None)",
+    ("VanillaAstar", "soft_policy_tiled"):
+        "(self, map_designs: 'torch.Tensor', goal_maps: 'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, "
+        "checkpoint_every: 'Optional[int]' = None)",
+    ("VanillaAstar", "policy_nll"):
+        "(self, map_designs: 'torch.Tensor', goal_maps: 'torch.Tensor', opt_policies: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, tiled: 'bool' = False, checkpoint_every: 'Optional[int]' = None) -> 'torch.Tensor'",
+    ("NeuralAstar", "soft_cost_to_go"):
+        "(self, map_designs: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, policies: 'bool' = False, differentiable: 'bool' = False)",
+    ("NeuralAstar", "soft_cost_to_go_tiled"):
+        "(self, map_designs: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, policies: 'bool' = False, differentiable: 'bool' = False, checkpoint_every: 'Optional[int]' = "
+        'None)',
+    ("NeuralAstar", "maxent_path_nll"):
+        "(self, map_designs: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', opt_trajs: 'torch.Tensor', "
+        "tau: 'float', horizon: 'Optional[int]' = None, tiled: 'bool' = False, checkpoint_every: 'Optional[int]' = None) -> "
+        "'torch.Tensor'",
+    ("NeuralAstar", "soft_policy"):
+        "(self, map_designs: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None)",
+    ("NeuralAstar", "soft_policy_tiled"):
+        "(self, map_designs: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', tau: 'float', horizon: "
+        "'Optional[int]' = None, checkpoint_every: 'Optional[int]' = None)",
+    ("NeuralAstar", "policy_nll"):
+        "(self, map_designs: 'torch.Tensor', start_maps: 'torch.Tensor', goal_maps: 'torch.Tensor', opt_policies: "
+        "'torch.Tensor', tau: 'float', horizon: 'Optional[int]' = None, tiled: 'bool' = False, checkpoint_every: "
+        "'Optional[int]' = None) -> 'torch.Tensor'",
+}
+
+
+def test_soft_family_public_signatures_are_frozen():
+    from neural_astar import ops, planner
+    from neural_astar.planner.differentiable_astar import DifferentiableAstar
+    assert len(OPS_SIGNATURES) == 16 and set(OPS_SIGNATURES) <= set(ops.__all__)
+    for name, signature in OPS_SIGNATURES.items():
+        assert str(inspect.signature(getattr(ops, name))) == signature, name
+    classes = {"DifferentiableAstar": DifferentiableAstar, "VanillaAstar": planner.VanillaAstar, "NeuralAstar": planner.NeuralAstar}
+    assert len(PLANNER_SIGNATURES) == 18
+    for (cls, name), signature in PLANNER_SIGNATURES.items():
+        assert str(inspect.signature(getattr(classes[cls], name))) == signature, (cls, name)
