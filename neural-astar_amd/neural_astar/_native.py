@@ -328,6 +328,18 @@ SOFT_POLICY_TILED_SIGNATURES = {
     "nastar_soft_policy_backward_tiled": "i ppppzippiiiudipppzp",
 }
 
+# the signatures of include/nastar_soft_routes.h (the eighteenth header: sampled routes from the maximum-entropy route distribution of the
+# thirteenth's field), same letter code; a table of its own (tests/test_soft_routes.py compares it with ITS header)
+SOFT_ROUTE_SIGNATURES = {
+    "nastar_soft_routes_abi": "i ",
+    "nastar_soft_routes_max_cells": "i ",
+    # cost, goal, passable, tape, tape_bytes, start_idx, B, S, N, H, W, neighbor_mask, tau, horizon, seed, uniforms, routes_out, route_cap,
+    # route_len_out, route_cost_out, log_prob_out, visits_out, status_out, stream
+    "nastar_soft_routes": "i ppppzpiiiiiudiqppipppppp",
+    # ... status_out, shape, stream
+    "nastar_soft_routes_with_shape": "i ppppzpiiiiiudiqppipppppip",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -493,6 +505,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, TICKET_SIGNATURES, TICKET_SIGNATURES)
     if hasattr(lib, "nastar_soft_policy_tiled_abi"):  # (and the seventeenth)
         _bind(lib, SOFT_POLICY_TILED_SIGNATURES, SOFT_POLICY_TILED_SIGNATURES)
+    if hasattr(lib, "nastar_soft_routes_abi"):  # (and the eighteenth)
+        _bind(lib, SOFT_ROUTE_SIGNATURES, SOFT_ROUTE_SIGNATURES)
     _lib = lib
     return lib
 

@@ -26,7 +26,8 @@ __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay",
            "SOFT_FIELDS_GRAD_MAX_CELLS", "soft_cost_to_go_tiled", "maxent_path_nll_tiled", "soft_fields_tiled_forward",
            "soft_fields_tiled_backward", "SOFT_FIELDS_TILED_MAX_CELLS",
            "soft_policy", "SoftPolicyOutput", "soft_policy_nll", "soft_policy_forward", "soft_policy_backward",
-           "soft_policy_tiled", "soft_policy_nll_tiled", "soft_policy_tiled_forward", "soft_policy_tiled_backward"]
+           "soft_policy_tiled", "soft_policy_nll_tiled", "soft_policy_tiled_forward", "soft_policy_tiled_backward",
+           "soft_routes", "SoftRoutes", "soft_routes_from_tape", "SOFT_ROUTES_MAX_CELLS", "SOFT_ROUTES_MAX_WALKERS"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -1654,10 +1655,11 @@ _SOFT_VARIANTS = {
 
 
 def _soft_forward(tiled: bool, logp: bool, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, policies: bool, tape: bool,
-                  checkpoint_every=None, sweeps_per_launch=None):
+                  checkpoint_every=None, sweeps_per_launch=None, tape_limit: Optional[int] = None):
     """the raw forward call of the four variants: the refusals in the family's one order, the outputs, ONE C call with its arguments in
     header order -> ``(dists, log_policies or None, policies or None, status, tape or None)``.  ``logp``: the log-policy beside the
-    other outputs; ``tiled``: ``checkpoint_every``, ``sweeps_per_launch`` and a workspace, which the one-workgroup call does not have."""
+    other outputs; ``tiled``: ``checkpoint_every``, ``sweeps_per_launch`` and a workspace, which the one-workgroup call does not have.
+    ``tape_limit``: the largest map a one-workgroup call with a tape takes, None = the backward's (``soft_routes`` reads every size)."""
     header, symbol, _, what, _ = _SOFT_VARIANTS[tiled, logp]
     t = _checked_tau(tau)
     maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
@@ -1668,7 +1670,8 @@ def _soft_forward(tiled: bool, logp: bool, cost_maps, goal_maps, obstacles_maps,
             raise ValueError(f"sweeps_per_launch must be a positive int or None, got {sweeps_per_launch!r}")
         _soft_tiled_limit(H, W, what)
     else:
-        limit = SOFT_FIELDS_GRAD_MAX_CELLS if tape else SOFT_FIELDS_MAX_CELLS
+        # (a tape is for the backward, which takes fewer cells than the forward -- unless the caller reads it itself: ``tape_limit``)
+        limit = (SOFT_FIELDS_GRAD_MAX_CELLS if tape_limit is None else tape_limit) if tape else SOFT_FIELDS_MAX_CELLS
         if H * W > limit:
             raise NotImplementedError(f"{what}: maps of {H}x{W} = {H * W} cells exceed the limit of {limit} cells{' of its backward' if tape else ''} "
                                       f"(one workgroup keeps one map in LDS{'' if logp else '; larger maps: soft_cost_to_go_tiled'})")
@@ -2121,3 +2124,141 @@ def soft_policy_nll_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obst
     _check_opt_policies(cost_maps, goal_maps, obstacles_maps, opt_policies, neighbor_mask)
     out = soft_policy_tiled(cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, checkpoint_every)
     return _nll_of_policy(out, opt_policies, horizon)
+
+
+# ---- include/nastar_soft_routes.h: sampled routes from the maximum-entropy route distribution of the soft field
+SOFT_ROUTES_MAX_CELLS = 12288  # nastar_soft_routes_max_cells(): every size the one-workgroup forward takes -- it writes a tape at each
+SOFT_ROUTES_MAX_WALKERS = 1 << 30  # the most (map, start, sample) walkers one call takes
+SOFT_ROUTES_SHAPES = {None: 0, "lds": 1, "gather": 2}  # ``shape`` of soft_routes_from_tape: the library's choice, or one kernel shape
+
+
+class SoftRoutes(NamedTuple):
+    """What ``soft_routes()`` returns: N sampled routes per (map, start) query.  ``routes`` [B,S,N,L] int32: flat cell indices r*W + c in
+    travel order, the goal last, then -1; a route longer than L keeps its LAST L cells.  ``route_lengths`` [B,S,N] int32: the true number of
+    route cells (at most horizon + 1).  ``route_costs`` [B,S,N] fp32: the cost of every route cell but the last.  ``log_probs`` [B,S,N]
+    fp32: log p(route) under the maximum-entropy route distribution, ``(dists[start] - route_costs) / tau`` up to rounding.  ``visits``
+    [B,S,H,W] int32 or None: how often the N routes of a query stood on each cell, the final goal cell not counted.  ``dists`` [B,1,H,W]:
+    the soft field V_K the walk was drawn from.  ``status`` [B,S] int32: 0, 1 (the index lies outside [0, H*W)), ``FIELD_BAD_COST`` (9) or
+    ``STATUS_UNSOLVABLE`` (3: ``dists`` is not finite at the start); a failed query has lengths 0, rows of -1, costs +inf and log_probs
+    -inf.  ``map_status`` [B] int32: the forward's per-map status."""
+
+    routes: torch.Tensor
+    route_lengths: torch.Tensor
+    route_costs: torch.Tensor
+    log_probs: torch.Tensor
+    visits: Optional[torch.Tensor]
+    dists: torch.Tensor
+    status: torch.Tensor
+    map_status: torch.Tensor
+
+
+def _checked_samples(num_samples) -> int:
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+        raise ValueError(f"num_samples must be an int >= 1, got {num_samples!r}")
+    return num_samples
+
+
+def _checked_seed(seed) -> int:
+    """``seed`` of the samplers: an int that fits the C call's long long, or None = one 63-bit draw from torch's default CPU generator"""
+    if seed is None:
+        return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    if isinstance(seed, bool) or not isinstance(seed, int) or not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError(f"seed must be an int in [-2**63, 2**63) or None (drawn from torch's default generator), got {seed!r}")
+    return seed
+
+
+def _checked_sample_len(max_route_len) -> None:
+    if max_route_len is not None and (isinstance(max_route_len, bool) or not isinstance(max_route_len, int) or max_route_len < 1):
+        raise ValueError(f"max_route_len must be an int >= 1 (or None: horizon + 1, which no route outgrows), got {max_route_len!r}")
+
+
+def soft_routes_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
+                          starts: torch.Tensor, tau: float, horizon: Optional[int] = None, num_samples: int = 1, seed: int = 0,
+                          neighbor_mask: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False,
+                          uniforms: Optional[torch.Tensor] = None, shape: Optional[str] = None):
+    """``nastar_soft_routes`` as it is (include/nastar_soft_routes.h) -> ``(routes, route_lengths, route_costs, log_probs, visits or None,
+    status)``: the maps, ``tau``, ``horizon`` and mask of the ``soft_fields_forward(..., tape=True)`` call that wrote ``tape``.  Two
+    launches (the rows' -1 and the counts' zeros, then the walkers) on the current stream, nothing is read back: it can be captured into a graph.  ``seed``: an int (the Philox key);
+    ``uniforms``: a float32 [B,S,N,horizon] tensor that replaces the generator.  ``max_route_len=None``: rows of ``horizon + 1`` cells, which
+    no route outgrows.  ``shape``: None, or "lds" / "gather" to pick the kernel shape (probes and tests; the same bits).  What
+    ``soft_routes`` runs behind its forward."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    N = _checked_samples(num_samples)
+    seed = _checked_seed(seed)
+    _checked_sample_len(max_route_len)
+    if shape not in SOFT_ROUTES_SHAPES:
+        raise ValueError(f"shape must be None, 'lds' or 'gather', got {shape!r}")
+    if H * W > SOFT_ROUTES_MAX_CELLS:
+        raise NotImplementedError(f"soft_routes: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_ROUTES_MAX_CELLS} cells (the "
+                                  "one-workgroup soft field; sampling from the tiled field's checkpointed tape is not implemented)")
+    idx = _start_indices(starts, B, H, W)
+    S = idx.shape[1]
+    if B * S * N > SOFT_ROUTES_MAX_WALKERS:
+        raise NotImplementedError(f"soft_routes: {B} maps x {S} starts x {N} samples exceed the limit of {SOFT_ROUTES_MAX_WALKERS} walkers per call")
+    if uniforms is not None and (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (B, S, N, K)):
+        raise ValueError(f"uniforms must be a float32 tensor of shape ({B}, {S}, {N}, {K}) = [B,S,N,horizon], got "
+                         f"{tuple(uniforms.shape) if torch.is_tensor(uniforms) else type(uniforms).__name__}")
+    dev = _field_device(maps)
+    for name, x in (("starts", idx), ("uniforms", uniforms)):
+        if x is not None and x.device != dev:
+            raise ValueError(f"the maps live on {dev}, {name} on {x.device}: they must share a device")
+    lib = _field_lib("nastar_soft_routes", "nastar_soft_routes.h")
+    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
+        raise ValueError(f"tape must be the contiguous uint8 tensor soft_fields_forward(..., tape=True) returned, on {dev}")
+    cap = K + 1 if max_route_len is None else max_route_len
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        idx = idx.contiguous()
+        uni = None if uniforms is None else uniforms.detach().contiguous()
+        routes = torch.empty((B, S, N, cap), dtype=torch.int32, device=dev)
+        lengths = torch.empty((B, S, N), dtype=torch.int32, device=dev)
+        costs = torch.empty((B, S, N), dtype=torch.float32, device=dev)
+        logp = torch.empty((B, S, N), dtype=torch.float32, device=dev)
+        counts = torch.empty((B, S, H, W), dtype=torch.int32, device=dev) if visits else None
+        status = torch.empty((B, S), dtype=torch.int32, device=dev)
+        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(), idx.data_ptr(), B, S, N, H, W, mask, t, K,
+                seed, _ptr(uni), routes.data_ptr(), cap, lengths.data_ptr(), costs.data_ptr(), logp.data_ptr(), _ptr(counts), status.data_ptr())
+        with torch.cuda.device(dev):
+            if shape is None:
+                rc = lib.nastar_soft_routes(*args, _stream_ptr(dev))
+            else:
+                rc = lib.nastar_soft_routes_with_shape(*args, SOFT_ROUTES_SHAPES[shape], _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_routes")
+    return routes, lengths, costs, logp, counts, status
+
+
+def soft_routes(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor, tau: float,
+                horizon: Optional[int] = None, num_samples: int = 1, seed: Optional[int] = None, neighbor_mask: Optional[int] = None,
+                max_route_len: Optional[int] = None, visits: bool = False, uniforms: Optional[torch.Tensor] = None) -> SoftRoutes:
+    """SAMPLE routes from the maximum-entropy route distribution of ``cost_maps`` (include/nastar_soft_routes.h) -> ``SoftRoutes``:
+    ``num_samples`` independent routes from each of S start cells per map, drawn with probability exp((V_K(start) - cost(route)) / tau)
+    among the routes that reach a goal within ``horizon`` moves -- the distribution ``maxent_path_nll`` trains.  The walker with k moves
+    left draws from pi_k, the softmax of -V_{k-1} / tau: the non-stationary chain, not the one plane ``soft_cost_to_go(policies=True)``
+    returns.  As ``tau`` goes to 0 every sample is ``field_routes``' optimal route.
+
+    The maps, ``tau``, ``horizon`` and ``neighbor_mask`` of ``soft_cost_to_go``, maps of at most ``SOFT_ROUTES_MAX_CELLS`` cells.
+    ``starts``: an integer [B,S] tensor of flat cell indices r*W + c, or a float [B,S,H,W] tensor of start maps (``field_routes``).
+    ``seed``: an int, or None = one 63-bit draw from torch's default CPU generator (``torch.manual_seed`` makes a run repeatable); a sample
+    is a pure function of the inputs, the seed and its (map, start, sample) numbers: the same seed gives the same bits, and the first N
+    samples of a query do not change when ``num_samples`` grows.  ``uniforms``: a float32 [B,S,N,horizon] tensor of the walkers' own
+    uniform numbers instead.  ``max_route_len``: the row length of ``routes`` (a longer route keeps its last cells); None = horizon + 1,
+    which no route outgrows.  ``visits=True`` also counts the cells the routes stood on.
+
+    An EVALUATION call on the current stream of the inputs' device: the forward launch with its tape (B * horizon * H * W fp32), a
+    launch that clears the rows and the counts and the walkers' launch; detached outputs, nothing is read back -- it can be captured into a graph -- and nothing raises for a
+    failed query or a bad map: read ``status`` and ``map_status``."""
+    _checked_samples(num_samples)
+    _checked_sample_len(max_route_len)
+    seed = _checked_seed(seed)
+    _, _, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    if H * W > SOFT_ROUTES_MAX_CELLS:
+        raise NotImplementedError(f"soft_routes: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_ROUTES_MAX_CELLS} cells (the "
+                                  "one-workgroup soft field; sampling from the tiled field's checkpointed tape is not implemented)")
+    _start_indices(starts, B, H, W)  # (refused before the forward launches anything)
+    dists, _, _, map_status, tape = _soft_forward(False, False, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, False, True,
+                                                  tape_limit=SOFT_ROUTES_MAX_CELLS)
+    routes, lengths, costs, logp, counts, status = soft_routes_from_tape(cost_maps, goal_maps, obstacles_maps, tape, starts, tau, horizon,
+                                                                         num_samples, seed, neighbor_mask, max_route_len, visits, uniforms)
+    return SoftRoutes(routes, lengths, costs, logp, counts, dists, status, map_status)

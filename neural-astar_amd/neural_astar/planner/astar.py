@@ -138,6 +138,13 @@ class VanillaAstar(nn.Module):
         start) with cost = passable = ``map_designs``: on a binary map, shortest routes.  An evaluation call."""
         return self.astar.plan_many(map_designs, starts, goal_maps, map_designs, max_route_len, paths)
 
+    def sample_routes(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, tau: float, num_samples: int = 1,
+                      seed: Optional[int] = None, horizon: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False):
+        """``num_samples`` routes from each of S start cells per map, sampled from the maximum-entropy route distribution
+        (``DifferentiableAstar.sample_routes``) with cost = passable = ``map_designs``: on a binary map a route of L moves has weight
+        exp(-L / tau).  An evaluation call."""
+        return self.astar.sample_routes(map_designs, starts, goal_maps, map_designs, tau, num_samples, seed, horizon, max_route_len, visits)
+
     def shortest_paths(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, lambda_: Optional[float] = None,
                        min_cost: float = 2.0 ** -10) -> PathOutput:
         """The exact optimal path of every map as a 0/1 mask (``DifferentiableAstar.shortest_paths``: field and chase in one launch) with
@@ -413,6 +420,23 @@ class NeuralAstar(VanillaAstar):
         cost_maps = self.encode(map_designs, torch.zeros_like(goal_maps), goal_maps).detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(goal_maps)
         return self.astar.plan_many(cost_maps, starts, goal_maps, obstacles_maps, max_route_len, paths)
+
+    def sample_routes(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, tau: float, num_samples: int = 1,
+                      seed: Optional[int] = None, horizon: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False):
+        """``num_samples`` routes from each of S start cells per map, sampled from the maximum-entropy route distribution of the PREDICTED
+        cost maps (``DifferentiableAstar.sample_routes``): what a model trained with ``maxent_path_nll`` generates.  For
+        ``encoder_input == "m"`` only, as ``plan_many``: the maps are encoded once (detached, with an all-zero start channel) and one soft
+        field serves every start; with "m+" NotImplementedError.  An evaluation call; ``learn_obstacles`` makes every cell passable."""
+        _checked_route_len(max_route_len)  # (every refusal before the encoder launches anything)
+        ops._checked_tau(tau)
+        ops._checked_samples(num_samples)
+        if self.encoder_input != "m":
+            raise NotImplementedError(f"NeuralAstar.sample_routes: with encoder_input={self.encoder_input!r} the predicted cost map depends on "
+                                      "the start, so one soft field cannot serve several starts; encode per start and call "
+                                      "planner.astar.sample_routes(cost_maps, starts, goal_maps, obstacles_maps, tau), or use encoder_input='m'")
+        cost_maps = self.encode(map_designs, torch.zeros_like(goal_maps), goal_maps).detach()
+        obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(goal_maps)
+        return self.astar.sample_routes(cost_maps, starts, goal_maps, obstacles_maps, tau, num_samples, seed, horizon, max_route_len, visits)
 
     def shortest_paths(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, lambda_: Optional[float] = None,
                        min_cost: float = 2.0 ** -10) -> PathOutput:

@@ -734,6 +734,16 @@ class DifferentiableAstar(nn.Module):
             masks = torch.zeros((B, S, H * W + 1), dtype=torch.int64, device=cell.device).scatter_(2, cell, 1)[..., :H * W].reshape(B, S, H, W)
         return FieldRoutesOutput(field.dists, r.routes, r.route_lengths, r.route_costs, r.status, masks)
 
+    def sample_routes(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tau: float,
+                      num_samples: int = 1, seed: Optional[int] = None, horizon: Optional[int] = None, max_route_len: Optional[int] = None,
+                      visits: bool = False) -> "ops.SoftRoutes":
+        """``num_samples`` routes from each of S start cells per map, SAMPLED from the maximum-entropy route distribution of ``cost_maps``
+        (``ops.soft_routes``, the kernel of include/nastar_soft_routes.h: the soft field with its tape, then one launch of walkers), under
+        this module's own move set -- what ``plan_many`` is to the hard field.  ``g_ratio``, ``Tmax`` and the heuristic play no part.  An
+        EVALUATION call: no autograd graph, detached tensors, nothing is read back; a failed query is reported in ``status``."""
+        return ops.soft_routes(cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask=self.neighbor_mask(),
+                               max_route_len=max_route_len, visits=visits)
+
     def shortest_paths(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
                        lambda_: Optional[float] = None, min_cost: float = 2.0 ** -10) -> PathOutput:
         """The EXACT optimal path of every map as a 0/1 mask (``ops.shortest_paths``, the kernel of include/nastar_path_masks.h: field and
