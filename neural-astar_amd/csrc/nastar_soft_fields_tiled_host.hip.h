@@ -102,6 +102,42 @@ inline int soft_tiled_forward(const float* cost, const float* goal, const float*
     return NASTAR_OK;
 }
 
+// THE SEGMENTS of a checkpointed tape, top down: what the backward and the walkers of nastar_soft_routes_tiled_capi.hip share.  `ck` is the
+// tape (slot j - 1 is plane j * c; slot K / c is plane K), V0 and C the prepare launch's planes, `seg` a buffer of sft_segment_planes(K, c)
+// planes of the tape's stride.  For every segment, the steps lo < k <= hi that read the planes lo .. hi - 1, from the top: the sweeps that
+// rebuild the planes lo + 1 .. hi - 1 from plane lo into `seg`, then visit(lo, hi, bottom, plane) -> a status, with plane(k) the plane
+// lo <= k < hi and `bottom` = max(lo + 1, lowest) the lowest step the caller walks (a segment wholly below `lowest` is skipped).
+template <typename Visit>
+inline int soft_tiled_each_segment(const float* C, const float* V0, const float* ck, float* seg, int K, int c, int lowest, unsigned neighbor_mask,
+                                   const SoftTiledGeometry& geo, hipStream_t s, Visit&& visit)
+{
+    SoftTileArgs fa{};
+    fa.C = C;
+    fa.tape = seg;
+    fa.g = geo.g;
+    fa.tape_every = 1;
+    fa.tape_count = INT_MAX;
+    fa.final_k = fa.final_slot = -1;
+    fa.nmask = neighbor_mask;
+    for (int j = K / c; j >= 0; --j) {
+        const int lo = j * c, hi = K - lo > c ? lo + c : K;
+        if (lo >= K) continue;                               // (K is a multiple of c: nothing lies above the last checkpoint)
+        const int bottom = std::max(lo + 1, lowest);
+        if (hi < bottom) continue;
+        const float* first = lo == 0 ? V0 : ck + (size_t)(j - 1) * geo.plane;
+        auto plane = [&](int k) -> const float* { return k == lo ? first : seg + (size_t)(k - lo - 1) * geo.plane; };
+        fa.tape_k0 = lo;
+        for (int k0 = lo; k0 < hi - 1; k0 += fa.n) {   // the planes lo + 1 .. hi - 1, every one kept: the next launch reads it there
+            fa.k0 = k0;
+            fa.n = std::min(kSoftTileSweeps, hi - 1 - k0);
+            fa.src = plane(k0);
+            if (int rc = soft_tiled_launch_sweeps(fa, geo, s)) return rc;
+        }
+        if (int rc = visit(lo, hi, bottom, plane)) return rc;
+    }
+    return NASTAR_OK;
+}
+
 // THE BACKWARD behind its refusals: prepare, launch_init(ga, geo, s) for A_K and the sums, then segment by segment, top down, the sweeps
 // that rebuild the segment's planes and launch_step(ga, k, plane_K, geo, s) for k = K .. 2 (ga.U is plane k - 1), and the store launch
 template <typename LaunchInit, typename LaunchStep>
@@ -120,37 +156,15 @@ inline int soft_tiled_backward(const float* cost, const float* goal, const float
     double* sum = reinterpret_cast<double*>(C + 4 * stride);
     float* seg = C + 6 * stride;                          // planes lo + 1, lo + 2, ... of the segment that starts behind plane lo
     const float* ck = static_cast<const float*>(tape);   // slot j - 1 is plane j * c; slot K / c is plane K
-    const int n_ck = K / c;
-    const float* plane_K = ck + (size_t)n_ck * geo.plane;
+    const float* plane_K = ck + (size_t)(K / c) * geo.plane;
     if (int rc = soft_tiled_prepare(cost, goal, passable, C, V0, flags, status_out, B, H * W, false, tau, s)) return rc;
 
     // (the tape is in units of tau * ln 2 and the gradient with respect to the cost needs no factor)
     SoftTileGradArgs ga{C, plane_K, nullptr, A[0], sum, grad_dist, grad_cost_out, flags, geo.g, neighbor_mask};
     if (int rc = launch_init(ga, geo, s)) return rc;
 
-    SoftTileArgs fa{};
-    fa.C = C;
-    fa.tape = seg;
-    fa.g = geo.g;
-    fa.tape_every = 1;
-    fa.tape_count = INT_MAX;
-    fa.final_k = fa.final_slot = -1;
-    fa.nmask = neighbor_mask;
-    int cur = 0;
-    for (int j = n_ck; j >= 0; --j) {
-        const int lo = j * c, hi = K - lo > c ? lo + c : K;  // the steps lo < k <= hi read the planes lo .. hi - 1; step 1 is never walked
-        if (lo >= K) continue;                               // (K is a multiple of c: nothing lies above the last checkpoint)
-        const int bottom = std::max(lo + 1, 2);
-        if (hi < bottom) continue;
-        const float* first = lo == 0 ? V0 : ck + (size_t)(j - 1) * geo.plane;
-        auto plane = [&](int k) -> const float* { return k == lo ? first : seg + (size_t)(k - lo - 1) * geo.plane; };
-        fa.tape_k0 = lo;
-        for (int k0 = lo; k0 < hi - 1; k0 += fa.n) {   // the planes lo + 1 .. hi - 1, every one kept: the next launch reads it there
-            fa.k0 = k0;
-            fa.n = std::min(kSoftTileSweeps, hi - 1 - k0);
-            fa.src = plane(k0);
-            if (int rc = soft_tiled_launch_sweeps(fa, geo, s)) return rc;
-        }
+    int cur = 0;  // (step 1 is never walked: lowest = 2)
+    const int rc = soft_tiled_each_segment(C, V0, ck, seg, K, c, 2, neighbor_mask, geo, s, [&](int, int hi, int bottom, auto&& plane) {
         for (int k = hi; k >= bottom; --k) {
             ga.U = plane(k - 1);
             ga.A_in = A[cur];
@@ -158,7 +172,9 @@ inline int soft_tiled_backward(const float* cost, const float* goal, const float
             if (int rc = launch_step(ga, k, plane_K, geo, s)) return rc;
             cur ^= 1;
         }
-    }
+        return (int)NASTAR_OK;
+    });
+    if (rc) return rc;
     return soft_tiled_launch_store(ga, geo, s);
 }
 

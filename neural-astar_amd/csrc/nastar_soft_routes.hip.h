@@ -1,7 +1,7 @@
 // nastar_soft_routes.hip.h -- sampled routes from the maximum-entropy route distribution of the soft field: N draws for each of S start
 // cells per map, with lengths, costs, log-probabilities and visit counts (include/nastar_soft_routes.h).
 //
-// The walker of one lane is written ONCE (`walk` in the kernel below): it reads the eight values of plane K-j-1 around its cell, forms the
+// One move of the walker of one lane is written ONCE (`srt_move` below): it reads the eight values of plane K-j-1 around its cell, forms the
 // weights, draws and moves.  Where the plane comes from is the kernel's compile-time switch:
 //   LDS      a workgroup of T lanes serves one map and T of its walkers.  All walkers of a map read the same plane at the same move, so the
 //            workgroup streams the tape BACKWARDS through LDS, one plane per move, double-buffered: the loads of plane K-j-2 are issued into
@@ -74,12 +74,111 @@ __device__ __forceinline__ uint32_t srt_philox(uint32_t c0, uint32_t c1, uint32_
 
 // in front of the walkers: routes[0, n_routes) = -1, visits[0, n_visits) = 0 (either may be empty); a grid-stride loop, coalesced stores
 constexpr int kSoftRoutesClearT = 256;
-__global__ __launch_bounds__(kSoftRoutesClearT) void nastar_soft_routes_clear_kernel(int32_t* routes, size_t n_routes, int32_t* visits, size_t n_visits)
+template <int T>
+__global__ __launch_bounds__(T) void nastar_soft_routes_clear_kernel(int32_t* routes, size_t n_routes, int32_t* visits, size_t n_visits)
 {
-    const size_t first = (size_t)blockIdx.x * kSoftRoutesClearT + threadIdx.x, stride = (size_t)gridDim.x * kSoftRoutesClearT;
+    const size_t first = (size_t)blockIdx.x * T + threadIdx.x, stride = (size_t)gridDim.x * T;
     for (size_t i = first; i < n_routes; i += stride) routes[i] = -1;
     for (size_t i = first; i < n_visits; i += stride) visits[i] = 0;
 }
+
+// the walker of one lane between two moves
+struct SrtWalker {
+    int n, r, c, len;   // the cell it stands on, as an index and as (row, column); the route cells so far
+    bool active;        // still on its way
+    double csum, lsum;  // the fp64 tallies of route_cost and log_prob
+};
+
+// ONE MOVE of one walker that is still on its way, written ONCE for every kernel that walks (the two shapes below and the walker of
+// nastar_soft_routes_tiled.hip.h): move j of walker (q, i), `row` its number in the batch.  value(m, is_goal&) -> U_{K-j-1}(m) is where the
+// kernels differ: the plane the move reads, in LDS or in device memory.  The eight reads, the draw, the move, the tallies.  kFirst: the pass
+// that tallies costs, log-probabilities and visits; visit(cell, l) sees route cell l.
+template <bool kFirst, typename Value, typename Visit>
+__device__ __forceinline__ void srt_move(const SoftRoutesArgs& a, const float* cost, SrtWalker& w, int j, int i, size_t q, size_t row,
+                                         Value&& value, Visit&& visit)
+{
+    const int H = a.H, W = a.W, n = w.n;
+    const float INF = INFINITY;
+    const uint32_t nm = a.nmask;
+    const bool up = w.r > 0, dn = w.r < H - 1, lf = w.c > 0, rt = w.c < W - 1;
+    float cn = 0.f;
+    if constexpr (kFirst) {
+        if (a.route_cost) cn = cost[n];
+    }
+    float u[8];
+    bool g[8];
+    float umin = INF;
+    fld_each<8>([&](auto k) __attribute__((always_inline)) {
+        constexpr int A = decltype(k)::value;
+        constexpr Move mv = kActionMoves[A];
+        float x = INF;
+        bool gg = false;
+        if ((nm & fld_bit(mv.dy, mv.dx)) && fld_inside(mv.dy, mv.dx, up, dn, lf, rt)) {
+            x = value(n + mv.dy * W + mv.dx, gg);
+            if (!(fabsf(x) < INF)) x = INF;  // a candidate has a finite value
+        }
+        u[A] = x;
+        g[A] = gg;
+        umin = fminf(umin, x);
+    });
+    if (!(umin < INF)) {
+        w.active = false;  // (a tape that is not these maps': the walk ends where it stands)
+        return;
+    }
+    float uu;
+    if (a.uniforms)
+        uu = a.uniforms[row * (size_t)a.K + (size_t)j];
+    else
+        uu = (float)(srt_philox((uint32_t)j, (uint32_t)i, (uint32_t)q, 0u, a.key0, a.key1) >> 8) * 0x1p-24f;
+    float wgt[8];
+    float Z = 0.f;
+    fld_each<8>([&](auto k) __attribute__((always_inline)) {
+        constexpr int A = decltype(k)::value;
+        wgt[A] = sfl_exp2(umin - u[A]);  // exp2(-inf) = 0: no candidate, and x + 0 is x
+        Z += wgt[A];
+    });
+    const float t = uu * Z;
+    float acc = 0.f;
+    int ch = -1, last = -1;
+    fld_each<8>([&](auto k) __attribute__((always_inline)) {
+        constexpr int A = decltype(k)::value;
+        if (u[A] < INF) {
+            acc += wgt[A];
+            last = A;
+            if (ch < 0 && acc > t) ch = A;
+        }
+    });
+    if (ch < 0) ch = last;  // rounding, u >= 1, a NaN u
+    float uc = INF;
+    bool gc = false;
+    int step = 0, dy = 0, dx = 0;
+    fld_each<8>([&](auto k) __attribute__((always_inline)) {
+        constexpr int A = decltype(k)::value;
+        constexpr Move mv = kActionMoves[A];
+        if (ch == A) {
+            uc = u[A];
+            gc = g[A];
+            dy = mv.dy;
+            dx = mv.dx;
+            step = mv.dy * W + mv.dx;
+        }
+    });
+    if constexpr (kFirst) {
+        if (a.visits) atomicAdd(&a.visits[q * ((size_t)H * W) + (size_t)n], 1);
+        w.csum += (double)cn;
+        if (a.log_prob) w.lsum += (double)(umin - uc) * M_LN2 - log((double)Z);
+    }
+    w.r += dy;
+    w.c += dx;
+    w.n += step;
+    visit(w.n, w.len);
+    ++w.len;
+    if (gc) w.active = false;
+}
+
+// its launch for B * SN rows of `cap` cells and B * S planes of HW counts (a NULL is left alone; nothing is launched for two NULLs) -> a
+// status.  Defined in nastar_soft_routes_capi.hip, the one translation unit that instantiates the kernel.
+int soft_routes_clear(int32_t* routes, int32_t* visits, int B, int S, long long SN, int HW, int cap, hipStream_t s);
 
 // blockIdx.x = map * groups + (slice of the map's S*N walkers); lane tid walks walker slice * T + tid.  R: the cells of a plane a lane
 // stages per move (R * T >= H*W; the LDS kernel only)
@@ -99,7 +198,6 @@ __global__ __launch_bounds__(T) void nastar_soft_routes_kernel(const SoftRoutesA
     const float* goal = a.goal + map * (size_t)HW;
     const float* pass = a.passable + map * (size_t)HW;
     const float* tape = a.tape + map * (size_t)K * HW;
-    const uint32_t nm = a.nmask;
 
     // ---- the map: the forward's BAD_COST rule, and the goal bytes ---------------------------------------------------------------------------
     if (tid < 8) flags[tid] = 0;
@@ -144,14 +242,12 @@ __global__ __launch_bounds__(T) void nastar_soft_routes_kernel(const SoftRoutesA
     // route cell j.  -> the number of route cells
     auto walk = [&](auto first, auto visit) __attribute__((always_inline)) -> int {
         constexpr bool kFirst = decltype(first)::value;
-        int n = n0, len = 0, r = 0, c = 0;
-        bool active = ok && !goal0;
-        double csum = 0.0, lsum = 0.0;
+        SrtWalker w{n0, 0, 0, 0, ok && !goal0, 0.0, 0.0};
         if (ok) {
-            len = 1;
+            w.len = 1;
             visit(n0, 0);
-            r = n0 / W;
-            c = n0 - r * W;
+            w.r = n0 / W;
+            w.c = n0 - w.r * W;
         }
         if constexpr (LDS) {  // plane K - 1 into buffer 0, and the three "still on its way" flags (flags[4..6]) start at zero
             for (int cell = tid; cell < HW; cell += T) buf[cell] = plane_cell(K - 1, cell);
@@ -170,89 +266,17 @@ __global__ __launch_bounds__(T) void nastar_soft_routes_kernel(const SoftRoutesA
                     }
                 }
             }
-            if (active) {
+            if (w.active) {
                 const float* cur = LDS ? buf + (size_t)(j & 1) * stride : (p >= 1 ? tape + (size_t)(p - 1) * HW : nullptr);
-                const bool up = r > 0, dn = r < H - 1, lf = c > 0, rt = c < W - 1;
-                float cn = 0.f;
-                if constexpr (kFirst) {
-                    if (a.route_cost) cn = cost[n];
-                }
-                float u[8];
-                bool g[8];
-                float umin = INF;
-                fld_each<8>([&](auto k) __attribute__((always_inline)) {
-                    constexpr int A = decltype(k)::value;
-                    constexpr Move mv = kActionMoves[A];
-                    float x = INF;
-                    bool gg = false;
-                    if ((nm & fld_bit(mv.dy, mv.dx)) && fld_inside(mv.dy, mv.dx, up, dn, lf, rt)) {
-                        const int m = n + mv.dy * W + mv.dx;
-                        if constexpr (LDS) {
-                            x = cur[m];
-                            gg = (gb[m] & 1) != 0;
-                        } else {
-                            gg = goal[m] != 0.f;
-                            x = cur ? cur[m] : (gg && pass[m] != 0.f) ? 0.f : INF;
-                        }
-                        if (!(fabsf(x) < INF)) x = INF;  // a candidate has a finite value
+                srt_move<kFirst>(a, cost, w, j, i, q, row, [&](int m, bool& gg) __attribute__((always_inline)) -> float {
+                    if constexpr (LDS) {
+                        gg = (gb[m] & 1) != 0;
+                        return cur[m];
+                    } else {
+                        gg = goal[m] != 0.f;
+                        return cur ? cur[m] : (gg && pass[m] != 0.f) ? 0.f : INF;
                     }
-                    u[A] = x;
-                    g[A] = gg;
-                    umin = fminf(umin, x);
-                });
-                if (umin < INF) {
-                    float uu;
-                    if (a.uniforms)
-                        uu = a.uniforms[row * (size_t)K + (size_t)j];
-                    else
-                        uu = (float)(srt_philox((uint32_t)j, (uint32_t)i, (uint32_t)q, 0u, a.key0, a.key1) >> 8) * 0x1p-24f;
-                    float wgt[8];
-                    float Z = 0.f;
-                    fld_each<8>([&](auto k) __attribute__((always_inline)) {
-                        constexpr int A = decltype(k)::value;
-                        wgt[A] = sfl_exp2(umin - u[A]);  // exp2(-inf) = 0: no candidate, and x + 0 is x
-                        Z += wgt[A];
-                    });
-                    const float t = uu * Z;
-                    float acc = 0.f;
-                    int ch = -1, last = -1;
-                    fld_each<8>([&](auto k) __attribute__((always_inline)) {
-                        constexpr int A = decltype(k)::value;
-                        if (u[A] < INF) {
-                            acc += wgt[A];
-                            last = A;
-                            if (ch < 0 && acc > t) ch = A;
-                        }
-                    });
-                    if (ch < 0) ch = last;  // rounding, u >= 1, a NaN u
-                    float uc = INF;
-                    bool gc = false;
-                    int step = 0, dy = 0, dx = 0;
-                    fld_each<8>([&](auto k) __attribute__((always_inline)) {
-                        constexpr int A = decltype(k)::value;
-                        constexpr Move mv = kActionMoves[A];
-                        if (ch == A) {
-                            uc = u[A];
-                            gc = g[A];
-                            dy = mv.dy;
-                            dx = mv.dx;
-                            step = mv.dy * W + mv.dx;
-                        }
-                    });
-                    if constexpr (kFirst) {
-                        if (a.visits) atomicAdd(&a.visits[q * (size_t)HW + (size_t)n], 1);
-                        csum += (double)cn;
-                        if (a.log_prob) lsum += (double)(umin - uc) * M_LN2 - log((double)Z);
-                    }
-                    r += dy;
-                    c += dx;
-                    n += step;
-                    visit(n, len);
-                    ++len;
-                    if (gc) active = false;
-                } else {
-                    active = false;  // (a tape that is not these maps': the walk ends where it stands)
-                }
+                }, visit);
             }
             if constexpr (LDS) {
                 if (p >= 1) {
@@ -267,23 +291,23 @@ __global__ __launch_bounds__(T) void nastar_soft_routes_kernel(const SoftRoutesA
                 // fld_sweep: the flag of move j is cleared during move j + 2, when nobody reads it.  (Not __syncthreads_or: it keeps a
                 // static __shared__ word in front of the dynamic region.)
                 const int slot = 4 + j % 3;
-                if (__ballot(active) && (tid & 63) == 0) __hip_atomic_store(&flags[slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (__ballot(w.active) && (tid & 63) == 0) __hip_atomic_store(&flags[slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (tid == 0) __hip_atomic_store(&flags[slot == 6 ? 4 : slot + 1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __syncthreads();
                 if (__hip_atomic_load(&flags[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) break;  // every walker has ended
             } else {
-                if (!active) break;
+                if (!w.active) break;
             }
         }
         if constexpr (kFirst) {
             if (has) {
-                a.len[row] = len;
-                if (a.route_cost) a.route_cost[row] = ok ? (float)csum : INF;
-                if (a.log_prob) a.log_prob[row] = ok ? (float)lsum : -INF;
+                a.len[row] = w.len;
+                if (a.route_cost) a.route_cost[row] = ok ? (float)w.csum : INF;
+                if (a.log_prob) a.log_prob[row] = ok ? (float)w.lsum : -INF;
                 if (i == 0) a.status[q] = st;
             }
         }
-        return len;
+        return w.len;
     };
 
     int32_t* out = a.routes ? a.routes + row * (size_t)a.cap : nullptr;  // (read by a lane with a walker only)

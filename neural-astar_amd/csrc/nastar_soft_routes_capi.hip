@@ -23,6 +23,19 @@ static_assert(kSoftRoutesMaxCells <= 12 * 1024 && 1024 <= 4 * 256 && 256 <= 4 * 
 
 enum { kShapeAuto = 0, kShapeLds = 1, kShapeGather = 2 };
 
+namespace nastar {
+
+int soft_routes_clear(int32_t* routes, int32_t* visits, int B, int S, long long SN, int HW, int cap, hipStream_t s)
+{
+    if (!routes && !visits) return NASTAR_OK;
+    const size_t n_routes = routes ? (size_t)B * SN * (size_t)cap : 0, n_visits = visits ? (size_t)B * S * (size_t)HW : 0;
+    const size_t blocks = (std::max(n_routes, n_visits) + kSoftRoutesClearT - 1) / kSoftRoutesClearT;
+    return launch_grid(nastar_soft_routes_clear_kernel<kSoftRoutesClearT>, dim3((unsigned)std::min<size_t>(blocks, 1u << 16)), dim3(kSoftRoutesClearT),
+                       0, s, routes, n_routes, visits, n_visits);
+}
+
+}  // namespace nastar
+
 static int soft_routes(const float* cost, const float* goal, const float* passable, const void* tape, size_t tape_bytes, const int32_t* start_idx,
                        int B, int S, int N, int H, int W, unsigned neighbor_mask, double tau, int horizon, long long seed, const float* uniforms,
                        int32_t* routes_out, int route_cap, int32_t* route_len_out, float* route_cost_out, float* log_prob_out,
@@ -43,13 +56,7 @@ static int soft_routes(const float* cost, const float* goal, const float* passab
                      log_prob_out, visits_out, status_out, 0, S, N, H, W, horizon, routes_out ? route_cap : 0, neighbor_mask,
                      (uint32_t)((unsigned long long)seed & 0xffffffffull), (uint32_t)((unsigned long long)seed >> 32)};
     // every row starts as -1 (the walkers store cells only) and every visit count as 0 (they add): one launch in front of the walkers'
-    if (routes_out || visits_out) {
-        const size_t n_routes = routes_out ? (size_t)B * SN * (size_t)route_cap : 0, n_visits = visits_out ? (size_t)B * S * (size_t)HW : 0;
-        const size_t blocks = (std::max(n_routes, n_visits) + kSoftRoutesClearT - 1) / kSoftRoutesClearT;
-        const int rc = launch_grid(nastar_soft_routes_clear_kernel, dim3((unsigned)std::min<size_t>(blocks, 1u << 16)), dim3(kSoftRoutesClearT), 0, s,
-                                   routes_out, n_routes, visits_out, n_visits);
-        if (rc) return rc;
-    }
+    if (int rc = soft_routes_clear(routes_out, visits_out, B, S, SN, HW, route_cap, s)) return rc;
     const bool lds = shape == kShapeAuto ? SN <= kSoftRoutesLdsWalkers : shape == kShapeLds;
     auto go = [&](auto kernel, int T) {
         a.groups = (int)((SN + T - 1) / T);

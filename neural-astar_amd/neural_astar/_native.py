@@ -340,6 +340,17 @@ SOFT_ROUTE_SIGNATURES = {
     "nastar_soft_routes_with_shape": "i ppppzpiiiiiudiqppipppppip",
 }
 
+# the signatures of include/nastar_soft_routes_tiled.h (the nineteenth header: the eighteenth's samples from the fourteenth's checkpointed
+# tape), same letter code; a table of its own (tests/test_soft_routes_tiled.py compares it with ITS header)
+SOFT_ROUTES_TILED_SIGNATURES = {
+    "nastar_soft_routes_tiled_abi": "i ",
+    "nastar_soft_routes_tiled_max_cells": "i ",
+    "nastar_soft_routes_tiled_workspace_bytes": "z iiiiiii",          # B, S, N, H, W, horizon, checkpoint_every
+    # cost, goal, passable, tape, tape_bytes, checkpoint_every, start_idx, B, S, N, H, W, neighbor_mask, tau, horizon, seed, uniforms,
+    # routes_out, route_cap, route_len_out, route_cost_out, log_prob_out, visits_out, status_out, workspace, workspace_bytes, stream
+    "nastar_soft_routes_tiled": "i ppppzipiiiiiudiqppippppppzp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -507,6 +518,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, SOFT_POLICY_TILED_SIGNATURES, SOFT_POLICY_TILED_SIGNATURES)
     if hasattr(lib, "nastar_soft_routes_abi"):  # (and the eighteenth)
         _bind(lib, SOFT_ROUTE_SIGNATURES, SOFT_ROUTE_SIGNATURES)
+    if hasattr(lib, "nastar_soft_routes_tiled_abi"):  # (and the nineteenth)
+        _bind(lib, SOFT_ROUTES_TILED_SIGNATURES, SOFT_ROUTES_TILED_SIGNATURES)
     _lib = lib
     return lib
 

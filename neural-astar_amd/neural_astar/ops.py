@@ -27,7 +27,8 @@ __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay",
            "soft_fields_tiled_backward", "SOFT_FIELDS_TILED_MAX_CELLS",
            "soft_policy", "SoftPolicyOutput", "soft_policy_nll", "soft_policy_forward", "soft_policy_backward",
            "soft_policy_tiled", "soft_policy_nll_tiled", "soft_policy_tiled_forward", "soft_policy_tiled_backward",
-           "soft_routes", "SoftRoutes", "soft_routes_from_tape", "SOFT_ROUTES_MAX_CELLS", "SOFT_ROUTES_MAX_WALKERS"]
+           "soft_routes", "SoftRoutes", "soft_routes_from_tape", "SOFT_ROUTES_MAX_CELLS", "SOFT_ROUTES_MAX_WALKERS", "soft_routes_tiled",
+           "soft_routes_tiled_from_tape"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -2172,31 +2173,35 @@ def _checked_sample_len(max_route_len) -> None:
         raise ValueError(f"max_route_len must be an int >= 1 (or None: horizon + 1, which no route outgrows), got {max_route_len!r}")
 
 
-def soft_routes_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
-                          starts: torch.Tensor, tau: float, horizon: Optional[int] = None, num_samples: int = 1, seed: int = 0,
-                          neighbor_mask: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False,
-                          uniforms: Optional[torch.Tensor] = None, shape: Optional[str] = None):
-    """``nastar_soft_routes`` as it is (include/nastar_soft_routes.h) -> ``(routes, route_lengths, route_costs, log_probs, visits or None,
-    status)``: the maps, ``tau``, ``horizon`` and mask of the ``soft_fields_forward(..., tape=True)`` call that wrote ``tape``.  Two
-    launches (the rows' -1 and the counts' zeros, then the walkers) on the current stream, nothing is read back: it can be captured into a graph.  ``seed``: an int (the Philox key);
-    ``uniforms``: a float32 [B,S,N,horizon] tensor that replaces the generator.  ``max_route_len=None``: rows of ``horizon + 1`` cells, which
-    no route outgrows.  ``shape``: None, or "lds" / "gather" to pick the kernel shape (probes and tests; the same bits).  What
-    ``soft_routes`` runs behind its forward."""
+def _soft_routes_limit(tiled: bool, H: int, W: int) -> None:
+    if tiled:
+        _soft_tiled_limit(H, W, "soft_routes_tiled")
+    elif H * W > SOFT_ROUTES_MAX_CELLS:
+        raise NotImplementedError(f"soft_routes: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_ROUTES_MAX_CELLS} cells (the "
+                                  "one-workgroup soft field; larger maps: soft_routes_tiled)")
+
+
+def _soft_routes_from_tape(tiled: bool, cost_maps, goal_maps, obstacles_maps, tape, starts, tau, horizon, num_samples, seed, neighbor_mask,
+                           max_route_len, visits, uniforms, shape=None, checkpoint_every=None):
+    """the raw walker call of ``soft_routes_from_tape`` and ``soft_routes_tiled_from_tape``: the refusals in one order, the outputs, ONE C
+    call with its arguments in header order -> ``(routes, route_lengths, route_costs, log_probs, visits or None, status)``.  ``tiled``:
+    ``checkpoint_every`` and a workspace, which the one-workgroup call does not have; ``shape`` is the one-workgroup call's."""
+    what = "soft_routes_tiled" if tiled else "soft_routes"
     t = _checked_tau(tau)
     maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     K = _checked_horizon(horizon, H, W)
     N = _checked_samples(num_samples)
     seed = _checked_seed(seed)
     _checked_sample_len(max_route_len)
-    if shape not in SOFT_ROUTES_SHAPES:
+    if tiled:
+        c = _checked_checkpoint_every(checkpoint_every, K)
+    elif shape not in SOFT_ROUTES_SHAPES:
         raise ValueError(f"shape must be None, 'lds' or 'gather', got {shape!r}")
-    if H * W > SOFT_ROUTES_MAX_CELLS:
-        raise NotImplementedError(f"soft_routes: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_ROUTES_MAX_CELLS} cells (the "
-                                  "one-workgroup soft field; sampling from the tiled field's checkpointed tape is not implemented)")
+    _soft_routes_limit(tiled, H, W)
     idx = _start_indices(starts, B, H, W)
     S = idx.shape[1]
     if B * S * N > SOFT_ROUTES_MAX_WALKERS:
-        raise NotImplementedError(f"soft_routes: {B} maps x {S} starts x {N} samples exceed the limit of {SOFT_ROUTES_MAX_WALKERS} walkers per call")
+        raise NotImplementedError(f"{what}: {B} maps x {S} starts x {N} samples exceed the limit of {SOFT_ROUTES_MAX_WALKERS} walkers per call")
     if uniforms is not None and (not torch.is_tensor(uniforms) or uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (B, S, N, K)):
         raise ValueError(f"uniforms must be a float32 tensor of shape ({B}, {S}, {N}, {K}) = [B,S,N,horizon], got "
                          f"{tuple(uniforms.shape) if torch.is_tensor(uniforms) else type(uniforms).__name__}")
@@ -2204,9 +2209,10 @@ def soft_routes_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obst
     for name, x in (("starts", idx), ("uniforms", uniforms)):
         if x is not None and x.device != dev:
             raise ValueError(f"the maps live on {dev}, {name} on {x.device}: they must share a device")
-    lib = _field_lib("nastar_soft_routes", "nastar_soft_routes.h")
+    symbol = "nastar_soft_routes_tiled" if tiled else "nastar_soft_routes"
+    lib = _field_lib(symbol, symbol + ".h")
     if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
-        raise ValueError(f"tape must be the contiguous uint8 tensor soft_fields_forward(..., tape=True) returned, on {dev}")
+        raise ValueError(f"tape must be the contiguous uint8 tensor soft_fields{'_tiled' if tiled else ''}_forward(..., tape=True) returned, on {dev}")
     cap = K + 1 if max_route_len is None else max_route_len
     with torch.no_grad():
         cost, goal, passable = (_maps3(m.detach()) for m in maps)
@@ -2218,15 +2224,52 @@ def soft_routes_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obst
         logp = torch.empty((B, S, N), dtype=torch.float32, device=dev)
         counts = torch.empty((B, S, H, W), dtype=torch.int32, device=dev) if visits else None
         status = torch.empty((B, S), dtype=torch.int32, device=dev)
-        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(), idx.data_ptr(), B, S, N, H, W, mask, t, K,
-                seed, _ptr(uni), routes.data_ptr(), cap, lengths.data_ptr(), costs.data_ptr(), logp.data_ptr(), _ptr(counts), status.data_ptr())
+        args = (cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel()) + ((c,) if tiled else ())
+        args += (idx.data_ptr(), B, S, N, H, W, mask, t, K, seed, _ptr(uni), routes.data_ptr(), cap, lengths.data_ptr(), costs.data_ptr(),
+                 logp.data_ptr(), _ptr(counts), status.data_ptr())
+        entry = symbol
+        if tiled:
+            ws_bytes = int(lib.nastar_soft_routes_tiled_workspace_bytes(B, S, N, H, W, K, c))
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            args += (ws.data_ptr(), ws_bytes)
+        elif shape is not None:
+            entry, args = symbol + "_with_shape", args + (SOFT_ROUTES_SHAPES[shape],)
         with torch.cuda.device(dev):
-            if shape is None:
-                rc = lib.nastar_soft_routes(*args, _stream_ptr(dev))
-            else:
-                rc = lib.nastar_soft_routes_with_shape(*args, SOFT_ROUTES_SHAPES[shape], _stream_ptr(dev))
-        _native.check(rc, "nastar_soft_routes")
+            rc = getattr(lib, entry)(*args, _stream_ptr(dev))
+        _native.check(rc, symbol)
     return routes, lengths, costs, logp, counts, status
+
+
+def _soft_routes(tiled: bool, cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask, max_route_len, visits,
+                 uniforms, checkpoint_every=None) -> "SoftRoutes":
+    """the body of ``soft_routes`` and ``soft_routes_tiled``: the refusals before anything is launched, the forward with its tape, the
+    walkers"""
+    _checked_samples(num_samples)
+    _checked_sample_len(max_route_len)
+    seed = _checked_seed(seed)
+    _, _, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    _soft_routes_limit(tiled, H, W)
+    _start_indices(starts, B, H, W)  # (refused before the forward launches anything)
+    dists, _, _, map_status, tape = _soft_forward(tiled, False, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, False, True,
+                                                  checkpoint_every, tape_limit=SOFT_ROUTES_MAX_CELLS)
+    routes, lengths, costs, logp, counts, status = _soft_routes_from_tape(tiled, cost_maps, goal_maps, obstacles_maps, tape, starts, tau, horizon,
+                                                                          num_samples, seed, neighbor_mask, max_route_len, visits, uniforms,
+                                                                          checkpoint_every=checkpoint_every)
+    return SoftRoutes(routes, lengths, costs, logp, counts, dists, status, map_status)
+
+
+def soft_routes_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
+                          starts: torch.Tensor, tau: float, horizon: Optional[int] = None, num_samples: int = 1, seed: int = 0,
+                          neighbor_mask: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False,
+                          uniforms: Optional[torch.Tensor] = None, shape: Optional[str] = None):
+    """``nastar_soft_routes`` as it is (include/nastar_soft_routes.h) -> ``(routes, route_lengths, route_costs, log_probs, visits or None,
+    status)``: the maps, ``tau``, ``horizon`` and mask of the ``soft_fields_forward(..., tape=True)`` call that wrote ``tape``.  Two
+    launches (the rows' -1 and the counts' zeros, then the walkers) on the current stream, nothing is read back: it can be captured into a graph.  ``seed``: an int (the Philox key);
+    ``uniforms``: a float32 [B,S,N,horizon] tensor that replaces the generator.  ``max_route_len=None``: rows of ``horizon + 1`` cells, which
+    no route outgrows.  ``shape``: None, or "lds" / "gather" to pick the kernel shape (probes and tests; the same bits).  What
+    ``soft_routes`` runs behind its forward."""
+    return _soft_routes_from_tape(False, cost_maps, goal_maps, obstacles_maps, tape, starts, tau, horizon, num_samples, seed, neighbor_mask,
+                                  max_route_len, visits, uniforms, shape)
 
 
 def soft_routes(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor, tau: float,
@@ -2238,7 +2281,8 @@ def soft_routes(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
     left draws from pi_k, the softmax of -V_{k-1} / tau: the non-stationary chain, not the one plane ``soft_cost_to_go(policies=True)``
     returns.  As ``tau`` goes to 0 every sample is ``field_routes``' optimal route.
 
-    The maps, ``tau``, ``horizon`` and ``neighbor_mask`` of ``soft_cost_to_go``, maps of at most ``SOFT_ROUTES_MAX_CELLS`` cells.
+    The maps, ``tau``, ``horizon`` and ``neighbor_mask`` of ``soft_cost_to_go``, maps of at most ``SOFT_ROUTES_MAX_CELLS`` cells
+    (NotImplementedError above; larger maps: ``soft_routes_tiled``).
     ``starts``: an integer [B,S] tensor of flat cell indices r*W + c, or a float [B,S,H,W] tensor of start maps (``field_routes``).
     ``seed``: an int, or None = one 63-bit draw from torch's default CPU generator (``torch.manual_seed`` makes a run repeatable); a sample
     is a pure function of the inputs, the seed and its (map, start, sample) numbers: the same seed gives the same bits, and the first N
@@ -2249,16 +2293,38 @@ def soft_routes(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
     An EVALUATION call on the current stream of the inputs' device: the forward launch with its tape (B * horizon * H * W fp32), a
     launch that clears the rows and the counts and the walkers' launch; detached outputs, nothing is read back -- it can be captured into a graph -- and nothing raises for a
     failed query or a bad map: read ``status`` and ``map_status``."""
-    _checked_samples(num_samples)
-    _checked_sample_len(max_route_len)
-    seed = _checked_seed(seed)
-    _, _, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
-    if H * W > SOFT_ROUTES_MAX_CELLS:
-        raise NotImplementedError(f"soft_routes: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_ROUTES_MAX_CELLS} cells (the "
-                                  "one-workgroup soft field; sampling from the tiled field's checkpointed tape is not implemented)")
-    _start_indices(starts, B, H, W)  # (refused before the forward launches anything)
-    dists, _, _, map_status, tape = _soft_forward(False, False, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, False, True,
-                                                  tape_limit=SOFT_ROUTES_MAX_CELLS)
-    routes, lengths, costs, logp, counts, status = soft_routes_from_tape(cost_maps, goal_maps, obstacles_maps, tape, starts, tau, horizon,
-                                                                         num_samples, seed, neighbor_mask, max_route_len, visits, uniforms)
-    return SoftRoutes(routes, lengths, costs, logp, counts, dists, status, map_status)
+    return _soft_routes(False, cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask, max_route_len, visits,
+                        uniforms)
+
+
+# ---- include/nastar_soft_routes_tiled.h: the same samples from the tiled field's checkpointed tape (DESIGN.md section 2, item 6q)
+def soft_routes_tiled_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
+                                starts: torch.Tensor, tau: float, horizon: Optional[int] = None, num_samples: int = 1, seed: int = 0,
+                                neighbor_mask: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False,
+                                uniforms: Optional[torch.Tensor] = None, checkpoint_every: Optional[int] = None):
+    """``nastar_soft_routes_tiled`` as it is (include/nastar_soft_routes_tiled.h) -> ``(routes, route_lengths, route_costs, log_probs,
+    visits or None, status)``: the maps, ``tau``, ``horizon``, mask and ``checkpoint_every`` of the ``soft_fields_tiled_forward(...,
+    tape=True)`` call that wrote ``tape``.  On the current stream: a prepare and a clear launch, then per segment of the tape the
+    forward's sweeps that rebuild its planes and one launch of walkers; nothing is read back.  With ``max_route_len`` below
+    ``horizon + 1`` the walk is replayed for the stores and every segment is rebuilt TWICE; None = rows of ``horizon + 1`` cells never
+    pays that.  The other arguments are ``soft_routes_from_tape``'s.  What ``soft_routes_tiled`` runs behind its forward."""
+    return _soft_routes_from_tape(True, cost_maps, goal_maps, obstacles_maps, tape, starts, tau, horizon, num_samples, seed, neighbor_mask,
+                                  max_route_len, visits, uniforms, checkpoint_every=checkpoint_every)
+
+
+def soft_routes_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor, tau: float,
+                      horizon: Optional[int] = None, num_samples: int = 1, seed: Optional[int] = None, neighbor_mask: Optional[int] = None,
+                      max_route_len: Optional[int] = None, visits: bool = False, uniforms: Optional[torch.Tensor] = None,
+                      checkpoint_every: Optional[int] = None) -> SoftRoutes:
+    """``soft_routes`` for maps of up to ``SOFT_FIELDS_TILED_MAX_CELLS`` cells (1024x1152: every map size the search takes), from the
+    tiled field's checkpointed tape (include/nastar_soft_routes_tiled.h) -> ``SoftRoutes``.  The same definition, the same arguments and,
+    on the maps both take, the same BITS in every output, whatever ``checkpoint_every`` is (None = ceil(sqrt(horizon)); 1 keeps every
+    plane); NotImplementedError above the limit, before anything is launched.
+
+    An EVALUATION call on the current stream: ``soft_cost_to_go_tiled``'s launches with the tape, then about one more forward -- the
+    sweeps that rebuild each segment of the tape, top down -- with one launch of walkers per segment; a walker lives in a workspace
+    between two launches.  With ``max_route_len`` below ``horizon + 1`` the walk is replayed, first for the lengths, then for the
+    stores, and every segment is rebuilt TWICE; the default rows of ``horizon + 1`` cells never pay that.  Detached outputs, nothing is
+    read back, nothing raises for a failed query or a bad map: read ``status`` and ``map_status``."""
+    return _soft_routes(True, cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask, max_route_len, visits,
+                        uniforms, checkpoint_every)

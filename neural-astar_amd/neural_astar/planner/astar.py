@@ -145,6 +145,14 @@ class VanillaAstar(nn.Module):
         exp(-L / tau).  An evaluation call."""
         return self.astar.sample_routes(map_designs, starts, goal_maps, map_designs, tau, num_samples, seed, horizon, max_route_len, visits)
 
+    def sample_routes_tiled(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, tau: float, num_samples: int = 1,
+                            seed: Optional[int] = None, horizon: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False,
+                            checkpoint_every: Optional[int] = None):
+        """``sample_routes`` from the tiled soft field's checkpointed tape (``DifferentiableAstar.sample_routes_tiled``: maps of up to
+        1024x1152, the same bits)."""
+        return self.astar.sample_routes_tiled(map_designs, starts, goal_maps, map_designs, tau, num_samples, seed, horizon, max_route_len, visits,
+                                              checkpoint_every)
+
     def shortest_paths(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, lambda_: Optional[float] = None,
                        min_cost: float = 2.0 ** -10) -> PathOutput:
         """The exact optimal path of every map as a 0/1 mask (``DifferentiableAstar.shortest_paths``: field and chase in one launch) with
@@ -434,9 +442,31 @@ class NeuralAstar(VanillaAstar):
             raise NotImplementedError(f"NeuralAstar.sample_routes: with encoder_input={self.encoder_input!r} the predicted cost map depends on "
                                       "the start, so one soft field cannot serve several starts; encode per start and call "
                                       "planner.astar.sample_routes(cost_maps, starts, goal_maps, obstacles_maps, tau), or use encoder_input='m'")
+        return self.astar.sample_routes(*self._sample_inputs(map_designs, starts, goal_maps), tau, num_samples, seed, horizon, max_route_len, visits)
+
+    def sample_routes_tiled(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, tau: float, num_samples: int = 1,
+                            seed: Optional[int] = None, horizon: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False,
+                            checkpoint_every: Optional[int] = None):
+        """``sample_routes`` on the PREDICTED cost maps from the tiled soft field's checkpointed tape
+        (``DifferentiableAstar.sample_routes_tiled``: maps of up to 1024x1152, the same bits): what a model trained with
+        ``maxent_path_nll(..., tiled=True)`` generates.  For ``encoder_input == "m"`` only, as ``sample_routes``."""
+        _checked_route_len(max_route_len)  # (every refusal before the encoder launches anything)
+        ops._checked_tau(tau)
+        ops._checked_samples(num_samples)
+        if self.encoder_input != "m":
+            raise NotImplementedError(f"NeuralAstar.sample_routes_tiled: with encoder_input={self.encoder_input!r} the predicted cost map depends "
+                                      "on the start, so one soft field cannot serve several starts; encode per start and call "
+                                      "planner.astar.sample_routes_tiled(cost_maps, starts, goal_maps, obstacles_maps, tau), or use "
+                                      "encoder_input='m'")
+        return self.astar.sample_routes_tiled(*self._sample_inputs(map_designs, starts, goal_maps), tau, num_samples, seed, horizon, max_route_len,
+                                              visits, checkpoint_every)
+
+    def _sample_inputs(self, map_designs, starts, goal_maps):
+        """the (cost, starts, goal, obstacles) maps of ``sample_routes`` / ``sample_routes_tiled``: encoded once, detached, with an all-zero
+        start channel"""
         cost_maps = self.encode(map_designs, torch.zeros_like(goal_maps), goal_maps).detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(goal_maps)
-        return self.astar.sample_routes(cost_maps, starts, goal_maps, obstacles_maps, tau, num_samples, seed, horizon, max_route_len, visits)
+        return cost_maps, starts, goal_maps, obstacles_maps
 
     def shortest_paths(self, map_designs: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, lambda_: Optional[float] = None,
                        min_cost: float = 2.0 ** -10) -> PathOutput:

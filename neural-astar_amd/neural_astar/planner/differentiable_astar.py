@@ -744,6 +744,18 @@ class DifferentiableAstar(nn.Module):
         return ops.soft_routes(cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask=self.neighbor_mask(),
                                max_route_len=max_route_len, visits=visits)
 
+    def sample_routes_tiled(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                            tau: float, num_samples: int = 1, seed: Optional[int] = None, horizon: Optional[int] = None,
+                            max_route_len: Optional[int] = None, visits: bool = False,
+                            checkpoint_every: Optional[int] = None) -> "ops.SoftRoutes":
+        """``sample_routes`` for maps of up to ``ops.SOFT_FIELDS_TILED_MAX_CELLS`` cells (``ops.soft_routes_tiled``, include/
+        nastar_soft_routes_tiled.h: the tiled soft field with its checkpointed tape, then the walkers segment by segment; the same bits on
+        the maps both take), under this module's own move set, with the tape's ``checkpoint_every``.  An EVALUATION call; a
+        ``max_route_len`` below ``horizon + 1`` rebuilds every segment of the tape twice."""
+        return ops.soft_routes_tiled(cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed,
+                                     neighbor_mask=self.neighbor_mask(), max_route_len=max_route_len, visits=visits,
+                                     checkpoint_every=checkpoint_every)
+
     def shortest_paths(self, cost_maps: torch.Tensor, start_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
                        lambda_: Optional[float] = None, min_cost: float = 2.0 ** -10) -> PathOutput:
         """The EXACT optimal path of every map as a 0/1 mask (``ops.shortest_paths``, the kernel of include/nastar_path_masks.h: field and
