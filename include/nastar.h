@@ -615,8 +615,9 @@ int nastar_upcat_bwd_f16(const uint16_t* dcat, uint16_t* dx, uint16_t* dskip, in
 int nastar_grad_add_f16(const uint16_t* a, const float* scale_a, const uint16_t* b, const float* scale_b, uint16_t* out, float* scale_out,
                         long long npix, int C, int split, void* stream);
 
-/* Resident forward workgroups (= maps) per CU the runtime reports for an HxW map, and the LDS bytes one map takes
- * (diagnostics for DESIGN.md / bench.py; returns -1 on error, 0 if the size is unsupported). */
+/* Resident forward workgroups (= maps) per CU the runtime reports for an HxW map, and the LDS bytes one map takes, both for the
+ * kernel a default launch takes.  At 16x16, 32x32 and 64x64 that is the hand-scheduled instantiation, whose layout has guard rows
+ * (10240 bytes at 32x32).  Diagnostics for DESIGN.md; returns -1 on error, 0 if the size is unsupported. */
 int nastar_debug_occupancy(int H, int W, int* lds_bytes_out);
 
 #ifdef __cplusplus

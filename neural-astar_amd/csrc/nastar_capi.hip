@@ -103,7 +103,7 @@ static bool needs_global_state(int H, int W)
     if (HW >= hybrid_from_cells()) return true;
     if (HW > 65535 - CCSZ) return true;
     const long long nchunks = (HW + CCSZ - 1) / CCSZ;
-    return compact_lds_bytes((int)(nchunks * CCSZ), (int)(((nchunks + 63) / 64) * 64)) > kMaxLdsBytes;
+    return compact_launch_lds_bytes(H, W, (int)(nchunks * CCSZ), (int)(((nchunks + 63) / 64) * 64), true) > kMaxLdsBytes;
 }
 
 // Workspace of a forward launch: [hybrid slabs (maps larger than LDS)] [marks: B int32 + the t_end cell, NASTAR_FLAG_MARK_COUPLED]
@@ -175,15 +175,24 @@ static auto compiled_compact_kernel()
     else return &nastar_forward_compact_kernel<kVec4, LOGW, LOGH, CPL_T, kFastDiv, kLog>;
 }
 
+// THE decision whether a launch takes a hand-scheduled instantiation (kKind as below; use_asm: Moore-8, no lock-step, not switched off).
+// forward_lds asks once and hands the answer on: the kernel (compact_kernel, the ranked kernels) and the launch's dynamic-LDS size
+// (compact_launch_lds_bytes: those instantiations carve guard rows) both follow it.
+static bool takes_asm_stream(const CompactDims& d, int kind, bool vec4, bool fast, bool use_asm)
+{
+    return kind == 0 && use_asm && vec4 && fast && compact_asm_shape(d.H, d.W);
+}
+
 // the compact-state kernel for a map: a hand-scheduled stream where one exists (Moore-8 only: the streams hard-wire the stencil), else the
 // compiled step loop -- compile-time sizes for 16x16, 32x32 and 64x64, one chunk minimum per lane, or runtime sizes
+// asm_stream: the answer of takes_asm_stream for this launch (false for every kKind but 0)
 template <int kKind, bool kLog>
-static auto compact_kernel(const CompactDims& d, bool vec4, bool fast, bool use_asm)
+static auto compact_kernel(const CompactDims& d, bool vec4, bool fast, bool asm_stream)
 {
     if constexpr (kKind == 0) {
-        if (use_asm && vec4 && fast && d.H == 32 && d.W == 32) return &nastar_forward_compact_kernel<true, 5, 5, 1, true, kLog, true>;
-        if (use_asm && vec4 && fast && d.H == 16 && d.W == 16) return &nastar_forward_compact_kernel<true, 4, 4, 1, true, kLog, true>;
-        if (use_asm && vec4 && fast && d.H == 64 && d.W == 64) return &nastar_forward_compact_kernel<true, 6, 6, 4, true, kLog, true>;
+        if (asm_stream && d.W == 32) return &nastar_forward_compact_kernel<true, 5, 5, 1, true, kLog, true>;
+        if (asm_stream && d.W == 16) return &nastar_forward_compact_kernel<true, 4, 4, 1, true, kLog, true>;
+        if (asm_stream && d.W == 64) return &nastar_forward_compact_kernel<true, 6, 6, 4, true, kLog, true>;
     }
     if (vec4 && fast && d.H == 32 && d.W == 32) return compiled_compact_kernel<kKind, true, 5, 5, 1, true, kLog>();
     if (vec4 && fast && d.H == 64 && d.W == 64) return compiled_compact_kernel<kKind, true, 6, 6, 4, true, kLog>();
@@ -354,8 +363,8 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     FwdCArgs c;
     int rc = make_cdims(f.B, f.H, f.W, f.max_iters, f.g_ratio, c.d);
     if (rc) return rc;
-    const size_t lds = f.nb.h0 ? compact_heur_lds_bytes(c.d.HWp, c.d.NCp) : compact_lds_bytes(c.d.HWp, c.d.NCp);
-    if (lds > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
+    const size_t state_lds = f.nb.h0 ? compact_heur_lds_bytes(c.d.HWp, c.d.NCp) : compact_lds_bytes(c.d.HWp, c.d.NCp);
+    if (state_lds > kMaxLdsBytes) return NASTAR_ERR_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(f.stream);
     c.cost = f.cost; c.start = f.start; c.goal = f.goal; c.passable = f.passable;
     c.hist = f.histories_out; c.paths = reinterpret_cast<long long*>(f.paths_out);
@@ -386,6 +395,10 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     const bool fast = fastdiv_verified(f.W);
     // the hand-scheduled streams: Moore-8 only, and lock-step mode lives in the compiled step loops
     const bool use_asm = !f.nb.masked && !(f.flags & (NASTAR_FLAG_NO_ASM | NASTAR_FLAG_LOCKSTEP));
+    // the launch's dynamic LDS: a hand-scheduled instantiation (Moore-8 kernel or the ranked one, built-in heuristic, one source) has guard rows
+    const int kind = f.nb.multi ? (f.nb.h0 ? 4 : 3) : f.nb.h0 ? 2 : f.nb.masked ? 1 : 0;  // (compiled_compact_kernel's kKind)
+    const bool asm_stream = takes_asm_stream(c.d, kind, vec4, fast, use_asm);
+    const size_t lds = asm_stream ? compact_launch_lds_bytes(f.H, f.W, c.d.HWp, c.d.NCp, true) : state_lds;
     // unit-cost layout: the caller promises cost == passable with values in {0, 1} (checked per map by the kernel); taken when the promise can
     // hold at all (ONE tensor), no selection log is wanted and the hand-scheduled stream exists for the size
     const bool unit = (f.flags & NASTAR_FLAG_UNIT_COST) && f.cost == f.passable && use_asm && !(f.flags & (NASTAR_FLAG_ASM_V2 | NASTAR_FLAG_ASM_V3)) &&
@@ -399,7 +412,7 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
     unsigned long long* const tw = f.ticket_word;
     const unsigned long long tv = f.ticket_value;
     if (f.levels) {  // (nastar_forward_levels checked the shape, the flags and the log: what is left is the alignment of the caller's pointers)
-        if (!vec4 || !fast || !use_asm || unit) return NASTAR_ERR_UNSUPPORTED;
+        if (!asm_stream || unit) return NASTAR_ERR_UNSUPPORTED;  // (the ranked kernel exists as hand-scheduled instantiations only)
         const int* lv = f.levels;
         rc = f.W == 32   ? launch(&nastar_forward_compact_ranked_kernel<true, 5, 5, 1, true, false, true>, f.B, lds, s, c, rcp, lv, tw, tv)
              : f.W == 16 ? launch(&nastar_forward_compact_ranked_kernel<true, 4, 4, 1, true, false, true>, f.B, lds, s, c, rcp, lv, tw, tv)
@@ -411,7 +424,7 @@ static int forward_lds(const FwdLaunch& f, int* marks_out, bool& packed_done)
         return launch(compact_kernel<(heur ? 4 : 3), lg>(c.d, vec4, fast, false), f.B, lds, s, c, rcp, f.nb.mask, f.nb.h0);
     }, f.nb.h0 != nullptr, f.sel_log_out != nullptr);
     else rc = with_bools([&](auto masked, auto heur, auto lg) {
-        const auto kern = compact_kernel<(heur ? 2 : masked ? 1 : 0), lg>(c.d, vec4, fast, use_asm);
+        const auto kern = compact_kernel<(heur ? 2 : masked ? 1 : 0), lg>(c.d, vec4, fast, asm_stream);
         if constexpr (heur) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask, f.nb.h0);
         else if constexpr (masked) return launch(kern, f.B, lds, s, c, rcp, f.nb.mask);
         else {
@@ -985,12 +998,14 @@ int nastar_debug_occupancy(int H, int W, int* lds_bytes_out)
 {
     CompactDims d;
     if (make_cdims(1, H, W, 1, 0.5, d)) return -1;
-    const size_t lds = compact_lds_bytes(d.HWp, d.NCp);
+    // the kernel and the size of a default launch: the hand-scheduled instantiation with its guard rows where one exists
+    const size_t lds = compact_launch_lds_bytes(H, W, d.HWp, d.NCp, true);
     if (lds_bytes_out) *lds_bytes_out = (int)lds;
     if (lds > kMaxLdsBytes) return 0;
     void (*kern)(const FwdCArgs, const float, unsigned long long*, const unsigned long long) = &nastar_forward_compact_kernel<true, 0, 0, 0, false, false>;
-    if (H == 32 && W == 32) kern = &nastar_forward_compact_kernel<true, 5, 5, 1, true, false>;
-    if (H == 64 && W == 64) kern = &nastar_forward_compact_kernel<true, 6, 6, 4, true, false>;
+    if (H == 16 && W == 16) kern = &nastar_forward_compact_kernel<true, 4, 4, 1, true, false, true>;
+    if (H == 32 && W == 32) kern = &nastar_forward_compact_kernel<true, 5, 5, 1, true, false, true>;
+    if (H == 64 && W == 64) kern = &nastar_forward_compact_kernel<true, 6, 6, 4, true, false, true>;
     if (ensure_lds(kern, lds)) return -1;
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 64, lds) != hipSuccess) return -1;

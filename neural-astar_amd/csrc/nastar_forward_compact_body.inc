@@ -47,7 +47,11 @@
         d.NCp = d.CPL * 64;
         d.magicW = (uint32_t)((1ull << 32) >> LOGW) + 1u;
     }
-    const CompactLds l = carve_compact_lds(smem, d);
+    CompactLds l;
+    if constexpr (kAsm) {  // guard rows around gc[], no dump words (nastar_search_compact.hip.h)
+        l = carve_compact_asm_lds(smem, d);
+        compact_store_guard_rows(l, d, lane);
+    } else l = carve_compact_lds(smem, d);
     const size_t off = (size_t)b * (size_t)d.HW;
 
     int start_idx, goal_idx;

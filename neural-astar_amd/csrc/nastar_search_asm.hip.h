@@ -25,15 +25,23 @@
 
 namespace nastar {
 
-// LDS byte offsets of the single-map compact layout with HW cells, 64 chunk minima (carve_compact_lds): gc | cmin | dump | pdir
+// LDS byte offsets of the hand-scheduled instantiations' layout (carve_compact_asm_lds, nastar_search_compact.hip.h):
+//   guard_lo (W cells) | gc (HW cells) | guard_hi (W cells) | cmin (CPL * 64 entries) | pdir (HW bytes)
+// A guard cell's g word is -inf for the whole launch: "row -1" and "row W" of the map, which the stored-heuristic step
+// (nastar_search_asm5.hip.h) reads instead of testing rows.  Every stream addresses gc[cell] as 8 * cell + GC through the
+// instruction's offset field, so a cell index may be negative (a DS address is VGPR + offset modulo 2^32).
 template <int LOGW>
 struct AsmLayout {
     static constexpr int W = 1 << LOGW;
     static constexpr int HW = W * W;
     static constexpr int CPL = (HW / 16 + 63) / 64;  // chunk minima per lane: 1 (<= 1024 cells) or 4 (64x64)
-    static constexpr int CMIN = HW * 8;
-    static constexpr int PDIR = CMIN + CPL * 64 * 8 + 256;
+    static constexpr int GC = W * 8;
+    static constexpr int CMIN = GC + HW * 8 + W * 8;
+    static constexpr int PDIR = CMIN + CPL * 64 * 8;
+    static constexpr int BYTES = PDIR + HW;
 };
+static_assert(AsmLayout<5>::BYTES == (int)compact_asm_lds_bytes(32, 1024, 64) && AsmLayout<5>::BYTES * 16 == 160 * 1024, "16 maps of 32x32 per CU");
+static_assert(AsmLayout<6>::BYTES == (int)compact_asm_lds_bytes(64, 4096, 256) && AsmLayout<4>::BYTES == (int)compact_asm_lds_bytes(16, 256, 64), "host and stream agree");
 
 #define NASTAR_ASM_ENTRY \
         "s_cmp_ge_u32 %[it], %[maxit]\n\t" \
@@ -110,8 +118,8 @@ struct AsmLayout {
         "v_cndmask_b32 v46, v24, v46, vcc\n\t" /* il: this lane's cell (s* itself for out-of-map neighbours / idle lanes) */ \
         "v_lshlrev_b32 v27, 3, v24\n\t" \
         "v_lshlrev_b32 v26, 3, v46\n\t" \
-        "ds_read_b64 v[28:29], v27\n\t" /* g[s*], cost[s*] */ \
-        "ds_read_b64 v[30:31], v26\n\t" /* g[il], cost[il] */ \
+        "ds_read_b64 v[28:29], v27 offset:%[GC]\n\t" /* g[s*], cost[s*] */ \
+        "ds_read_b64 v[30:31], v26 offset:%[GC]\n\t" /* g[il], cost[il] */ \
  /* h0 = get_heuristic at il (:26-52), in the shadow of the LDS round trip */ \
         "v_lshrrev_b32 v32, %[LOGW], v46\n\t" \
         "v_and_b32 v33, %[WM1], v46\n\t" \
@@ -153,7 +161,7 @@ struct AsmLayout {
  /* lane 8 closes s* (:222-225) and empties its chunk's entry; the chunk's open cells (without s*) then re-enter it through \
     the same 64-bit atomic minimum the relaxed neighbours use: (key, cell) lexicographic = first flat index on ties */ \
         "s_mov_b64 exec, 0x100\n\t" \
-        "ds_write_b32 v27, %[vminf]\n\t" \
+        "ds_write_b32 v27, %[vminf] offset:%[GC]\n\t" \
         "ds_write_b64 v52, v[48:49] offset:%[CMIN]\n\t" \
         "s_mov_b64 exec, -1\n\t" \
         "v_cmpx_gt_f32 vcc, v30, v44\n\t" /* chunk lanes other than s* whose g > -inf ... */ \
@@ -161,7 +169,7 @@ struct AsmLayout {
         "ds_min_u64 v50, v[46:47] offset:%[CMIN]\n\t" \
         "s_mov_b64 exec, -1\n\t" \
         "v_cmpx_gt_f32 vcc, v30, v45\n\t" /* :229,:235 g[n] > g2 on in-map neighbour lanes */ \
-        "ds_write_b32 v26, v40\n\t" /* :238 g[n] = g2 */ \
+        "ds_write_b32 v26, v40 offset:%[GC]\n\t" /* :238 g[n] = g2 */ \
         "ds_write_b8 v46, %[pcode] offset:%[PDIR]\n\t" /* :246-249 parent = s* */ \
         "ds_min_u64 v50, v[46:47] offset:%[CMIN]\n\t" /* :242 (key, n) enters its chunk's minimum */ \
         "s_mov_b64 exec, -1\n\t"
@@ -184,7 +192,7 @@ struct AsmLayout {
           [vinf] "v"(v_inf), [vminf] "v"(v_minf), [loc] "v"(v_loc), [goal] "s"(goal_idx), [gr] "s"(goal_r), [gc] "s"(goal_c), \
           [maxit] "s"(max_iters), [cgr] "s"(d.gr), [comg] "s"(d.omg), [csq] "s"(d.sqrtW), [crcp] "s"(rcp_sqrtW), \
           [mnb] "s"(m_nb), [mchk] "s"(m_chk), [msb] "s"(msb), [logp] "s"(logp), \
-          [CMIN] "i"(L::CMIN), [CMIN16] "i"(L::CMIN + 16), [PDIR] "i"(L::PDIR), [LOGW] "i"(LOGW), [WM1] "i"(L::W - 1), [W] "i"(L::W) \
+          [GC] "i"(L::GC), [CMIN] "i"(L::CMIN), [CMIN16] "i"(L::CMIN + 16), [PDIR] "i"(L::PDIR), [LOGW] "i"(LOGW), [WM1] "i"(L::W - 1), [W] "i"(L::W) \
         : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v24", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", \
           "v34", "v35", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v52", "s40", "s41", "s42", \
           "s43", "s44", "s45", "s46", "s47", "s50", "s51", "s52", "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49"

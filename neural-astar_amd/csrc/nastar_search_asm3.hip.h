@@ -85,7 +85,7 @@ namespace nastar {
         "v_lshl_add_u32 v46, v32, %[LOGW], v33\n\t" /* this lane's cell (garbage outside the map) */ \
         "v_cmp_gt_u32 vcc, %[W], v23\n\t" /* inside the map (conv2d zero padding, :77-93); true for lane 8 and the chunk lanes */ \
         "v_lshlrev_b32 v27, 3, v24\n\t" \
-        "ds_read_b64 v[28:29], v27\n\t" /* g[s*], cost[s*] */ \
+        "ds_read_b64 v[28:29], v27 offset:%[GC]\n\t" /* g[s*], cost[s*] */ \
         "s_and_b64 s[54:55], vcc, %[mnb]\n\t" /* in-map neighbour lanes */ \
         "v_cndmask_b32 v46, v24, v46, vcc\n\t" /* il: s* itself for out-of-map neighbours */ \
         "v_lshlrev_b32 v26, 3, v46\n\t" \
@@ -94,11 +94,11 @@ namespace nastar {
 #define NASTAR_ASM3_X_CLOSE \
  /* lane 8 (il == s*) closes s* (:222-225) and empties its chunk's entry BEFORE the lanes read their cells */ \
         "s_mov_b64 exec, 0x100\n\t" \
-        "ds_write_b32 v27, %[vminf]\n\t" \
+        "ds_write_b32 v27, %[vminf] offset:%[GC]\n\t" \
         "ds_write_b64 v50, v[48:49] offset:%[CMIN]\n\t" \
         "s_mov_b64 exec, -1\n\t"
 #define NASTAR_ASM3_X_READCELL \
-        "ds_read_b64 v[30:31], v26\n\t" /* g[il], cost[il] */
+        "ds_read_b64 v[30:31], v26 offset:%[GC]\n\t" /* g[il], cost[il] */
 #define NASTAR_ASM3_X_HEUR \
  /* h0 = get_heuristic at (r_l, c_l) (:26-52) on integers, in the shadow of the LDS round trip */ \
         "v_sad_u32 v35, v32, %[gr], 0\n\t" /* |dr| */ \
@@ -130,7 +130,7 @@ namespace nastar {
         "s_mov_b64 exec, s[54:55]\n\t" \
         "v_cmpx_gt_f32 vcc, v30, v40\n\t" /* :229,:235 g[n] > g2 on in-map neighbour lanes */ \
         SET55 \
-        "ds_write_b32 v26, v40\n\t" /* :238 g[n] = g2 */ \
+        "ds_write_b32 v26, v40 offset:%[GC]\n\t" /* :238 g[n] = g2 */ \
         "ds_write_b8 v46, %[pcode] offset:%[PDIR]\n\t" /* :246-249 parent = s* */ \
         "s_or_b64 exec, exec, s[58:59]\n\t" \
         "ds_min_u64 v50, v[46:47] offset:%[CMIN]\n\t" /* :242 relaxed neighbours AND the chunk's open cells enter the chunk minima: ONE atomic */ \
@@ -220,7 +220,7 @@ namespace nastar {
           [vminf] "v"(v_minf), [goal] "s"(goal_idx), [gr] "s"(goal_r), [gc] "s"(goal_c), \
           [maxit] "s"(max_iters), [cgr] "s"(d.gr), [comg] "s"(d.omg), [csq] "s"(d.sqrtW), [crcp] "s"(rcp_sqrtW), \
           [mnb] "s"(m_nb), [logp] "s"(logp), \
-          [CMIN] "i"(L::CMIN), [CMIN16] "i"(L::CMIN + 16), [PDIR] "i"(L::PDIR), [LOGW] "i"(LOGW), [WM1] "i"(L::W - 1), [W] "i"(L::W) \
+          [GC] "i"(L::GC), [CMIN] "i"(L::CMIN), [CMIN16] "i"(L::CMIN + 16), [PDIR] "i"(L::PDIR), [LOGW] "i"(LOGW), [WM1] "i"(L::W - 1), [W] "i"(L::W) \
         : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v24", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", \
           "v34", "v35", "v36", "v37", "v40", "v41", "v42", "v43", "v46", "v47", "v48", "v49", "v50", "s40", "s41", "s42", \
           "s43", "s44", "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49", \

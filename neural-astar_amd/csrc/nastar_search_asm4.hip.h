@@ -32,6 +32,7 @@ struct AsmLayoutUnit {
     static constexpr int W = 1 << LOGW;
     static constexpr int HW = W * W;
     static constexpr int CPL = (HW / 16 + 63) / 64;
+    static constexpr int GC = 0;  // no guard rows: g[] starts the layout
     static constexpr int CMIN = HW * 4;
     static constexpr int PDIR = CMIN + CPL * 64 * 8;
     static constexpr int BYTES = PDIR + HW;
@@ -139,7 +140,7 @@ struct AsmLayoutUnit {
           [vminf] "v"(v_minf), [goal] "s"(goal_idx), [gr] "s"(goal_r), [gc] "s"(goal_c), \
           [maxit] "s"(max_iters), [cgr] "s"(cgr), [comg] "s"(comg), [csq] "s"(csq), [crcp] "s"(rcp_sqrtW), \
           [mnb] "s"(m_nb), [logp] "s"(logp), \
-          [CMIN] "i"(CMIN), [CMIN16] "i"(CMIN + 16), [PDIR] "i"(PDIR), [LOGW] "i"(LOGW), [WM1] "i"((1 << LOGW) - 1), [W] "i"(1 << LOGW) \
+          [GC] "i"(GC), [CMIN] "i"(CMIN), [CMIN16] "i"(CMIN + 16), [PDIR] "i"(PDIR), [LOGW] "i"(LOGW), [WM1] "i"((1 << LOGW) - 1), [W] "i"(1 << LOGW) \
         : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v24", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", \
           "v34", "v35", "v36", "v37", "v40", "v41", "v42", "v43", "v46", "v47", "v48", "v49", "v50", "s40", "s41", "s42", \
           "s43", "s44", "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49", \
@@ -158,6 +159,7 @@ __device__ __forceinline__ int search_loop_asm4(float cgr, float comg, float csq
     using LG = AsmLayout<LOGW>;
     using LU = AsmLayoutUnit<LOGW>;
     constexpr int CPL = LG::CPL;
+    constexpr int GC = kUnit ? LU::GC : LG::GC;
     constexpr int CMIN = kUnit ? LU::CMIN : LG::CMIN;
     constexpr int PDIR = kUnit ? LU::PDIR : LG::PDIR;
     static_assert((CPL == 1 || CPL == 4) && LG::HW >= 256, "1 or 4 chunk minima per lane, chunks inside one map row");
@@ -182,10 +184,10 @@ __device__ __forceinline__ int search_loop_asm4(float cgr, float comg, float csq
     unsigned long long logp = reinterpret_cast<unsigned long long>(log_row);
 #define NASTAR_A4_SH_G "3"
 #define NASTAR_A4_SH_U "2"
-#define NASTAR_A4_RDS_G "ds_read_b64 v[28:29], v27\n\t"
-#define NASTAR_A4_RDS_U "ds_read_b32 v28, v27\n\t"
-#define NASTAR_A4_RDC_G "ds_read_b64 v[30:31], v26\n\t"
-#define NASTAR_A4_RDC_U "ds_read_b32 v30, v26\n\t"
+#define NASTAR_A4_RDS_G "ds_read_b64 v[28:29], v27 offset:%[GC]\n\t"
+#define NASTAR_A4_RDS_U "ds_read_b32 v28, v27 offset:%[GC]\n\t"
+#define NASTAR_A4_RDC_G "ds_read_b64 v[30:31], v26 offset:%[GC]\n\t"
+#define NASTAR_A4_RDC_U "ds_read_b32 v30, v26 offset:%[GC]\n\t"
 #define NASTAR_A4_ADDH_G "v_add_f32 v34, v34, v31\n\t"
 #define NASTAR_A4_ADDH_U "v_add_f32 v34, 1.0, v34\n\t"
 #define NASTAR_A4_ADDG_G "v_add_f32 v40, v28, v29\n\t"

@@ -1,5 +1,5 @@
 // nastar_search_asm5.hip.h -- the round-4 stream (nastar_search_asm4.hip.h, whose sections it reuses) for maps that keep the HEURISTIC
-// where the cost word was ("stored_h"): 60 instructions per 32x32 step at g_ratio == 0.5 instead of 71.
+// where the cost word was ("stored_h"): 55 instructions per 32x32 step at g_ratio == 0.5 instead of the general stream's 71.
 //
 // VanillaAstar hands ONE binary tensor over as cost map AND obstacle map (reference astar.py:93-94).  Every cell the search can relax
 // or key then costs exactly 1.0 (only passable cells are opened, :228-229; a START on an obstacle is the one exception, handled as in
@@ -9,40 +9,62 @@
 // word for every cell: same bytes per map, same maps per CU, same LDS carve.  In the step
 //   * the ten instructions of the heuristic (NASTAR_ASM3_X_HEUR, one of them v_sqrt_f32) and the add of the cost go: the key is
 //     f = fl(g + hh) from the (g, hh) pair the cell read delivers anyway;  g2 = fl(g[s*] + 1.0), a 4-byte read of g[s*];
-//   * the lanes no longer need (r_l, c_l) before their reads: the cell is (s* & colmask) + delta, two VALU instructions in place of
-//     six, bit for bit the index the round-4 prefix forms (out-of-map neighbour lanes keep that garbage index and only READ with it);
-//     s* goes into the shift of its byte offset as an SGPR operand (no v_mov);
-//   * the in-map test needs nothing from LDS and moves BEHIND the cell read, into the shadow the heuristic leaves.
-// In front of the two cell reads the step has 12 instructions instead of 16, behind the wait one fewer.
-// CLOSE, WAIT, RELAX, SELECT, the read-back, the exits, the log part and the dive are the round-4 / round-3 sections, token for token.
-// Hazard rules as in nastar_search_asm.hip.h.  s42 (s*, written by v_readlane) is now read by a VALU instruction at the head of the
+//   * the lanes need no (r_l, c_l) at all: the cell is (s* & colmask) + delta, two VALU instructions in place of six;  s* goes into
+//     the shift of its byte offset as an SGPR operand (no v_mov);
+//   * conv2d's zero padding (:77-93) is not computed, the map geometry fixes it.  COLUMNS: which neighbour lanes leave the map depends
+//     on c* alone, and c* is the low bits of s*: a loop-invariant VGPR holds in lane L the 8-bit mask of the neighbour lanes that stay
+//     inside for c* = L & (W - 1), and ONE v_readlane_b32 with s* as the lane select (the instruction takes it modulo 64: lane
+//     (r* & 1, c*) at 32x32, c* at 64x64, (r* & 3, c*) at 16x16) yields the low half of the relaxation's EXEC mask; the high half is
+//     zeroed once in the block's entry.  ROWS: the layout has a guard row of W cells on either side of gc[] whose g words are -inf
+//     (AsmLayout, carve_compact_asm_lds).  With its column inside the map, a neighbour lane of row -1 or row W reads a guard cell, and
+//     "g[n] > g2" fails on -inf for every g2 -- the blocked start's 0.0 included -- as it does on a closed cell: the lane never writes.
+//     A lane whose column is outside reads a cell of the neighbouring row (or a guard cell, or garbage in front of / behind the state)
+//     and is not in the EXEC mask.  One instruction in place of eight;
+//   * lane 8's reset of the chunk entry moves behind the cell read with the two instructions of the chunk offset: it only has to
+//     precede this step's ds_min_u64, and a wave's LDS operations stay in order.  The cell read's shadow thus keeps six instructions
+//     (lookup, chunk offset, reset).  The wait in front of the key is s_waitcnt lgkmcnt(1): LDS operations return in order, so it
+//     covers the two reads and the close and NOT the reset behind them -- with lgkmcnt(0) the reset's write latency lands on every
+//     step's critical path and the step is slower than the one it replaces (measured: DESIGN.md 4.1, profiles/guard_rows.json).
+// In front of the cell read the step has 8 instructions instead of 11, behind it six that cover its round trip, behind the wait as
+// many as before: 55 per 32x32 step at g_ratio == 0.5 instead of 60.
+// RELAX, SELECT, the read-back, the exits, the log part and the dive are the round-4 / round-3 sections, token for token.
+// Hazard rules as in nastar_search_asm.hip.h.  s42 (s*, written by v_readlane) is read by a VALU instruction at the head of the
 // prefix: s_cmp_eq_u32 + s_cbranch_scc1 of the goal test stand between (2 wait states, the 2 that VALU-written SGPR -> VALU read
-// needs; the log part and the dive's way in only add to them).
+// needs; the log part and the dive's way in only add to them), and as a LANE SELECT nine instructions later (4 wait states needed).
+// s54 is VALU-written (v_readlane) and read by a scalar instruction only (s_mov_b64 exec), ten instructions later: no rule applies.
 #pragma once
 #include "nastar_search_asm4.hip.h"
 
 namespace nastar {
 
+#define NASTAR_ASM5_ENTRY \
+        "s_mov_b32 s55, 0\n\t" /* high half of the relaxation's EXEC mask s[54:55]: neighbour lanes are lanes 0-7 */
 #define NASTAR_ASM5_X_PREFIX \
         "v_and_b32 v46, s42, %[cmask]\n\t" /* chunk lanes: first cell of the chunk of s*; others: s* */ \
         "v_lshlrev_b32_e64 v27, 3, s42\n\t" \
-        "v_add_u32 v46, v46, %[delta]\n\t" /* this lane's cell; garbage on out-of-map neighbour lanes, which only ever READ with it */ \
-        "ds_read_b32 v28, v27\n\t" /* g[s*] */ \
-        "v_lshlrev_b32 v26, 3, v46\n\t" \
-        "v_lshrrev_b32 v50, 4, v46\n\t" \
-        "v_lshlrev_b32 v50, 3, v50\n\t" /* byte offset of cmin[chunk of this lane's cell] */
+        "v_add_u32 v46, v46, %[delta]\n\t" /* this lane's cell; a guard cell or garbage on out-of-map neighbour lanes, which only ever READ with it */ \
+        "ds_read_b32 v28, v27 offset:%[GC]\n\t" /* g[s*] */ \
+        "v_lshlrev_b32 v26, 3, v46\n\t"
+#define NASTAR_ASM5_X_CLOSE \
+ /* lane 8 closes s* (:222-225) BEFORE the lanes read their cells.  (All 64 lanes storing the wave-uniform value without the two EXEC \
+    writes is 1.7 ns faster on the lone step and 1.3 % slower on the headline batch: measured) */ \
+        "s_mov_b64 exec, 0x100\n\t" \
+        "ds_write_b32 v27, %[vminf] offset:%[GC]\n\t" \
+        "s_mov_b64 exec, -1\n\t"
 #define NASTAR_ASM5_X_READCELL \
-        "ds_read_b64 v[30:31], v26\n\t" /* g[il], hh[il] = fl(h0 + 1.0) */
-#define NASTAR_ASM5_X_INMAP \
- /* conv2d zero padding (:77-93), in the shadow of the LDS round trip */ \
-        "s_lshr_b32 s43, s42, %[LOGW]\n\t" /* r* */ \
-        "s_and_b32 s44, s42, %[WM1]\n\t" /* c* */ \
-        "v_add_u32 v32, s43, %[dr]\n\t" /* r_l */ \
-        "v_and_b32 v33, s44, %[cmask]\n\t" \
-        "v_add_u32 v33, v33, %[dcc]\n\t" /* c_l */ \
-        "v_max_u32 v23, v32, v33\n\t" \
-        "v_cmp_gt_u32 vcc, %[W], v23\n\t" /* inside the map; true for lane 8 and the chunk lanes */ \
-        "s_and_b64 s[54:55], vcc, %[mnb]\n\t" /* in-map neighbour lanes */
+        "ds_read_b64 v[30:31], v26 offset:%[GC]\n\t" /* g[il], hh[il] = fl(h0 + 1.0) */
+#define NASTAR_ASM5_X_SHADOW \
+ /* in the shadow of the LDS round trip: conv2d's zero padding (:77-93) for the COLUMNS -- lane (s* & 63) of colmask holds the neighbour \
+    lanes whose column stays inside the map for c* = s* & (W - 1); v_readlane_b32 takes the lane select modulo 64 -- the chunk offset, \
+    and lane 8 (whose cell is s*) empties the entry of the chunk of s*: ahead of this step's ds_min_u64, a wave's LDS operations stay in order */ \
+        "v_readlane_b32 s54, %[colmask], s42\n\t" \
+        "v_lshrrev_b32 v50, 4, v46\n\t" \
+        "v_lshlrev_b32 v50, 3, v50\n\t" /* byte offset of cmin[chunk of this lane's cell] */ \
+        "s_mov_b64 exec, 0x100\n\t" \
+        "ds_write_b64 v50, v[48:49] offset:%[CMIN]\n\t" \
+        "s_mov_b64 exec, -1\n\t"
+#define NASTAR_ASM5_X_WAIT \
+        "s_waitcnt lgkmcnt(1)\n\t" /* LDS operations return in order: all but the reset above, which nothing here waits for */
 #define NASTAR_ASM5_X_KEY(MULH, MULG) \
         "v_add_f32 v40, 1.0, v28\n\t" /* :234 g2 = g[s*] + cost[s*], cost[s*] = 1.0 */ \
         MULH /* :206 (1-g_ratio)*h */ \
@@ -57,14 +79,14 @@ namespace nastar {
 
 #define NASTAR_ASM5_OPERANDS \
         : [it] "+s"(it), [sel] "=s"(sel), [mkey] "=s"(mkey) \
-        : [l8] "v"(v_l8), [dr] "v"(v_dr), [cmask] "v"(v_cmask), [dcc] "v"(v_dcc), [delta] "v"(v_delta), [pcode] "v"(v_pcode), \
+        : [l8] "v"(v_l8), [cmask] "v"(v_cmask), [colmask] "v"(v_colmask), [delta] "v"(v_delta), [pcode] "v"(v_pcode), \
           [cls] "v"(v_cls), [vminf] "v"(v_minf), [goal] "s"(goal_idx), \
           [maxit] "s"(max_iters), [cgr] "s"(cgr), [comg] "s"(comg), [csq] "s"(csq), [crcp] "s"(rcp_sqrtW), \
           [mnb] "s"(m_nb), [logp] "s"(logp), \
-          [CMIN] "i"(CMIN), [CMIN16] "i"(CMIN + 16), [PDIR] "i"(PDIR), [LOGW] "i"(LOGW), [WM1] "i"((1 << LOGW) - 1), [W] "i"(1 << LOGW) \
-        : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v26", "v27", "v28", "v30", "v31", "v32", "v33", \
+          [GC] "i"(GC), [CMIN] "i"(CMIN), [CMIN16] "i"(CMIN + 16), [PDIR] "i"(PDIR) \
+        : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v26", "v27", "v28", "v30", "v31", \
           "v40", "v41", "v42", "v43", "v46", "v47", "v48", "v49", "v50", "s40", "s41", "s42", \
-          "s43", "s44", "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49", \
+          "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49", \
           "s50", "s51", "v55", "v56", "v57", "s56", "s58", "s59", "s60", "s61"
 
 // Contract of search_loop_asm4 on the compact layout, with these preconditions on top: gc[i].y = fl(h0(i) + 1.0f) for every cell i
@@ -76,14 +98,13 @@ __device__ __forceinline__ int search_loop_asm5(float cgr, float comg, float csq
 {
     using LG = AsmLayout<LOGW>;
     constexpr int CPL = LG::CPL;
+    constexpr int GC = LG::GC;
     constexpr int CMIN = LG::CMIN;
     constexpr int PDIR = LG::PDIR;
     static_assert((CPL == 1 || CPL == 4) && LG::HW >= 256, "1 or 4 chunk minima per lane, chunks inside one map row");
     int dr, dc;
     neighbour_delta(lane & 7, dr, dc);
     const bool is_nb = lane < 8, is_chk = (lane & 48) == 16;
-    const int v_dr = is_nb ? dr : 0;
-    const int v_dcc = is_nb ? dc : (is_chk ? (lane & 15) : 0);
     const int v_delta = is_nb ? dr * (1 << LOGW) + dc : (is_chk ? (lane & 15) : 0);
     const uint32_t v_cmask = is_chk ? 0xFFFFFFF0u : 0xFFFFFFFFu;
     const uint32_t v_cls = is_chk ? 0x1F8u : 0u;  // finite = open
@@ -91,6 +112,10 @@ __device__ __forceinline__ int search_loop_asm5(float cgr, float comg, float csq
     const uint32_t v_l8 = (uint32_t)lane * 8u * CPL;
     const float v_minf = NASTAR_NEG_INF;
     const unsigned long long m_nb = 0xFFull;
+    // lane L: the neighbour lanes (bit j = lane j, the order of neighbour_delta: dc = -1 on lanes 0, 3, 5, dc = +1 on lanes 2, 4, 7) whose
+    // column stays inside the map when s* sits in column L & (W - 1); the step reads it at lane s* & 63
+    const int col = lane & ((1 << LOGW) - 1);
+    const uint32_t v_colmask = 0xFFu & ~(col == 0 ? 0x29u : 0u) & ~(col == (1 << LOGW) - 1 ? 0x94u : 0u);
     int it = __builtin_amdgcn_readfirstlane(iters);
     goal_idx = __builtin_amdgcn_readfirstlane(goal_idx);
     max_iters = __builtin_amdgcn_readfirstlane(max_iters);
@@ -98,15 +123,15 @@ __device__ __forceinline__ int search_loop_asm5(float cgr, float comg, float csq
     uint32_t mkey = 0;
     unsigned long long logp = reinterpret_cast<unsigned long long>(log_row);
 #define NASTAR_A5_EXPAND(MH, MG, SET55) \
-    NASTAR_ASM5_X_PREFIX NASTAR_ASM3_X_CLOSE NASTAR_ASM5_X_READCELL NASTAR_ASM5_X_INMAP NASTAR_ASM3_X_WAIT NASTAR_ASM5_X_KEY(MH, MG) \
+    NASTAR_ASM5_X_PREFIX NASTAR_ASM5_X_CLOSE NASTAR_ASM5_X_READCELL NASTAR_ASM5_X_SHADOW NASTAR_ASM5_X_WAIT NASTAR_ASM5_X_KEY(MH, MG) \
         NASTAR_ASM3_X_RELAX(SET55)
     /* entry -> select -> [log] expand, prefetch -> budget test -> select ... */
 #define NASTAR_A5_BODY(N, MH, MG, LOGPART) \
-    NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT LOGPART NASTAR_A5_EXPAND(MH, MG, ) \
+    NASTAR_ASM5_ENTRY NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT LOGPART NASTAR_A5_EXPAND(MH, MG, ) \
         NASTAR_ASM_READ_##N NASTAR_ASM4_LOOPEND
     /* entry -> select; [dive lookup ->] selected: log, expand, prefetch, budget + dive test -> dive | select -> selected */
 #define NASTAR_A5_BODY_DIVE(N, MH, MG, LOGPART) \
-    NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N "s_branch .Lsel%=\n" NASTAR_ASM4_DIVE_LOOKUP LOGPART \
+    NASTAR_ASM5_ENTRY NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N "s_branch .Lsel%=\n" NASTAR_ASM4_DIVE_LOOKUP LOGPART \
         NASTAR_A5_EXPAND(MH, MG, "v_cmp_lt_u32_e64 s[60:61], v47, s40\n\t") NASTAR_ASM_READ_##N NASTAR_ASM3_DIVE_TEST ".Lsel%=:\n\t" \
         "s_waitcnt lgkmcnt(0)\n\t" NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT "s_branch .Lselected%=\n" NASTAR_ASM4_EXITS
 #define NASTAR_A5_RUN2(BODY, N, MH, MG) \

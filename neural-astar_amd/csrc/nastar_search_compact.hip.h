@@ -20,6 +20,10 @@
 //   expand  = as before (lanes 0..7 own the Moore neighbours, :228-249), plus the exact re-minimisation of chunk C without
 //             s* from recomputed keys (a 4-step DPP row reduction over lanes 16..31).
 // Everything is fp32 with one rounding per reference op (TU compiled with -ffp-contract=off).
+//
+// Two carves of that state: carve_compact_lds (gc | cmin | dump | pdir: the compiled step loops, which park idle lanes' stores in `dump`) and
+// carve_compact_asm_lds (guard_lo | gc | guard_hi | cmin | pdir: the hand-scheduled instantiations -- a row of closed cells on either side of
+// the map stands in for the row test of the stored-heuristic step).  compact_launch_lds_bytes is the one place a launch's size comes from.
 #pragma once
 #include "nastar_search.hip.h"
 
@@ -47,6 +51,22 @@ struct CompactLds {
 
 __host__ __device__ inline size_t compact_lds_bytes(int HWp, int NCp) { return (size_t)HWp * 9 + (size_t)NCp * 8 + 256; }
 
+// The hand-scheduled instantiations (kAsm: 16x16, 32x32, 64x64) never touch `dump` and put a GUARD ROW of W cells on either side of gc[]:
+//   guard_lo (8 W bytes) | gc (8 HW) | guard_hi (8 W) | cmin (8 NCp) | pdir (HW)
+// Every guard cell's g word is -inf from the load on ("closed"), its second word is never used.  A neighbour lane of the stored-heuristic
+// step whose row is -1 or W reads a guard cell and fails "g[n] > g2" like any closed cell: conv2d's zero padding needs no row test
+// (nastar_search_asm5.hip.h).  16 W bytes of guards for the 256 of dump: 10240 B at 32x32 = 160 KiB / 16, 39936 B at 64x64 (4 per CU).
+__host__ __device__ constexpr size_t compact_asm_lds_bytes(int W, int HWp, int NCp) { return (size_t)HWp * 9 + (size_t)NCp * 8 + (size_t)W * 16; }
+__host__ __device__ inline bool compact_asm_shape(int H, int W) { return H == W && (W == 16 || W == 32 || W == 64); }
+
+// THE dynamic-LDS size of a compact-state launch: `asm_stream` = it takes a hand-scheduled instantiation (which exist for compact_asm_shape
+// only).  The launch, the resident capacity that decides how its maps are ranked, the occupancy report and the "does it fit LDS at all"
+// test all ask here (the last one with asm_stream = true: the larger of the two layouts a shape can get).
+__host__ __device__ inline size_t compact_launch_lds_bytes(int H, int W, int HWp, int NCp, bool asm_stream)
+{
+    return (asm_stream && compact_asm_shape(H, W)) ? compact_asm_lds_bytes(W, HWp, NCp) : compact_lds_bytes(HWp, NCp);
+}
+
 // the kernels with a caller-supplied heuristic keep hh = fl((1-g_ratio) fl(h0 + cost)) per cell behind the compact state: 13 B per cell
 __host__ __device__ inline size_t compact_heur_lds_bytes(int HWp, int NCp) { return compact_lds_bytes(HWp, NCp) + (size_t)HWp * 4; }
 
@@ -58,6 +78,24 @@ __device__ __forceinline__ CompactLds carve_compact_lds(unsigned char* smem, con
     l.dump = reinterpret_cast<uint32_t*>(l.cmin + d.NCp);
     l.pdir = reinterpret_cast<uint8_t*>(l.dump + 64);
     return l;
+}
+
+// the layout of compact_asm_lds_bytes (square maps, d.HWp == d.HW)
+__device__ __forceinline__ CompactLds carve_compact_asm_lds(unsigned char* smem, const CompactDims& d)
+{
+    CompactLds l;
+    l.gc = reinterpret_cast<float2*>(smem) + d.W;
+    l.cmin = reinterpret_cast<unsigned long long*>(l.gc + d.HW + d.W);
+    l.pdir = reinterpret_cast<uint8_t*>(l.cmin + d.NCp);
+    l.dump = nullptr;
+    return l;
+}
+
+// ... and its guard cells: g = -inf in gc[-W .. -1] and gc[HW .. HW + W - 1] (one 8-byte store per lane at 32x32: lanes 0..W-1 the low row,
+// W..2W-1 the high one).  Called in front of the map load, whose wave_sync publishes them.
+__device__ __forceinline__ void compact_store_guard_rows(const CompactLds& l, const CompactDims& d, int lane)
+{
+    for (int i = lane; i < 2 * d.W; i += 64) l.gc[i < d.W ? i - d.W : d.HW + i - d.W] = make_float2(NASTAR_NEG_INF, 0.f);
 }
 
 __device__ __forceinline__ unsigned long long cmin_entry(uint32_t key, uint32_t idx)
