@@ -37,11 +37,12 @@
     if (lockstep && a.marks != nullptr && a.marks[b] == 0) return;    // not in the batch-coupled class: the early-exit launch's outputs stand
     const int lane = threadIdx.x;
     CompactDims d = a.d;
+    constexpr int kCcl = kAsm ? compact_asm_ccl(LOGW) : CCL;  // cells per chunk minimum (log2): the hand-scheduled 32x32 layout keeps one per map ROW
     if constexpr (LOGH > 0 && LOGW > 0) {
         d.H = 1 << LOGH;
         d.W = 1 << LOGW;
         d.HW = 1 << (LOGH + LOGW);
-        d.nchunks = d.HW >> CCL;
+        d.nchunks = d.HW >> kCcl;  // kAsm at 32x32: 32 live entries; CPL and NCp below stay 1 and 64 (entries 32..63 idle for good), as the carve expects
         d.HWp = d.HW;
         d.CPL = (d.nchunks + 63) / 64;
         d.NCp = d.CPL * 64;
@@ -112,7 +113,7 @@
             }
             wave_sync();
         } else
-        compact_open_start<kFastDiv>(d, l, lane, start_idx, goal_r, goal_c, rcp_sqrtW, raw, half);
+        compact_open_start<kFastDiv>(d, l, lane, start_idx, goal_r, goal_c, rcp_sqrtW, raw, half, kCcl);
         int s = 0;
         if constexpr (kAsm) {
             // ONE binary tensor as cost map and obstacle map (VanillaAstar, reference astar.py:93-94): every cell the search can relax costs

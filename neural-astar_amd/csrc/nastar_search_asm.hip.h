@@ -34,7 +34,11 @@ template <int LOGW>
 struct AsmLayout {
     static constexpr int W = 1 << LOGW;
     static constexpr int HW = W * W;
-    static constexpr int CPL = (HW / 16 + 63) / 64;  // chunk minima per lane: 1 (<= 1024 cells) or 4 (64x64)
+    static constexpr int CCL = compact_asm_ccl(LOGW);  // log2(cells per chunk): 5 at 32x32 (a chunk is a map row), 4 at 16x16 and 64x64
+    static constexpr int CPL = ((HW >> CCL) + 63) / 64;  // chunk minima per lane: 1 (<= 1024 cells) or 4 (64x64)
+    // DPP rows whose lanes hold LIVE chunk minima: 1 (16x16: 16 minima), 2 (32x32: 32) or 4 (64x64); the other lanes read idle entries
+    // (key all ones), and the selection's finish (NASTAR_ASM_FIN_*) combines exactly the live rows
+    static constexpr int ROWS = CPL > 1 ? 4 : ((HW >> CCL) + 15) / 16;
     static constexpr int GC = W * 8;
     static constexpr int CMIN = GC + HW * 8 + W * 8;
     static constexpr int PDIR = CMIN + CPL * 64 * 8;
@@ -71,7 +75,34 @@ static_assert(AsmLayout<6>::BYTES == (int)compact_asm_lds_bytes(64, 4096, 256) &
         "v_cndmask_b32 v20, v20, v16, vcc\n\t" \
         "v_cndmask_b32_e64 v20, v20, v14, s[48:49]\n\t" \
         "v_cndmask_b32_e64 v20, v20, v12, s[50:51]\n\t"
-#define NASTAR_ASM_SELECT \
+/* The selection's FINISH: after the row_mirror stage every lane of a 16-lane DPP row holds its row's minimum in v22; what is left is
+   the combine across the rows that hold live chunk minima (AsmLayout::ROWS), into s40 = M, the minimal key.
+     four rows: row_bcast:15, row_bcast:31 (each behind the two wait states VALU write -> DPP read needs) leave M in lane 63;
+     two rows:  one v_readlane_b32 per row (lanes 0 and 16; the second lands in s53, the log part's scratch register, and NOT in s41: the pick reads
+                s41 as a lane select three instructions later, and a VALU-written lane select wants four wait states even
+                with the SALU write in between, as LLVM counts it) and ONE s_min_u32.  The s_nop 0 is
+                the wait state VALU write VGPR -> v_readlane read needs.  s40 is then SALU-written: no wait state in front of the
+                v_cmp_eq_u32 that reads it (the rule is VALU-written SGPR -> VALU read);
+     one row:   lane 0 holds M.  The two instructions of the empty test stand between the v_readlane and the v_cmp_eq_u32.
+   The lanes of the other rows read idle entries: their key (all ones) never equals a finite M, and with an empty open list lane 0
+   wins the pick like before. */ \
+
+#define NASTAR_ASM_FIN_4 \
+        "s_nop 1\n\t" \
+        "v_min_u32_dpp v22, v22, v22 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
+        "s_nop 1\n\t" \
+        "v_min_u32_dpp v22, v22, v22 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
+        "s_nop 0\n\t" \
+        "v_readlane_b32 s40, v22, 63\n\t" /* M = minimal key */
+#define NASTAR_ASM_FIN_2 \
+        "s_nop 0\n\t" \
+        "v_readlane_b32 s40, v22, 0\n\t" \
+        "v_readlane_b32 s53, v22, 16\n\t" \
+        "s_min_u32 s40, s40, s53\n\t" /* M = minimal key */
+#define NASTAR_ASM_FIN_1 \
+        "s_nop 0\n\t" \
+        "v_readlane_b32 s40, v22, 0\n\t" /* M = minimal key */
+#define NASTAR_ASM_SELECT(FIN) \
  /* ---- select: first cell of the minimal (key, index) chunk entry ------------------------------------------- */ \
         "v_min_u32_dpp v22, v21, v21 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t" \
         "s_nop 1\n\t" \
@@ -80,12 +111,7 @@ static_assert(AsmLayout<6>::BYTES == (int)compact_asm_lds_bytes(64, 4096, 256) &
         "v_min_u32_dpp v22, v22, v22 row_half_mirror row_mask:0xf bank_mask:0xf\n\t" \
         "s_nop 1\n\t" \
         "v_min_u32_dpp v22, v22, v22 row_mirror row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" \
-        "v_min_u32_dpp v22, v22, v22 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" \
-        "v_min_u32_dpp v22, v22, v22 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-        "s_nop 0\n\t" \
-        "v_readlane_b32 s40, v22, 63\n\t" /* M = minimal key */ \
+        FIN \
         "s_cmp_eq_u32 s40, -1\n\t" \
         "s_cbranch_scc1 .Lempty%=\n\t" /* open list empty */ \
         "v_cmp_eq_u32 vcc, s40, v21\n\t" \
@@ -105,7 +131,7 @@ static_assert(AsmLayout<6>::BYTES == (int)compact_asm_lds_bytes(64, 4096, 256) &
  /* ---- expand ----------------------------------------------------------------------------------------- */ \
         "s_lshr_b32 s43, s42, %[LOGW]\n\t" /* r */ \
         "s_and_b32 s44, s42, %[WM1]\n\t" /* c */ \
-        "s_and_b32 s45, s42, 0xfffffff0\n\t" /* first cell of the chunk of s* */ \
+        "s_and_b32 s45, s42, %[CBASE]\n\t" /* first cell of the chunk of s* (0xfffffff0, or 0xffffffe0 with row-wide chunks) */ \
         "v_add_u32 v23, s43, %[dr]\n\t" \
         "v_add_u32 v24, s44, %[dc]\n\t" \
         "v_max_u32 v23, v23, v24\n\t" \
@@ -136,10 +162,10 @@ static_assert(AsmLayout<6>::BYTES == (int)compact_asm_lds_bytes(64, 4096, 256) &
         "v_sub_f32 v35, v35, v32\n\t" /* chebyshev */ \
         "v_mul_f32 v34, 0x3a83126f, v34\n\t" /* fl32(0.001) * euclid */ \
         "v_add_f32 v34, v35, v34\n\t" /* h0 */ \
-        "s_lshr_b32 s47, s42, 4\n\t" \
+        "s_lshr_b32 s47, s42, %[CCL]\n\t" \
         "s_lshl_b32 s47, s47, 3\n\t" /* byte offset of cmin[chunk of s*] */ \
-        "s_and_b32 s46, s42, 15\n\t" \
-        "s_add_u32 s46, s46, 16\n\t" /* the chunk lane that holds s* itself */ \
+        "s_and_b32 s46, s42, %[CCM1]\n\t" \
+        "s_add_u32 s46, s46, %[CLANE0]\n\t" /* the chunk lane that holds s* itself */ \
         "s_waitcnt lgkmcnt(0)\n\t" \
         "v_add_f32 v34, v34, v31\n\t" /* :191-192 h = h0 + cost */ \
         "v_mul_f32 v34, %[comg], v34\n\t" /* :206 (1-g_ratio)*h */ \
@@ -155,7 +181,7 @@ static_assert(AsmLayout<6>::BYTES == (int)compact_asm_lds_bytes(64, 4096, 256) &
         "v_bitop3_b32 v47, v43, v42, %[msb] bitop3:0x36\n\t" /* order-preserving u32 key: [v46:v47] = (cell, key) */ \
         "v_cndmask_b32_e64 v45, %[vinf], v40, s[54:55]\n\t" /* value to beat: g2 for in-map neighbour lanes, +inf elsewhere */ \
         "v_cndmask_b32 v44, %[loc], %[vinf], vcc\n\t" /* chunk lanes: -inf (any finite g is open), +inf for s* itself and other lanes */ \
-        "v_lshrrev_b32 v50, 4, v46\n\t" \
+        "v_lshrrev_b32 v50, %[CCL], v46\n\t" \
         "v_lshlrev_b32 v50, 3, v50\n\t" /* byte offset of cmin[chunk of il] */ \
         "v_mov_b32 v52, s47\n\t" \
  /* lane 8 closes s* (:222-225) and empties its chunk's entry; the chunk's open cells (without s*) then re-enter it through \
@@ -186,13 +212,17 @@ static_assert(AsmLayout<6>::BYTES == (int)compact_asm_lds_bytes(64, 4096, 256) &
         ".Lgoal%=:\n\t" \
         "s_mov_b32 %[sel], s42\n" \
         ".Lend%=:\n\t"
+/* [it] is an EARLY-CLOBBER output ("+&s") in all four streams: the string writes it in every step while it still reads its inputs, and
+   without the mark the compiler may give it a register of an input whose value it starts with -- it did, with the low half of m_chk
+   (0, like the counter) once the chunk lanes became lanes 32-63 */
 #define NASTAR_ASM_OPERANDS \
-        : [it] "+s"(it), [sel] "=s"(sel) \
+        : [it] "+&s"(it), [sel] "=s"(sel) \
         : [l8] "v"(v_l8), [lane] "v"(lane), [dr] "v"(v_dr), [dc] "v"(v_dc), [off] "v"(v_off), [pcode] "v"(v_pcode), \
           [vinf] "v"(v_inf), [vminf] "v"(v_minf), [loc] "v"(v_loc), [goal] "s"(goal_idx), [gr] "s"(goal_r), [gc] "s"(goal_c), \
           [maxit] "s"(max_iters), [cgr] "s"(d.gr), [comg] "s"(d.omg), [csq] "s"(d.sqrtW), [crcp] "s"(rcp_sqrtW), \
           [mnb] "s"(m_nb), [mchk] "s"(m_chk), [msb] "s"(msb), [logp] "s"(logp), \
-          [GC] "i"(L::GC), [CMIN] "i"(L::CMIN), [CMIN16] "i"(L::CMIN + 16), [PDIR] "i"(L::PDIR), [LOGW] "i"(LOGW), [WM1] "i"(L::W - 1), [W] "i"(L::W) \
+          [GC] "i"(L::GC), [CMIN] "i"(L::CMIN), [CMIN16] "i"(L::CMIN + 16), [PDIR] "i"(L::PDIR), [LOGW] "i"(LOGW), [WM1] "i"(L::W - 1), [W] "i"(L::W), \
+          [CCL] "i"(L::CCL), [CCM1] "i"((1 << L::CCL) - 1), [CBASE] "i"(~((1u << L::CCL) - 1u)), [CLANE0] "i"(L::ROWS == 2 ? 32 : 16) \
         : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v24", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", \
           "v34", "v35", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v52", "s40", "s41", "s42", \
           "s43", "s44", "s45", "s46", "s47", "s50", "s51", "s52", "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49"
@@ -204,17 +234,18 @@ __device__ __forceinline__ int compact_search_loop_asm(const CompactDims& d, int
                                                        int max_iters, int& iters, float rcp_sqrtW, int* log_row)
 {
     using L = AsmLayout<LOGW>;
-    static_assert((L::CPL == 1 || L::CPL == 4) && L::HW >= 256, "1 or 4 chunk minima per lane, chunks inside one map row");
+    static_assert((L::CPL == 1 || L::CPL == 4) && L::HW >= 256 && (1 << L::CCL) <= L::W, "1 or 4 chunk minima per lane, chunks inside one map row");
     int dr, dc;
     neighbour_delta(lane & 7, dr, dc);
-    const bool is_nb = lane < 8, is_chk = (lane & 48) == 16;
+    // lane roles: neighbours 0-7, lane 8 closes s*, one CHUNK lane per cell of the chunk of s*: lanes 16-31, or lanes 32-63 where a chunk is a 32-cell map row
+    const bool is_nb = lane < 8, is_chk = L::ROWS == 2 ? lane >= 32 : (lane & 48) == 16;
     const int v_dr = is_nb ? dr : 0, v_dc = is_nb ? dc : 0;
-    const int v_off = is_nb ? dr * L::W + dc : (is_chk ? (lane & 15) : 0);
+    const int v_off = is_nb ? dr * L::W + dc : (is_chk ? (lane & ((1 << L::CCL) - 1)) : 0);
     const uint32_t v_pcode = P_PASS | (uint32_t)(lane & 7);
     const uint32_t v_l8 = (uint32_t)lane * 8u * L::CPL;
     const float v_inf = NASTAR_POS_INF, v_minf = NASTAR_NEG_INF;
     const float v_loc = is_chk ? NASTAR_NEG_INF : NASTAR_POS_INF;  // lower bound of "open" for the chunk re-insertion
-    const unsigned long long m_nb = 0xFFull, m_chk = 0xFFFF0000ull;
+    const unsigned long long m_nb = 0xFFull, m_chk = L::ROWS == 2 ? 0xFFFFFFFF00000000ull : 0xFFFF0000ull;
     const uint32_t msb = 0x80000000u;
     int it = __builtin_amdgcn_readfirstlane(iters);
     goal_idx = __builtin_amdgcn_readfirstlane(goal_idx);  // wave-uniform by construction; the "s" constraints need it provable
@@ -223,16 +254,19 @@ __device__ __forceinline__ int compact_search_loop_asm(const CompactDims& d, int
     max_iters = __builtin_amdgcn_readfirstlane(max_iters);
     int sel;
     unsigned long long logp = reinterpret_cast<unsigned long long>(log_row);
-#define NASTAR_ASM_BODY(N, LOGPART) \
-    NASTAR_ASM_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM_SELECT LOGPART NASTAR_ASM_EXPAND \
+#define NASTAR_ASM_BODY(N, FIN, LOGPART) \
+    NASTAR_ASM_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM_SELECT(FIN) LOGPART NASTAR_ASM_EXPAND \
         NASTAR_ASM_READ_##N NASTAR_ASM_LOOPEND
-    if constexpr (L::CPL == 1) {
-        if constexpr (kLog) asm volatile(NASTAR_ASM_BODY(1, NASTAR_ASM_LOG) NASTAR_ASM_OPERANDS);
-        else asm volatile(NASTAR_ASM_BODY(1, ) NASTAR_ASM_OPERANDS);
-    } else {
-        if constexpr (kLog) asm volatile(NASTAR_ASM_BODY(4, NASTAR_ASM_LOG) NASTAR_ASM_OPERANDS);
-        else asm volatile(NASTAR_ASM_BODY(4, ) NASTAR_ASM_OPERANDS);
-    }
+#define NASTAR_ASM_RUN(N, FIN) \
+    do { \
+        if constexpr (kLog) asm volatile(NASTAR_ASM_BODY(N, FIN, NASTAR_ASM_LOG) NASTAR_ASM_OPERANDS); \
+        else asm volatile(NASTAR_ASM_BODY(N, FIN, ) NASTAR_ASM_OPERANDS); \
+    } while (0)
+    if constexpr (L::CPL == 4) NASTAR_ASM_RUN(4, NASTAR_ASM_FIN_4);
+    else if constexpr (L::ROWS == 4) NASTAR_ASM_RUN(1, NASTAR_ASM_FIN_4);
+    else if constexpr (L::ROWS == 2) NASTAR_ASM_RUN(1, NASTAR_ASM_FIN_2);
+    else NASTAR_ASM_RUN(1, NASTAR_ASM_FIN_1);
+#undef NASTAR_ASM_RUN
 #undef NASTAR_ASM_BODY
     iters = it;
     return sel;

@@ -24,7 +24,7 @@
 
 namespace nastar {
 
-#define NASTAR_ASM3_SELECT \
+#define NASTAR_ASM3_SELECT(FIN) \
  /* ---- select: first cell of the minimal (key, index) chunk entry.  v21 arrives from LDS (no VALU->DPP hazard), so the three      \
     quad permutations all read IT and only the combined quad minimum waits for the next stage: 4 instructions, no s_nop;       \
     the step counter moves into one of the remaining wait states (the exits below undo it) */ \
@@ -37,12 +37,7 @@ namespace nastar {
         "v_min_u32_dpp v22, v22, v22 row_half_mirror row_mask:0xf bank_mask:0xf\n\t" \
         "s_nop 1\n\t" \
         "v_min_u32_dpp v22, v22, v22 row_mirror row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" \
-        "v_min_u32_dpp v22, v22, v22 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" \
-        "v_min_u32_dpp v22, v22, v22 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-        "s_nop 0\n\t" \
-        "v_readlane_b32 s40, v22, 63\n\t" /* M = minimal key */ \
+        FIN /* s40 = M, the minimal key, from the rows that hold live chunk minima: NASTAR_ASM_FIN_4 / _2 / _1 (nastar_search_asm.hip.h) */ \
         "s_cmp_eq_u32 s40, -1\n\t" \
         "s_cbranch_scc1 .Lempty%=\n\t" /* open list empty */ \
         "v_cmp_eq_u32 vcc, s40, v21\n\t" \
@@ -89,7 +84,7 @@ namespace nastar {
         "s_and_b64 s[54:55], vcc, %[mnb]\n\t" /* in-map neighbour lanes */ \
         "v_cndmask_b32 v46, v24, v46, vcc\n\t" /* il: s* itself for out-of-map neighbours */ \
         "v_lshlrev_b32 v26, 3, v46\n\t" \
-        "v_lshrrev_b32 v50, 4, v46\n\t" \
+        "v_lshrrev_b32 v50, %[CCL], v46\n\t" \
         "v_lshlrev_b32 v50, 3, v50\n\t" /* byte offset of cmin[chunk of il] */
 #define NASTAR_ASM3_X_CLOSE \
  /* lane 8 (il == s*) closes s* (:222-225) and empties its chunk's entry BEFORE the lanes read their cells */ \
@@ -215,12 +210,12 @@ namespace nastar {
 //     four wavefronts are VALU-issue bound during the first ~150 steps.
 
 #define NASTAR_ASM3_OPERANDS \
-        : [it] "+s"(it), [sel] "=s"(sel) \
+        : [it] "+&s"(it), [sel] "=s"(sel) \
         : [l8] "v"(v_l8), [dr] "v"(v_dr), [cmask] "v"(v_cmask), [dcc] "v"(v_dcc), [pcode] "v"(v_pcode), [cls] "v"(v_cls), \
           [vminf] "v"(v_minf), [goal] "s"(goal_idx), [gr] "s"(goal_r), [gc] "s"(goal_c), \
           [maxit] "s"(max_iters), [cgr] "s"(d.gr), [comg] "s"(d.omg), [csq] "s"(d.sqrtW), [crcp] "s"(rcp_sqrtW), \
           [mnb] "s"(m_nb), [logp] "s"(logp), \
-          [GC] "i"(L::GC), [CMIN] "i"(L::CMIN), [CMIN16] "i"(L::CMIN + 16), [PDIR] "i"(L::PDIR), [LOGW] "i"(LOGW), [WM1] "i"(L::W - 1), [W] "i"(L::W) \
+          [GC] "i"(L::GC), [CMIN] "i"(L::CMIN), [CMIN16] "i"(L::CMIN + 16), [PDIR] "i"(L::PDIR), [LOGW] "i"(LOGW), [WM1] "i"(L::W - 1), [W] "i"(L::W), [CCL] "i"(L::CCL) \
         : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v24", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", \
           "v34", "v35", "v36", "v37", "v40", "v41", "v42", "v43", "v46", "v47", "v48", "v49", "v50", "s40", "s41", "s42", \
           "s43", "s44", "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49", \
@@ -234,13 +229,14 @@ __device__ __forceinline__ int compact_search_loop_asm3(const CompactDims& d, in
                                                         int max_iters, int& iters, float rcp_sqrtW, int* log_row)
 {
     using L = AsmLayout<LOGW>;
-    static_assert((L::CPL == 1 || L::CPL == 4) && L::HW >= 256, "1 or 4 chunk minima per lane, chunks inside one map row");
+    static_assert((L::CPL == 1 || L::CPL == 4) && L::HW >= 256 && (1 << L::CCL) <= L::W, "1 or 4 chunk minima per lane, chunks inside one map row");
     int dr, dc;
     neighbour_delta(lane & 7, dr, dc);
-    const bool is_nb = lane < 8, is_chk = (lane & 48) == 16;
+    // chunk lanes: lanes 16-31, or lanes 32-63 where a chunk is a 32-cell map row (lane roles: nastar_search_asm.hip.h)
+    const bool is_nb = lane < 8, is_chk = L::ROWS == 2 ? lane >= 32 : (lane & 48) == 16;
     const int v_dr = is_nb ? dr : 0;
-    const int v_dcc = is_nb ? dc : (is_chk ? (lane & 15) : 0);
-    const uint32_t v_cmask = is_chk ? 0xFFFFFFF0u : 0xFFFFFFFFu;
+    const int v_dcc = is_nb ? dc : (is_chk ? (lane & ((1 << L::CCL) - 1)) : 0);
+    const uint32_t v_cmask = is_chk ? ~((1u << L::CCL) - 1u) : 0xFFFFFFFFu;
     const uint32_t v_cls = is_chk ? 0x1F8u : 0u;  // v_cmp_class: -normal | -denormal | -0 | +0 | +denormal | +normal = finite = open
     const uint32_t v_pcode = P_PASS | (uint32_t)(lane & 7);
     const uint32_t v_l8 = (uint32_t)lane * 8u * L::CPL;
@@ -253,24 +249,26 @@ __device__ __forceinline__ int compact_search_loop_asm3(const CompactDims& d, in
     max_iters = __builtin_amdgcn_readfirstlane(max_iters);
     int sel;
     unsigned long long logp = reinterpret_cast<unsigned long long>(log_row);
-#define NASTAR_ASM3_BODY(N, LOGPART) \
-    NASTAR_ASM_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM3_SELECT LOGPART NASTAR_ASM3_EXPAND \
+#define NASTAR_ASM3_BODY(N, FIN, LOGPART) \
+    NASTAR_ASM_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM3_SELECT(FIN) LOGPART NASTAR_ASM3_EXPAND \
         NASTAR_ASM_READ_##N NASTAR_ASM3_LOOPEND
     /* entry -> select; [dive lookup ->] selected: log, expand, prefetch, budget + dive test -> dive | select -> selected */
-#define NASTAR_ASM3_BODY_DIVE(N, LOGPART) \
+#define NASTAR_ASM3_BODY_DIVE(N, FIN, LOGPART) \
     NASTAR_ASM_ENTRY NASTAR_ASM_READ_##N "s_branch .Lsel%=\n" NASTAR_ASM3_DIVE_LOOKUP LOGPART NASTAR_ASM3_EXPAND_DIVE NASTAR_ASM_READ_##N \
-        NASTAR_ASM3_DIVE_TEST ".Lsel%=:\n\t" "s_waitcnt lgkmcnt(0)\n\t" NASTAR_ASM_LOCALMIN_##N NASTAR_ASM3_SELECT \
+        NASTAR_ASM3_DIVE_TEST ".Lsel%=:\n\t" "s_waitcnt lgkmcnt(0)\n\t" NASTAR_ASM_LOCALMIN_##N NASTAR_ASM3_SELECT(FIN) \
         "s_branch .Lselected%=\n" NASTAR_ASM3_EXITS
+#define NASTAR_ASM3_RUN(BODY, N, FIN) \
+    do { \
+        if constexpr (kLog) asm volatile(BODY(N, FIN, NASTAR_ASM3_LOG) NASTAR_ASM3_OPERANDS); \
+        else asm volatile(BODY(N, FIN, ) NASTAR_ASM3_OPERANDS); \
+    } while (0)
     if constexpr (L::CPL == 1) {
-        if constexpr (kLog) asm volatile(NASTAR_ASM3_BODY(1, NASTAR_ASM3_LOG) NASTAR_ASM3_OPERANDS);
-        else asm volatile(NASTAR_ASM3_BODY(1, ) NASTAR_ASM3_OPERANDS);
-    } else if constexpr (kDive) {
-        if constexpr (kLog) asm volatile(NASTAR_ASM3_BODY_DIVE(4, NASTAR_ASM3_LOG) NASTAR_ASM3_OPERANDS);
-        else asm volatile(NASTAR_ASM3_BODY_DIVE(4, ) NASTAR_ASM3_OPERANDS);
-    } else {
-        if constexpr (kLog) asm volatile(NASTAR_ASM3_BODY(4, NASTAR_ASM3_LOG) NASTAR_ASM3_OPERANDS);
-        else asm volatile(NASTAR_ASM3_BODY(4, ) NASTAR_ASM3_OPERANDS);
-    }
+        if constexpr (L::ROWS == 4) NASTAR_ASM3_RUN(NASTAR_ASM3_BODY, 1, NASTAR_ASM_FIN_4);
+        else if constexpr (L::ROWS == 2) NASTAR_ASM3_RUN(NASTAR_ASM3_BODY, 1, NASTAR_ASM_FIN_2);
+        else NASTAR_ASM3_RUN(NASTAR_ASM3_BODY, 1, NASTAR_ASM_FIN_1);
+    } else if constexpr (kDive) NASTAR_ASM3_RUN(NASTAR_ASM3_BODY_DIVE, 4, NASTAR_ASM_FIN_4);
+    else NASTAR_ASM3_RUN(NASTAR_ASM3_BODY, 4, NASTAR_ASM_FIN_4);
+#undef NASTAR_ASM3_RUN
 #undef NASTAR_ASM3_BODY_DIVE
 #undef NASTAR_ASM3_BODY
     iters = it;

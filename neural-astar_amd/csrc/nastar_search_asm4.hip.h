@@ -44,7 +44,31 @@ struct AsmLayoutUnit {
         "v_mov_b32 v48, %[goal]\n\t" /* [v48:v49] = an idle chunk entry: (cell = goal, key = all ones) */ \
         "v_mov_b32 v49, -1\n\t"
 
-#define NASTAR_ASM4_SELECT \
+/* The selection's finish (see NASTAR_ASM_FIN_* in nastar_search_asm.hip.h) with the step counter in one of its slots: from behind the
+   row_mirror stage to in front of the pick's v_cmp_eq_u32, s40 = M = the minimal key (all ones: open list empty -> the pick yields the goal).
+     four rows: 8 instructions.  two rows (32x32, a chunk is a map row): 4 -- the counter is the wait state VALU write VGPR ->
+     v_readlane read needs, and s40 comes from the SALU, so the v_cmp_eq_u32 follows at once.  one row (16x16): 3 -- s40 comes from
+     the v_readlane, and s_nop 1 is the two wait states VALU-written SGPR -> VALU read needs. */ \
+
+#define NASTAR_ASM4_FIN_4 \
+        "s_nop 1\n\t" \
+        "v_min_u32_dpp v22, v22, v22 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
+        "s_nop 1\n\t" \
+        "v_min_u32_dpp v22, v22, v22 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
+        "s_nop 0\n\t" \
+        "v_readlane_b32 s40, v22, 63\n\t" /* M = minimal key (all ones: open list empty -> the pick below yields the goal) */ \
+        "s_add_u32 %[it], %[it], 1\n\t" /* two wait states: VALU-written SGPR -> VALU read */ \
+        "s_nop 0\n\t"
+#define NASTAR_ASM4_FIN_2 \
+        "s_add_u32 %[it], %[it], 1\n\t" /* the wait state VALU write VGPR -> v_readlane read */ \
+        "v_readlane_b32 s40, v22, 0\n\t" /* rows 0-15 */ \
+        "v_readlane_b32 s53, v22, 16\n\t" /* rows 16-31 */ \
+        "s_min_u32 s40, s40, s53\n\t"
+#define NASTAR_ASM4_FIN_1 \
+        "s_add_u32 %[it], %[it], 1\n\t" /* the wait state VALU write VGPR -> v_readlane read */ \
+        "v_readlane_b32 s40, v22, 0\n\t" \
+        "s_nop 1\n\t" /* two wait states: VALU-written SGPR -> VALU read */
+#define NASTAR_ASM4_SELECT(FIN) \
         "v_min_u32_dpp v22, v21, v21 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t" \
         "v_min_u32_dpp v23, v21, v21 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t" \
         "v_min_u32_dpp v22, v21, v22 quad_perm:[3,2,1,0] row_mask:0xf bank_mask:0xf\n\t" \
@@ -53,14 +77,7 @@ struct AsmLayoutUnit {
         "v_min_u32_dpp v22, v22, v22 row_half_mirror row_mask:0xf bank_mask:0xf\n\t" \
         "s_nop 1\n\t" \
         "v_min_u32_dpp v22, v22, v22 row_mirror row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" \
-        "v_min_u32_dpp v22, v22, v22 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" \
-        "v_min_u32_dpp v22, v22, v22 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-        "s_nop 0\n\t" \
-        "v_readlane_b32 s40, v22, 63\n\t" /* M = minimal key (all ones: open list empty -> the pick below yields the goal) */ \
-        "s_add_u32 %[it], %[it], 1\n\t" /* two wait states: VALU-written SGPR -> VALU read */ \
-        "s_nop 0\n\t" \
+        FIN \
         "v_cmp_eq_u32 vcc, s40, v21\n\t" \
         "s_ff1_i32_b64 s41, vcc\n\t" \
         "v_readlane_b32 s42, v20, s41\n\t" \
@@ -81,7 +98,7 @@ struct AsmLayoutUnit {
         RDS /* g[s*] (, cost[s*]) */ \
         "v_lshlrev_b32 v26, " SH ", v46\n\t" \
         "s_and_b64 s[54:55], vcc, %[mnb]\n\t" /* in-map neighbour lanes */ \
-        "v_lshrrev_b32 v50, 4, v46\n\t" \
+        "v_lshrrev_b32 v50, %[CCL], v46\n\t" \
         "v_lshlrev_b32 v50, 3, v50\n\t" /* byte offset of cmin[chunk of this lane's cell] */
 
 #define NASTAR_ASM4_X_KEY(ADDH, ADDG, MULH, MULG) \
@@ -135,12 +152,12 @@ struct AsmLayoutUnit {
         NASTAR_ASM4_EXITS
 
 #define NASTAR_ASM4_OPERANDS \
-        : [it] "+s"(it), [sel] "=s"(sel), [mkey] "=s"(mkey) \
+        : [it] "+&s"(it), [sel] "=s"(sel), [mkey] "=s"(mkey) \
         : [l8] "v"(v_l8), [dr] "v"(v_dr), [cmask] "v"(v_cmask), [dcc] "v"(v_dcc), [pcode] "v"(v_pcode), [cls] "v"(v_cls), \
           [vminf] "v"(v_minf), [goal] "s"(goal_idx), [gr] "s"(goal_r), [gc] "s"(goal_c), \
           [maxit] "s"(max_iters), [cgr] "s"(cgr), [comg] "s"(comg), [csq] "s"(csq), [crcp] "s"(rcp_sqrtW), \
           [mnb] "s"(m_nb), [logp] "s"(logp), \
-          [GC] "i"(GC), [CMIN] "i"(CMIN), [CMIN16] "i"(CMIN + 16), [PDIR] "i"(PDIR), [LOGW] "i"(LOGW), [WM1] "i"((1 << LOGW) - 1), [W] "i"(1 << LOGW) \
+          [GC] "i"(GC), [CMIN] "i"(CMIN), [CMIN16] "i"(CMIN + 16), [PDIR] "i"(PDIR), [LOGW] "i"(LOGW), [WM1] "i"((1 << LOGW) - 1), [W] "i"(1 << LOGW), [CCL] "i"(CCLS) \
         : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v24", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", \
           "v34", "v35", "v36", "v37", "v40", "v41", "v42", "v43", "v46", "v47", "v48", "v49", "v50", "s40", "s41", "s42", \
           "s43", "s44", "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49", \
@@ -162,13 +179,17 @@ __device__ __forceinline__ int search_loop_asm4(float cgr, float comg, float csq
     constexpr int GC = kUnit ? LU::GC : LG::GC;
     constexpr int CMIN = kUnit ? LU::CMIN : LG::CMIN;
     constexpr int PDIR = kUnit ? LU::PDIR : LG::PDIR;
-    static_assert((CPL == 1 || CPL == 4) && LG::HW >= 256, "1 or 4 chunk minima per lane, chunks inside one map row");
+    // cells per chunk (log2) and DPP rows of live chunk minima: the unit-cost layout keeps 16-cell chunks at every size (64 live minima at 32x32)
+    constexpr int CCLS = kUnit ? CCL : LG::CCL;
+    constexpr int ROWS = CPL > 1 ? 4 : ((LG::HW >> CCLS) + 15) / 16;
+    static_assert((CPL == 1 || CPL == 4) && LG::HW >= 256 && (1 << CCLS) <= LG::W, "1 or 4 chunk minima per lane, chunks inside one map row");
     int dr, dc;
     neighbour_delta(lane & 7, dr, dc);
-    const bool is_nb = lane < 8, is_chk = (lane & 48) == 16;
+    // chunk lanes: lanes 16-31, or lanes 32-63 where a chunk is a 32-cell map row (lane roles: nastar_search_asm.hip.h)
+    const bool is_nb = lane < 8, is_chk = CCLS == 5 ? lane >= 32 : (lane & 48) == 16;
     const int v_dr = is_nb ? dr : 0;
-    const int v_dcc = is_nb ? dc : (is_chk ? (lane & 15) : 0);
-    const uint32_t v_cmask = is_chk ? 0xFFFFFFF0u : 0xFFFFFFFFu;
+    const int v_dcc = is_nb ? dc : (is_chk ? (lane & ((1 << CCLS) - 1)) : 0);
+    const uint32_t v_cmask = is_chk ? ~((1u << CCLS) - 1u) : 0xFFFFFFFFu;
     const uint32_t v_cls = is_chk ? 0x1F8u : 0u;  // finite = open
     const uint32_t v_pcode = P_PASS | (uint32_t)(lane & 7);
     const uint32_t v_l8 = (uint32_t)lane * 8u * CPL;
@@ -198,30 +219,37 @@ __device__ __forceinline__ int search_loop_asm4(float cgr, float comg, float csq
     NASTAR_ASM4_X_PREFIX(NASTAR_A4_SH_##L, NASTAR_A4_RDS_##L) NASTAR_ASM3_X_CLOSE NASTAR_A4_RDC_##L NASTAR_ASM3_X_HEUR NASTAR_ASM3_X_WAIT \
         NASTAR_ASM4_X_KEY(NASTAR_A4_ADDH_##L, NASTAR_A4_ADDG_##L, MH, MG) NASTAR_ASM3_X_RELAX(SET55)
     /* entry -> select -> [log] expand, prefetch -> budget test -> select ... */
-#define NASTAR_A4_BODY(N, L, MH, MG, LOGPART) \
-    NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT LOGPART NASTAR_A4_EXPAND(L, MH, MG, ) \
+#define NASTAR_A4_BODY(N, L, MH, MG, FIN, LOGPART) \
+    NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT(FIN) LOGPART NASTAR_A4_EXPAND(L, MH, MG, ) \
         NASTAR_ASM_READ_##N NASTAR_ASM4_LOOPEND
     /* entry -> select; [dive lookup ->] selected: log, expand, prefetch, budget + dive test -> dive | select -> selected */
-#define NASTAR_A4_BODY_DIVE(N, L, MH, MG, LOGPART) \
+#define NASTAR_A4_BODY_DIVE(N, L, MH, MG, FIN, LOGPART) \
     NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N "s_branch .Lsel%=\n" NASTAR_ASM4_DIVE_LOOKUP LOGPART \
         NASTAR_A4_EXPAND(L, MH, MG, "v_cmp_lt_u32_e64 s[60:61], v47, s40\n\t") NASTAR_ASM_READ_##N NASTAR_ASM3_DIVE_TEST ".Lsel%=:\n\t" \
-        "s_waitcnt lgkmcnt(0)\n\t" NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT "s_branch .Lselected%=\n" NASTAR_ASM4_EXITS
-#define NASTAR_A4_RUN2(BODY, N, L, MH, MG) \
+        "s_waitcnt lgkmcnt(0)\n\t" NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT(FIN) "s_branch .Lselected%=\n" NASTAR_ASM4_EXITS
+#define NASTAR_A4_RUN2(BODY, N, L, MH, MG, FIN) \
     do { \
-        if constexpr (kLog) asm volatile(BODY(N, L, MH, MG, NASTAR_ASM3_LOG) NASTAR_ASM4_OPERANDS); \
-        else asm volatile(BODY(N, L, MH, MG, ) NASTAR_ASM4_OPERANDS); \
+        if constexpr (kLog) asm volatile(BODY(N, L, MH, MG, FIN, NASTAR_ASM3_LOG) NASTAR_ASM4_OPERANDS); \
+        else asm volatile(BODY(N, L, MH, MG, FIN, ) NASTAR_ASM4_OPERANDS); \
     } while (0)
-#define NASTAR_A4_RUN(BODY, N) \
+#define NASTAR_A4_RUN(BODY, N, FIN) \
     do { \
-        if constexpr (kUnit && kHalf) NASTAR_A4_RUN2(BODY, N, U, , ); \
-        else if constexpr (kUnit) NASTAR_A4_RUN2(BODY, N, U, NASTAR_A4_MULH, NASTAR_A4_MULG); \
-        else if constexpr (kHalf) NASTAR_A4_RUN2(BODY, N, G, , ); \
-        else NASTAR_A4_RUN2(BODY, N, G, NASTAR_A4_MULH, NASTAR_A4_MULG); \
+        if constexpr (kUnit && kHalf) NASTAR_A4_RUN2(BODY, N, U, , , FIN); \
+        else if constexpr (kUnit) NASTAR_A4_RUN2(BODY, N, U, NASTAR_A4_MULH, NASTAR_A4_MULG, FIN); \
+        else if constexpr (kHalf) NASTAR_A4_RUN2(BODY, N, G, , , FIN); \
+        else NASTAR_A4_RUN2(BODY, N, G, NASTAR_A4_MULH, NASTAR_A4_MULG, FIN); \
     } while (0)
-    if constexpr (CPL == 1 && kDive) NASTAR_A4_RUN(NASTAR_A4_BODY_DIVE, 1);
-    else if constexpr (CPL == 1) NASTAR_A4_RUN(NASTAR_A4_BODY, 1);
-    else if constexpr (kDive) NASTAR_A4_RUN(NASTAR_A4_BODY_DIVE, 4);
-    else NASTAR_A4_RUN(NASTAR_A4_BODY, 4);
+    /* the finish of the selection by the rows of live chunk minima */
+#define NASTAR_A4_RUN_ROWS(BODY) \
+    do { \
+        if constexpr (CPL == 4) NASTAR_A4_RUN(BODY, 4, NASTAR_ASM4_FIN_4); \
+        else if constexpr (ROWS == 4) NASTAR_A4_RUN(BODY, 1, NASTAR_ASM4_FIN_4); \
+        else if constexpr (ROWS == 2) NASTAR_A4_RUN(BODY, 1, NASTAR_ASM4_FIN_2); \
+        else NASTAR_A4_RUN(BODY, 1, NASTAR_ASM4_FIN_1); \
+    } while (0)
+    if constexpr (kDive) NASTAR_A4_RUN_ROWS(NASTAR_A4_BODY_DIVE);
+    else NASTAR_A4_RUN_ROWS(NASTAR_A4_BODY);
+#undef NASTAR_A4_RUN_ROWS
 #undef NASTAR_A4_RUN
 #undef NASTAR_A4_RUN2
 #undef NASTAR_A4_BODY_DIVE

@@ -1,5 +1,5 @@
 // nastar_search_asm5.hip.h -- the round-4 stream (nastar_search_asm4.hip.h, whose sections it reuses) for maps that keep the HEURISTIC
-// where the cost word was ("stored_h"): 55 instructions per 32x32 step at g_ratio == 0.5 instead of the general stream's 71.
+// where the cost word was ("stored_h"): 51 instructions per 32x32 step at g_ratio == 0.5 (55 before the row-wide chunks, below), the general stream 67.
 //
 // VanillaAstar hands ONE binary tensor over as cost map AND obstacle map (reference astar.py:93-94).  Every cell the search can relax
 // or key then costs exactly 1.0 (only passable cells are opened, :228-229; a START on an obstacle is the one exception, handled as in
@@ -27,7 +27,16 @@
 //     step's critical path and the step is slower than the one it replaces (measured: DESIGN.md 4.1, profiles/guard_rows.json).
 // In front of the cell read the step has 8 instructions instead of 11, behind it six that cover its round trip, behind the wait as
 // many as before: 55 per 32x32 step at g_ratio == 0.5 instead of 60.
-// RELAX, SELECT, the read-back, the exits, the log part and the dive are the round-4 / round-3 sections, token for token.
+// ROW-WIDE CHUNKS (32x32): a chunk minimum covers a whole map row (AsmLayout::CCL = 5; cmin[] keeps 64 entries, 32..63 idle for good), so
+// the 32 live minima sit in lanes 0-31, two DPP rows, and the selection needs no stage across four rows: behind row_mirror it ends with
+//     s_add_u32 it, it, 1 | v_readlane_b32 s40, v22, 0 | v_readlane_b32 s53, v22, 16 | s_min_u32 s40, s40, s53
+// (NASTAR_ASM4_FIN_2) where the four-row finish has eight instructions (two row_bcast stages, three s_nop around them, the v_readlane
+// of lane 63, the counter, one more s_nop): 51 per step instead of 55.  s40 is SALU-written, so the pick's v_cmp_eq_u32 follows at once.
+// The chunk lanes are lanes 32-63, cell (s* & ~31) | (lane & 31); lanes 9-31 idle (cell s*, class mask 0).  The lowest lane with the
+// minimal key is the lowest row, and a row's entry names its lowest minimal cell (ds_min_u64 on (key, cell)): the first flat index, as
+// before.  16x16 has 16 live minima in one DPP row with the 16-cell chunks it always had and ends with one v_readlane (50 per step);
+// 64x64 keeps the four-row finish and its machine code.
+// RELAX, SELECT's stages, the read-back, the exits, the log part and the dive are the round-4 / round-3 sections, token for token.
 // Hazard rules as in nastar_search_asm.hip.h.  s42 (s*, written by v_readlane) is read by a VALU instruction at the head of the
 // prefix: s_cmp_eq_u32 + s_cbranch_scc1 of the goal test stand between (2 wait states, the 2 that VALU-written SGPR -> VALU read
 // needs; the log part and the dive's way in only add to them), and as a LANE SELECT nine instructions later (4 wait states needed).
@@ -58,7 +67,7 @@ namespace nastar {
     lanes whose column stays inside the map for c* = s* & (W - 1); v_readlane_b32 takes the lane select modulo 64 -- the chunk offset, \
     and lane 8 (whose cell is s*) empties the entry of the chunk of s*: ahead of this step's ds_min_u64, a wave's LDS operations stay in order */ \
         "v_readlane_b32 s54, %[colmask], s42\n\t" \
-        "v_lshrrev_b32 v50, 4, v46\n\t" \
+        "v_lshrrev_b32 v50, %[CCL], v46\n\t" \
         "v_lshlrev_b32 v50, 3, v50\n\t" /* byte offset of cmin[chunk of this lane's cell] */ \
         "s_mov_b64 exec, 0x100\n\t" \
         "ds_write_b64 v50, v[48:49] offset:%[CMIN]\n\t" \
@@ -78,12 +87,12 @@ namespace nastar {
 #define NASTAR_ASM5_MULG "v_mul_f32 v41, %[cgr], v41\n\t"
 
 #define NASTAR_ASM5_OPERANDS \
-        : [it] "+s"(it), [sel] "=s"(sel), [mkey] "=s"(mkey) \
+        : [it] "+&s"(it), [sel] "=s"(sel), [mkey] "=s"(mkey) \
         : [l8] "v"(v_l8), [cmask] "v"(v_cmask), [colmask] "v"(v_colmask), [delta] "v"(v_delta), [pcode] "v"(v_pcode), \
           [cls] "v"(v_cls), [vminf] "v"(v_minf), [goal] "s"(goal_idx), \
           [maxit] "s"(max_iters), [cgr] "s"(cgr), [comg] "s"(comg), [csq] "s"(csq), [crcp] "s"(rcp_sqrtW), \
           [mnb] "s"(m_nb), [logp] "s"(logp), \
-          [GC] "i"(GC), [CMIN] "i"(CMIN), [CMIN16] "i"(CMIN + 16), [PDIR] "i"(PDIR) \
+          [GC] "i"(GC), [CMIN] "i"(CMIN), [CMIN16] "i"(CMIN + 16), [PDIR] "i"(PDIR), [CCL] "i"(LG::CCL) \
         : "memory", "vcc", "scc", "v20", "v21", "v22", "v23", "v26", "v27", "v28", "v30", "v31", \
           "v40", "v41", "v42", "v43", "v46", "v47", "v48", "v49", "v50", "s40", "s41", "s42", \
           "s54", "s55", "s53", "v53", "v54", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "s48", "s49", \
@@ -101,12 +110,14 @@ __device__ __forceinline__ int search_loop_asm5(float cgr, float comg, float csq
     constexpr int GC = LG::GC;
     constexpr int CMIN = LG::CMIN;
     constexpr int PDIR = LG::PDIR;
-    static_assert((CPL == 1 || CPL == 4) && LG::HW >= 256, "1 or 4 chunk minima per lane, chunks inside one map row");
+    constexpr int ROWS = LG::ROWS;
+    static_assert((CPL == 1 || CPL == 4) && LG::HW >= 256 && (1 << LG::CCL) <= LG::W, "1 or 4 chunk minima per lane, chunks inside one map row");
     int dr, dc;
     neighbour_delta(lane & 7, dr, dc);
-    const bool is_nb = lane < 8, is_chk = (lane & 48) == 16;
-    const int v_delta = is_nb ? dr * (1 << LOGW) + dc : (is_chk ? (lane & 15) : 0);
-    const uint32_t v_cmask = is_chk ? 0xFFFFFFF0u : 0xFFFFFFFFu;
+    // chunk lanes: lanes 16-31, or lanes 32-63 where a chunk is a 32-cell map row: cell (s* & ~31) | (lane & 31)
+    const bool is_nb = lane < 8, is_chk = ROWS == 2 ? lane >= 32 : (lane & 48) == 16;
+    const int v_delta = is_nb ? dr * (1 << LOGW) + dc : (is_chk ? (lane & ((1 << LG::CCL) - 1)) : 0);
+    const uint32_t v_cmask = is_chk ? ~((1u << LG::CCL) - 1u) : 0xFFFFFFFFu;
     const uint32_t v_cls = is_chk ? 0x1F8u : 0u;  // finite = open
     const uint32_t v_pcode = P_PASS | (uint32_t)(lane & 7);
     const uint32_t v_l8 = (uint32_t)lane * 8u * CPL;
@@ -126,28 +137,35 @@ __device__ __forceinline__ int search_loop_asm5(float cgr, float comg, float csq
     NASTAR_ASM5_X_PREFIX NASTAR_ASM5_X_CLOSE NASTAR_ASM5_X_READCELL NASTAR_ASM5_X_SHADOW NASTAR_ASM5_X_WAIT NASTAR_ASM5_X_KEY(MH, MG) \
         NASTAR_ASM3_X_RELAX(SET55)
     /* entry -> select -> [log] expand, prefetch -> budget test -> select ... */
-#define NASTAR_A5_BODY(N, MH, MG, LOGPART) \
-    NASTAR_ASM5_ENTRY NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT LOGPART NASTAR_A5_EXPAND(MH, MG, ) \
+#define NASTAR_A5_BODY(N, MH, MG, FIN, LOGPART) \
+    NASTAR_ASM5_ENTRY NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N NASTAR_ASM_LOOPTOP NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT(FIN) LOGPART NASTAR_A5_EXPAND(MH, MG, ) \
         NASTAR_ASM_READ_##N NASTAR_ASM4_LOOPEND
     /* entry -> select; [dive lookup ->] selected: log, expand, prefetch, budget + dive test -> dive | select -> selected */
-#define NASTAR_A5_BODY_DIVE(N, MH, MG, LOGPART) \
+#define NASTAR_A5_BODY_DIVE(N, MH, MG, FIN, LOGPART) \
     NASTAR_ASM5_ENTRY NASTAR_ASM4_ENTRY NASTAR_ASM_READ_##N "s_branch .Lsel%=\n" NASTAR_ASM4_DIVE_LOOKUP LOGPART \
         NASTAR_A5_EXPAND(MH, MG, "v_cmp_lt_u32_e64 s[60:61], v47, s40\n\t") NASTAR_ASM_READ_##N NASTAR_ASM3_DIVE_TEST ".Lsel%=:\n\t" \
-        "s_waitcnt lgkmcnt(0)\n\t" NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT "s_branch .Lselected%=\n" NASTAR_ASM4_EXITS
-#define NASTAR_A5_RUN2(BODY, N, MH, MG) \
+        "s_waitcnt lgkmcnt(0)\n\t" NASTAR_ASM_LOCALMIN_##N NASTAR_ASM4_SELECT(FIN) "s_branch .Lselected%=\n" NASTAR_ASM4_EXITS
+#define NASTAR_A5_RUN2(BODY, N, MH, MG, FIN) \
     do { \
-        if constexpr (kLog) asm volatile(BODY(N, MH, MG, NASTAR_ASM3_LOG) NASTAR_ASM5_OPERANDS); \
-        else asm volatile(BODY(N, MH, MG, ) NASTAR_ASM5_OPERANDS); \
+        if constexpr (kLog) asm volatile(BODY(N, MH, MG, FIN, NASTAR_ASM3_LOG) NASTAR_ASM5_OPERANDS); \
+        else asm volatile(BODY(N, MH, MG, FIN, ) NASTAR_ASM5_OPERANDS); \
     } while (0)
-#define NASTAR_A5_RUN(BODY, N) \
+#define NASTAR_A5_RUN(BODY, N, FIN) \
     do { \
-        if constexpr (kHalf) NASTAR_A5_RUN2(BODY, N, , ); \
-        else NASTAR_A5_RUN2(BODY, N, NASTAR_ASM5_MULH, NASTAR_ASM5_MULG); \
+        if constexpr (kHalf) NASTAR_A5_RUN2(BODY, N, , , FIN); \
+        else NASTAR_A5_RUN2(BODY, N, NASTAR_ASM5_MULH, NASTAR_ASM5_MULG, FIN); \
     } while (0)
-    if constexpr (CPL == 1 && kDive) NASTAR_A5_RUN(NASTAR_A5_BODY_DIVE, 1);
-    else if constexpr (CPL == 1) NASTAR_A5_RUN(NASTAR_A5_BODY, 1);
-    else if constexpr (kDive) NASTAR_A5_RUN(NASTAR_A5_BODY_DIVE, 4);
-    else NASTAR_A5_RUN(NASTAR_A5_BODY, 4);
+    /* the finish of the selection by the rows of live chunk minima (nastar_search_asm4.hip.h) */
+#define NASTAR_A5_RUN_ROWS(BODY) \
+    do { \
+        if constexpr (CPL == 4) NASTAR_A5_RUN(BODY, 4, NASTAR_ASM4_FIN_4); \
+        else if constexpr (ROWS == 4) NASTAR_A5_RUN(BODY, 1, NASTAR_ASM4_FIN_4); \
+        else if constexpr (ROWS == 2) NASTAR_A5_RUN(BODY, 1, NASTAR_ASM4_FIN_2); \
+        else NASTAR_A5_RUN(BODY, 1, NASTAR_ASM4_FIN_1); \
+    } while (0)
+    if constexpr (kDive) NASTAR_A5_RUN_ROWS(NASTAR_A5_BODY_DIVE);
+    else NASTAR_A5_RUN_ROWS(NASTAR_A5_BODY);
+#undef NASTAR_A5_RUN_ROWS
 #undef NASTAR_A5_RUN
 #undef NASTAR_A5_RUN2
 #undef NASTAR_A5_BODY_DIVE

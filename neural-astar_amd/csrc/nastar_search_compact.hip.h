@@ -31,6 +31,10 @@ namespace nastar {
 
 constexpr int CCL = 4;          // log2(cells per chunk)
 constexpr int CCSZ = 1 << CCL;  // 16 cells per chunk == one DPP row
+// ... of the hand-scheduled instantiations (kAsm): a whole map ROW at 32x32 -- 32 chunk minima, which fill two DPP rows instead of four, so
+// the selection ends after its row stages with two v_readlane and one s_min_u32 (nastar_search_asm.hip.h); cmin[] keeps its 64 entries
+// (the upper 32 stay idle) and the carve its offsets.  16 cells at 16x16 (16 minima, one DPP row) and 64x64 (256 minima, four per lane).
+__host__ __device__ constexpr int compact_asm_ccl(int logw) { return logw == 5 ? 5 : CCL; }
 
 struct CompactDims {
     int H, W, HW;
@@ -264,9 +268,10 @@ __device__ __forceinline__ bool compact_load_heuristic(const CompactDims& d, con
 
 // open list = {start} (:187), g[start] = 0 (:193).  raw_key: the key is the bit pattern of q itself (nastar_search_asm3.hip.h, q >= +0)
 // half_key: g_ratio == 0.5 form of the round-4 stream -- the key of q' = fl(fl(g + h) / sqrt(W)) = 2 q (nastar_search_asm4.hip.h)
+// ccl: log2(cells per chunk) of the caller's layout (compact_asm_ccl for the hand-scheduled instantiations)
 template <bool kFastDiv>
 __device__ __forceinline__ void compact_open_start(const CompactDims& d, const CompactLds& l, int lane, int sidx, int goal_r,
-                                                   int goal_c, float rcp_sqrtW, bool raw_key = false, bool half_key = false)
+                                                   int goal_c, float rcp_sqrtW, bool raw_key = false, bool half_key = false, int ccl = CCL)
 {
     if (lane == 0) {
         const int r = (int)row_magic((uint32_t)sidx, d.magicW, d.W);
@@ -275,7 +280,7 @@ __device__ __forceinline__ void compact_open_start(const CompactDims& d, const C
         uint32_t k0 = compact_key<kFastDiv>(d, 0.0f, hh, rcp_sqrtW);
         if (raw_key) k0 = __float_as_uint(ord_to_f32(k0));
         l.gc[sidx].x = 0.0f;
-        l.cmin[sidx >> CCL] = cmin_entry(k0, (uint32_t)sidx);
+        l.cmin[sidx >> ccl] = cmin_entry(k0, (uint32_t)sidx);
         l.pdir[sidx] = (uint8_t)(PARENT_UNSET | P_PASS);  // the start is expanded even if it sits on an obstacle (:187)
     }
     wave_sync();
