@@ -351,6 +351,17 @@ SOFT_ROUTES_TILED_SIGNATURES = {
     "nastar_soft_routes_tiled": "i ppppzipiiiiiudiqppippppppzp",
 }
 
+# the signatures of include/nastar_soft_routes_grad.h (the twentieth header: the score-function backward of the eighteenth's samples), same
+# letter code; a table of its own (tests/test_soft_routes_grad.py compares it with ITS header)
+SOFT_ROUTES_GRAD_SIGNATURES = {
+    "nastar_soft_routes_grad_abi": "i ",
+    "nastar_soft_routes_grad_max_cells": "i ",
+    "nastar_soft_routes_grad_workspace_bytes": "z iii",
+    # cost, goal, passable, tape, tape_bytes, start_idx, routes, route_cap, route_len, status, grad_log_prob, B, S, N, H, W, neighbor_mask,
+    # tau, horizon, grad_cost_out, status_out, workspace, workspace_bytes, stream
+    "nastar_soft_routes_backward": "i ppppzppipppiiiiiudipppzp",
+}
+
 
 class NativeLibraryMissing(RuntimeError):
     pass
@@ -520,6 +531,8 @@ def load() -> ctypes.CDLL:
         _bind(lib, SOFT_ROUTE_SIGNATURES, SOFT_ROUTE_SIGNATURES)
     if hasattr(lib, "nastar_soft_routes_tiled_abi"):  # (and the nineteenth)
         _bind(lib, SOFT_ROUTES_TILED_SIGNATURES, SOFT_ROUTES_TILED_SIGNATURES)
+    if hasattr(lib, "nastar_soft_routes_grad_abi"):  # (and the twentieth)
+        _bind(lib, SOFT_ROUTES_GRAD_SIGNATURES, SOFT_ROUTES_GRAD_SIGNATURES)
     _lib = lib
     return lib
 

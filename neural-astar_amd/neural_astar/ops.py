@@ -28,7 +28,7 @@ __all__ = ["astar_forward", "astar_backward_replay", "astar_backward_l1_replay",
            "soft_policy", "SoftPolicyOutput", "soft_policy_nll", "soft_policy_forward", "soft_policy_backward",
            "soft_policy_tiled", "soft_policy_nll_tiled", "soft_policy_tiled_forward", "soft_policy_tiled_backward",
            "soft_routes", "SoftRoutes", "soft_routes_from_tape", "SOFT_ROUTES_MAX_CELLS", "SOFT_ROUTES_MAX_WALKERS", "soft_routes_tiled",
-           "soft_routes_tiled_from_tape"]
+           "soft_routes_tiled_from_tape", "soft_routes_backward", "route_score_loss", "SOFT_ROUTES_GRAD_MAX_CELLS"]
 
 
 def max_iters_for(W: int, Tmax: float, training: bool) -> int:
@@ -2241,21 +2241,43 @@ def _soft_routes_from_tape(tiled: bool, cost_maps, goal_maps, obstacles_maps, ta
 
 
 def _soft_routes(tiled: bool, cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask, max_route_len, visits,
-                 uniforms, checkpoint_every=None) -> "SoftRoutes":
+                 uniforms, checkpoint_every=None, differentiable: bool = False) -> "SoftRoutes":
     """the body of ``soft_routes`` and ``soft_routes_tiled``: the refusals before anything is launched, the forward with its tape, the
-    walkers"""
-    _checked_samples(num_samples)
+    walkers; ``differentiable``: ``log_probs`` as the output of ``_SoftRoutesNode`` when there is something to differentiate"""
+    N = _checked_samples(num_samples)
     _checked_sample_len(max_route_len)
     seed = _checked_seed(seed)
+    if not isinstance(differentiable, bool):
+        raise TypeError(f"differentiable must be a bool, got {differentiable!r}")
     _, _, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
     _soft_routes_limit(tiled, H, W)
-    _start_indices(starts, B, H, W)  # (refused before the forward launches anything)
+    idx = _start_indices(starts, B, H, W)  # (refused before the forward launches anything)
+    if differentiable:
+        if tiled:
+            raise NotImplementedError("soft_routes_tiled: differentiable=True is not built (the score-function backward reads the whole tape of "
+                                      f"the one-workgroup field: soft_routes(..., differentiable=True), maps of at most {SOFT_ROUTES_GRAD_MAX_CELLS} cells)")
+        _checked_tau(tau)
+        K = _checked_horizon(horizon, H, W)
+        if max_route_len is not None and max_route_len < K + 1:
+            raise ValueError(f"soft_routes: differentiable=True needs max_route_len >= horizon + 1 = {K + 1} (or None), got {max_route_len}: the "
+                             "backward reads whole routes and does not replay walks")
+        _soft_routes_grad_limits("soft_routes: differentiable=True", H, W, idx.shape[1], N, K)
+        if cost_maps.requires_grad and torch.is_grad_enabled():
+            return SoftRoutes(*_SoftRoutesNode.apply(cost_maps, goal_maps, obstacles_maps, idx, uniforms,
+                                                     (tau, K, N, seed, neighbor_mask, max_route_len, visits)))
+    return _soft_routes_run(tiled, cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask, max_route_len,
+                            visits, uniforms, checkpoint_every)[0]
+
+
+def _soft_routes_run(tiled: bool, cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask, max_route_len, visits,
+                     uniforms, checkpoint_every=None):
+    """the launches of ``_soft_routes``, its arguments checked: the forward with its tape, then the walkers -> ``(SoftRoutes, tape)``"""
     dists, _, _, map_status, tape = _soft_forward(tiled, False, cost_maps, goal_maps, obstacles_maps, tau, horizon, neighbor_mask, False, True,
                                                   checkpoint_every, tape_limit=SOFT_ROUTES_MAX_CELLS)
     routes, lengths, costs, logp, counts, status = _soft_routes_from_tape(tiled, cost_maps, goal_maps, obstacles_maps, tape, starts, tau, horizon,
                                                                           num_samples, seed, neighbor_mask, max_route_len, visits, uniforms,
                                                                           checkpoint_every=checkpoint_every)
-    return SoftRoutes(routes, lengths, costs, logp, counts, dists, status, map_status)
+    return SoftRoutes(routes, lengths, costs, logp, counts, dists, status, map_status), tape
 
 
 def soft_routes_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
@@ -2274,7 +2296,8 @@ def soft_routes_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obst
 
 def soft_routes(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor, tau: float,
                 horizon: Optional[int] = None, num_samples: int = 1, seed: Optional[int] = None, neighbor_mask: Optional[int] = None,
-                max_route_len: Optional[int] = None, visits: bool = False, uniforms: Optional[torch.Tensor] = None) -> SoftRoutes:
+                max_route_len: Optional[int] = None, visits: bool = False, uniforms: Optional[torch.Tensor] = None,
+                differentiable: bool = False) -> SoftRoutes:
     """SAMPLE routes from the maximum-entropy route distribution of ``cost_maps`` (include/nastar_soft_routes.h) -> ``SoftRoutes``:
     ``num_samples`` independent routes from each of S start cells per map, drawn with probability exp((V_K(start) - cost(route)) / tau)
     among the routes that reach a goal within ``horizon`` moves -- the distribution ``maxent_path_nll`` trains.  The walker with k moves
@@ -2292,9 +2315,149 @@ def soft_routes(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps
 
     An EVALUATION call on the current stream of the inputs' device: the forward launch with its tape (B * horizon * H * W fp32), a
     launch that clears the rows and the counts and the walkers' launch; detached outputs, nothing is read back -- it can be captured into a graph -- and nothing raises for a
-    failed query or a bad map: read ``status`` and ``map_status``."""
+    failed query or a bad map: read ``status`` and ``map_status``.
+
+    ``differentiable=True``: the same launches and the same bits, and ``log_probs`` is the one differentiable output of an autograd node
+    when ``cost_maps`` requires a gradient and grad mode is on -- the SCORE-FUNCTION estimator: the routes are samples, not functions of
+    the costs, and log p(route) = (V_K(start) - cost(route)) / tau is.  Its backward is ``soft_routes_backward`` (include/
+    nastar_soft_routes_grad.h): at most five launches on the current stream, nothing read back, the same bits from two calls; the gradient
+    goes to ``cost_maps`` alone.  The gradient that arrives for the ``log_probs`` of a failed query is never read; ``log_probs`` is -inf
+    there, so a loss masks those entries with ``torch.where`` -- ``route_score_loss`` does.  Every other output stays detached.  Refused
+    before anything is launched: ``max_route_len`` below ``horizon + 1`` (ValueError: the backward reads whole routes), maps of more than
+    ``SOFT_ROUTES_GRAD_MAX_CELLS`` cells and S * N * horizon above 2^31 (NotImplementedError)."""
     return _soft_routes(False, cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask, max_route_len, visits,
-                        uniforms)
+                        uniforms, differentiable=differentiable)
+
+
+# ---- include/nastar_soft_routes_grad.h: the score-function backward of the sampled routes (DESIGN.md section 2, item 6r)
+SOFT_ROUTES_GRAD_MAX_CELLS = 6144  # nastar_soft_routes_grad_max_cells(): the limit of the field's backward
+SOFT_ROUTES_GRAD_MIN_BITS = 30  # the fewest fraction bits P = min(40, 61 - ceil(log2(S * N * horizon))) a call may be left with
+
+
+def _soft_routes_grad_limits(what: str, H: int, W: int, S: int, N: int, K: int) -> None:
+    """what the score-function backward refuses beyond the walkers' own limits: the map size and the P rule"""
+    if H * W > SOFT_ROUTES_GRAD_MAX_CELLS:
+        raise NotImplementedError(f"{what}: maps of {H}x{W} = {H * W} cells exceed the limit of {SOFT_ROUTES_GRAD_MAX_CELLS} cells of the "
+                                  f"backward (the forward alone takes {SOFT_ROUTES_MAX_CELLS})")
+    bits = min(40, 61 - (S * N * K - 1).bit_length())
+    if bits < SOFT_ROUTES_GRAD_MIN_BITS:
+        raise NotImplementedError(f"{what}: {S} starts x {N} samples x horizon {K} leave {bits} fraction bits to the fixed-point sums, fewer than "
+                                  f"{SOFT_ROUTES_GRAD_MIN_BITS} (S * N * horizon must stay at or below 2^31: split the samples over calls)")
+
+
+def soft_routes_backward(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, tape: torch.Tensor,
+                         starts: torch.Tensor, routes: torch.Tensor, route_lengths: torch.Tensor, status: torch.Tensor,
+                         grad_log_probs: torch.Tensor, tau: float, horizon: Optional[int] = None,
+                         neighbor_mask: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``nastar_soft_routes_backward`` as it is (include/nastar_soft_routes_grad.h) -> ``(grad_cost [B,H,W], status [B] int32)``: the
+    gradient with respect to the costs of ``(grad_log_probs * log_probs).sum()``.  The maps, ``tau``, ``horizon`` and mask of the
+    ``soft_fields_forward(..., tape=True)`` call that wrote ``tape``; ``starts`` and the ``routes`` [B,S,N,L >= horizon + 1] int32,
+    ``route_lengths`` [B,S,N] int32 and ``status`` [B,S] int32 of the walkers' call; ``grad_log_probs`` [B,S,N] float32, never read at a
+    failed query.  At most five launches on the current stream, nothing is read back: it can be captured into a graph.  Fixed-point sums:
+    the same bits from two calls.  What the backward of ``soft_routes(..., differentiable=True)`` runs."""
+    t = _checked_tau(tau)
+    maps, mask, (B, H, W) = _field_inputs(cost_maps, goal_maps, obstacles_maps, neighbor_mask)
+    K = _checked_horizon(horizon, H, W)
+    idx = _start_indices(starts, B, H, W)
+    S = idx.shape[1]
+    if not torch.is_tensor(routes) or routes.dtype != torch.int32 or routes.ndim != 4 or tuple(routes.shape[:2]) != (B, S) or routes.shape[2] < 1:
+        raise ValueError(f"routes must be the int32 [B,S,N,L] tensor of soft_routes for {B} maps and {S} starts, got "
+                         f"{tuple(routes.shape) if torch.is_tensor(routes) else type(routes).__name__}")
+    N, cap = int(routes.shape[2]), int(routes.shape[3])
+    if cap < K + 1:
+        raise ValueError(f"soft_routes_backward: routes has rows of {cap} cells, fewer than horizon + 1 = {K + 1}: the backward reads whole "
+                         "routes and does not replay walks")
+    for name, x, dtype, shape in (("route_lengths", route_lengths, torch.int32, (B, S, N)), ("status", status, torch.int32, (B, S)),
+                                  ("grad_log_probs", grad_log_probs, torch.float32, (B, S, N))):
+        if not torch.is_tensor(x) or x.dtype != dtype or tuple(x.shape) != shape:
+            raise ValueError(f"{name} must be a {str(dtype).replace('torch.', '')} tensor of shape {shape}, got "
+                             f"{(tuple(x.shape), x.dtype) if torch.is_tensor(x) else type(x).__name__}")
+    if B * S * N > SOFT_ROUTES_MAX_WALKERS:
+        raise NotImplementedError(f"soft_routes_backward: {B} maps x {S} starts x {N} samples exceed the limit of {SOFT_ROUTES_MAX_WALKERS} "
+                                  "walkers per call")
+    _soft_routes_grad_limits("soft_routes_backward", H, W, S, N, K)
+    dev = _field_device(maps)
+    for name, x in (("starts", idx), ("routes", routes), ("route_lengths", route_lengths), ("status", status), ("grad_log_probs", grad_log_probs)):
+        if x.device != dev:
+            raise ValueError(f"the maps live on {dev}, {name} on {x.device}: they must share a device")
+    lib = _field_lib("nastar_soft_routes_backward", "nastar_soft_routes_grad.h")
+    if not torch.is_tensor(tape) or tape.dtype != torch.uint8 or tape.device != dev or not tape.is_contiguous():
+        raise ValueError(f"tape must be the contiguous uint8 tensor soft_fields_forward(..., tape=True) returned, on {dev}")
+    with torch.no_grad():
+        cost, goal, passable = (_maps3(m.detach()) for m in maps)
+        idx, rows, lens, st = idx.contiguous(), routes.detach().contiguous(), route_lengths.detach().contiguous(), status.detach().contiguous()
+        up = grad_log_probs.detach().contiguous()
+        grad = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        map_status = torch.empty((B,), dtype=torch.int32, device=dev)
+        ws_bytes = int(lib.nastar_soft_routes_grad_workspace_bytes(B, H, W))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.nastar_soft_routes_backward(cost.data_ptr(), goal.data_ptr(), passable.data_ptr(), tape.data_ptr(), tape.numel(),
+                                                 idx.data_ptr(), rows.data_ptr(), cap, lens.data_ptr(), st.data_ptr(), up.data_ptr(), B, S, N, H, W,
+                                                 mask, t, K, grad.data_ptr(), map_status.data_ptr(), ws.data_ptr(), ws_bytes, _stream_ptr(dev))
+        _native.check(rc, "nastar_soft_routes_backward")
+    return grad, map_status
+
+
+class _SoftRoutesNode(torch.autograd.Function):
+    """``soft_routes`` as an autograd node whose ONE differentiable output is ``log_probs``: the forward is the evaluation call (the
+    field with its tape, then the walkers), the backward one call of ``nastar_soft_routes_backward`` with the upstream gradient of
+    ``log_probs``; the gradient goes to ``cost_maps`` alone.  ``idx``: the checked [B,S] int32 start cells; ``call``: the checked
+    ``(tau, horizon, num_samples, seed, neighbor_mask, max_route_len, visits)``.  What the backward reads is saved under autograd's version
+    check: an in-place change of ``routes`` or ``cost_maps`` in between raises torch's own error."""
+
+    @staticmethod
+    def forward(ctx, cost_maps, goal_maps, obstacles_maps, idx, uniforms, call):
+        tau, K, N, seed, mask, max_route_len, visits = call
+        out, tape = _soft_routes_run(False, cost_maps, goal_maps, obstacles_maps, idx, tau, K, N, seed, mask, max_route_len, visits, uniforms)
+        ctx.save_for_backward(cost_maps, goal_maps, obstacles_maps, tape, idx, out.routes, out.route_lengths, out.status)
+        ctx.call = (tau, K, mask)
+        ctx.mark_non_differentiable(*(x for x in out if x is not None and x is not out.log_probs))
+        ctx.set_materialize_grads(False)
+        return tuple(out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        g_logp = grads[3]  # (SoftRoutes: routes, route_lengths, route_costs, log_probs, ...)
+        if g_logp is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        cost_maps, goal_maps, obstacles_maps, tape, idx, routes, lengths, status = ctx.saved_tensors
+        grad = soft_routes_backward(cost_maps, goal_maps, obstacles_maps, tape, idx, routes, lengths, status, g_logp, *ctx.call)[0]
+        return (_widen_grad(grad, tuple(cost_maps.shape)), None, None, None, None, None)
+
+
+def route_score_loss(log_probs: torch.Tensor, rewards: torch.Tensor, status: torch.Tensor, baseline="mean") -> torch.Tensor:
+    """The surrogate whose gradient is the REINFORCE (score-function) estimate of the gradient of the expected reward -> a scalar: the mean,
+    over the walkers of the queries with ``status == 0``, of ``(rewards - baseline).detach() * log_probs``.  ``log_probs`` [B,S,N] of
+    ``soft_routes(..., differentiable=True)``; ``rewards`` [B,S,N]: any number per sampled route -- its length, its clearance, a
+    simulator's verdict -- and no function of the costs; ``status`` [B,S] of the same call.  ``baseline``: "mean" (per query, over its N
+    samples), None, or a tensor that broadcasts against ``rewards``.  A failed query has ``log_probs`` of -inf and whatever reward the
+    caller computed from rows of -1: its entries are MASKED with ``torch.where`` -- a product with 0 would make NaN of them, in the value
+    and in the gradient -- so they add nothing and receive a zero gradient; with no ok walker at all the loss is 0.  Plain torch: no
+    kernel, no host read."""
+    if not torch.is_tensor(log_probs) or log_probs.ndim != 3 or not log_probs.is_floating_point():
+        raise ValueError(f"log_probs must be a float [B,S,N] tensor, got {tuple(log_probs.shape) if torch.is_tensor(log_probs) else type(log_probs).__name__}")
+    if not torch.is_tensor(rewards) or tuple(rewards.shape) != tuple(log_probs.shape):
+        raise ValueError(f"rewards must be a tensor of the shape of log_probs {tuple(log_probs.shape)}, got "
+                         f"{tuple(rewards.shape) if torch.is_tensor(rewards) else type(rewards).__name__}")
+    if not torch.is_tensor(status) or tuple(status.shape) != tuple(log_probs.shape[:2]) or status.is_floating_point():
+        raise ValueError(f"status must be the integer [B,S] tensor of the call, {tuple(log_probs.shape[:2])}, got "
+                         f"{tuple(status.shape) if torch.is_tensor(status) else type(status).__name__}")
+    ok = (status == 0).unsqueeze(-1).expand_as(log_probs)
+    r = torch.where(ok, rewards.detach().to(log_probs.dtype), torch.zeros_like(log_probs))
+    if isinstance(baseline, str) and baseline == "mean":
+        base = r.mean(-1, keepdim=True)
+    elif baseline is None:
+        base = torch.zeros_like(r)
+    elif torch.is_tensor(baseline):
+        base = baseline.detach().to(log_probs.dtype)
+    else:
+        raise ValueError(f'baseline must be "mean", None or a tensor, got {baseline!r}')
+    zero = torch.zeros_like(log_probs)
+    advantage = torch.where(ok, r - base, zero).detach()
+    terms = advantage * torch.where(ok, log_probs, zero)
+    return terms.sum() / ok.sum().clamp(min=1).to(log_probs.dtype)
 
 
 # ---- include/nastar_soft_routes_tiled.h: the same samples from the tiled field's checkpointed tape (DESIGN.md section 2, item 6q)
@@ -2315,7 +2478,7 @@ def soft_routes_tiled_from_tape(cost_maps: torch.Tensor, goal_maps: torch.Tensor
 def soft_routes_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor, starts: torch.Tensor, tau: float,
                       horizon: Optional[int] = None, num_samples: int = 1, seed: Optional[int] = None, neighbor_mask: Optional[int] = None,
                       max_route_len: Optional[int] = None, visits: bool = False, uniforms: Optional[torch.Tensor] = None,
-                      checkpoint_every: Optional[int] = None) -> SoftRoutes:
+                      differentiable: bool = False, checkpoint_every: Optional[int] = None) -> SoftRoutes:
     """``soft_routes`` for maps of up to ``SOFT_FIELDS_TILED_MAX_CELLS`` cells (1024x1152: every map size the search takes), from the
     tiled field's checkpointed tape (include/nastar_soft_routes_tiled.h) -> ``SoftRoutes``.  The same definition, the same arguments and,
     on the maps both take, the same BITS in every output, whatever ``checkpoint_every`` is (None = ceil(sqrt(horizon)); 1 keeps every
@@ -2325,6 +2488,7 @@ def soft_routes_tiled(cost_maps: torch.Tensor, goal_maps: torch.Tensor, obstacle
     sweeps that rebuild each segment of the tape, top down -- with one launch of walkers per segment; a walker lives in a workspace
     between two launches.  With ``max_route_len`` below ``horizon + 1`` the walk is replayed, first for the lengths, then for the
     stores, and every segment is rebuilt TWICE; the default rows of ``horizon + 1`` cells never pay that.  Detached outputs, nothing is
-    read back, nothing raises for a failed query or a bad map: read ``status`` and ``map_status``."""
+    read back, nothing raises for a failed query or a bad map: read ``status`` and ``map_status``.  ``differentiable=True`` is not built
+    for the tiled tape: NotImplementedError."""
     return _soft_routes(True, cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask, max_route_len, visits,
-                        uniforms, checkpoint_every)
+                        uniforms, checkpoint_every, differentiable)

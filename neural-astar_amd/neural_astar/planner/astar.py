@@ -145,6 +145,14 @@ class VanillaAstar(nn.Module):
         exp(-L / tau).  An evaluation call."""
         return self.astar.sample_routes(map_designs, starts, goal_maps, map_designs, tau, num_samples, seed, horizon, max_route_len, visits)
 
+    def sample_routes_differentiable(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, tau: float,
+                                     num_samples: int = 1, seed: Optional[int] = None, horizon: Optional[int] = None,
+                                     max_route_len: Optional[int] = None, visits: bool = False):
+        """``sample_routes`` with ``log_probs`` as a differentiable output (``DifferentiableAstar.sample_routes_differentiable``) with
+        cost = passable = ``map_designs``: the score-function gradient goes to ``map_designs`` as the cost when it requires one."""
+        return self.astar.sample_routes_differentiable(map_designs, starts, goal_maps, map_designs, tau, num_samples, seed, horizon, max_route_len,
+                                                       visits)
+
     def sample_routes_tiled(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, tau: float, num_samples: int = 1,
                             seed: Optional[int] = None, horizon: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False,
                             checkpoint_every: Optional[int] = None):
@@ -444,6 +452,24 @@ class NeuralAstar(VanillaAstar):
                                       "planner.astar.sample_routes(cost_maps, starts, goal_maps, obstacles_maps, tau), or use encoder_input='m'")
         return self.astar.sample_routes(*self._sample_inputs(map_designs, starts, goal_maps), tau, num_samples, seed, horizon, max_route_len, visits)
 
+    def sample_routes_differentiable(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, tau: float,
+                                     num_samples: int = 1, seed: Optional[int] = None, horizon: Optional[int] = None,
+                                     max_route_len: Optional[int] = None, visits: bool = False):
+        """``sample_routes`` on the PREDICTED cost maps with ``log_probs`` as a differentiable output
+        (``DifferentiableAstar.sample_routes_differentiable``): encodes as ``sample_routes`` does -- once, with an all-zero start channel,
+        ``encoder_input == "m"`` only -- but NOT detached, so ``ops.route_score_loss(out.log_probs, rewards, out.status).backward()``
+        trains the encoder on any reward per sampled route (REINFORCE); no graph under ``torch.no_grad()``."""
+        _checked_route_len(max_route_len)  # (every refusal before the encoder launches anything)
+        ops._checked_tau(tau)
+        ops._checked_samples(num_samples)
+        if self.encoder_input != "m":
+            raise NotImplementedError(f"NeuralAstar.sample_routes_differentiable: with encoder_input={self.encoder_input!r} the predicted cost "
+                                      "map depends on the start, so one soft field cannot serve several starts; encode per start and call "
+                                      "planner.astar.sample_routes_differentiable(cost_maps, starts, goal_maps, obstacles_maps, tau), or use "
+                                      "encoder_input='m'")
+        return self.astar.sample_routes_differentiable(*self._sample_inputs(map_designs, starts, goal_maps, detach=False), tau, num_samples, seed,
+                                                       horizon, max_route_len, visits)
+
     def sample_routes_tiled(self, map_designs: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, tau: float, num_samples: int = 1,
                             seed: Optional[int] = None, horizon: Optional[int] = None, max_route_len: Optional[int] = None, visits: bool = False,
                             checkpoint_every: Optional[int] = None):
@@ -461,10 +487,12 @@ class NeuralAstar(VanillaAstar):
         return self.astar.sample_routes_tiled(*self._sample_inputs(map_designs, starts, goal_maps), tau, num_samples, seed, horizon, max_route_len,
                                               visits, checkpoint_every)
 
-    def _sample_inputs(self, map_designs, starts, goal_maps):
-        """the (cost, starts, goal, obstacles) maps of ``sample_routes`` / ``sample_routes_tiled``: encoded once, detached, with an all-zero
-        start channel"""
-        cost_maps = self.encode(map_designs, torch.zeros_like(goal_maps), goal_maps).detach()
+    def _sample_inputs(self, map_designs, starts, goal_maps, detach: bool = True):
+        """the (cost, starts, goal, obstacles) maps of ``sample_routes`` and its siblings: encoded once, with an all-zero start channel;
+        detached unless the samples' ``log_probs`` are to train the encoder"""
+        cost_maps = self.encode(map_designs, torch.zeros_like(goal_maps), goal_maps)
+        if detach:
+            cost_maps = cost_maps.detach()
         obstacles_maps = map_designs if not self.learn_obstacles else torch.ones_like(goal_maps)
         return cost_maps, starts, goal_maps, obstacles_maps
 

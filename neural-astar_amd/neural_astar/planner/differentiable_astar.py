@@ -744,6 +744,17 @@ class DifferentiableAstar(nn.Module):
         return ops.soft_routes(cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask=self.neighbor_mask(),
                                max_route_len=max_route_len, visits=visits)
 
+    def sample_routes_differentiable(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
+                                     tau: float, num_samples: int = 1, seed: Optional[int] = None, horizon: Optional[int] = None,
+                                     max_route_len: Optional[int] = None, visits: bool = False) -> "ops.SoftRoutes":
+        """``sample_routes`` with ``log_probs`` as a differentiable output (``ops.soft_routes(..., differentiable=True)``, include/
+        nastar_soft_routes_grad.h): the same launches and the same samples, and a loss on ``log_probs`` -- ``ops.route_score_loss`` with
+        any reward per sampled route -- carries the score-function gradient to ``cost_maps``.  Maps of at most
+        ``ops.SOFT_ROUTES_GRAD_MAX_CELLS`` cells, rows of ``horizon + 1`` cells (``max_route_len`` None or at least that).  A method of
+        its own: ``sample_routes`` keeps its signature."""
+        return ops.soft_routes(cost_maps, goal_maps, obstacles_maps, starts, tau, horizon, num_samples, seed, neighbor_mask=self.neighbor_mask(),
+                               max_route_len=max_route_len, visits=visits, differentiable=True)
+
     def sample_routes_tiled(self, cost_maps: torch.Tensor, starts: torch.Tensor, goal_maps: torch.Tensor, obstacles_maps: torch.Tensor,
                             tau: float, num_samples: int = 1, seed: Optional[int] = None, horizon: Optional[int] = None,
                             max_route_len: Optional[int] = None, visits: bool = False,
