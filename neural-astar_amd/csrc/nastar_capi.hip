@@ -539,7 +539,8 @@ static int batchloop_finish(const FwdLaunch& f)
     int rc = forward(run);
     if (rc) return rc;
     // 2. the first step at which EVERY map of the batch selects its goal
-    const int lds_words = words < 16384 ? words : 16384;
+    // (the kernel's own __shared__ cells count against the 64 KiB a launch may own without a raised limit: longer budgets AND in global memory)
+    const int lds_words = words < kTendMaxLdsWords ? words : kTendMaxLdsWords;
     rc = launch_grid(nastar_batchloop_tend_kernel, dim3(1), dim3(kTendThreads), (size_t)lds_words * 4, reinterpret_cast<hipStream_t>(f.stream),
                      f.iters_out, f.status_out, marks, bitmap, words, f.B, f.max_iters, tcell, lds_words);
     if (rc) return rc;

@@ -323,6 +323,8 @@ __global__ __launch_bounds__(256) void nastar_unpack_kernel(const uint8_t* __res
 // tcell = {t_end (-1: no map is marked -- nothing to re-run), number of marked maps, t_max = max over the solved maps of their goal step}.
 // ONE workgroup: the bitmaps of the marked maps are AND-ed word by word in LDS (words from t_max on).
 constexpr int kTendThreads = 1024;
+constexpr int kTendStaticLdsBytes = 16;  // s_tmax, s_nm, s_first below (12 bytes), rounded up
+constexpr int kTendMaxLdsWords = (64 * 1024 - kTendStaticLdsBytes) / 4;  // static + dynamic LDS of the launch stay within 64 KiB
 __global__ __launch_bounds__(kTendThreads) void nastar_batchloop_tend_kernel(const int* __restrict__ iters, const int* __restrict__ status,
                                                                             const int* __restrict__ marks, const uint32_t* __restrict__ bitmap,
                                                                             int words, int B, int max_iters, int* __restrict__ tcell, int lds_words)
